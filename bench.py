@@ -3,6 +3,7 @@
 bench.py -- throughput of the PLS resampling hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--mode weak]
+                    [--full] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 launches N ranks itself (one process per GPU,
 ``torch.distributed.run`` on 127.0.0.1) unless it is already running under a
@@ -23,14 +24,25 @@ every rank runs its own PERMS + BOOTS per step on a full replica of X.
 passes over X (R = A X on the matrix pipe).  The product's default permutation
 route for PLS-C is the S x S dual-space shortcut (no pass over X per
 permutation); SURVEY.md section 8d asks for it to be reported separately, so
-the same step with that route is timed in a second region of the same run and
-reported as ``value_dual`` / ``ms_per_step_dual``.
+under ``--full`` the same step with that route is timed in a region of its own
+in the same run and reported as ``value_dual`` / ``ms_per_step_dual``.
 
-The driver's command (``--gpus 1``, default config) also embeds, under
-``configs``, one compact sub-record per other BASELINE config (c2, c3,
-c4split, c5: value, ms_per_step, roofline.frac, cpu_baseline) and the
-end-to-end public call at the headline shape (``c4_analysis``: index
-generation inside the clock); ``--no-configs`` skips them.
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline
+needs: set-up, W warm-up steps, K timed steps, the line.  ``--full`` adds
+everything else the line used to carry: the dual-route region, the CPU
+baseline (``--cpu-sample``, default 8 under ``--full``), the measured MFMA
+peak, and -- default config, one GPU -- one compact sub-record per other
+BASELINE config under ``configs`` (c2, c3, c4split, c5: value, ms_per_step,
+roofline.frac, cpu_baseline) plus the end-to-end public call at the headline
+shape (``c4_analysis``: index generation inside the clock; ``--no-configs``
+skips them), or -- ``--gpus N > 1`` -- the sharded records under ``sharded``.
+
+``--dump-outputs DIR`` writes what the timed path computed in its last timed
+step (the arrays the step's one collective hands back) to ``DIR/<name>.npy``
+in float64, at most 64 MB in all: an array too large for its share keeps a
+fixed, seeded sample of its leading-axis rows.  The inputs of a given command
+line are the same from run to run, so two builds can be compared output for
+output.
 
 ``--mode strong``: one step = ONE analysis of --perms + --boots resamples
 (default 10000 + 10000) split over the ranks with parallel.shard_bounds, run
@@ -127,6 +139,44 @@ def quad_closing_work(S, mt, gpl):
     return float(S) * (S + 1), issued
 
 
+DUMP_BYTES = 60 * 2 ** 20            # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def result_arrays(result, gathered_names, summed_names):
+    """{name: float64 ndarray} of a step's ``parallel.gather_device`` result: every gathered array with the rank
+    axis folded into the resample axis (world x nmax rows, padding rows included), every summed array as is."""
+    gathered, summed = result
+    out = {}
+    for name, t in zip(gathered_names, gathered):
+        out[name] = t.reshape((-1,) + tuple(t.shape[2:])).double().cpu().numpy()
+    for name, t in zip(summed_names, summed):
+        out[name] = t.double().cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array} as ``path/<name>.npy`` in float64.  Smallest first, every array gets an equal share of
+    what is left of DUMP_BYTES; one that does not fit keeps a fixed, seeded sample of its leading-axis rows, in
+    order -- the same rows in every run of the same shapes.  Returns {name: {'shape', 'rows_kept', 'rows'}}."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    left = DUMP_BYTES
+    info = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].nbytes)):
+        a, share = arrays[name], left // (len(arrays) - i)
+        if a.ndim == 0 or a.nbytes // max(a.shape[0], 1) > share:
+            a = a.reshape(-1)                             # rows too large for the share: sample elements
+        n = a.shape[0]
+        kept = n
+        if a.nbytes > share:
+            kept = share // (a.nbytes // n)
+            a = a[np.sort(np.random.RandomState(0).choice(n, kept, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+        left -= a.nbytes
+        info[name] = {'shape': list(a.shape), 'rows_kept': kept, 'rows': n}
+    return info
+
+
 class PLSC(object):
     """behavioral / mean-centred PLS: permutations + bootstraps."""
 
@@ -192,6 +242,10 @@ class PLSC(object):
 
     def units_per_step(self, world):
         return (self.perms + self.boots) * (world if self.args.mode == 'weak' else 1)
+
+    def outputs(self):
+        """Singular values of the permutations, bootstrap distrib, sum U and sum U^2 over the bootstraps."""
+        return result_arrays(self.result, ['perm_singval', 'boot_distrib'], ['boot_usum', 'boot_usq'])
 
     def step(self, i, timed=False):
         import torch
@@ -486,6 +540,10 @@ class Simpls(object):
     def units_per_step(self, world):
         return (self.perms + self.boots) * world
 
+    def outputs(self):
+        """pctvar of the permuted Y, bootstrap y-loadings, sum and sum of squares of the bootstrap x-weights."""
+        return result_arrays(self.result, ['perm_pctvar', 'boot_y_loadings'], ['boot_usum', 'boot_usq'])
+
     def step(self, i, timed=False):
         import torch
         from pypyls_amd import parallel
@@ -625,6 +683,10 @@ class SplitHalf(object):
 
     def units_per_step(self, world):
         return self.arr * self.ns * (1 if self.strong else world)
+
+    def outputs(self):
+        """Split-half correlations of the left and right singular vectors per arrangement and split."""
+        return result_arrays(self.result, ['split_ucorr', 'split_vcorr'], [])
 
     def step(self, i, timed=False):
         import torch
@@ -847,10 +909,10 @@ def make_workload(args):
 
 def measure(args, wl, env):
     """Time ``args.steps`` steps of workload ``wl`` (after ``args.warmup`` untimed ones) between barriers and
-    device syncs, slowest rank counts; returns the record (rank 0) or None.  For PLS-C a second timed region
-    runs the same step with the other permutation route, so that BOTH are on record:
-    ``value`` = permutations through the feature pass R_p = A_p X (the north-star pipeline),
-    ``value_dual`` = the product's default, the S x S dual-space route (no pass over X per permutation)."""
+    device syncs, slowest rank counts; returns the record (rank 0) or None.  For PLS-C ``value`` = permutations
+    through the feature pass R_p = A_p X (the north-star pipeline); under --full the product's default,
+    the S x S dual-space route (no pass over X per permutation), is timed first in a region of its own, so that
+    BOTH are on record (``value_dual``)."""
     import torch
     import torch.distributed as dist
     world, rank, dev, backend, collective = env['world'], env['rank'], env['dev'], env['backend'], env['collective']
@@ -881,6 +943,11 @@ def measure(args, wl, env):
             elapsed = float(t.item())
         return elapsed
 
+    # without --full the one region is the headline's: permutations through the feature pass (PLS-C)
+    primal_only = isinstance(wl, PLSC) and not args.full and not args.no_primal
+    if primal_only:
+        dual_default = eng.set_perm_path(None)          # the product's route, for --emulate-world
+        eng.set_perm_path(False)
     elapsed = timed_region()
     timing = eng.last_timing()
     kt = eng.kernel_timing()
@@ -889,7 +956,7 @@ def measure(args, wl, env):
     eng.set_timing(False)
     dual = bool(timing.get('dual_perm', 0))
 
-    # second region: permutations through the feature pass (the north-star pipeline)
+    # second region (--full): permutations through the feature pass (the north-star pipeline)
     elapsed_primal = None
     if isinstance(wl, PLSC) and dual and not args.no_primal:
         eng.set_perm_path(False)
@@ -899,12 +966,16 @@ def measure(args, wl, env):
         eng.set_timing(False)
         eng.set_perm_path(True)
 
+    dumped = None
+    if args.dump_outputs and rank == 0:                 # the last timed step's results, before anything reuses them
+        dumped = dump_outputs(args.dump_outputs, wl.outputs())
+
     emu = None
     if args.emulate_world and isinstance(wl, PLSC) and args.mode == 'strong' and world == 1:
         worlds = sorted({1} | {int(v) for v in args.emulate_world.split(',') if v.strip()})
         emu = {}
         for route, is_dual in (('dual', True), ('feature_pass', False)):
-            if is_dual and not dual:
+            if is_dual and not (dual_default if primal_only else dual):
                 continue
             eng.set_perm_path(is_dual)
             tab = wl.emulate(worlds)
@@ -984,6 +1055,8 @@ def measure(args, wl, env):
                 else 'feature pass'
             roof['pipeline_frac_mfma'], roof['pipeline_hbm_algorithmic_over_peak'] = pm, ph
             roof['pipeline_work'] = wl.pipeline_formula
+            if primal_only:
+                out['hbm_algorithmic_TBps'] = out['value'] / world * 8.0 * wl.S * (wl.B + wl.Tp) / 1e12
     roof['traffic'] = None
     tpath = os.path.join(ROOT, 'profiles', 'traffic_{}.json'.format(wl.name))
     if os.path.exists(tpath):
@@ -1039,7 +1112,10 @@ def measure(args, wl, env):
                                                   'algorithmic.  Valid for the literal 5000 + 5000 step only'}
         except Exception:
             pass
-    roof['measured_mfma_f64_peak_tflops'] = eng.mfma_f64_peak()
+    if args.full:
+        roof['measured_mfma_f64_peak_tflops'] = eng.mfma_f64_peak()
+    if dumped is not None:
+        out['outputs'] = dumped
     if world == 1 and args.cpu_sample > 0:
         v, sample = wl.cpu_baseline()
         out['cpu_baseline'] = {'value': v, 'unit': wl.unit, 'cores': os.cpu_count() or 1, 'kind': 'port',
@@ -1061,7 +1137,7 @@ def sub_records(args, env):
     t_all = time.perf_counter()
     for cfg in SUB_CONFIGS:
         a = copy.copy(args)
-        a.config, a.mode, a.perms, a.boots, a.emulate_world = cfg, 'weak', 0, 0, ''
+        a.config, a.mode, a.perms, a.boots, a.emulate_world, a.dump_outputs = cfg, 'weak', 0, 0, '', None
         a.steps, a.warmup = (2, 1) if cfg == 'c4split' else (3, 1)
         a.cpu_sample = 8
         t0 = time.perf_counter()
@@ -1140,7 +1216,7 @@ def sharded_records(args, env):
     t0 = time.perf_counter()
     try:
         a = copy.copy(args)
-        a.config, a.mode, a.emulate_world = 'c4split', 'strong', ''
+        a.config, a.mode, a.emulate_world, a.dump_outputs = 'c4split', 'strong', '', None
         a.perms, a.boots, a.steps, a.warmup, a.cpu_sample = args.split_arrangements, 0, 2, 1, 0
         wl = make_workload(a)
         rec = measure(a, wl, env)
@@ -1164,11 +1240,16 @@ def sharded_records(args, env):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=3)
-    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=3, help='timed steps')
+    ap.add_argument('--warmup', type=int, default=1, help='untimed steps before them')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the dual permutation route, the CPU baseline, '
+                         'the MFMA peak, and the other configs (one GPU) or the sharded records (N GPUs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)')
     ap.add_argument('--config', default='c4', choices=['c4', 'c2', 'c3', 'c5', 'c4split'])
     ap.add_argument('--mode', default='weak', choices=['weak', 'strong', 'analysis'])
     ap.add_argument('--splits', type=int, default=0, help='--mode analysis: n_split of the call (0 = no split-half)')
@@ -1178,26 +1259,39 @@ def main():
     ap.add_argument('--perms', type=int, default=0,
                     help='permutations per step (per GPU in weak mode, total in strong mode)')
     ap.add_argument('--boots', type=int, default=0, help='bootstraps per step (same convention)')
-    ap.add_argument('--cpu-sample', type=int, default=8,
-                    help='permutations and bootstraps (each) timed for the CPU baseline; 0 = skip')
+    ap.add_argument('--cpu-sample', type=int, default=None,
+                    help='permutations and bootstraps (each) timed for the CPU baseline; 0 = skip '
+                         '(default: 8 under --full, else 0)')
     ap.add_argument('--no-primal', action='store_true', help='skip the second (feature-pass) timed region')
     ap.add_argument('--no-configs', action='store_true',
-                    help='default run only: skip the sub-records of the other BASELINE configs (configs: {...})')
+                    help='default run with --full: skip the sub-records of the other BASELINE configs (configs: {...}) '
+                         'or the sharded records')
     ap.add_argument('--strong-resamples', type=int, default=10000,
-                    help='--gpus N > 1, default run: n_perm = n_boot of the ONE sharded end-to-end analysis embedded '
-                         'under "sharded" (strong scaling)')
+                    help='--gpus N > 1, default run with --full: n_perm = n_boot of the ONE sharded end-to-end analysis '
+                         'embedded under "sharded" (strong scaling)')
     ap.add_argument('--split-arrangements', type=int, default=64,
-                    help='--gpus N > 1, default run: arrangements (x n_split = 100) of the ONE sharded split-half leg '
-                         'embedded under "sharded"')
+                    help='--gpus N > 1, default run with --full: arrangements (x n_split = 100) of the ONE sharded '
+                         'split-half leg embedded under "sharded"')
     ap.add_argument('--sharded-timeout', type=float, default=600.0,
-                    help='--gpus N > 1, default run: seconds the sharded sub-records may take before the headline line is '
-                         'printed without them')
+                    help='--gpus N > 1, default run with --full: seconds the sharded sub-records may take before the '
+                         'headline line is printed without them')
     ap.add_argument('--n-split', type=int, default=0, help='--config c4split: splits per arrangement (default 100)')
     ap.add_argument('--emulate-world', default='',
                     help='strong mode, one GPU: comma-separated world sizes N; times the critical path of one '
                          'analysis on rank 0 and on rank N-1 of an emulated world N (full index generation, own '
                          'shard only, no gather) on both permutation routes and reports the implied efficiency')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.mode == 'analysis':
+        ap.error('--dump-outputs times the resampling step: not with --mode analysis')
+    if args.cpu_sample is None:
+        args.cpu_sample = 8 if args.full else 0
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args))
     # The one JSON line must be the LAST thing on stdout.  RCCL prints a version
@@ -1253,13 +1347,13 @@ def main():
     else:
         wl = make_workload(args)
         out = measure(args, wl, env)
-        if (out is not None and world == 1 and args.config == 'c4' and args.mode == 'weak' and not args.no_configs
-                and (args.S, args.B, args.T) == (500, 200000, 50)):
+        if (out is not None and world == 1 and args.config == 'c4' and args.mode == 'weak' and args.full
+                and not args.no_configs and (args.S, args.B, args.T) == (500, 200000, 50)):
             del wl.eng
             del wl
             torch.cuda.empty_cache()
             out['configs'] = sub_records(args, env)
-        elif world > 1 and args.config == 'c4' and args.mode == 'weak' and not args.no_configs:
+        elif world > 1 and args.config == 'c4' and args.mode == 'weak' and args.full and not args.no_configs:
             del wl                                          # (its engine and scratch go with it)
             torch.cuda.empty_cache()
             # The sub-records are collective calls that have never run on several real GPUs: if they hang (a rank that

@@ -224,7 +224,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = dict(os.environ, PLSX_BENCH_SHARE_GPU='1', PLSX_BENCH_BACKEND='gloo', PLSX_SCRATCH_GB='4')
     env.pop('WORLD_SIZE', None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1',
-           '--B', '20000', '--perms', '56', '--boots', '56', '--cpu-sample', '0']
+           '--B', '20000', '--perms', '56', '--boots', '56', '--cpu-sample', '0', '--full']
     small = ['--strong-resamples', '300', '--split-arrangements', '5', '--n-split', '12']
     proc = subprocess.run(cmd + small, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
@@ -272,7 +272,7 @@ def test_bench_config_lines(config):
     env = dict(os.environ, PLSX_SCRATCH_GB='8')
     env.pop('WORLD_SIZE', None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', config, '--steps', '2',
-                           '--warmup', '1'], env=env, capture_output=True, text=True, timeout=900)
+                           '--warmup', '1', '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                       # ONE JSON line, nothing after it
@@ -310,14 +310,14 @@ def test_bench_analysis_mode_line():
 
 
 def test_bench_default_line_embeds_every_config():
-    """The driver's command (`bench.py --gpus 1 --steps K --warmup W`) ends in ONE line that carries the headline
-    (value = feature-pass pipeline, value_dual beside it) AND a sub-record per other BASELINE config plus the
+    """The driver's full command (`bench.py --gpus 1 --steps K --warmup W --full`) ends in ONE line that carries the
+    headline (value = feature-pass pipeline, value_dual beside it) AND a sub-record per other BASELINE config plus the
     end-to-end call, each with value / ms_per_step / roofline.frac / cpu_baseline."""
     import json
     env = dict(os.environ)
     env.pop('WORLD_SIZE', None)
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1'],
-                          env=env, capture_output=True, text=True, timeout=1500)
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                           '--full'], env=env, capture_output=True, text=True, timeout=1500)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -332,3 +332,47 @@ def test_bench_default_line_embeds_every_config():
     assert 'unpinned' in cfgs['c5']['parity_note']
     assert 'error' not in cfgs['c4_analysis'] and cfgs['c4_analysis']['value'] > 0
     assert cfgs['wall_s'] < 300
+
+
+def test_bench_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times only the headline step (feature-pass permutations), for exactly --steps steps, and
+    --dump-outputs writes what its last timed step computed: the same arrays from run to run, and the same arrays
+    as the --full run, whose last timed region is that same step."""
+    import json
+    env = dict(os.environ, PLSX_SCRATCH_GB='4')
+    env.pop('WORLD_SIZE', None)
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+           '--B', '20000', '--perms', '56', '--boots', '56']
+
+    def run(tag, *extra):
+        proc = subprocess.run(cmd + ['--dump-outputs', str(tmp_path / tag)] + list(extra), env=env,
+                              capture_output=True, text=True, timeout=900)
+        assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
+        lines = [l for l in proc.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    plain = run('a')
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in plain, key
+    assert plain['steps'] == 3 and plain['ms_per_step'] > 0 and plain['dtype'] == 'f64'
+    assert abs(plain['value'] - 112 / (plain['ms_per_step'] * 1e-3)) <= 1e-6 * plain['value']
+    for key in ('value_dual', 'configs', 'cpu_baseline'):
+        assert key not in plain, key
+    assert 'measured_mfma_f64_peak_tflops' not in plain['roofline']
+    assert plain['config']['perm_path'] == 'feature pass'
+    assert set(plain['outputs']) == {'perm_singval', 'boot_distrib', 'boot_usum', 'boot_usq'}
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == sorted(n + '.npy' for n in plain['outputs'])
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) <= 64e6
+    again = run('b')
+    full = run('c', '--full')
+    assert full['value_dual'] > 0 and full['cpu_baseline']['kind'] == 'port' and full['steps'] == 3
+    assert full['outputs'] == plain['outputs']
+    for name in plain['outputs']:
+        a = np.load(str(tmp_path / 'a' / (name + '.npy')))
+        assert a.dtype == np.float64 and np.isfinite(a).all() and np.abs(a).max() > 0, name
+        for other in ('b', 'c'):
+            b = np.load(str(tmp_path / other / (name + '.npy')))
+            assert b.shape == a.shape, (name, other)
+            assert np.max(np.abs(a - b)) <= 1e-9 * np.max(np.abs(a)), (name, other)

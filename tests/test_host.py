@@ -396,3 +396,41 @@ def test_resolve_devices_maps_n_proc_to_gpus(monkeypatch):
     import pytest
     with pytest.raises(ValueError):
         team.resolve_devices(None, device_ids=[8])
+
+
+def test_bench_options_plain_and_full():
+    """bench.py: the extra measurements are off unless --full; --steps / --warmup are what the line times."""
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (plain.full, plain.cpu_sample, plain.dump_outputs, plain.steps, plain.warmup) == (False, 0, None, 7, 2)
+    full = bench.parse_args(['--full', '--dump-outputs', 'out'])
+    assert (full.full, full.cpu_sample, full.dump_outputs) == (True, 8, 'out')
+    assert bench.parse_args(['--full', '--cpu-sample', '0']).cpu_sample == 0
+    for bad in (['--steps', '0'], ['--mode', 'analysis', '--dump-outputs', 'out']):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_dump_outputs_fixed_sample_under_the_cap(tmp_path):
+    """--dump-outputs: float64 .npy files, at most 64 MB in all; an array too large for its share keeps the same
+    seeded rows in every run, in order."""
+    import bench
+    rs = np.random.RandomState(3)
+    arrays = {'perm_singval': rs.randn(1008, 50), 'boot_distrib': rs.randn(1008, 50, 50),
+              'boot_usum': rs.randn(200000, 50), 'boot_usq': rs.randn(200000, 50).astype(np.float32)}
+    info = bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    again = bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    assert info == again
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == sorted(n + '.npy' for n in arrays)
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) <= 64e6
+    for name, want in arrays.items():
+        got = np.load(str(tmp_path / 'a' / (name + '.npy')))
+        assert got.dtype == np.float64 and list(got.shape) == info[name]['shape']
+        np.testing.assert_array_equal(got, np.load(str(tmp_path / 'b' / (name + '.npy'))))
+        if info[name]['rows_kept'] == want.shape[0]:
+            np.testing.assert_array_equal(got, want)
+        else:                                           # a subset of the rows, in their order
+            rows = [np.flatnonzero((want == r).all(axis=tuple(range(1, want.ndim))))[0] for r in got[:50]]
+            assert rows == sorted(rows) and len(set(rows)) == len(rows)
+    assert info['perm_singval']['rows_kept'] == 1008 and info['boot_usum']['rows_kept'] < 200000

@@ -4,7 +4,7 @@
 tag=$1; ctr=$2
 repo=$(pwd); mkdir -p "$repo/gpurun_out"
 cd /tmp && export TMPDIR=/tmp; rm -rf /tmp/pmc_$tag
-rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d /tmp/pmc_$tag -o p -- python "$repo/bench.py" --cpu-sample 0 --steps 1 --warmup 1 ${BENCH_ARGS:---perms 560 --boots 560} > /tmp/pmc_$tag.log 2>&1
+rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d /tmp/pmc_$tag -o p -- python "$repo/bench.py" --cpu-sample 0 --steps 1 --warmup 1 --full ${BENCH_ARGS:---perms 560 --boots 560} > /tmp/pmc_$tag.log 2>&1
 f=$(find /tmp/pmc_$tag -name "*counter_collection.csv" | head -1)
 [ -n "$f" ] || { echo "no counter csv"; tail -5 /tmp/pmc_$tag.log; exit 1; }
 python - "$f" "$repo/gpurun_out/${tag}_pmc.csv" <<'PY'

@@ -46,10 +46,10 @@ with open(sys.argv[2], "w") as f:
 PY
 }
 
-echo "== default bench"; stats c4 --steps 5 --warmup 2 --no-configs
-echo "== c4split"; stats c4split --config c4split --steps 2 --warmup 1
-echo "== c5"; stats c5 --config c5 --steps 2 --warmup 1
-echo "== c2"; stats c2 --config c2 --steps 3 --warmup 1
-echo "== c3"; stats c3 --config c3 --steps 3 --warmup 1
+echo "== default bench"; stats c4 --steps 5 --warmup 2 --full --no-configs
+echo "== c4split"; stats c4split --config c4split --steps 2 --warmup 1 --full
+echo "== c5"; stats c5 --config c5 --steps 2 --warmup 1 --full
+echo "== c2"; stats c2 --config c2 --steps 3 --warmup 1 --full
+echo "== c3"; stats c3 --config c3 --steps 3 --warmup 1 --full
 echo "== pmc"; pmc FETCH_SIZE; pmc WRITE_SIZE; pmc "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES"
 echo "== traffic"; cd "$repo"; for c in c4 c3 c5 c4split c2; do tools/traffic.sh $c $tag; done
