@@ -324,6 +324,174 @@ def single_boot(spec, X, Y, inds, x_weights, d_orig=None):
     return distrib, U_boot
 
 
+# --------------------------------------------------------------------------
+# batched restatement of single_perm / single_boot (behavioral PLS)
+# --------------------------------------------------------------------------
+# The same maths as the per-resample hooks above, over a chunk of resamples at
+# once, with the cross-correlations written as one matrix product per chunk:
+# thousands of small per-resample products cost more in per-call overhead than
+# in arithmetic at c2 size.  tests/test_oracle.py pins these against
+# single_perm / single_boot.
+
+#: host bytes of one per-chunk (n, T', B) block (a few of them live at once)
+BATCH_BYTES = 128 * 2 ** 20
+
+
+def _chunks(n, per_resample_bytes):
+    step = max(1, int(BATCH_BYTES // max(per_resample_bytes, 1)))
+    return [(a, min(a + step, n)) for a in range(0, n, step)]
+
+
+def _cell_slices(spec):
+    """Row range of every cell (dummy_label orders the rows cell by cell)."""
+    out = []
+    for c in spec.dummy.T.astype(bool):
+        rows = np.flatnonzero(c)
+        assert rows[-1] - rows[0] + 1 == len(rows)
+        out.append(slice(rows[0], rows[-1] + 1))
+    return out
+
+
+def _zscore_batch(A, covariance):
+    """Column z-score (ddof=1) of every (S, k) slice of A (..., S, k), as xcorr does."""
+    Ac = A - A.mean(axis=-2, keepdims=True)
+    if not covariance:
+        with np.errstate(divide='ignore', invalid='ignore'):
+            Ac = Ac / A.std(axis=-2, ddof=1, keepdims=True)
+    return Ac
+
+
+def _yz_t(spec, Y):
+    """z-scored Y of every resample and cell, transposed: [(n, T, n_c)]."""
+    return [np.ascontiguousarray(np.swapaxes(_zscore_batch(Y[:, c, :], spec.covariance), -1, -2))
+            for c in _cell_slices(spec)]
+
+
+def _covcorr_fixed_x(spec, X, Y):
+    """gen_covcorr (behavioral) with one X (S, B) and a batch Y (n, S, T) -> (n, T', B)."""
+    n, _, T = Y.shape
+    out = []
+    for c, Yt in zip(_cell_slices(spec), _yz_t(spec, Y)):
+        Xz = _zscore_batch(X[c], spec.covariance)
+        out.append((Yt.reshape(n * T, -1) @ Xz).reshape(n, T, -1) / (c.stop - c.start - 1))
+    return np.concatenate(out, axis=-2)
+
+
+def _covcorr_gathered(spec, X, Y):
+    """gen_covcorr (behavioral) of a batch X (n, S, k), Y (n, S, T) -> (n, T', k)."""
+    return np.concatenate([np.matmul(Yt, _zscore_batch(X[:, c, :], spec.covariance)) / (c.stop - c.start - 1)
+                           for c, Yt in zip(_cell_slices(spec), _yz_t(spec, Y))], axis=-2)
+
+
+def _covcorr_rows(spec, X, Y, rows):
+    """gen_covcorr (behavioral) of X[rows[i]], Y[rows[i]] for every row i of ``rows`` (n, S) -> (n, T', B),
+    without forming X[rows[i]]: the resampled rows enter as a one-hot (n, S, S) operand, and the column means and
+    standard deviations of every resample as count-weighted moments of X."""
+    X = X - X.mean(axis=0)                          # (a shift of X changes nothing but the rounding of the moments)
+    X2 = X ** 2
+    n, S = rows.shape
+    T = Y.shape[1]
+    out = []
+    for c, Yt in zip(_cell_slices(spec), _yz_t(spec, Y[rows])):
+        nc = c.stop - c.start
+        hot = (rows[:, c, None] == np.arange(len(X))).astype(float)             # (n, n_c, S)
+        W = np.matmul(Yt, hot)                                                   # (n, T, S): Yz^T of the drawn rows
+        cnt = hot.sum(axis=1)                                                    # (n, S)
+        mean = cnt @ X / nc                                                      # (n, B)
+        R = (W.reshape(n * T, -1) @ X).reshape(n, T, -1) - Yt.sum(axis=-1)[:, :, None] * mean[:, None, :]
+        if not spec.covariance:
+            var = np.maximum(cnt @ X2 / nc - mean ** 2, 0.0) * (nc / (nc - 1.0))
+            with np.errstate(divide='ignore', invalid='ignore'):
+                R /= np.sqrt(var)[:, None, :]
+        out.append(R / (nc - 1))
+    return np.concatenate(out, axis=-2)
+
+
+def _flip_batch(A, Bt):
+    """svd_flip_first on every (A, Bt) pair of a batch."""
+    idx = np.argmax(np.abs(A), axis=-2)
+    signs = np.sign(np.take_along_axis(A, idx[:, None, :], axis=-2))[:, 0, :]
+    signs[signs == 0] = 1.0
+    return A * signs[:, None, :], Bt * signs[:, :, None]
+
+
+def _svd_batch(R):
+    """svd() of every (T', B) slice of R -> U (n, B, L), d (n, L), V (n, T', L)."""
+    if R.shape[-2] <= R.shape[-1]:
+        U, d, Vt = np.linalg.svd(np.swapaxes(R, -1, -2), full_matrices=False)
+        U, Vt = _flip_batch(U, Vt)
+        return U, d, np.swapaxes(Vt, -1, -2)
+    V, d, Ut = np.linalg.svd(R, full_matrices=False)
+    V, Ut = _flip_batch(V, Ut)
+    return np.swapaxes(Ut, -1, -2), d, V
+
+
+def _require_behavioral(spec):
+    if spec.method != 'behavioral':
+        raise ValueError('the batched oracle restates behavioral PLS only')
+
+
+def batch_perm(spec, X, Y, perminds, y_weights):
+    """single_perm (no split-half) of every column of ``perminds`` (S, P) -> (L, P), the same array as stacking
+    ``single_perm(spec, X, Y, perminds[:, i], y_weights)[0]`` along the last axis."""
+    _require_behavioral(spec)
+    X = np.asarray(X, dtype=float)
+    Y = np.asarray(Y, dtype=float)
+    perminds = np.asarray(perminds)
+    Tp = spec.dummy.shape[1] * Y.shape[1]
+    out = []
+    for a, b in _chunks(perminds.shape[1], 8 * Tp * X.shape[1]):
+        _, d, V = _svd_batch(_covcorr_fixed_x(spec, X, Y[perminds[:, a:b].T]))
+        if spec.rotate:                                             # procrustes(y_weights, V, diag(d))
+            N, _, P = np.linalg.svd(np.matmul(y_weights.T, V), full_matrices=False)
+            rot = np.matmul(V * d[:, None, :], np.matmul(np.swapaxes(P, -1, -2), np.swapaxes(N, -1, -2)))
+            out.append(np.sqrt(np.sum(rot ** 2, axis=-2)))
+        else:
+            out.append(d)
+    return np.concatenate(out, axis=0).T
+
+
+def batch_boot(spec, X, Y, inds, x_weights, d_orig=None, sums=False):
+    """single_boot of every column of ``inds`` (S, R).
+
+    Returns (distrib (T', L, R), U_boot (B, L, R)): the two arrays of ``single_boot(spec, X, Y, inds[:, i],
+    x_weights, d_orig)`` stacked along the last axis.  With ``sums=True`` the rotated weights come back summed
+    instead, (distrib, sum of U_boot, sum of U_boot ** 2), so that a long series stays within host memory."""
+    _require_behavioral(spec)
+    X = np.asarray(X, dtype=float)
+    Y = np.asarray(Y, dtype=float)
+    inds = np.asarray(inds)
+    x_weights = np.asarray(x_weights, dtype=float)
+    S, B = X.shape
+    L = x_weights.shape[1]
+    Tp = spec.dummy.shape[1] * Y.shape[1]
+    live_o = np.flatnonzero(np.ones(L, bool) if d_orig is None else live_lvs(d_orig))
+    XW = X @ normalize(x_weights)                                   # gen_distrib: rows of X[inds] @ normalize(U)
+    dist, ub = [], []
+    usum, usq = np.zeros((B, L)), np.zeros((B, L))
+    for a, b in _chunks(inds.shape[1], 8 * Tp * B):
+        rows = inds[:, a:b].T                                       # (n, S)
+        U, d, _ = _svd_batch(_covcorr_rows(spec, X, Y, rows))
+        dist.append(_covcorr_gathered(spec, XW[rows], Y[rows]))
+        live_p = d > RANK_RTOL * d.max(axis=-1, keepdims=True)
+        rot = np.zeros((b - a, B, L))
+        for pat in np.unique(live_p, axis=0):                       # procrustes_live, one live pattern at a time
+            sel = np.flatnonzero(np.all(live_p == pat, axis=1))
+            Up = U[sel][:, :, pat]
+            N, _, P = np.linalg.svd(np.matmul(x_weights[:, live_o].T, Up), full_matrices=False)
+            rot[sel[:, None], :, live_o[None, :]] = np.moveaxis(np.matmul(
+                Up * d[sel][:, None, pat], np.matmul(np.swapaxes(P, -1, -2), np.swapaxes(N, -1, -2))), -1, 1)
+        if sums:
+            usum += rot.sum(axis=0)
+            usq += (rot ** 2).sum(axis=0)
+        else:
+            ub.append(rot)
+    distrib = np.moveaxis(np.concatenate(dist, axis=0), 0, -1)
+    if sums:
+        return distrib, usum, usq
+    return distrib, np.moveaxis(np.concatenate(ub, axis=0), 0, -1)
+
+
 def rescale_test(X_train, X_test, Y_train, U, V):
     """compute.rescale_test, pyls/compute.py:129-151: z-map the test rows with
     the training mean / std (ddof=1), project, add the training mean of Y."""

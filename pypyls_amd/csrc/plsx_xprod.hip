@@ -90,6 +90,7 @@ int run_xprod_fixed(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, co
     const int groups = ceil_div(nres, ctx->npgf);
     if (int e = ensure_scratch(ctx, groups)) return e;
     if (ctx->timing) ctx->timed_units += nres;
+    ctx->last_compact_n = 0;                            // dense launch: plsx_last_timing reports no compact blocks
     HIPCHK(hipMemsetAsync(ctx->Afrag.p, 0, (size_t)groups * ctx->group_stride_f * 8, st));
     GroupLayout lay;
     lay.n = ctx->npgf; lay.Tp = ctx->Tp; lay.J = ctx->J; lay.T = ctx->T; lay.MT = ctx->MTf;

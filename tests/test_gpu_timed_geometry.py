@@ -1,0 +1,345 @@
+"""The oracle at the batch geometry bench.py times.
+
+``bench.py`` (weak mode, ``PLSC.step``) runs one analysis-sized step on a long-lived engine with a fixed 48 GB
+super-batch scratch: ``perm_into`` -- on the feature pass in the plain (headline) run, which sets
+``set_perm_path(False)`` before its timed region; ``--full`` also times the product's default S x S dual route --
+then ONE bootstrap series (``boot_begin`` / ``boot_into`` / ``boot_finish``) whose resamples cross launch and group
+boundaries.  The other parity tests submit a
+few resamples on the default, measured scratch, so they never take that geometry.  Here:
+
+* c4 (X 500 x 200 000, Y 500 x 50): the bench's weak step with 11 distinct permutations and 11 distinct bootstraps
+  replicated over the 1008 slots of the step by a seeded random map (distinct resamples on both sides of every
+  launch and group boundary, and in the first and last slot).  Replicas agree among themselves, every slot agrees
+  with the oracle of its resample on both permutation routes, sum U / sum U^2 with the replication-weighted oracle
+  sums;
+* c2 (80 x 10 000 x 10): every one of the 5000 + 5000 resamples of the literal front-end call, and of the bench's
+  weak step on the same index arrays, against the batched oracle (``cpu_ref.batch_perm`` / ``batch_boot``);
+* c4 through the public call (n_split = 4): a sample of resamples on both sides of the front-end's index-chunk
+  boundary (``IndexStream.chunks``: 256 rows, then 4 x longer).
+
+Each bench step also pins the geometry the engine reports (``Engine.last_timing``).  When a tuning change moves the
+bench's geometry these tests fail and say so: re-pin them at the new geometry so that the step the headline number
+times is still the step tested here.
+"""
+import numpy as np
+import pytest
+
+from conftest import assert_close, assert_close_per_lv
+from oracle import cpu_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+BENCH_SCRATCH_GB = 48.0                     # bench.py _engine_kwargs: the fixed super-batch scratch of a bench run
+
+# Engine.last_timing() of the bench's weak step (keys: include/plsx.h, plsx_last_timing)
+C4_PERM_DUAL = dict(dual_perm=1, xprod_launches=0)
+# (the fixed-X layout packs 8 permutations a group; the report's resamples_per_group is that of the general layout)
+C4_PERM_FEATURE = dict(dual_perm=0, xprod_launches=2, xprod_resamples=1008, superbatch=616, compact_row_fraction=0)
+# compact blocks (one bootstrap per block), two launches of 504 (balanced_batch(1008, 616, 1)), in-place sums
+C4_BOOT = dict(xprod_launches=2, xprod_resamples=1008, resamples_per_group=1, superbatch=616, quad_series=0)
+C4_BOOT_ROUTE = 0                           # boot_begin(1008): 0 = sums accumulated per batch (k_urot), no closing pass
+C2_PERM_DUAL = dict(dual_perm=1, xprod_launches=0)
+C2_PERM_FEATURE = dict(dual_perm=0, xprod_launches=1, xprod_resamples=5000, compact_row_fraction=0)
+# dense layout, two launches (balanced_batch(5000, 4096, 32) = 2528: 2528 + 2472)
+C2_BOOT = dict(xprod_launches=2, xprod_resamples=5000, resamples_per_group=32, superbatch=4096, quad_series=0,
+               compact_row_fraction=0)
+C2_BOOT_ROUTE = 0
+
+
+def _synth(S, B, T, seed=0):
+    """bench.py synth(): the data of the bench's headline and c2 records."""
+    rs = np.random.RandomState(seed)
+    X = rs.randn(S, B)
+    Y = rs.randn(S, T) + 0.3 * X[:, :T]
+    return X, Y
+
+
+def _assert_geometry(got, pinned, what):
+    for key, want in pinned.items():
+        assert got.get(key) == want, (
+            'bench geometry moved: {} reports {} = {} where this test pins {} (full report: {}). The step bench.py '
+            'times is no longer the one tested here: re-pin this test at the new geometry.'.format(
+                what, key, got.get(key), want, got))
+
+
+def _bench_engine(X, Y):
+    """The engine of a bench run, set up as PLSC.setup does."""
+    from pypyls_amd import hostmath, resampling as rsmp
+    from pypyls_amd.engine import Engine
+    eng = Engine(scratch_gb=BENCH_SCRATCH_GB)
+    eng.set_data(X, Y, rsmp.cell_of_row([len(X)], 1), 1, 1, 0)
+    xw, sv, yw = eng.decompose()
+    xw, yw = hostmath.sign_convention(xw, yw)
+    eng.set_original(xw, sv, yw)
+    return eng, xw, sv, yw
+
+
+def _weak_step(eng, perms, boots):
+    """One weak step of PLSC.step on index arrays (S, P) / (S, R), on the permutation route of the plain bench run
+    (bench.py measure: set_perm_path(False) before the timed region; the step's set_perm_path(None) keeps it).  Returns the permuted singular values (P, L),
+    sum U, sum U^2 (B, L), distrib (R, T', L), what boot_begin reported, and last_timing() of both legs."""
+    import torch
+    P, R = perms.shape[1], boots.shape[1]
+    perm_idx, boot_idx = eng.index_tensor(perms), eng.index_tensor(boots)
+    out_sv = torch.zeros((P, eng.L), dtype=torch.float64, device=eng.device)
+    usum = torch.zeros((eng.B, eng.L), dtype=torch.float64, device=eng.device)
+    usq = torch.zeros_like(usum)
+    dist = torch.zeros((R, eng.Tp, eng.L), dtype=torch.float64, device=eng.device)
+    eng.set_perm_path(False)
+    eng.set_timing(True)
+    eng.set_perm_path(None)
+    eng.perm_into(perm_idx, out_sv, rotate=True)
+    eng.sync()
+    tm_perm = eng.last_timing()
+    eng.set_timing(True)
+    route = eng.boot_begin(R)
+    eng.boot_into(boot_idx, usum, usq, dist)
+    eng.boot_finish(usum, usq)
+    eng.sync()
+    tm_boot = eng.last_timing()
+    eng.set_timing(False)
+    return (out_sv.cpu().numpy(), usum.cpu().numpy(), usq.cpu().numpy(), dist.cpu().numpy(), route,
+            tm_perm, tm_boot)
+
+
+def _other_perm_route(eng, perms):
+    """The permutation leg again on the other route (the dual S x S route after _weak_step)."""
+    import torch
+    dual = bool(eng.set_perm_path(None))
+    eng.set_perm_path(not dual)
+    out = torch.zeros((perms.shape[1], eng.L), dtype=torch.float64, device=eng.device)
+    eng.set_timing(True)
+    eng.perm_into(eng.index_tensor(perms), out, rotate=True)
+    eng.sync()
+    tm = eng.last_timing()
+    eng.set_timing(False)
+    eng.set_perm_path(dual)
+    return out.cpu().numpy(), tm
+
+
+def _slot_map(n, nd, boundaries, seed):
+    """slot -> distinct resample: seeded random, every distinct one used, and different resamples on the two sides
+    of every boundary b (slots b - 1 and b) and in the first and last slot."""
+    rs = np.random.RandomState(seed)
+    which = rs.randint(nd, size=n)
+    which[:nd] = rs.permutation(nd)                     # (every distinct resample at least once)
+    rs.shuffle(which)
+    for b in sorted(set(boundaries) | {n - 1}):
+        if 0 < b < n and which[b] == which[b - 1]:
+            taken = {which[b - 1]} | ({which[b + 1]} if b + 1 < n else set())
+            which[b] = min(set(range(nd)) - taken)
+    assert which[0] != which[-1] and len(np.unique(which)) == nd
+    for b in boundaries:
+        assert which[b] != which[b - 1], b
+    return which
+
+
+def _rel_per_column(a, b):
+    """max |a - b| / max |b| of every trailing-axis column."""
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    axes = tuple(range(a.ndim - 1))
+    return np.max(np.abs(a - b), axis=axes) / np.max(np.abs(b), axis=axes)
+
+
+def _assert_replicas(vals, which, rtol, what):
+    """vals (n, ...): slots that hold the same resample agree to rtol of that resample's own scale (per LV when the
+    last axis is the LV axis)."""
+    for d in np.unique(which):
+        slots = np.flatnonzero(which == d)
+        v = vals[slots]
+        err = np.max(np.abs(v - v[:1]), axis=tuple(range(v.ndim - 1)))
+        scale = np.max(np.abs(v[0]), axis=tuple(range(v.ndim - 2))) if v.ndim > 2 else np.abs(v[0])
+        bad = err > rtol * scale
+        assert not np.any(bad), '{}: resample {} differs between its slots {} (LVs {}, max rel err {:.3e})'.format(
+            what, d, slots[np.argmax(np.max(np.abs(v - v[:1]).reshape(len(slots), -1), axis=1))],
+            np.flatnonzero(bad), float(np.max(err / scale)))
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# c4: the bench's weak step, replicated, at the literal shape
+# ----------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope='module')
+def c4_data():
+    return _synth(500, 200000, 50)
+
+
+def test_c4_bench_weak_step_replicated_against_oracle(c4_data):
+    """PLSC.step (weak) at c4 -- 1008 permutations through the feature pass in two launches of 504, one series of 1008 bootstraps in two compact
+    launches of 504 -- with 11 + 11 distinct resamples spread over the 1008 slots.  Catches a wrong group base or
+    offset in one launch, slots swapped between groups, and a sum U that drops or doubles a super-batch."""
+    from pypyls_amd import resampling as rsmp
+    X, Y = c4_data
+    S, B = X.shape
+    n, nd = 1008, 11
+    perms_d = rsmp.gen_permsamp([S], 1, nd, seed=4401, verbose=False)
+    boots_d = rsmp.gen_bootsamp([S], 1, nd, seed=4402, verbose=False)
+    # launch boundary 504; groups of 7 (feature-pass permutations) and of 8 (dual route)
+    bounds = list(range(7, n, 7)) + list(range(8, n, 8)) + [504]
+    pw = _slot_map(n, nd, bounds, seed=4403)
+    bw = _slot_map(n, nd, bounds, seed=4404)
+    eng, xw, sv, yw = _bench_engine(X, Y)
+    try:
+        got_p, usum, usq, dist, route, tm_p, tm_b = _weak_step(eng, perms_d[:, pw], boots_d[:, bw])
+        _assert_geometry(tm_p, C4_PERM_FEATURE, 'c4 permutation leg (feature pass)')
+        assert route == C4_BOOT_ROUTE, 'bench geometry moved: c4 boot_begin(1008) reports route {}, pinned {}'.format(
+            route, C4_BOOT_ROUTE)
+        _assert_geometry(tm_b, C4_BOOT, 'c4 bootstrap leg')
+        assert tm_b['compact_row_fraction'] > 0, 'bench geometry moved: c4 bootstraps left the compact route ' \
+                                                 '({})'.format(tm_b)
+        other_p, tm_o = _other_perm_route(eng, perms_d[:, pw])
+        _assert_geometry(tm_o, C4_PERM_DUAL, 'c4 permutation leg (dual route)')
+    finally:
+        eng.close()
+    # replicas agree among themselves ...
+    _assert_replicas(got_p, pw, 1e-12, 'c4 permutation singular values (feature pass)')
+    _assert_replicas(other_p, pw, 1e-12, 'c4 permutation singular values (dual route)')
+    _assert_replicas(dist, bw, 1e-12, 'c4 bootstrap distrib')
+    # ... and every slot with the oracle of its resample, on the (U, d, V) given to set_original
+    spec = ref.Spec('behavioral', [S], 1)
+    for d in range(nd):
+        want = ref.single_perm(spec, X, Y, perms_d[:, d], yw)[0]
+        for label, got in (('feature-pass', got_p), ('dual', other_p)):
+            rel = _rel_per_column(got[pw == d].T, np.repeat(want[:, None], np.sum(pw == d), 1))
+            assert np.all(rel <= 1e-9), 'c4 permutation {} ({} route) vs oracle: slot {} rel err {:.3e}'.format(
+                d, label, np.flatnonzero(pw == d)[np.argmax(rel)], rel.max())
+    want_us, want_uq = np.zeros((B, eng.L)), np.zeros((B, eng.L))
+    for d in range(nd):
+        wd, wu = ref.single_boot(spec, X, Y, boots_d[:, d], xw, np.diag(sv))
+        for slot in np.flatnonzero(bw == d):
+            assert_close_per_lv(dist[slot], wd, 1, 1e-9, what='c4 bootstrap {} distrib in slot {}'.format(d, slot))
+        mult = int(np.sum(bw == d))
+        want_us += mult * wu
+        want_uq += mult * wu ** 2
+    assert_close_per_lv(usum, want_us, 1, 1e-8, what='c4 sum U of the 1008-bootstrap series')
+    assert_close_per_lv(usq, want_uq, 1, 1e-8, what='c4 sum U^2 of the 1008-bootstrap series')
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# c2: every resample of the literal call and of the bench step
+# ----------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope='module')
+def c2_case():
+    """The literal c2 front-end call and the batched oracle of all of its 5000 + 5000 resamples (on the original
+    the call used: its x_weights, singvals, y_weights)."""
+    import pypyls_amd as pls
+    S, B, T = 80, 10000, 10
+    X, Y = _synth(S, B, T)
+    res = pls.behavioral_pls(X, Y, n_perm=5000, n_boot=5000, test_split=0, seed=1234, verbose=False)
+    spec = ref.Spec('behavioral', [S], 1)
+    U, d, V = ref.decompose(spec, X, Y)
+    assert_close(res.singvals, np.diag(d), 1e-9, what='c2 front-end singvals')
+    assert_close_per_lv(res.x_weights, U, 1, 1e-7, what='c2 front-end x_weights')
+    perms, boots = res.permres.permsamples, res.bootres.bootsamples
+    want_p = ref.batch_perm(spec, X, Y, perms, res.y_weights)
+    want_d, want_us, want_uq = ref.batch_boot(spec, X, Y, boots, res.x_weights, np.diag(res.singvals), sums=True)
+    return dict(X=X, Y=Y, res=res, perms=perms, boots=boots, want_p=want_p, want_d=want_d, want_us=want_us,
+                want_uq=want_uq)
+
+
+def _assert_columns(got, want, rtol, what):
+    rel = _rel_per_column(got, want)
+    assert np.all(rel <= rtol), '{}: resample {} max rel err {:.3e} ({} of {} resamples above {:g})'.format(
+        what, int(np.argmax(rel)), rel.max(), int(np.sum(rel > rtol)), rel.size, rtol)
+
+
+def test_c2_literal_call_every_resample_against_batched_oracle(c2_case):
+    """behavioral_pls(X, Y, n_perm=5000, n_boot=5000, test_split=0, seed=1234) at 80 x 10 000 x 10: every
+    permutation column, every bootstrap slice, the p-value counts, the bootstrap ratios and standard errors (from
+    the oracle's sums over all 5000 bootstraps plus the original, n_boot + 1) and the percentile intervals."""
+    c = c2_case
+    res, want_p, want_d = c['res'], c['want_p'], c['want_d']
+    P, R = want_p.shape[1], want_d.shape[-1]
+    _assert_columns(res.permres.perm_singval, want_p, 1e-8, 'c2 literal perm_singval')
+    # p-values as integer counts (strict >, compute.py:178); only a permutation the oracle puts within 1e-9 of
+    # the original is left undecided
+    orig = res.singvals[:, None]
+    tie = np.abs(want_p - orig) <= 1e-9 * orig
+    assert tie.sum() <= 5, 'c2: {} permutations within 1e-9 of the original'.format(int(tie.sum()))
+    lo = np.sum((want_p > orig) & ~tie, axis=1)
+    count = np.rint(res.permres.pvals * (P + 1)).astype(int) - 1
+    assert np.allclose(res.permres.pvals * (P + 1), count + 1, rtol=0, atol=1e-6)
+    assert np.all((count >= lo) & (count <= lo + tie.sum(axis=1))), (count, lo)
+    _assert_columns(res.bootres.y_loadings_boot, want_d, 1e-8, 'c2 literal y_loadings_boot')
+    bs = res.x_weights * res.singvals
+    bsr, se = ref.boot_rel(bs, c['want_us'] + bs, c['want_uq'] + bs ** 2, R + 1)
+    assert_close_per_lv(res.bootres.x_weights_stderr, se, 1, 1e-6, what='c2 literal x_weights_stderr')
+    assert_close_per_lv(res.bootres.x_weights_normed, bsr, 1, 1e-6, what='c2 literal x_weights_normed')
+    ci = np.stack(ref.boot_ci(want_d), -1)
+    assert_close(res.bootres.y_loadings_ci, ci, 1e-8, what='c2 literal y_loadings_ci')
+
+
+def test_c2_bench_weak_step_every_resample_against_batched_oracle(c2_case):
+    """PLSC.step (weak) at c2 on the literal call's 5000 + 5000 index arrays: permutations through the feature pass
+    (one launch; again on the dual route), one series of 5000 bootstraps in two launches under the 4096 cap;
+    every resample and the series' sum U / sum U^2 against the batched oracle."""
+    c = c2_case
+    X, Y, res = c['X'], c['Y'], c['res']
+    eng, xw, sv, yw = _bench_engine(X, Y)
+    try:
+        got_p, usum, usq, dist, route, tm_p, tm_b = _weak_step(eng, c['perms'], c['boots'])
+        _assert_geometry(tm_p, C2_PERM_FEATURE, 'c2 permutation leg (feature pass)')
+        assert route == C2_BOOT_ROUTE, 'bench geometry moved: c2 boot_begin(5000) reports route {}, pinned {}'.format(
+            route, C2_BOOT_ROUTE)
+        _assert_geometry(tm_b, C2_BOOT, 'c2 bootstrap leg')
+        other_p, tm_o = _other_perm_route(eng, c['perms'])
+        _assert_geometry(tm_o, C2_PERM_DUAL, 'c2 permutation leg (dual route)')
+    finally:
+        eng.close()
+    # the bench's original is the front-end's to rounding, so the oracle of the front-end's original applies
+    assert_close(sv, res.singvals, 1e-12, what='c2 bench-step singvals')
+    assert_close_per_lv(xw, res.x_weights, 1, 1e-10, what='c2 bench-step x_weights')
+    assert_close_per_lv(yw, res.y_weights, 1, 1e-10, what='c2 bench-step y_weights')
+    _assert_columns(got_p.T, c['want_p'], 1e-8, 'c2 bench-step permutations (feature pass)')
+    _assert_columns(other_p.T, c['want_p'], 1e-8, 'c2 bench-step permutations (dual route)')
+    _assert_columns(np.moveaxis(dist, 0, -1), c['want_d'], 1e-8, 'c2 bench-step distrib')
+    assert_close_per_lv(usum, c['want_us'], 1, 1e-8, what='c2 bench-step sum U')
+    assert_close_per_lv(usq, c['want_uq'], 1, 1e-8, what='c2 bench-step sum U^2')
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# c4 through the public call
+# ----------------------------------------------------------------------------------------------------------------
+
+def test_c4_public_call_sampled_against_oracle(c4_data):
+    """behavioral_pls(X, Y, n_perm=1008, n_boot=1008, n_split=4, test_split=0, seed=1234) at 500 x 200 000 x 50:
+    the front-end ships its index arrays in chunks (IndexStream.chunks: rows [0, 256), then [256, 1008)), which
+    neither the bench step nor the replicated test takes.  Six permutations and six bootstraps -- on both sides of
+    the chunk boundary, the last one, and a seeded sample -- against the oracle: their perm_singval column, the
+    first two split masks of each (gen_splits(seed=i), base.py:705-708) through the device's split-half and
+    ref.split_half, their split null vs the device's own splits, their y_loadings_boot slice; singular values;
+    p-values as counts of the returned null."""
+    from pypyls_amd import plsc, resampling as rsmp
+    X, Y = c4_data
+    S = len(X)
+    n, ns = 1008, 4
+    run = plsc._PLSCRun('behavioral', X, Y, groups=None, n_cond=1, n_perm=n, n_boot=n, n_split=ns, test_size=0.25,
+                        test_split=0, covariance=False, rotate=True, ci=95, permsamples=None, bootsamples=None,
+                        seed=1234, verbose=False, n_proc=None)                 # what behavioral_pls(...) runs
+    res = run.run()
+    spec = ref.Spec('behavioral', [S], 1)
+    U, d, V = ref.decompose(spec, X, Y)
+    assert_close(res.singvals, np.diag(d), 1e-9, what='c4 public call singvals')
+    P = res.permres.perm_singval.shape[1]
+    assert P == n and res.bootres.y_loadings_boot.shape[-1] == n
+    counts = np.sum(res.permres.perm_singval > res.singvals[:, None], axis=1)
+    assert np.array_equal(res.permres.pvals, (counts + 1) / (n + 1))
+    rs = np.random.RandomState(99)
+    pick = lambda: sorted({255, 256, n - 1} | set(rs.choice(np.r_[1:255, 257:n - 1], 3, replace=False).tolist()))
+    perms, boots = res.permres.permsamples, res.bootres.bootsamples
+    ucn, vcn = run.split_null
+    eng = run.engine_used
+    for i in pick():
+        masks = rsmp.gen_splits([S], 1, ns, seed=int(i))                        # what permutation i drew
+        ssd, wu, wv = ref.single_perm(spec, X, Y, perms[:, i], res.y_weights, splitsamp=masks[:, :2])
+        assert_close(res.permres.perm_singval[:, i], ssd, 1e-9, what='c4 public call permutation {}'.format(i))
+        uc, vc = eng.split_half(masks[None], perms=perms[:, [i]])
+        assert np.max(np.abs(uc[0][:, :2].mean(-1) - wu)) <= 1e-9, 'c4 split-half ucorr of permutation {}'.format(i)
+        assert np.max(np.abs(vc[0][:, :2].mean(-1) - wv)) <= 1e-9, 'c4 split-half vcorr of permutation {}'.format(i)
+        assert np.max(np.abs(uc[0].mean(-1) - ucn[:, i])) <= 1e-12, 'c4 split null (u) of permutation {}'.format(i)
+        assert np.max(np.abs(vc[0].mean(-1) - vcn[:, i])) <= 1e-12, 'c4 split null (v) of permutation {}'.format(i)
+    for i in pick():
+        wd, _ = ref.single_boot(spec, X, Y, boots[:, i], res.x_weights, np.diag(res.singvals))
+        assert_close_per_lv(res.bootres.y_loadings_boot[..., i], wd, 1, 1e-9,
+                            what='c4 public call bootstrap {} y_loadings_boot'.format(i))

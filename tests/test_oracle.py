@@ -6,7 +6,7 @@ known-answer numbers.  CPU only.
 import numpy as np
 import pytest
 
-from conftest import load_golden, golden_names, live_lvs, assert_close
+from conftest import load_golden, golden_names, live_lvs, assert_close, assert_close_per_lv
 from oracle import cpu_ref as ref
 
 # oracle (exact thin SVD) vs reference (sklearn randomized_svd, 4 LU-normalised
@@ -313,3 +313,56 @@ def test_mpls_oracle_against_the_reference_seed_envelope(tag):
     # the live columns of the ORIGINAL decomposition do not depend on the seed (only its null columns do)
     o = [g['{}_ref_original_seed{}'.format(tag, s)] for s in (0, 3)]
     assert np.abs(o[0][:, live] - o[1][:, live]).max() < 1e-12 and np.abs(o[0][:, ~live] - o[1][:, ~live]).max() > 1e-3
+
+
+def _resamples(groups, n_cond, n, seed):
+    """Within-cell permutation and bootstrap index arrays (S, n) drawn here, independent of the product."""
+    rs = np.random.RandomState(seed)
+    cells = np.split(np.arange(sum(groups) * n_cond), np.cumsum(np.repeat(groups, n_cond))[:-1])
+    perms = np.stack([rs.permutation(sum(groups) * n_cond) for _ in range(n)], -1)
+    boots = np.stack([np.concatenate([rs.choice(c, len(c)) for c in cells]) for _ in range(n)], -1)
+    return perms, boots
+
+
+@pytest.mark.parametrize('shape', ['c2', 'rank_deficient', 'cells_cov', 'no_rotate'])
+def test_batched_oracle_equals_single_resample_oracle(shape):
+    """batch_perm / batch_boot (the oracle of every resample of a c2-sized series, tests/test_gpu_timed_geometry.py)
+    restate single_perm / single_boot over chunks of resamples: same arrays to 1e-12 of every LV's own scale, at the
+    c2 shape (64 resamples, several chunks), at a rank-deficient shape (S - 1 < T': exactly-null LVs, live-LV
+    Procrustes), with several cells in covariance mode, and without rotation."""
+    S, B, T, groups, n_cond, n, cov, rot = dict(
+        c2=(80, 10000, 10, [80], 1, 64, False, True),
+        rank_deficient=(12, 40, 16, [12], 1, 6, False, True),
+        cells_cov=(36, 300, 4, [10, 8], 2, 9, True, True),
+        no_rotate=(40, 500, 6, [40], 1, 7, False, False))[shape]
+    rs = np.random.RandomState(5)
+    X = rs.randn(S, B) * (1.0 + rs.rand(1, B))
+    Y = rs.randn(S, T) + 0.3 * X[:, :T]
+    spec = ref.Spec('behavioral', groups, n_cond, covariance=cov, rotate=rot)
+    U, d, V = ref.decompose(spec, X, Y)
+    live = ref.live_lvs(d)
+    assert live.all() == (shape != 'rank_deficient')
+    perms, boots = _resamples(groups, n_cond, n, seed=6)
+    old = ref.BATCH_BYTES
+    ref.BATCH_BYTES = 8 * T * n_cond * len(groups) * B * 5        # five resamples per chunk: chunk edges are crossed
+    try:
+        got_p = ref.batch_perm(spec, X, Y, perms, V)
+        got_d, got_u = ref.batch_boot(spec, X, Y, boots, U, d)
+        sum_d, got_s, got_q = ref.batch_boot(spec, X, Y, boots, U, d, sums=True)
+    finally:
+        ref.BATCH_BYTES = old
+    want_p = np.stack([ref.single_perm(spec, X, Y, perms[:, i], V)[0] for i in range(n)], -1)
+    single = [ref.single_boot(spec, X, Y, boots[:, i], U, d) for i in range(n)]
+    want_d = np.stack([s[0] for s in single], -1)
+    want_u = np.stack([s[1] for s in single], -1)
+    assert got_p.shape == want_p.shape and got_d.shape == want_d.shape and got_u.shape == want_u.shape
+    for i in range(n):
+        assert_close(got_p[:, i], want_p[:, i], 1e-12, what='batched perm {}'.format(i))
+        assert_close_per_lv(got_d[..., i], want_d[..., i], 1, 1e-12, keep=live, what='batched distrib {}'.format(i))
+        assert_close_per_lv(got_u[..., i], want_u[..., i], 1, 1e-12, keep=live, what='batched U_boot {}'.format(i))
+    assert np.all(got_u[:, ~live] == 0)
+    assert np.array_equal(sum_d, got_d)
+    assert_close_per_lv(got_s, want_u.sum(-1), 1, 1e-12, keep=live, what='batched sum U')
+    assert_close_per_lv(got_q, (want_u ** 2).sum(-1), 1, 1e-12, keep=live, what='batched sum U^2')
+    with pytest.raises(ValueError):
+        ref.batch_perm(ref.Spec('meancentered', groups, n_cond), X, spec.dummy, perms, V)

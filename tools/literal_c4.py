@@ -14,6 +14,10 @@ it returned against the oracle (oracle/cpu_ref.py) on the SAME index arrays and 
   * singular values, p-value COUNTS recomputed from the returned null, split-half of the original data.
 
     python tools/literal_c4.py [--perms 10000 --boots 10000 --splits 100] > profiles/r04_literal_c4.json
+
+This is a recording tool (wall times and a sampled parity record of the full-length call).  The check is
+tests/test_gpu_timed_geometry.py::test_c4_public_call_sampled_against_oracle, which runs the same comparison at
+n_perm = n_boot = 1008, n_split = 4 under pytest.
 """
 import argparse
 import json
