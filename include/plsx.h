@@ -75,6 +75,12 @@ int plsx_sync(plsx_ctx* ctx);
  *   mean_centering in {0,1,2} (pyls/compute.py:267-317), ignored for behavioral
  * The library keeps its own centred, padded copy; the caller may release d_X /
  * d_Y afterwards.
+ * PLSX_REGRESSION also forms K = X0 X0^T (S x S doubles) here and refuses
+ * (PLSX_ERR_UNSUPPORTED) when K does not fit in free device memory, or when
+ * the T x T work of one wave's slice of LDS, 8 (T^2 + 5 T + 2 k) bytes, exceeds
+ * 158 KB.  S has no other bound: beyond 8 (T^2 + S) <= 158 KB (S ~ 20 000 at
+ * T = 10) the component steps keep their S-long data in device scratch (the
+ * route the "simpls_global" option forces at any S).
  */
 int plsx_set_data(plsx_ctx* ctx, int method, const double* d_X, const double* d_Y,
                   const int32_t* d_cell_of_row, int S, int B, int T,
@@ -364,7 +370,8 @@ int plsx_set_perm_path(plsx_ctx* ctx, int dual);
  *     themselves, instead of the 12-wave block with dedicated construction waves; bit 1: wave kinds in runs of
  *     four waves instead of interleaved wave by wave),
  *     "split_inblock", "no_gram4", "urot_generic", "urot_no_tail4", "simpls_jacobi" (SIMPLS: full Jacobi instead
- *     of the leading-eigenpair solver), "quad_sums" (plsx_boot_begin: 1 = the quadratic-form route whenever it
+ *     of the leading-eigenpair solver), "simpls_global" (SIMPLS: the component-step kernels with their S-long
+ *     buffers in device memory, the route S beyond the on-chip bound takes anyway), "quad_sums" (plsx_boot_begin: 1 = the quadratic-form route whenever it
  *     applies, -1 = never), "percentile_sort" (plsx_percentile_ci: always the full sort instead of the tail
  *     selection);
  *     "expect_resamples" = n: the caller is about to ship n resamples in several calls (chunks of one analysis):

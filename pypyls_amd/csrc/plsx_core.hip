@@ -420,9 +420,22 @@ try {
         return fail(ctx, PLSX_ERR_ARG, "plsx_set_data: mean_centering must be 0, 1 or 2");
     const int J = n_groups * n_cond;
     const int Tp = (method == PLSX_BEHAVIORAL) ? J * T : (method == PLSX_REGRESSION ? ncomp : J);
-    if (method == PLSX_REGRESSION && simpls_step_lds_bytes(S, T, ncomp) > 158 * 1024)
-        return fail(ctx, PLSX_ERR_UNSUPPORTED,
-                    "SIMPLS: S / T too large for the on-chip component step (8 (T^2 + S) bytes must fit 158 KB)");
+    if (method == PLSX_REGRESSION) {
+        // what bounds SIMPLS: the T x T work of a wave's LDS slice (the S-long data leave it for device memory when
+        // they do not fit, simpls_global), and K = Xc Xc^T, S^2 doubles of device memory
+        if (simpls_global_lds_bytes(T, ncomp) > 158 * 1024)
+            return fail(ctx, PLSX_ERR_UNSUPPORTED,
+                        "SIMPLS: T too large for the on-chip component step (8 (T^2 + 5 T + 2 k) bytes must fit 158 KB)");
+        size_t fre = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fre, &tot));
+        const double kbytes = (double)S * S * 8, avail = (double)fre + (double)ctx->Kmat.bytes;
+        if (kbytes > avail) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "SIMPLS: K = X X^T of S = %d subjects (S^2 doubles = %.1f GB) does not fit in the "
+                     "free device memory (%.1f GB)", S, kbytes / 1073741824.0, avail / 1073741824.0);
+            return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+        }
+    }
     // 32-bit buffer offsets (the kernels address one resample's cross-covariance matrix R_r, T'pp x Bpad doubles, through a
     // buffer resource whose byte offsets are 31 bits; offsets beyond read as zero): ONE R_r must stay below 2 GB.  That is
     // the real limit -- it allows 5.1 million features at the headline T' = 50 and 16 million for mean-centred designs,
@@ -559,10 +572,7 @@ try {
     if (int e = ensure(ctx, ctx->d0, (size_t)ctx->L * 8)) return e;
     if (method == PLSX_REGRESSION) {
         // K = Xc Xc^T (S x S): the only B-sized work the dual-space SIMPLS solver needs
-        if (int e = ensure(ctx, ctx->Kmat, (size_t)S * S * 8)) return e;
-        if (int e = run_nt(ctx, ptr<double>(ctx->Xc), 0, ctx->Bpad, S, ptr<double>(ctx->Xc), 0, ctx->Bpad, S,
-                           nullptr, 0, 0, 0, B, 1, ptr<double>(ctx->Kmat), 0, S, nullptr, 0, 0, st, true))
-            return e;
+        if (int e = simpls_form_K(ctx, st)) return e;
     }
     HIPCHK(hipStreamSynchronize(st));
     ctx->has_data = true;

@@ -104,13 +104,18 @@ struct SdArgs {
     int jacobi_eig;             // 1: full one-sided Jacobi for the leading eigenpair (round 3) instead of wave_top_eig
     int weights;                // 1: the dual weights / scores are wanted (bootstraps, decomposition); 0: permutations --
                                 // only pctvar leaves the solver, the Yd c pass and what hangs on it are skipped
+    // global route (GL = true instantiations): no S-long LDS buffer; the scatter to subject space reads these tables
+    int* sfirst;                // [nres][S] first included position p with xs_p = i (INT_MAX: subject not drawn)
+    int* scnt;                  // [nres][S] number of included positions with xs_p = i
 };
 
-// doubles of LDS one wave of k_sd_step needs
+// doubles of LDS one wave of k_sd_step needs (on-chip route: the last S of them are the scatter buffer)
 __host__ __device__ inline size_t sd_step_lds(int S, int T, int k)
 {
     return (size_t)T * (T | 1) + 3 * (size_t)T + 2 * (size_t)k + (size_t)S + 8;
 }
+// ... on the global route: the scatter buffer is gone, T doubles remain (the workspace of wave_top_eig)
+__host__ __device__ inline size_t sd_step_lds_global(int T, int k) { return sd_step_lds(T, T, k); }
 
 // Scatter a position-space vector to subject space through the wave's LDS buffer
 // (w[i] = sum over included positions p with xs_p = i) and write it to dst[0..S).
@@ -130,9 +135,37 @@ __device__ __forceinline__ void sd_scatter(double* buf, const int* xs, int S, in
     wave_sync();
 }
 
+// The same scatter on the global route (no LDS): subject i takes the value of its first position, added as often as
+// the subject was drawn -- the addends of the atomics above, added in the only order identical addends have, so both
+// routes write bit-identical vectors.  `first` / `cnt` were built by k_sd_init<true>; value(p) reads positions owned by
+// other lanes, so what this wave wrote before must be visible (the caller fences).
+template <class F>
+__device__ __forceinline__ void sd_scatter_g(const int* first, const int* cnt, int S, int lane, double* dst, F value)
+{
+    for (int i = lane; i < S; i += 64) {
+        const int n = cnt[i];
+        double s = 0.0;
+        if (n > 0) {
+            const double v = value(first[i]);
+            for (int m = 0; m < n; ++m) s += v;
+        }
+        dst[i] = s;
+    }
+}
+
+// what lanes of this wave stored to global memory is visible to its other lanes
+__device__ __forceinline__ void wave_global_sync()
+{
+    wave_sync();
+    __threadfence();
+    wave_sync();
+}
+
 // Resample setup: sources, masks, Y0 = Jc Y[ys], sum of squares, and the T + 1
 // subject-space vectors scatter(Y0[:, t]), cnt for GEMM 0.
-// dynamic LDS: S doubles per wave.
+// dynamic LDS: S doubles per wave (GL: none -- the scatter tables sfirst / scnt are built here instead, with
+// integer atomics: exact in any order).
+template <bool GL>
 static __global__ __launch_bounds__(256)
 void k_sd_init(SdArgs a)
 {
@@ -140,7 +173,7 @@ void k_sd_init(SdArgs a)
     const int S = a.S, T = a.T, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
     const int r = blockIdx.x * (blockDim.x >> 6) + wave;
     if (r >= a.nres) return;
-    double* buf = sm_sd + (size_t)wave * S;
+    double* buf = GL ? nullptr : sm_sd + (size_t)wave * S;
     int* xs = a.xs + (size_t)r * S;
     int* ys = a.ys + (size_t)r * S;
     const double* Ysrc = a.Yc + (size_t)r * a.y_stride;
@@ -155,6 +188,16 @@ void k_sd_init(SdArgs a)
         cnt += ok;
     }
     const double ninc = wave_sum(cnt);
+    if constexpr (GL) {
+        int* first = a.sfirst + (size_t)r * S;
+        int* nct = a.scnt + (size_t)r * S;
+        for (int i = lane; i < S; i += 64) { first[i] = 0x7fffffff; nct[i] = 0; }
+        wave_global_sync();
+        for (int p = lane; p < S; p += 64) {
+            const int x = xs[p];
+            if (x >= 0) { atomicAdd(&nct[x], 1); atomicMin(&first[x], p); }
+        }
+    }
     double ssy = 0.0;
     for (int t = 0; t < T; ++t) {
         double part = 0.0;
@@ -171,9 +214,18 @@ void k_sd_init(SdArgs a)
     if (lane == 0) { a.scal[(size_t)r * 4] = ninc; a.scal[(size_t)r * 4 + 1] = ssY; }
     // subject-space operands of GEMM 0: vectors 0..T-1 = columns of Y0, vector T = counts
     double* Wt = a.Wt + (size_t)r * (T + 1) * S;
-    for (int t = 0; t <= T; ++t)
-        sd_scatter(buf, xs, S, lane, Wt + (size_t)t * S,
-                   [&](int p) { return t < T ? Y0[(size_t)t * S + p] : 1.0; });
+    if constexpr (GL) {
+        wave_global_sync();                    // Y0 and the tables, as the other lanes wrote them
+        const int* first = a.sfirst + (size_t)r * S;
+        const int* nct = a.scnt + (size_t)r * S;
+        for (int t = 0; t <= T; ++t)
+            sd_scatter_g(first, nct, S, lane, Wt + (size_t)t * S,
+                         [&](int p) { return t < T ? Y0[(size_t)t * S + p] : 1.0; });
+    } else {
+        for (int t = 0; t <= T; ++t)
+            sd_scatter(buf, xs, S, lane, Wt + (size_t)t * S,
+                       [&](int p) { return t < T ? Y0[(size_t)t * S + p] : 1.0; });
+    }
 }
 
 // The kernels below are latency chains of ONE wave (a launch lasts as long as its slowest
@@ -352,7 +404,7 @@ void k_sd_post0(SdArgs a)
 //     c = sqrt((1 + |d| / h) / 2),  s = sign(d g) |g| / (2 h c)
 // -- the same inner rotation (|t| <= pi/4) as t = sign(z) / (|z| + sqrt(1 + z^2)), z = d / g.
 template <int IT>
-__device__ void wave_jacobi_cols(double* A, int m, int n, int ld, int lane, double tol)
+__device__ __forceinline__ void wave_jacobi_cols(double* A, int m, int n, int ld, int lane, double tol)
 {
     constexpr int LANES = 4;
     const int sub = lane % LANES, grp = lane / LANES, ngrp = 64 / LANES;
@@ -646,12 +698,13 @@ __device__ double wave_top_eig(double* A, int n, int ld, int lane, double* ws, d
 }
 
 // Component step c (see the header): closes component c - 1 when c > 0, opens component c
-// unless c == k.  dynamic LDS: sd_step_lds(S, T, k) doubles per wave.
+// unless c == k.  dynamic LDS: sd_step_lds(S, T, k) doubles per wave (GL: sd_step_lds_global(T, k) -- the scatter of
+// the new basis vector goes through sd_scatter_g).
 // TC: class of T the instantiation serves (0: T <= 32, 1: T <= 64, 2: any) -- the register allocation of a kernel is
 // the maximum over its paths, and the Jacobi fall-back for large T (36 rows of two columns per lane) would otherwise
 // set it for every T.  JAC: the leading eigenpair by the full one-sided Jacobi solve (T > 64, T > S, or the
 // `simpls_jacobi` option) instead of wave_top_eig.
-template <int TC, bool JAC, int RC>
+template <int TC, bool JAC, int RC, bool GL = false>
 #if defined(PLSX_JV) && PLSX_JV == 8                    // (probe: the attribute of the build in which <16> was first seen wrong)
 static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RC >= 16 ? 1 : 3, RC >= 16 ? 2 : 4)))
 #else
@@ -664,13 +717,13 @@ void k_sd_step(SdArgs a)
     const int r = blockIdx.x * (blockDim.x >> 6) + wave;
     if (r >= a.nres) return;
     const int ldh = T | 1;
-    double* Hw = sm_sd + (size_t)wave * sd_step_lds(S, T, k);   // [T][ldh] Jacobi work copy of H
+    double* Hw = sm_sd + (size_t)wave * (GL ? sd_step_lds_global(T, k) : sd_step_lds(S, T, k));   // [T][ldh] Jacobi work copy of H
     double* cv = Hw + (size_t)T * ldh;         // [T]
     double* gv = cv + T;                       // [T]
     double* gn = gv + T;                       // [T] new row of G
     double* gc = gn + T;                       // [k]
     double* mj = gc + k;                       // [k]
-    double* buf = mj + k;                      // [S] scatter buffer
+    double* buf = mj + k;                      // [S] scatter buffer (GL: [T], the eigen-solver's workspace only)
     const int* xs = a.xs + (size_t)r * S;
     const double* Y0 = a.Y0 + (size_t)r * S * T;
     const double* Z0 = a.Z0 + (size_t)r * S * T;
@@ -1025,7 +1078,13 @@ void k_sd_step(SdArgs a)
     }
     SD_MARK(11);
     // centred beta (consumed by the next launch) scattered to subject space for GEMM c
-    sd_scatter(buf, xs, S, lane, a.Wt + (size_t)r * S, [&](int p) { return va[p]; });
+    if constexpr (GL) {
+        wave_global_sync();
+        sd_scatter_g(a.sfirst + (size_t)r * S, a.scnt + (size_t)r * S, S, lane, a.Wt + (size_t)r * S,
+                     [&](int p) { return va[p]; });
+    } else {
+        sd_scatter(buf, xs, S, lane, a.Wt + (size_t)r * S, [&](int p) { return va[p]; });
+    }
     SD_MARK(12);
 }
 
@@ -1037,8 +1096,8 @@ void k_sd_step(SdArgs a)
 // (w0c centred over the features, wd_c centred over the positions), so the feature pass can
 // accumulate the aligned weights directly (k_xprod EPI = 2) instead of writing them, forming
 // their cross-Gram with the original and reading them back for the sign and the sums.
-// dynamic LDS: k (+ S with a.Vd) doubles per wave.
-template <int RC, int TC>
+// dynamic LDS: k + S doubles per wave (GL: k -- the scatters go through sd_scatter_g).
+template <int RC, int TC, bool GL = false>
 static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SD_WPE)))
 void k_sd_final(SdArgs a)
 {
@@ -1046,7 +1105,7 @@ void k_sd_final(SdArgs a)
     const int S = a.S, T = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
     const int r = blockIdx.x * (blockDim.x >> 6) + wave;
     if (r >= a.nres) return;
-    double* flip = sm_sd + (size_t)wave * (k + S);      // [k] signs + [S] scatter buffer
+    double* flip = sm_sd + (size_t)wave * (GL ? k : k + S);      // [k] signs + [S] scatter buffer
     const int* xs = a.xs + (size_t)r * S;
     const int* ys = a.ys + (size_t)r * S;
     const double* Ysrc = a.Yc + (size_t)r * a.y_stride;
@@ -1136,7 +1195,25 @@ void k_sd_final(SdArgs a)
             }
     }
 #undef SD_YL
-    if (a.Afrag) {
+    if (GL && a.Afrag) {
+        const int g = r / a.lay.n, rr = r % a.lay.n;
+        double* A = a.Afrag + (size_t)g * a.group_stride;
+        const int* first = a.sfirst + (size_t)r * S;
+        const int* nct = a.scnt + (size_t)r * S;
+        for (int c = 0; c < k; ++c) {
+            const double f = flip[c];
+            const double* wdc = WD + (size_t)c * S;
+            for (int i = lane; i < S; i += 64) {
+                const int n = nct[i];
+                double s = 0.0;
+                if (n > 0) {
+                    const double v = f * wdc[first[i]];
+                    for (int m = 0; m < n; ++m) s += v;
+                }
+                A[afrag_off(rr * a.lay.Tp + c, i, a.lay.MT)] = s;
+            }
+        }
+    } else if (a.Afrag) {
         const int g = r / a.lay.n, rr = r % a.lay.n;
         double* A = a.Afrag + (size_t)g * a.group_stride;
         // through the wave's LDS buffer, one component at a time (a subject drawn more than once receives bit-identical
@@ -1164,7 +1241,11 @@ void k_sd_final(SdArgs a)
         for (int c = 0; c < k; ++c) {
             const double f = flip[c];
             const double* wdc = WD + (size_t)c * S;
-            sd_scatter(buf, xs, S, lane, V + (size_t)c * S, [&](int p) { return f * wdc[p]; });
+            if constexpr (GL)
+                sd_scatter_g(a.sfirst + (size_t)r * S, a.scnt + (size_t)r * S, S, lane, V + (size_t)c * S,
+                             [&](int p) { return f * wdc[p]; });
+            else
+                sd_scatter(buf, xs, S, lane, V + (size_t)c * S, [&](int p) { return f * wdc[p]; });
         }
     }
 }

@@ -6,6 +6,69 @@ using namespace plsxi;
 
 namespace plsxi {
 
+// Route of the component-step kernels.  On-chip: a wave's LDS slice holds its resample's S-long scatter buffer
+// (sd_step_lds, at most 158 KB of a CU's 160).  Global (the `simpls_global` option, or S beyond that bound): the
+// S-long data stay in the resample's scratch and the scatter reads the tables sfirst / scnt there; the LDS slice keeps
+// the T x T work (sd_step_lds_global), which bounds T alone.
+bool simpls_onchip_fits(int S, int T, int k) { return sd_step_lds(S, T, k) * 8 <= 158 * 1024; }
+size_t simpls_global_lds_bytes(int T, int k) { return sd_step_lds_global(T, k) * 8; }
+static bool simpls_global(const plsx_ctx* ctx)
+{
+    return ctx->opt[OPT_SIMPLS_GLOBAL] != 0 || !simpls_onchip_fits(ctx->S, ctx->T, ctx->ncomp);
+}
+
+// doubles of run_simpls_dual's scratch per resample: the state carved out below plus the two GEMM operands
+static size_t sd_scratch_doubles(int S, int T, int k, bool gl)
+{
+    const size_t per = (size_t)S /* xs, ys as ints share one S-double slot */ + 2 * (size_t)S * T + 4 * (size_t)k * S +
+                       2 * (size_t)S + 2 * (size_t)T * T + 2 * (size_t)k * T + 4 + (size_t)T +
+                       (gl ? (size_t)S : 0) /* sfirst, scnt */;
+    return per + 2 * (size_t)(T + 1) * S;
+}
+
+// Resamples per solver batch.  Up to `want` (the on-chip route's fixed 8192, see the batch entries) when they fit half
+// the scratch budget -- every shape of the on-chip route at the default 48 GB, so their batches are what they always
+// were -- otherwise as many whole groups of `unit` resamples as fit it (S = 24 000, T = 20, k = 15: 28 MB of state per
+// resample; 8192 of them would need 230 GB).  `extra`: bytes per resample beyond the solver state (A operand, dense
+// dual weights).
+static int sd_batch(const plsx_ctx* ctx, int want, int unit, double extra)
+{
+    const double per = 8.0 * (double)sd_scratch_doubles(ctx->S, ctx->T, ctx->ncomp, simpls_global(ctx)) + extra;
+    const double budget = 0.5 * ctx->scratch_gb * 1073741824.0;
+    if ((double)want * per <= budget) return want;
+    const long long fit = (long long)(budget / per);
+    return (int)std::max<long long>(unit, fit / unit * unit);
+}
+
+// C = A Bm^T (A: Ma x Kc, Bm: N x Kc, row-major) on the direct path of run_nt, in strips of rows that keep the grid of
+// k_nt_gemm below 65536 blocks in y.  Each output entry is one block's full contraction wherever a strip covers the
+// chip (a strip of a few tiles on a small chip-wide grid falls back to run_nt's split contraction).
+static int nt_strips(plsx_ctx* ctx, const double* A, int lda, int Ma, const double* Bm, int ldb, int N, int Kc,
+                     double* C, int ldc, hipStream_t st)
+{
+    const int rows = std::max(2, 2 * (65535 / ceil_div(N, 64))) * 64;
+    for (int m0 = 0; m0 < Ma; m0 += rows)
+        if (int e = run_nt(ctx, A + (size_t)m0 * lda, 0, lda, std::min(rows, Ma - m0), Bm, 0, ldb, N, nullptr, 0, 0, 0,
+                           Kc, 1, C + (size_t)m0 * ldc, 0, ldc, nullptr, 0, 0, st))
+            return e;
+    return 0;
+}
+
+// K = Xc Xc^T (S x S) of the bound data.  On-chip route: one symmetric product (upper blocks, mirrored from partial
+// tiles: 2 S^2 doubles of partials).  Beyond it those partials would be twice K (37 GB at S = 48 000): every block of
+// the full product stores its own tile instead -- twice the flop of the symmetric form (2 S^2 B: 2.3 Tflop at
+// S = 24 000, B = 2000), once per binding, and no partial buffer.
+int simpls_form_K(plsx_ctx* ctx, hipStream_t st)
+{
+    const int S = ctx->S;
+    if (int e = ensure(ctx, ctx->Kmat, (size_t)S * S * 8)) return e;
+    double* K = ptr<double>(ctx->Kmat);
+    if (simpls_onchip_fits(S, ctx->T, ctx->ncomp))
+        return run_nt(ctx, ptr<double>(ctx->Xc), 0, ctx->Bpad, S, ptr<double>(ctx->Xc), 0, ctx->Bpad, S,
+                      nullptr, 0, 0, 0, ctx->B, 1, K, 0, S, nullptr, 0, 0, st, true);
+    return nt_strips(ctx, ptr<double>(ctx->Xc), ctx->Bpad, S, ptr<double>(ctx->Xc), ctx->Bpad, S, ctx->B, K, S, st);
+}
+
 int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, bool scatter,
                     double* pctvar, double* yload, double* cvec, hipStream_t st,
                     const double* ystack = nullptr, bool align_signs = false, double* Vd = nullptr)
@@ -25,12 +88,15 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     a.oky = ctx->has_oky ? ptr<uint8_t>(ctx->oky) : nullptr;
     a.xsrc = xsrc; a.ysrc = ysrc;
     // per-resample state, carved out of one scratch buffer (doubles)
+    const bool gl = simpls_global(ctx);
     const size_t n = (size_t)nres;
-    const size_t per = (size_t)S /* xs, ys as ints share one S-double slot */ + 2 * (size_t)S * T + 4 * (size_t)k * S +
-                       2 * (size_t)S + 2 * (size_t)T * T + 2 * (size_t)k * T + 4 + (size_t)T;
     const size_t gemm_rows = n * (T + 1);
-    if (int e = ensure(ctx, ctx->swork, (n * per + 2 * gemm_rows * S + 64) * 8)) return e;
+    if (int e = ensure(ctx, ctx->swork, (n * sd_scratch_doubles(S, T, k, gl) + 64 + (gl ? 2 : 0)) * 8)) return e;
     double* w = ptr<double>(ctx->swork);
+    if (gl) {
+        a.sfirst = reinterpret_cast<int*>(w);    w += n * S / 2 + 1;
+        a.scnt = reinterpret_cast<int*>(w);      w += n * S / 2 + 1;
+    }
     a.xs = reinterpret_cast<int*>(w);            w += n * S / 2 + 1;
     a.ys = reinterpret_cast<int*>(w);            w += n * S / 2 + 1;
     a.Y0 = w; w += n * S * T;
@@ -62,20 +128,28 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     }
     const double* K = ptr<double>(ctx->Kmat);
     // one wavefront per resample; as many waves per block as keep >= 2 blocks of k_sd_step on a CU
-    const size_t step_wave = sd_step_lds(S, T, k) * 8;
+    const size_t step_wave = gl ? simpls_global_lds_bytes(T, k) : sd_step_lds(S, T, k) * 8;
     const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (72 * 1024) / step_wave));
     const dim3 grid(ceil_div(nres, wpb)), block(wpb * 64);
-    const bool big = nres > 2048;          // more waves than two per SIMD of the chip: the three-waves-per-SIMD variants (SD_RC)
-    {
-        const size_t lds = (size_t)wpb * S * 8;
-        HIPCHK(set_lds(k_sd_init, lds));
+    // more waves than two per SIMD of the chip: the three-waves-per-SIMD variants (SD_RC).  (The global route keeps the
+    // 16-position tiles: its batches are bounded by the scratch, and its kernels exist in that form only.)
+    const bool big = nres > 2048 && !gl;
+    if (gl) {
         KTimer tm(ctx, KC_SIMPLS, st);
-        hipLaunchKernelGGL(k_sd_init, grid, block, lds, st, a);
+        hipLaunchKernelGGL(k_sd_init<true>, grid, block, 0, st, a);
+        LAUNCHCHK();
+    } else {
+        const size_t lds = (size_t)wpb * S * 8;
+        HIPCHK(set_lds(k_sd_init<false>, lds));
+        KTimer tm(ctx, KC_SIMPLS, st);
+        hipLaunchKernelGGL(k_sd_init<false>, grid, block, lds, st, a);
         LAUNCHCHK();
     }
     // GEMM 0: (T + 1) subject-space vectors per resample against K (symmetric)
-    if (int e = run_nt(ctx, a.Wt, 0, S, (int)gemm_rows, K, 0, S, S, nullptr, 0, 0, 0, S, 1, a.Zt, 0, S,
-                       nullptr, 0, 0, st))
+    if (gl) {
+        if (int e = nt_strips(ctx, a.Wt, S, (int)gemm_rows, K, S, S, S, a.Zt, S, st)) return e;
+    } else if (int e = run_nt(ctx, a.Wt, 0, S, (int)gemm_rows, K, 0, S, S, nullptr, 0, 0, 0, S, 1, a.Zt, 0, S,
+                              nullptr, 0, 0, st))
         return e;
     {
         KTimer tm(ctx, KC_SIMPLS, st);
@@ -90,6 +164,9 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     // the 16-rows-per-lane instantiation of 32 < T <= 64 is back, see k_sd_step)
     const bool jac = a.jacobi_eig || T > 64 || T > S;
     void (*step_kernel)(SdArgs) =
+        gl ? (jac ? (T <= 32 ? k_sd_step<0, true, 16, true> : (T <= 64 ? k_sd_step<1, true, 16, true>
+                                                                       : k_sd_step<2, true, 16, true>))
+                  : (T <= 32 ? k_sd_step<0, false, 16, true> : k_sd_step<1, false, 16, true>)) :
         jac ? (T <= 32 ? (big ? k_sd_step<0, true, 8> : k_sd_step<0, true, 16>)
                        : (T <= 64 ? k_sd_step<1, true, 16> : k_sd_step<2, true, 16>))
             : (T <= 32 ? (big ? k_sd_step<0, false, 8> : k_sd_step<0, false, 16>)
@@ -103,7 +180,9 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
             LAUNCHCHK();
         }
         // GEMM c: K beta for every resample of the batch (the last component needs none)
-        if (c + 1 < k)
+        if (c + 1 < k && gl) {
+            if (int e = nt_strips(ctx, a.Wt, S, nres, K, S, S, S, a.Zt, S, st)) return e;
+        } else if (c + 1 < k)
             if (int e = run_nt(ctx, a.Wt, 0, S, nres, K, 0, S, S, nullptr, 0, 0, 0, S, 1, a.Zt, 0, S,
                                nullptr, 0, 0, st))
                 return e;
@@ -111,8 +190,10 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     if (scatter) {          // (permutations: pctvar is all that leaves the solver -- no y-loadings, no weights)
         a.Qs = align_signs ? ptr<double>(ctx->Qs) : nullptr;
         KTimer tm(ctx, KC_SIMPLS, st);
-        const size_t lds_f = (size_t)wpb * (k + S) * 8;       // (per wave: the signs and one subject-space scatter buffer)
+        // (per wave: the signs and, on the on-chip route, one subject-space scatter buffer)
+        const size_t lds_f = (size_t)wpb * (gl ? k : k + S) * 8;
         void (*final_kernel)(SdArgs) =
+            gl ? (T <= 32 ? k_sd_final<16, 0, true> : (T <= 64 ? k_sd_final<16, 1, true> : k_sd_final<16, 2, true>)) :
             T <= 32 ? (big ? k_sd_final<8, 0> : k_sd_final<16, 0>)
                     : (T <= 64 ? (big ? k_sd_final<8, 1> : k_sd_final<16, 1>) : k_sd_final<16, 2>);
         HIPCHK(set_lds(final_kernel, lds_f));
@@ -142,7 +223,6 @@ bool simpls_single_pass(const plsx_ctx* ctx)
     return (size_t)2 * ctx->ncomp * PLSX_ACC_PITCH * 8 <= 72 * 1024 && ctx->Qs.p && !ctx->opt[OPT_TWO_PASS_BOOT];
 }
 
-size_t simpls_step_lds_bytes(int S, int T, int k) { return sd_step_lds(S, T, k) * 8; }
 
 }  // namespace plsxi
 
@@ -192,7 +272,8 @@ try {
     HIPCHK(hipSetDevice(ctx->device));
     // solver batches are as large as the call: a launch of the component step lasts as long as one
     // wave's latency chain whatever the batch (one wave per resample, up to 8 per SIMD)
-    const int nb = 8192;
+    // (8192, or fewer where the solver state of 8192 resamples would exceed half the scratch budget: sd_batch)
+    const int nb = sd_batch(ctx, 8192, 1, 0.0);
     if (int e = ensure(ctx, ctx->spct, (size_t)nb * ctx->T * ctx->ncomp * 8)) return e;
     if (int e = ensure(ctx, ctx->sc, (size_t)nb * ctx->T * ctx->ncomp * 8)) return e;
     for (int off = 0; off < n; off += nb) {
@@ -247,6 +328,10 @@ try {
         if (!simpls_single_pass(ctx)) return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_boot_batch: open series on a route that left it");
         nbs = (int)std::max<long long>(ctx->npg, std::min<long long>(nbs, (1LL << 30) / ((long long)k * ctx->S * 8)));
     }
+    // ... and within half the scratch budget with the solver state and the batch's A operand (or dense V): unchanged
+    // wherever that already held
+    nbs = sd_batch(ctx, nbs, ctx->npg,
+                   ctx->quad_active ? 8.0 * k * ctx->S : 8.0 * (double)ctx->group_stride / std::max(ctx->npg, 1));
     if (int e = ensure(ctx, ctx->spct, (size_t)std::min(n, nbs) * k * 8)) return e;
     if (int e = ensure(ctx, ctx->sc, (size_t)std::min(n, nbs) * T * k * 8)) return e;
     for (int off = 0; off < n; off += nbs) {

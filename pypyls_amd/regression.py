@@ -299,9 +299,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         off = 0
         eng.boot_begin(sum(hi - lo for lo, hi in bchunks))     # (plsx_boot_begin: the feature pass may move to boot_finish)
         bars.append(Bar('Running bootstraps', sum(hi - lo for lo, hi in bchunks), show, eng.device))
+        # 3-D Y: a (n, S, T) Y stack per chunk, at most 256 of them and at most 256 MB (S = 24 000, T = 20: 69 rows)
+        ylim = max(1, min(256, (256 << 20) // (S * T * 8)))
         for lo, hi in bchunks:
-            for a, b in bstream.chunks(lo, hi, first=2048 if third is None else 256, grow=4 if third is None else 1,
-                                       limit=None if third is None else 256):
+            for a, b in bstream.chunks(lo, hi, first=2048 if third is None else ylim, grow=4 if third is None else 1,
+                                       limit=None if third is None else ylim):
                 ystack = None
                 if third is not None:
                     # Y aggregated over the resampled third axis, NOT centred
