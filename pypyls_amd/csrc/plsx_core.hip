@@ -435,6 +435,27 @@ try {
                      "free device memory (%.1f GB)", S, kbytes / 1073741824.0, avail / 1073741824.0);
             return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
         }
+    } else {
+        // PLS-C: the dual-space routes (permutations; the single-pass bootstrap of the unscaled modes) keep K = X X^T,
+        // S x round_up(S, 8) doubles, and the symmetric form of K (nt_sym_fits) 2 x 64^2 doubles of partials per upper
+        // block pair.  Only a binding that would take those routes (ctx->dual below: the fixed feature matrix exists
+        // and no_dual_perm is off) is refused; shapes below 1 GB of K skip the query.
+        const bool dual = (method == PLSX_MEANCENTERED || (flags & PLSX_FLAG_COVARIANCE) || !ctx->opt[OPT_NO_FIXED_X]) &&
+                          !ctx->opt[OPT_NO_DUAL_PERM];
+        const double mt = (double)ceil_div(S, 64);
+        const double kbytes = (double)S * round_up(S, 8) * 8, pbytes = nt_sym_fits(S) ? mt * mt * 2 * 4096 * 8 : 0.0;
+        if (dual && kbytes + pbytes > 1073741824.0) {
+            size_t fre = 0, tot = 0;
+            HIPCHK(hipMemGetInfo(&fre, &tot));
+            const double avail = (double)fre + (double)ctx->Kd.bytes + (double)ctx->part.bytes;
+            if (kbytes + pbytes > avail) {
+                char msg[256];
+                snprintf(msg, sizeof msg, "PLS-C: K = X X^T of S = %d subjects (%.1f GB with its partial tiles) does not "
+                         "fit in the free device memory (%.1f GB)", S, (kbytes + pbytes) / 1073741824.0,
+                         avail / 1073741824.0);
+                return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+            }
+        }
     }
     // 32-bit buffer offsets (the kernels address one resample's cross-covariance matrix R_r, T'pp x Bpad doubles, through a
     // buffer resource whose byte offsets are 31 bits; offsets beyond read as zero): ONE R_r must stay below 2 GB.  That is
@@ -738,9 +759,7 @@ int perm_dual(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ystack, 
     if (!ctx->has_Kd) {
         if (int e = ensure(ctx, ctx->Kd, (size_t)S * Sd * 8, true)) return e;
         const double* Xf = ctx->has_Xn ? ptr<double>(ctx->Xn) : ptr<double>(ctx->Xc);
-        if (int e = run_nt(ctx, Xf, 0, ctx->Bpad, S, Xf, 0, ctx->Bpad, S, nullptr, 0, 0, 0, ctx->B, 1,
-                           ptr<double>(ctx->Kd), 0, Sd, nullptr, 0, 0, st, true))
-            return e;
+        if (int e = form_gram_K(ctx, Xf, ctx->Bpad, S, ctx->B, ptr<double>(ctx->Kd), Sd, st)) return e;
         ctx->has_Kd = 1;
     }
     // resamples per pass: 2 GB operands, grid.y / grid.z limits of the tiled GEMM
@@ -861,10 +880,7 @@ int boot_single_pass(plsx_ctx* ctx, const int32_t* d_boot_idx, int n, double* d_
     const size_t gstride = (size_t)ctx->nks * MT * 64;
     if (!ctx->has_Kd) {
         if (int e = ensure(ctx, ctx->Kd, (size_t)S * Sd * 8, true)) return e;
-        const double* Xf = ptr<double>(ctx->Xc);
-        if (int e = run_nt(ctx, Xf, 0, ctx->Bpad, S, Xf, 0, ctx->Bpad, S, nullptr, 0, 0, 0, ctx->B, 1,
-                           ptr<double>(ctx->Kd), 0, Sd, nullptr, 0, 0, st, true))
-            return e;
+        if (int e = form_gram_K(ctx, ptr<double>(ctx->Xc), ctx->Bpad, S, ctx->B, ptr<double>(ctx->Kd), Sd, st)) return e;
         ctx->has_Kd = 1;
     }
     if (ctx->npg_w != npg_w) {
@@ -1021,7 +1037,7 @@ try {
     const size_t cbytes = (size_t)L * S * S * 8;
     // (C_l itself and the partial tiles of the batched S x S products, 2 x 64 x 64 doubles per tile and LV)
     const size_t pbytes = (size_t)L * round_up(S, 64) * round_up(S, 64) * 16;
-    if (cbytes + pbytes > (size_t)(0.25 * ctx->scratch_gb * 1073741824.0)) return PLSX_OK;
+    if (cbytes + pbytes > (size_t)(0.25 * ctx->scratch_gb * 1073741824.0) || !nt_sym_fits(S)) return PLSX_OK;
     if (int e = ensure(ctx, ctx->Cq, cbytes)) return e;
     if (int e = ensure(ctx, ctx->Vsumq, (size_t)L * S * 8)) return e;
     HIPCHK(hipMemsetAsync(ctx->Cq.p, 0, cbytes, st));

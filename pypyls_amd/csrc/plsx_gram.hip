@@ -43,18 +43,51 @@ int run_nt(plsx_ctx* ctx, const double* A, long long strideA, int lda, int Ma,
     LAUNCHCHK();
     if (direct) return 0;
     {
-        dim3 g(ceil_div(Ma * N1, 256), batch);
+        dim3 g((unsigned)(((long long)Ma * N1 + 255) / 256), batch);
         hipLaunchKernelGGL(k_reduce_part, g, dim3(256), 0, st, a.part, nchunk, batch, a.mtiles,
                            a.ntiles, 0, C1, strideC1, ldc1, Ma, N1, a.sym ? 6 : 0, accumulate ? 1 : 0);
         LAUNCHCHK();
     }
     if (B2) {
-        dim3 g(ceil_div(Ma * N2, 256), batch);
+        dim3 g((unsigned)(((long long)Ma * N2 + 255) / 256), batch);
         hipLaunchKernelGGL(k_reduce_part, g, dim3(256), 0, st, a.part, nchunk, batch, a.mtiles,
                            a.ntiles, 1, C2, strideC2, ldc2, Ma, N2, 0);
         LAUNCHCHK();
     }
     return 0;
+}
+
+// The symmetric form of K = X X^T (S x S) launches ceil(mtiles / 2) * mtiles blocks of k_nt_gemm<2> in y, and HIP's
+// grid stops at 65 535 there: S <= 23 168.  (Its partial tiles, 2 S^2 doubles, and k_reduce_part's element count
+// S^2 then stay far inside their own limits.)
+bool nt_sym_fits(int S)
+{
+    const long long mt = ceil_div(S, 64);
+    return (mt + 1) / 2 * mt <= 65535;
+}
+
+// C = A Bm^T (A: Ma x Kc, Bm: N x Kc, row-major) on the direct path of run_nt, in strips of rows that keep the grid of
+// k_nt_gemm below 65536 blocks in y.  Each output entry is one block's full contraction wherever a strip covers the
+// chip (a strip of a few tiles on a small chip-wide grid falls back to run_nt's split contraction).
+int nt_strips(plsx_ctx* ctx, const double* A, int lda, int Ma, const double* Bm, int ldb, int N, int Kc,
+              double* C, int ldc, hipStream_t st)
+{
+    const int rows = std::max(2, 2 * (65535 / ceil_div(N, 64))) * 64;
+    for (int m0 = 0; m0 < Ma; m0 += rows)
+        if (int e = run_nt(ctx, A + (size_t)m0 * lda, 0, lda, std::min(rows, Ma - m0), Bm, 0, ldb, N, nullptr, 0, 0, 0,
+                           Kc, 1, C + (size_t)m0 * ldc, 0, ldc, nullptr, 0, 0, st))
+            return e;
+    return 0;
+}
+
+// K = X X^T (S x S, row pitch ldk) of the dual-space routes: the symmetric product (upper blocks, mirrored from
+// partial tiles) while its grid fits -- every cohort that ran before keeps its launch and its bits --, beyond that
+// the full product in row strips (twice the flop, no partial buffer).
+int form_gram_K(plsx_ctx* ctx, const double* X, int ldx, int S, int Kc, double* K, int ldk, hipStream_t st)
+{
+    if (nt_sym_fits(S))
+        return run_nt(ctx, X, 0, ldx, S, X, 0, ldx, S, nullptr, 0, 0, 0, Kc, 1, K, 0, ldk, nullptr, 0, 0, st, true);
+    return nt_strips(ctx, X, ldx, S, X, ldx, S, Kc, K, ldk, st);
 }
 
 // G_r = W_r A_r^T (T' x T') and, with ScT, P_r = A_r Sc (T' x L) of the dual-space routes.  Small T' (mean-centred

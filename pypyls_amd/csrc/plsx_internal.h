@@ -315,6 +315,10 @@ int run_nt(plsx_ctx* ctx, const double* A, long long strideA, int lda, int Ma,
            const double* B2, long long strideB2, int ldb2, int N2, int K, int batch,
            double* C1, long long strideC1, int ldc1, double* C2, long long strideC2, int ldc2,
            hipStream_t st, bool sym = false, bool accumulate = false);
+bool nt_sym_fits(int S);
+int nt_strips(plsx_ctx* ctx, const double* A, int lda, int Ma, const double* Bm, int ldb, int N, int Kc,
+              double* C, int ldc, hipStream_t st);
+int form_gram_K(plsx_ctx* ctx, const double* X, int ldx, int S, int Kc, double* K, int ldk, hipStream_t st);
 int run_dual_gp(plsx_ctx* ctx, int m, int Sd, const double* ScT, int L, hipStream_t st);
 int run_gram_ex(plsx_ctx* ctx, int nres, int mode, const double* E, int Erows, double* Pout,
                 hipStream_t st, const double* Rsrc = nullptr);

@@ -641,9 +641,12 @@ static __global__ void k_reduce_part(const double* __restrict__ part, int nchunk
                               int accumulate = 0)
 {
     const int b = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= M * N) return;
-    int m = idx / N, n = idx % N;
+    // (element counts past 2^31: S x S products; the 32-bit division where the count allows it)
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, count = (long long)M * N;
+    if (idx >= count) return;
+    int m, n;
+    if (count < (1LL << 31)) { m = (int)idx / N; n = (int)idx % N; }
+    else { m = (int)(idx / N); n = (int)(idx % N); }
     const int mo = m, no = n;
     if (sym && (m >> sym) > (n >> sym)) { const int t = m; m = n; n = t; }   // sym = log2 of the block size whose upper triangle was computed
     const int tile = (m / 64) * ntiles + (n / 64);

@@ -40,20 +40,6 @@ static int sd_batch(const plsx_ctx* ctx, int want, int unit, double extra)
     return (int)std::max<long long>(unit, fit / unit * unit);
 }
 
-// C = A Bm^T (A: Ma x Kc, Bm: N x Kc, row-major) on the direct path of run_nt, in strips of rows that keep the grid of
-// k_nt_gemm below 65536 blocks in y.  Each output entry is one block's full contraction wherever a strip covers the
-// chip (a strip of a few tiles on a small chip-wide grid falls back to run_nt's split contraction).
-static int nt_strips(plsx_ctx* ctx, const double* A, int lda, int Ma, const double* Bm, int ldb, int N, int Kc,
-                     double* C, int ldc, hipStream_t st)
-{
-    const int rows = std::max(2, 2 * (65535 / ceil_div(N, 64))) * 64;
-    for (int m0 = 0; m0 < Ma; m0 += rows)
-        if (int e = run_nt(ctx, A + (size_t)m0 * lda, 0, lda, std::min(rows, Ma - m0), Bm, 0, ldb, N, nullptr, 0, 0, 0,
-                           Kc, 1, C + (size_t)m0 * ldc, 0, ldc, nullptr, 0, 0, st))
-            return e;
-    return 0;
-}
-
 // K = Xc Xc^T (S x S) of the bound data.  On-chip route: one symmetric product (upper blocks, mirrored from partial
 // tiles: 2 S^2 doubles of partials).  Beyond it those partials would be twice K (37 GB at S = 48 000): every block of
 // the full product stores its own tile instead -- twice the flop of the symmetric form (2 S^2 B: 2.3 Tflop at
