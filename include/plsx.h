@@ -274,6 +274,26 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           row are dropped per resample (get_mask,
  *                           regression.py:48-53).  NULL = all rows usable.  The
  *                           bound X / Y must hold zeros in the masked rows.
+ *   plsx_simpls_crossval_batch  cross-validated prediction per component count
+ *                           (the reference has none for PLSRegression,
+ *                           regression.py:237-238; per split this follows
+ *                           BehavioralPLS._single_crossval, behavioral.py:126-170,
+ *                           with simpls in place of the SVD).  For each of m
+ *                           splits: SIMPLS with k components on the training rows,
+ *                           centred by the training means; the test rows predicted
+ *                           by the first c = 1 .. k components plus the intercept
+ *                           ([1, x] @ simpls(X_tr, Y_tr, c)['beta']); each
+ *                           prediction scored per behaviour.
+ *                           d_masks (m, S) uint8, 1 = training row; rows masked by
+ *                           plsx_simpls_set_row_masks are on neither side.
+ *                           d_r, d_r2 (m, k, T) out: Pearson r (efficient_corr) and
+ *                           R^2 (sklearn r2_score, raw values) of the c-component
+ *                           model; d_sse (m, k + 1, T) out: squared error summed
+ *                           over the test rows, row 0 = intercept only (yhat = the
+ *                           training mean).  Valid once plsx_set_data bound
+ *                           regression data; PLSX_ERR_STATE otherwise.  Every split
+ *                           needs >= 2 usable test rows and k <= n_train - 1 (the
+ *                           caller checks).  Bit-reproducible run to run.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -282,6 +302,8 @@ int plsx_simpls_perm_batch(plsx_ctx* ctx, const int32_t* d_perm_idx, int n, doub
 int plsx_simpls_boot_batch(plsx_ctx* ctx, const int32_t* d_boot_idx, const double* d_ystack, int n,
                            double* d_usum, double* d_usq, double* d_yload, void* stream);
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream);
+int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2,
+                               double* d_sse, void* stream);
 
 /* Bootstrap ratios -- compute.boot_rel (pyls/compute.py:212-237), elementwise
  * on (B, L) arrays: se = sqrt(|usq - usum^2/n| / (n-1)), bsr = orig / se.

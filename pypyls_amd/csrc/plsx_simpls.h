@@ -36,6 +36,7 @@
 // 2 c sequential dot products of the Gram-Schmidt pass -- left the kernels 10 x off their
 // memory traffic):
 //   k_sd_init -> [GEMM 0] -> k_sd_post0 -> { k_sd_step(c) -> [GEMM c] } x k -> k_sd_final
+//   cross-validation appends:  k_sd_final (dual weights dense, Vd) -> [Z = Vd . K] -> k_sd_cv_score
 // k_sd_step(c) finishes component c - 1 (what follows its K beta product: basis pair,
 // deflation coefficients, H -= g g^T) and opens component c (leading eigenpair of H, scores,
 // dual weights, new basis vector scattered for GEMM c); the last component needs no
@@ -97,7 +98,7 @@ struct SdArgs {
     double* yload;              // [nres][T][k]  Y[ys]^T (X[xs] W), signs not yet aligned
     double* cvec;               // [nres][T][k]  right singular vectors c_c (sign rule when B <= T)
     double* Afrag;              // dual weights scattered into k_xprod's A operand (or nullptr)
-    double* Vd;                 // or: scattered dense, [nres][k][S] (zeroed by the caller; quadratic-form route), or nullptr
+    double* Vd;                 // or: scattered dense, [nres][k][S] (every entry written; quadratic-form route, cross-validation), or nullptr
     const double* Qs;           // [S][k] Xc . W0c^T (centred original weights): bootstrap sign alignment in dual space, or nullptr
     size_t group_stride;
     GroupLayout lay;
@@ -107,6 +108,13 @@ struct SdArgs {
     // global route (GL = true instantiations): no S-long LDS buffer; the scatter to subject space reads these tables
     int* sfirst;                // [nres][S] first included position p with xs_p = i (INT_MAX: subject not drawn)
     int* scnt;                  // [nres][S] number of included positions with xs_p = i
+    // cross-validation (plsx_simpls_crossval_batch): a split is a resample with identity sources whose test positions
+    // are excluded
+    const uint8_t* pmask;       // [nres][S] 1 = position included (training row), or nullptr: every position
+    double* cvZ;                // [nres][k][S] Vd . K: un-centred scores of every row (k_sd_cv_score centres them in place)
+    double* cvr;                // [nres][k][T] Pearson r of the nested predictions on the test rows
+    double* cvr2;               // [nres][k][T] R^2
+    double* cvsse;              // [nres][k + 1][T] squared error summed over the test rows (row 0: intercept only)
 };
 
 // doubles of LDS one wave of k_sd_step needs (on-chip route: the last S of them are the scatter buffer)
@@ -182,7 +190,7 @@ void k_sd_init(SdArgs a)
     for (int p = lane; p < S; p += 64) {
         const int x = a.xsrc ? a.xsrc[(size_t)r * S + p] : p;
         const int y = a.ysrc ? a.ysrc[(size_t)r * S + p] : p;
-        const int ok = (!a.okx || a.okx[x]) && (!a.oky || a.oky[y]);
+        const int ok = (!a.okx || a.okx[x]) && (!a.oky || a.oky[y]) && (!a.pmask || a.pmask[(size_t)r * S + p]);
         xs[p] = ok ? x : -1;
         ys[p] = y;
         cnt += ok;
@@ -1246,6 +1254,153 @@ void k_sd_final(SdArgs a)
                              [&](int p) { return f * wdc[p]; });
             else
                 sd_scatter(buf, xs, S, lane, V + (size_t)c * S, [&](int p) { return f * wdc[p]; });
+        }
+    }
+}
+
+// Cross-validation of one train / test split (plsx_simpls_crossval_batch), after the solver ran on the training rows
+// (a.pmask: test positions excluded like masked rows) and Z = Vd . K was formed.  With wd_j the dual weights (centred
+// over the training rows, zero elsewhere) and K of the bound, globally centred data,
+//     (x_i - xbar_tr)^T w_j = Z_j[i] - mean_{p in tr} Z_j[p] = t_j[i]     for EVERY row i, training or test,
+//     q_j = (Y_tr - ybar_tr)^T t_j = sum_p Y0[.][p] t_j[p]                (Y0 is zero off the training rows),
+//     yhat_c[i] = ybar_tr + sum_{j <= c} t_j[i] q_j^T,   c = 1 .. k, nested
+// -- what [1, x_i] @ simpls(X_tr, Y_tr, c)['beta'] predicts.  Per behaviour t and component count c the test rows give
+// Pearson r (compute.efficient_corr), R^2 (sklearn r2_score, raw values) and the summed squared error; row 0 of the
+// latter is the intercept-only model.  The residual y - yhat is accumulated directly (sum y^2 - 2 sum y yhat + sum yhat^2
+// cancels when the model fits), the means are taken first (the mean of yhat_c over the test rows follows from the means
+// of the scores), reductions are wave_sum4 in fixed order.  One wavefront per split, lanes over positions; no LDS on
+// either route: the running prediction lives in the split's `va` (idle once the solver is through), every position
+// of every S-long vector is only ever touched by the lane that owns it.  Four components at a time.
+template <int RC>
+static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SD_WPE)))
+void k_sd_cv_score(SdArgs a)
+{
+    const int S = a.S, T = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
+    const int r = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (r >= a.nres) return;
+    const int* xs = a.xs + (size_t)r * S;
+    const uint8_t* pm = a.pmask + (size_t)r * S;
+    const double* Y0 = a.Y0 + (size_t)r * S * T;
+    const double* ym = a.ymean + (size_t)r * T;
+    const double* Yc = a.Yc;                               // identity sources: the observed row of position p is row p
+    double* Z = a.cvZ + (size_t)r * k * S;
+    double* yh = a.va + (size_t)r * S;
+    double* out_r = a.cvr + (size_t)r * k * T;
+    double* out_r2 = a.cvr2 + (size_t)r * k * T;
+    double* out_sse = a.cvsse + (size_t)r * (k + 1) * T;
+    const double ninc = a.scal[(size_t)r * 4];
+    // usable test position: outside the training mask and not a masked (all-NaN) row
+    auto is_test = [&](int p) { return !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[p]); };
+    // ---- scores of every position, centred by their training mean (in place)
+    for (int j0 = 0; j0 < k; j0 += 4) {
+        double* z0 = Z + (size_t)min(j0, k - 1) * S;
+        double* z1 = Z + (size_t)min(j0 + 1, k - 1) * S;
+        double* z2 = Z + (size_t)min(j0 + 2, k - 1) * S;
+        double* z3 = Z + (size_t)min(j0 + 3, k - 1) * S;
+        double m[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int p0 = 0; p0 < S; p0 += SD_TILE) {
+            SD_TILE_PC(pc, p0);
+            SD_OWN(i) {
+                const bool tr = SD_IN(p0, i) && xs[pc[i]] >= 0;
+                const double a0 = z0[pc[i]], a1 = z1[pc[i]], a2 = z2[pc[i]], a3 = z3[pc[i]];
+                m[0] += tr ? a0 : 0.0; m[1] += tr ? a1 : 0.0; m[2] += tr ? a2 : 0.0; m[3] += tr ? a3 : 0.0;
+            }
+        }
+        wave_sum4(m[0], m[1], m[2], m[3]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) m[u] /= ninc;
+        for (int p0 = 0; p0 < S; p0 += SD_TILE) {
+            SD_TILE_PC(pc, p0);
+            SD_OWN(i) {
+                const double a0 = z0[pc[i]], a1 = z1[pc[i]], a2 = z2[pc[i]], a3 = z3[pc[i]];
+                if (SD_IN(p0, i)) {
+                    z0[pc[i]] = a0 - m[0];
+                    if (j0 + 1 < k) z1[pc[i]] = a1 - m[1];
+                    if (j0 + 2 < k) z2[pc[i]] = a2 - m[2];
+                    if (j0 + 3 < k) z3[pc[i]] = a3 - m[3];
+                }
+            }
+        }
+    }
+    double cnt = 0.0;
+    for (int p = lane; p < S; p += 64) cnt += is_test(p) ? 1.0 : 0.0;
+    const double nte = wave_sum(cnt);
+    for (int t = 0; t < T; ++t) {
+        const double ymt = ym[t];
+        // observed test values: mean, then the sums of squares about it and about the training mean
+        double sy = 0.0;
+        for (int p = lane; p < S; p += 64) sy += is_test(p) ? Yc[(size_t)p * T + t] : 0.0;
+        const double ybar = wave_sum(sy) / nte;
+        double syy = 0.0, se0 = 0.0;
+        for (int p = lane; p < S; p += 64) {
+            const bool te = is_test(p);
+            const double y = Yc[(size_t)p * T + t];
+            const double d = y - ybar, e = y - ymt;
+            syy += te ? d * d : 0.0;
+            se0 += te ? e * e : 0.0;
+        }
+        syy = wave_sum(syy);
+        se0 = wave_sum(se0);
+        if (lane == 0) out_sse[t] = se0;
+        const double* y0t = Y0 + (size_t)t * S;
+        double mhat = ymt;                                 // mean of the running prediction over the test rows
+        for (int c0 = 0; c0 < k; c0 += 4) {
+            const double* z0 = Z + (size_t)min(c0, k - 1) * S;
+            const double* z1 = Z + (size_t)min(c0 + 1, k - 1) * S;
+            const double* z2 = Z + (size_t)min(c0 + 2, k - 1) * S;
+            const double* z3 = Z + (size_t)min(c0 + 3, k - 1) * S;
+            // y-loadings q_c[t] of the four components and the test means of their scores
+            double q[4] = {0.0, 0.0, 0.0, 0.0}, mt[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int p0 = 0; p0 < S; p0 += SD_TILE) {
+                SD_TILE_PC(pc, p0);
+                SD_OWN(i) {
+                    const bool in = SD_IN(p0, i), te = in && is_test(pc[i]);
+                    const double yv = y0t[pc[i]], y = in ? yv : 0.0;
+                    const double a0 = z0[pc[i]], a1 = z1[pc[i]], a2 = z2[pc[i]], a3 = z3[pc[i]];
+                    q[0] += y * a0; q[1] += y * a1; q[2] += y * a2; q[3] += y * a3;
+                    mt[0] += te ? a0 : 0.0; mt[1] += te ? a1 : 0.0; mt[2] += te ? a2 : 0.0; mt[3] += te ? a3 : 0.0;
+                }
+            }
+            wave_sum4(q[0], q[1], q[2], q[3]);
+            wave_sum4(mt[0], mt[1], mt[2], mt[3]);
+            double mh[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (c0 + u >= k) q[u] = 0.0;               // (a clamped row: the prediction stays as it is)
+                mhat += (mt[u] / nte) * q[u];
+                mh[u] = mhat;
+            }
+            double se[4] = {0.0, 0.0, 0.0, 0.0}, shh[4] = {0.0, 0.0, 0.0, 0.0}, shy[4] = {0.0, 0.0, 0.0, 0.0};
+            const bool more = c0 + 4 < k;
+            for (int p0 = 0; p0 < S; p0 += SD_TILE) {
+                SD_TILE_PC(pc, p0);
+                SD_OWN(i) {
+                    const bool te = SD_IN(p0, i) && is_test(pc[i]);
+                    const double y = Yc[(size_t)pc[i] * T + t];
+                    const double zz[4] = {z0[pc[i]], z1[pc[i]], z2[pc[i]], z3[pc[i]]};
+                    double pred = c0 == 0 ? ymt : yh[pc[i]];
+                    const double dy = y - ybar;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        pred += zz[u] * q[u];
+                        const double e = y - pred, d = pred - mh[u];
+                        se[u] += te ? e * e : 0.0;
+                        shh[u] += te ? d * d : 0.0;
+                        shy[u] += te ? d * dy : 0.0;
+                    }
+                    if (more && te) yh[pc[i]] = pred;
+                }
+            }
+            wave_sum4(se[0], se[1], se[2], se[3]);
+            wave_sum4(shh[0], shh[1], shh[2], shh[3]);
+            wave_sum4(shy[0], shy[1], shy[2], shy[3]);
+            if (lane == 0)
+                for (int u = 0; u < 4 && c0 + u < k; ++u) {
+                    const double rr = shy[u] / sqrt(shh[u] * syy);
+                    out_r[(size_t)(c0 + u) * T + t] = rr > 1.0 ? 1.0 : (rr < -1.0 ? -1.0 : rr);      // (NaN stays NaN)
+                    out_r2[(size_t)(c0 + u) * T + t] = 1.0 - se[u] / syy;
+                    out_sse[(size_t)(c0 + u + 1) * T + t] = se[u];
+                }
         }
     }
 }

@@ -57,9 +57,12 @@ int simpls_form_K(plsx_ctx* ctx, hipStream_t st)
 
 int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, bool scatter,
                     double* pctvar, double* yload, double* cvec, hipStream_t st,
-                    const double* ystack = nullptr, bool align_signs = false, double* Vd = nullptr)
+                    const double* ystack = nullptr, bool align_signs = false, double* Vd = nullptr,
+                    const uint8_t* pmask = nullptr, SdArgs* args_out = nullptr)
 {
-    // Vd (with scatter): the aligned dual weights go out dense, [nres][k][S] (zeroed here), not into the A operand
+    // Vd (with scatter): the dual weights go out dense, [nres][k][S] (k_sd_final writes every entry), not into the A operand
+    // pmask: [nres][S] positions a resample keeps (cross-validation: its training rows); args_out: the carved-out
+    // state of the batch, for a kernel that runs after the chain (valid until the next call)
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
     const int groups = ceil_div(nres, ctx->npg);
     if (int e = ensure_scratch(ctx, std::min(groups, ctx->Gcap))) return e;
@@ -73,6 +76,7 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     a.okx = ctx->has_okx ? ptr<uint8_t>(ctx->okx) : nullptr;
     a.oky = ctx->has_oky ? ptr<uint8_t>(ctx->oky) : nullptr;
     a.xsrc = xsrc; a.ysrc = ysrc;
+    a.pmask = pmask;
     // per-resample state, carved out of one scratch buffer (doubles)
     const bool gl = simpls_global(ctx);
     const size_t n = (size_t)nres;
@@ -186,6 +190,7 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
         hipLaunchKernelGGL(final_kernel, grid, block, lds_f, st, a);
         LAUNCHCHK();
     }
+    if (args_out) *args_out = a;
 #ifdef PLSX_SD_PROBE
     {
         unsigned long long h[16][32];
@@ -269,6 +274,54 @@ try {
                                     d_out + (size_t)off * ctx->ncomp, ptr<double>(ctx->spct),
                                     ptr<double>(ctx->sc), st))
             return e;
+    }
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, double* d_sse,
+                               void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_crossval_batch: data not bound for regression");
+    if (!d_masks || !d_r || !d_r2 || !d_sse || m < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_crossval_batch: bad arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    const bool gl = simpls_global(ctx);
+    // solver batches as for the permutations; a split also holds its dense dual weights Vd and Z = Vd . K
+    const int nb = std::min(m, sd_batch(ctx, 8192, 1, 2.0 * k * S * 8.0));
+    if (int e = ensure(ctx, ctx->spct, (size_t)nb * (T + 1) * k * 8)) return e;     // pctvar [nb][k], y-loadings [nb][T][k]
+    if (int e = ensure(ctx, ctx->sc, (size_t)nb * T * k * 8)) return e;
+    if (int e = ensure(ctx, ctx->Vdq, (size_t)nb * k * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->Zcv, (size_t)nb * k * S * 8)) return e;
+    const double* K = ptr<double>(ctx->Kmat);
+    double* Vd = ptr<double>(ctx->Vdq);
+    double* Z = ptr<double>(ctx->Zcv);
+    for (int off = 0; off < m; off += nb) {
+        const int ms = std::min(nb, m - off);
+        SdArgs a;
+        // the fit on the training rows: identity sources, the test positions excluded, weights wanted; the signs stay
+        // as the solver produced them (t_j q_j^T does not depend on them)
+        if (int e = run_simpls_dual(ctx, nullptr, nullptr, ms, true, ptr<double>(ctx->spct),
+                                    ptr<double>(ctx->spct) + (size_t)nb * k, ptr<double>(ctx->sc), st, nullptr, false, Vd,
+                                    d_masks + (size_t)off * S, &a))
+            return e;
+        // ONE product with K: the scores of all k nested models at every row, training and test
+        if (gl) {
+            if (int e = nt_strips(ctx, Vd, S, ms * k, K, S, S, S, Z, S, st)) return e;
+        } else if (int e = run_nt(ctx, Vd, 0, S, ms * k, K, 0, S, S, nullptr, 0, 0, 0, S, 1, Z, 0, S, nullptr, 0, 0, st))
+            return e;
+        a.cvZ = Z;
+        a.cvr = d_r + (size_t)off * k * T;
+        a.cvr2 = d_r2 + (size_t)off * k * T;
+        a.cvsse = d_sse + (size_t)off * (k + 1) * T;
+        KTimer tm(ctx, KC_CVSCORE, st);
+        // (more waves than two per SIMD of the chip: the three-waves-per-SIMD variant, as in the solver)
+        void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8> : k_sd_cv_score<16>;
+        hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+        LAUNCHCHK();
     }
     return PLSX_OK;
 } PLSX_CATCH(ctx)

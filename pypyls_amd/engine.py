@@ -88,6 +88,7 @@ def _load():
         'plsx_simpls_perm_batch': ([vp, vp, i32, vp, vp], i32),
         'plsx_simpls_boot_batch': ([vp, vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_set_row_masks': ([vp, vp, vp, vp], i32),
+        'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_bootsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_permsamp_stream': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp, ctypes.POINTER(i32)], i32),
@@ -123,7 +124,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -733,6 +734,19 @@ class Engine(object):
         """idx_dev (n, S) int32, out_dev (n, k): pctvar of the permuted Y."""
         self._check(self.lib.plsx_simpls_perm_batch(self.ctx, idx_dev.data_ptr(), idx_dev.shape[0],
                                                     out_dev.data_ptr(), self._stream()))
+
+    def simpls_crossval_into(self, masks_dev, r_dev, r2_dev, sse_dev):
+        """masks_dev (m, S) uint8, 1 = training row; r_dev / r2_dev (m, k, T): Pearson r and R^2 of the test rows under
+        the first c = 1 .. k components; sse_dev (m, k + 1, T): squared error summed over the test rows, row 0 the
+        intercept-only model (plsx_simpls_crossval_batch)."""
+        m = masks_dev.shape[0]
+        if tuple(masks_dev.shape) != (m, self.S) or masks_dev.dtype != _torch().uint8 or not masks_dev.is_contiguous():
+            raise ValueError('split masks must be a contiguous (m, {}) uint8 tensor'.format(self.S))
+        for t, rows in ((r_dev, self.k), (r2_dev, self.k), (sse_dev, self.k + 1)):
+            if tuple(t.shape) != (m, rows, self.T) or not t.is_contiguous():
+                raise ValueError('cross-validation outputs must be contiguous (m, k, T), (m, k, T) and (m, k + 1, T)')
+        self._check(self.lib.plsx_simpls_crossval_batch(self.ctx, masks_dev.data_ptr(), m, r_dev.data_ptr(),
+                                                        r2_dev.data_ptr(), sse_dev.data_ptr(), self._stream()))
 
     def simpls_boot_into(self, idx_dev, usum, usq, yl_dev, ystack=None):
         """idx_dev (n, S) int32; usum / usq (B, k) accumulated in place; yl_dev (n, T, k);

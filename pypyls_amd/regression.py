@@ -21,6 +21,11 @@ Differences from the reference at this commit, on purpose:
     rejects; here the equivalent object array is built explicitly.  The
     Rows (or, for 3-D Y, subjects) that are only partly NaN raise
     NotImplementedError (they poison the reference's fit as well).
+  * ``test_split > 0`` cross-validates the prediction per component count (the reference forces ``test_split=0``:
+    "not implemented for PLSRegression", regression.py:237-238).  Per split (behavioral.py:126-170 with simpls in
+    place of the SVD): SIMPLS with ``n_components`` on the training rows, the test rows predicted by the first
+    c = 1 .. n_components components plus the intercept, each prediction scored per behaviour
+    (plsx_simpls_crossval_batch; csrc/plsx_simpls.h, k_sd_cv_score).
 """
 import numpy as np
 
@@ -60,9 +65,32 @@ def _row_ok(A):
     return ~allnan
 
 
+def _usable_rows(X, Y_agg):
+    """get_mask (regression.py:48-53) without a pass over the whole of X: only rows whose first entry is NaN can be
+    NaN throughout."""
+    ok = ~np.isnan(Y_agg).all(axis=1)
+    cand = np.flatnonzero(np.isnan(X[:, 0])) if X.shape[1] else np.zeros(0, dtype=int)
+    if len(cand):
+        ok[cand[np.isnan(X[cand]).all(axis=1)]] = False
+    return ok
+
+
+def _check_cvsplits(masks, usable, k, B):
+    """masks (S, n) bool, True = training row; usable (S,) bool: every split needs two usable test rows (Pearson r)
+    and enough usable training rows for k components."""
+    n_tr = (masks & usable[:, None]).sum(axis=0)
+    n_te = (~masks & usable[:, None]).sum(axis=0)
+    if len(n_te) and n_te.min() < 2:
+        raise ValueError('Every cross-validation split needs at least 2 usable test rows; split {} has {}'
+                         .format(int(n_te.argmin()), int(n_te.min())))
+    if len(n_tr) and k > min(int(n_tr.min()) - 1, B):
+        raise ValueError('Provided `n_components` cannot be greater than {} when cross-validating: the smallest '
+                         'training set has {} usable rows'.format(max(min(int(n_tr.min()) - 1, B), 0), int(n_tr.min())))
+
+
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
-                   n_proc=None, **kwargs):
+                   n_proc=None, test_split=0, test_size=0.25, cvsamples=None, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -70,7 +98,14 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     Missing data: rows of X or Y that are NaN THROUGHOUT are masked like the reference's ``get_mask`` masks them
     (pyls/types/regression.py:48-53).  A row that is only PARTLY NaN raises NotImplementedError here; in the
     reference it is not masked and turns the weights of the whole fit into NaN (regression.py:313, 324-325) --
-    a behavioural difference of this drop-in, on purpose: impute or drop such rows first."""
+    a behavioural difference of this drop-in, on purpose: impute or drop such rows first.
+
+    Cross-validation: ``test_split`` train / test splits (0, the default, or ``test_size=0``: none), drawn with
+    ``gen_splits([S], 1, test_split, test_size=test_size)`` after everything else the call draws, or given as
+    ``cvsamples`` (S, test_split) bool, True = training row.  ``cvres`` then holds ``pearson_r`` / ``r_squared``
+    (T, test_split) of the full model, ``pearson_r_ncomp`` / ``r_squared_ncomp`` (T, n_components, test_split) of the
+    nested models, ``mse`` (n_components + 1, test_split) -- row 0 the intercept-only model -- and ``cvsamples``.
+    Masked rows belong to neither side."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -134,12 +169,39 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     else:
         Y_agg = Y
         bootsamples_out = None
-    kwargs.update(n_split=0, test_split=0)         # regression.py:238
+    kwargs.update(n_split=0)                       # regression.py:238 (test_split is NOT forced to 0 here)
     kwargs.setdefault('permindices', True)
+    test_split = int(test_split or 0)
     inputs = PLSInputs(X=X, Y=Y, groups=[S], n_cond=1, n_components=n_components, n_perm=n_perm,
                        n_boot=n_boot, rotate=rotate, ci=ci, aggfunc=aggfunc,
                        permsamples=permsamples, bootsamples=bootsamples_out if Y.ndim == 3 else bootsamples,
-                       seed=seed, verbose=verbose, n_proc=n_proc, **kwargs)
+                       seed=seed, verbose=verbose, n_proc=n_proc, test_split=test_split, test_size=test_size,
+                       **kwargs)
+    # ---- cross-validation: validated on the host before any engine is created or looked up
+    n_cv = test_split if (test_size or 0) > 0 else 0
+    cvmasks = None
+    if n_cv > 0:
+        if cvsamples is not None:
+            cvmasks = np.asarray(cvsamples)
+            if cvmasks.ndim != 2 or cvmasks.shape != (S, n_cv):
+                raise ValueError('Provided `cvsamples` must have shape (S, test_split) = ({}, {}); got {}'
+                                 .format(S, n_cv, cvmasks.shape))
+            cvmasks = cvmasks.astype(bool)
+            _check_cvsplits(cvmasks, _usable_rows(X, Y_agg), n_components, X.shape[1])
+        else:
+            # gen_splits keeps ceil or floor of S (1 - test_size) training rows.  Whichever side the masked (all-NaN)
+            # rows fall on, every split it can draw must pass: the worst case is checked, so nothing is left to
+            # check once the masks exist
+            n_bad = int((~_usable_rows(X, Y_agg)).sum())
+            lo_tr = int(np.floor(S * (1 - test_size))) - n_bad
+            lo_te = S - int(np.ceil(S * (1 - test_size))) - n_bad
+            if lo_te < 2:
+                raise ValueError('Every cross-validation split needs at least 2 usable test rows; test_size = {} can '
+                                 'leave {} of {} ({} rows are NaN throughout)'.format(test_size, max(lo_te, 0), S, n_bad))
+            if n_components > min(lo_tr - 1, X.shape[1]):
+                raise ValueError('Provided `n_components` cannot be greater than {} when cross-validating: the '
+                                 'smallest training set has {} usable rows'
+                                 .format(max(min(lo_tr - 1, X.shape[1]), 0), max(lo_tr, 0)))
     rs = resampling.check_random_state(seed)
     k = n_components
     B, T = X.shape[1], Y_agg.shape[1]
@@ -173,6 +235,14 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             if bs.ndim != 2 or bs.shape[0] != S:
                 raise ValueError('resampling array must have shape (S, n) with S = {}; got {}'.format(S, bs.shape))
             bstream = resampling.IndexStream.of_array(check_index_array(bs, S))
+    cv = None
+    if n_cv > 0:
+        cv = dict(n=n_cv, masks=cvmasks)
+        if cvmasks is None:
+            # one more job at the END of the list: what a seeded call drew before, it draws still
+            def cv_draw(r):
+                cv['masks'] = resampling.gen_splits([S], 1, n_cv, seed=r, test_size=test_size)
+            jobs.append(cv_draw)
     from .engine import default_engine, touch_idle_release
     from . import team as _team
     touch_idle_release()                               # (a pending idle release is pushed back before the engine is looked up)
@@ -192,7 +262,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
         if team is not None:
             res = team.run(lambda rank, world, e: _run_device(
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
-                k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team)))
+                k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -201,7 +271,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 try:
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
-                                      kwargs.get('_emulate'))
+                                      kwargs.get('_emulate'), cv=cv)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -215,7 +285,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
-                bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None):
+                bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None):
     import time
     import torch
     S = len(X)
@@ -329,6 +399,22 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     for st in (pstream, bstream):
         if st is not None and lead:
             st.warn()
+    # cross-validation: this rank's contiguous shard of the splits (the masks exist once the draws are through), in
+    # calls of at most one solver batch
+    d_cv = None
+    if cv is not None:
+        cvmasks = cv['masks']
+        lo, hi = parallel.shard_bounds(cv['n'], rank, world)
+        d_cv = [eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k + 1, T))]
+        bars.append(Bar('Running cross-validation', hi - lo, show, eng.device))
+        for a in range(lo, hi, 8192):
+            b = min(hi, a + 8192)
+            dm = torch.from_numpy(np.ascontiguousarray(cvmasks[:, a:b].T, dtype=np.uint8)).to(eng.device)
+            eng.simpls_crossval_into(dm, *(t[a - lo:b - lo] for t in d_cv))
+            for done in bars:
+                done.poll()
+            bars[-1].queued(b - a)
+        tick('crossval')
     for bar in bars:
         bar.watch()
     try:
@@ -338,8 +424,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             bar.close()
     slices = [t for t in (d_perm, d_yl) if t is not None]
     totals = [n for t, n in ((d_perm, n_perm_tot), (d_yl, n_boot_tot)) if t is not None]
+    cyclic = [len(slices) - 1] if d_yl is not None else []
+    if d_cv is not None:                                # the cross-validation rows ride in the same buffer: ONE collective
+        slices, totals = slices + d_cv, totals + [cv['n']] * 3
     full, summed = parallel.collect_device(slices, totals, [usum, usq] if usum is not None else [], emulate=emulate,
-                                           cyclic=[len(slices) - 1] if d_yl is not None else [], team=team)
+                                           cyclic=cyclic, team=team)
     if not lead:
         return None                                     # rank 0 holds everything the ranks computed: it finishes
     full = [t.detach().cpu().numpy() for t in full]
@@ -353,6 +442,14 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         i += 1
     if bstream is not None:
         distrib = np.ascontiguousarray(np.moveaxis(full[i], 0, -1))  # (T, k, n_boot)
+        i += 1
+    if d_cv is not None:
+        cv_r, cv_r2, cv_sse = (np.ascontiguousarray(full[i + j].transpose(2, 1, 0)) for j in range(3))   # (T, k [+ 1], n)
+        n_test = (~cv['masks'] & mask[:, None]).sum(axis=0)
+        res['cvres'].update(dict(
+            pearson_r=np.ascontiguousarray(cv_r[:, k - 1]), r_squared=np.ascontiguousarray(cv_r2[:, k - 1]),
+            pearson_r_ncomp=cv_r, r_squared_ncomp=cv_r2, mse=cv_sse.sum(axis=0) / n_test[None, :],
+            cvsamples=np.asarray(cv['masks'], dtype=bool)))
     if permsamp is not None:
         res['permres']['pvals'] = hostmath.perm_sig(pctvar, d_perm)
         res['permres']['permsamples'] = permsamp

@@ -130,7 +130,9 @@ class PLSSplitHalfResults(KeyedRecord):
 
 
 class PLSCrossValidationResults(KeyedRecord):
-    allowed = ('pearson_r', 'r_squared')
+    # pearson_r_ncomp / r_squared_ncomp (T, k, n), mse (k + 1, n), cvsamples (S, n): pls_regression's cross-validation
+    # per component count (no counterpart in the reference, which cross-validates behavioral PLS only)
+    allowed = ('pearson_r', 'r_squared', 'pearson_r_ncomp', 'r_squared_ncomp', 'mse', 'cvsamples')
 
 
 class PLSResults(KeyedRecord):
