@@ -294,6 +294,34 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           regression data; PLSX_ERR_STATE otherwise.  Every split
  *                           needs >= 2 usable test rows and k <= n_train - 1 (the
  *                           caller checks).  Bit-reproducible run to run.
+ *   plsx_simpls_coef_begin / plsx_simpls_coef_finish
+ *                           a coefficient series that rides along the bootstrap
+ *                           batches: the model of the first c components,
+ *                           Y ~ intercept + X . coefs, coefs = W[:, :c] Q[:, :c]^T
+ *                           (B, T) with Q the simpls y_loadings of the resample
+ *                           (beta of regression.py:149-151 without its intercept
+ *                           row).  While a series is open every solver batch of
+ *                           plsx_simpls_boot_batch also writes
+ *                           A_b = sum_{j <= c} wd_j q_j^T dense in subject space
+ *                           (kernel k_sd_coef; coefs_b = Xc^T A_b) and accumulates
+ *                           sum_b A_b (T, S) and C_t = sum_b a_bt a_bt^T (T, S, S);
+ *                           _finish passes the features ONCE:
+ *                           d_bsum (B, T) += sum_b coefs_b = Xc^T sum_b A_b,
+ *                           d_bsq (B, T) += sum_b coefs_b^2, [f][t] = x_f^T C_t x_f.
+ *                           coefs depend on neither the signs nor the order of the
+ *                           components: no alignment.  Everything else a batch
+ *                           computes keeps its bits, on either route of the weights
+ *                           (option quad_sums); row masks and d_ystack apply as ever.
+ *                           Limits: _begin returns PLSX_ERR_ARG for c outside
+ *                           1 .. k, PLSX_ERR_STATE without bound regression data or
+ *                           before plsx_simpls_set_original, PLSX_ERR_UNSUPPORTED
+ *                           (context still usable) when 8 T S^2 bytes plus the
+ *                           partial tiles of the S x S products (16 T S^2) do not
+ *                           fit in free device memory next to K or in the scratch
+ *                           budget (plsx_set_scratch), or S > 23168.  _finish
+ *                           without an open series: PLSX_ERR_STATE.  plsx_set_data
+ *                           and plsx_simpls_set_original end an open series.
+ *                           Fixed-order reductions: bit-reproducible run to run.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -304,6 +332,8 @@ int plsx_simpls_boot_batch(plsx_ctx* ctx, const int32_t* d_boot_idx, const doubl
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream);
 int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2,
                                double* d_sse, void* stream);
+int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream);
+int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* stream);
 
 /* Bootstrap ratios -- compute.boot_rel (pyls/compute.py:212-237), elementwise
  * on (B, L) arrays: se = sqrt(|usq - usum^2/n| / (n-1)), bsr = orig / se.

@@ -8,7 +8,7 @@ namespace plsxi {
 
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
-                                                 "k_sd_cv_score"};
+                                                 "k_sd_cv_score", "k_sd_coef"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -362,7 +362,7 @@ try {
                    &ctx->Xn, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
-                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Zcv, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
+                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->Zcv, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     delete ctx;
@@ -479,6 +479,7 @@ try {
         return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
     }
     ctx->has_data = ctx->has_orig = false;
+    ctx->coef_active = 0; ctx->coef_n = 0;             // (an open coefficient series ends with the binding it belonged to)
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;
     HIPCHK(hipMemsetAsync(ctx->status.p, 0, 4 * sizeof(int), st));
@@ -836,9 +837,13 @@ int perm_batch_impl(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ys
 namespace plsxi {
 
 // Per batch: V dense [m][L * S] (ctx->Vdq) -> transposed [L * S][mpad] -> C_l += Vt_l Vt_l^T, Vsum += row sums.
-int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st)
+// qs: another accumulator set with its own L and source (the coefficient series); the transposed copy is shared scratch.
+int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st, const QuadSet* qs)
 {
-    const int S = ctx->S, L = ctx->method == PLSX_REGRESSION ? ctx->ncomp : ctx->L;
+    const int S = ctx->S, L = qs ? qs->L : (ctx->method == PLSX_REGRESSION ? ctx->ncomp : ctx->L);
+    const double* Vd = qs ? qs->Vd : ptr<double>(ctx->Vdq);
+    double* C = ptr<double>(qs ? *qs->C : ctx->Cq);
+    double* Vsum = ptr<double>(qs ? *qs->Vsum : ctx->Vsumq);
     const int mpad = round_up(m, 2);
     const long long rows = (long long)L * S;
     if (int e = ensure(ctx, ctx->Vtq, (size_t)rows * mpad * 8)) return e;
@@ -846,16 +851,17 @@ int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st)
         KTimer tm(ctx, KC_BUILD, st);
         if (mpad != m) HIPCHK(hipMemsetAsync(ctx->Vtq.p, 0, (size_t)rows * mpad * 8, st));
         hipLaunchKernelGGL(k_transpose, dim3(ceil_div((int)rows, 32), ceil_div(m, 32)), dim3(32, 8), 0, st,
-                           ptr<double>(ctx->Vdq), m, (int)rows, (int)rows, ptr<double>(ctx->Vtq), mpad);
+                           Vd, m, (int)rows, (int)rows, ptr<double>(ctx->Vtq), mpad);
         LAUNCHCHK();
         hipLaunchKernelGGL(k_rowsum_acc, dim3(ceil_div((int)rows, 4)), dim3(256), 0, st, ptr<double>(ctx->Vtq), mpad, m,
-                           (int)rows, ptr<double>(ctx->Vsumq));
+                           (int)rows, Vsum);
         LAUNCHCHK();
     }
     const double* Vt = ptr<double>(ctx->Vtq);
     if (int e = run_nt(ctx, Vt, (long long)S * mpad, mpad, S, Vt, (long long)S * mpad, mpad, S, nullptr, 0, 0, 0, m, L,
-                       ptr<double>(ctx->Cq), (long long)S * S, S, nullptr, 0, 0, st, true, true))
+                       C, (long long)S * S, S, nullptr, 0, 0, st, true, true))
         return e;
+    if (qs) return 0;
     ctx->quad_n += m;
     return 0;
 }

@@ -116,6 +116,12 @@ struct plsx_ctx {
     Buf Cq, Vsumq, Vdq, Vtq, Afrag_q, qpart;
     int quad_active = 0;                                // 1: a series is open on the quadratic-form route
     long long quad_n = 0, series_total = 0;             // bootstraps accumulated / announced in the open series
+    // coefficient series of the SIMPLS bootstrap (plsx_simpls_coef_begin / _finish): a second accumulator set of the
+    // same route -- C_t = sum_b a_bt a_bt^T (T x S x S), sum_b A_b (T x S) -- fed by k_sd_coef: the batch's A dense
+    // [n][T][S] and its y-loadings q [n][c][T].  The weights' own series (above) never sees it.
+    Buf Cc, Asumc, Adc, Qc;
+    int coef_active = 0, coef_c = 0;                    // 1: a coefficient series is open; its component count
+    long long coef_n = 0;                               // bootstraps accumulated in it
     bool has_okx = false, has_oky = false;
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
     int ncomp = 0;
@@ -215,7 +221,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 }
 
 // kernel classes of plsx_kernel_timing()
-enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COUNT };
+enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -288,7 +294,10 @@ int pick_parts(long long units, int slots, int lo, int hi);
 SmallArgs small_args(plsx_ctx* ctx, int mode);
 bool plsc_single_pass(const plsx_ctx* ctx);
 int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st);
-int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st);
+// One accumulator set of the quadratic-form route: C (L x S x S), Vsum (L x S), fed from Vd dense [m][L][S].  nullptr
+// where a QuadSet is optional: the weights' own set (ctx->Cq, ctx->Vsumq, ctx->Vdq; L = LVs / components).
+struct QuadSet { Buf* C; Buf* Vsum; const double* Vd; int L; };
+int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st, const QuadSet* qs = nullptr);
 bool quad_applicable(const plsx_ctx* ctx);
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);
@@ -300,7 +309,7 @@ int ensure_compact_maps(plsx_ctx* ctx);
 int run_xprod(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, hipStream_t st,
               bool prebuilt = false, const double* ystack = nullptr, long long ystride = -1, bool sparse_rows = false);
 int launch_xprod_split(plsx_ctx* ctx, int groups, SplitEpi se, hipStream_t st);
-int quad_finish(plsx_ctx* ctx, double* d_usum, double* d_usq, hipStream_t st);
+int quad_finish(plsx_ctx* ctx, double* d_usum, double* d_usq, hipStream_t st, const QuadSet* qs = nullptr);
 // Row blocks per LV of the closing pass of a bootstrap series (quad_finish): blocks of 8 tiles = 128 rows.  A block
 // multiplies its rows of the symmetric C_l against the columns from its own first row on, so the work issued beyond
 // the upper triangle is the lower halves of the diagonal blocks: 1.34 x the needed flop with 3 blocks of 21 tiles at

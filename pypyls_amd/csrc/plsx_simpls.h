@@ -37,6 +37,7 @@
 // memory traffic):
 //   k_sd_init -> [GEMM 0] -> k_sd_post0 -> { k_sd_step(c) -> [GEMM c] } x k -> k_sd_final
 //   cross-validation appends:  k_sd_final (dual weights dense, Vd) -> [Z = Vd . K] -> k_sd_cv_score
+//   an open coefficient series appends to a bootstrap batch:  k_sd_coef (A_b = sum_{j <= c} wd_j q_j^T, dense)
 // k_sd_step(c) finishes component c - 1 (what follows its K beta product: basis pair,
 // deflation coefficients, H -= g g^T) and opens component c (leading eigenpair of H, scores,
 // dual weights, new basis vector scattered for GEMM c); the last component needs no
@@ -115,6 +116,10 @@ struct SdArgs {
     double* cvr;                // [nres][k][T] Pearson r of the nested predictions on the test rows
     double* cvr2;               // [nres][k][T] R^2
     double* cvsse;              // [nres][k + 1][T] squared error summed over the test rows (row 0: intercept only)
+    // coefficient series (plsx_simpls_coef_begin): k_sd_coef runs on resamples cf_r0 .. cf_r0 + cf_n - 1 of the batch
+    double* cfA;                // [cf_n][T][S] A_b = sum_{j < cf_c} wd_j q_j^T scattered to subject space (every entry written), or nullptr
+    double* cfq;                // [cf_n][cf_c][T] q_j = Y0^T t_j (simpls y_loadings of the resample)
+    int cf_c, cf_r0, cf_n;
 };
 
 // doubles of LDS one wave of k_sd_step needs (on-chip route: the last S of them are the scatter buffer)
@@ -1402,6 +1407,96 @@ void k_sd_cv_score(SdArgs a)
                     out_sse[(size_t)(c0 + u + 1) * T + t] = se[u];
                 }
         }
+    }
+}
+
+// Coefficients of the c-component model of one bootstrap (plsx_simpls_coef_begin), after the solver chain of its batch.
+// With wd_j the dual weights (position space, centred over the included positions) and t_j the unit-norm scores,
+//     q_j = (Y_r - ybar_r)^T t_j = sum_p Y0[.][p] XW[j][p]      simpls y_loadings (Y0 sums to zero over the included
+//                                                               positions and is zero elsewhere: the mean XW carries drops out)
+//     beta_c = W[:, :c] Q[:, :c]^T = Xc^T A,   A[t] = scatter(sum_{j < c} q_j[t] wd_j)   (T rows in subject space)
+// -- a product of t_j and wd_j, so the signs of the components cancel and no alignment is needed.  The T x c products
+// q go through the matrix pipe where they fit two tiles each way (wave_mfma_nt, as k_sd_final's y-loadings), otherwise
+// four at a time through wave_sum4; both in fixed order.  The scatter is sd_scatter / sd_scatter_g: a subject drawn
+// more than once receives bit-identical addends.  One wavefront per resample; dynamic LDS per wave: cf_c doubles (the
+// q_j[t] of the row being written) + S (the scatter buffer; GL: none).
+template <int RC, bool GL>
+static __global__ __launch_bounds__(256)
+void k_sd_coef(SdArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm_sd[];
+    const int S = a.S, T = a.T, k = a.k, cc = a.cf_c, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
+    const int rl = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (rl >= a.cf_n) return;
+    const int r = a.cf_r0 + rl;
+    double* qt = sm_sd + (size_t)wave * (GL ? cc : cc + S);      // [cc] q_j[t] of the open row + [S] scatter buffer
+    const int* xs = a.xs + (size_t)r * S;
+    const double* Y0 = a.Y0 + (size_t)r * S * T;
+    const double* XW = a.XW + (size_t)r * k * S;
+    const double* WD = a.WD + (size_t)r * k * S;
+    double* q = a.cfq + (size_t)rl * cc * T;
+    double* A = a.cfA + (size_t)rl * T * S;
+    auto rows = [&](const double* M, int nrows) {
+        return [=](int t, int p, double (&v)[4]) {
+            const double* src = M + (size_t)min(t, nrows - 1) * S;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double x = src[min(p + j, S - 1)];
+                v[j] = (t < nrows && p + j < S) ? x : 0.0;
+            }
+        };
+    };
+    const int tt = (T + 15) >> 4, kt = (cc + 15) >> 4;
+#define SD_CQ(MTL, NTL) {                                                                                          \
+        d4 acc[MTL][NTL];                                                                                          \
+        _Pragma("unroll") for (int i_ = 0; i_ < MTL; ++i_)                                                         \
+            _Pragma("unroll") for (int j_ = 0; j_ < NTL; ++j_) acc[i_][j_] = (d4){0.0, 0.0, 0.0, 0.0};            \
+        wave_mfma_nt<MTL, NTL>(acc, S, lane, rows(Y0, T), rows(XW, cc));                                           \
+        _Pragma("unroll") for (int mt = 0; mt < MTL; ++mt)                                                         \
+            _Pragma("unroll") for (int nt = 0; nt < NTL; ++nt)                                                     \
+                _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                    \
+                    const int t = mt * 16 + (lane >> 4) + 4 * i, c = nt * 16 + (lane & 15);                        \
+                    if (t < T && c < cc) q[(size_t)c * T + t] = acc[mt][nt][i];                                    \
+                }                                                                                                  \
+    }
+    if (tt == 1 && kt == 1) SD_CQ(1, 1)
+    else if (tt == 2 && kt == 1) SD_CQ(2, 1)
+    else if (tt <= 2 && kt <= 2) SD_CQ(2, 2)
+    else {
+        for (int t = 0; t < T; ++t) {
+            const double* y0t = Y0 + (size_t)t * S;
+            for (int c0 = 0; c0 < cc; c0 += 4) {
+                const double *w0 = XW + (size_t)min(c0, cc - 1) * S, *w1 = XW + (size_t)min(c0 + 1, cc - 1) * S,
+                             *w2 = XW + (size_t)min(c0 + 2, cc - 1) * S, *w3 = XW + (size_t)min(c0 + 3, cc - 1) * S;
+                double s4[4] = {0.0, 0.0, 0.0, 0.0};
+                for (int p0 = 0; p0 < S; p0 += SD_TILE) {
+                    SD_TILE_PC(pc, p0);
+                    SD_OWN(i) {
+                        const double yv = y0t[pc[i]], y = SD_IN(p0, i) ? yv : 0.0;
+                        s4[0] += y * w0[pc[i]]; s4[1] += y * w1[pc[i]]; s4[2] += y * w2[pc[i]]; s4[3] += y * w3[pc[i]];
+                    }
+                }
+                wave_sum4(s4[0], s4[1], s4[2], s4[3]);
+                if (lane == 0)
+                    for (int u = 0; u < 4 && c0 + u < cc; ++u) q[(size_t)(c0 + u) * T + t] = s4[u];
+            }
+        }
+    }
+#undef SD_CQ
+    wave_global_sync();                        // q, as the other lanes wrote it
+    for (int t = 0; t < T; ++t) {
+        for (int j = lane; j < cc; j += 64) qt[j] = q[(size_t)j * T + t];
+        wave_sync();
+        auto value = [&](int p) {
+            double s = 0.0;
+            for (int j = 0; j < cc; ++j) s += qt[j] * WD[(size_t)j * S + p];
+            return s;
+        };
+        if constexpr (GL)
+            sd_scatter_g(a.sfirst + (size_t)r * S, a.scnt + (size_t)r * S, S, lane, A + (size_t)t * S, value);
+        else
+            sd_scatter(qt + cc, xs, S, lane, A + (size_t)t * S, value);
+        wave_sync();
     }
 }
 

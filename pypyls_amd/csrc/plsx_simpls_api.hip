@@ -215,6 +215,42 @@ bool simpls_single_pass(const plsx_ctx* ctx)
 }
 
 
+// The coefficient series' share of a solver batch (plsx_simpls_coef_begin): k_sd_coef writes A_b of `ms` bootstraps
+// dense, in chunks of at most 1 GB, and each chunk goes through quad_accumulate on the series' own accumulator set.
+// `a`: the state run_simpls_dual just left (args_out).  The solver batches themselves are what they are without a
+// series, so everything else a call computes keeps its bits.
+static QuadSet coef_set(plsx_ctx* ctx) { return QuadSet{&ctx->Cc, &ctx->Asumc, ptr<double>(ctx->Adc), ctx->T}; }
+
+static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
+{
+    const int S = ctx->S, T = ctx->T, cc = ctx->coef_c;
+    const bool gl = simpls_global(ctx);
+    const int chunk = (int)std::max<long long>(1, std::min<long long>(ms, (1LL << 30) / ((long long)T * S * 8)));
+    if (int e = ensure(ctx, ctx->Adc, (size_t)chunk * T * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->Qc, (size_t)chunk * cc * T * 8)) return e;
+    const size_t per_wave = ((size_t)cc + (gl ? 0 : (size_t)S)) * 8;
+    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / per_wave));
+    const size_t lds = (size_t)wpb * per_wave;
+    a.cfA = ptr<double>(ctx->Adc); a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
+    for (int r0 = 0; r0 < ms; r0 += chunk) {
+        const int mc = std::min(chunk, ms - r0);
+        a.cf_r0 = r0; a.cf_n = mc;
+        {
+            KTimer tm(ctx, KC_COEF, st);
+            // (more waves than two per SIMD of the chip: the short position tiles, as in the solver)
+            void (*coef_kernel)(SdArgs) = gl ? k_sd_coef<16, true> : (ms > 2048 ? k_sd_coef<8, false> : k_sd_coef<16, false>);
+            HIPCHK(set_lds(coef_kernel, lds));
+            hipLaunchKernelGGL(coef_kernel, dim3(ceil_div(mc, wpb)), dim3(wpb * 64), lds, st, a);
+            LAUNCHCHK();
+        }
+        const QuadSet qs = coef_set(ctx);
+        if (int e = quad_accumulate(ctx, mc, st, &qs)) return e;
+    }
+    ctx->coef_n += ms;
+    return 0;
+}
+
+
 }  // namespace plsxi
 
 extern "C" {
@@ -251,6 +287,7 @@ try {
                        nullptr, 0, 0, 0, ctx->B, 1, ptr<double>(ctx->Qs), 0, ctx->ncomp, nullptr, 0, 0, st))
         return e;
     ctx->has_orig = true; ctx->quad_active = 0;
+    ctx->coef_active = 0; ctx->coef_n = 0;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -326,6 +363,63 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_begin: data not bound for regression");
+    if (!ctx->has_orig) return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_begin: plsx_simpls_set_original has not been called");
+    ctx->coef_active = 0; ctx->coef_n = 0;
+    if (c < 1 || c > ctx->ncomp) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "plsx_simpls_coef_begin: c = %d outside 1 .. n_components = %d", c, ctx->ncomp);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int S = ctx->S, T = ctx->T;
+    // C_t (T x S x S) and the partial tiles of its batched S x S products (2 x 64 x 64 doubles per tile and behaviour)
+    // must fit in free device memory (what an earlier series left allocated counts as free) and in the scratch budget
+    const double cbytes = 8.0 * T * (double)S * S;
+    const double pbytes = 16.0 * T * (double)round_up(S, 64) * round_up(S, 64);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const double have = (double)free_b + (double)ctx->Cc.bytes + (double)ctx->part.bytes;
+    const double budget = ctx->scratch_gb * 1073741824.0;
+    if (cbytes + pbytes > have || cbytes + pbytes > budget || !nt_sym_fits(S)) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "plsx_simpls_coef_begin: the coefficient series needs T S^2 doubles (%.2f GB for T = %d, "
+                 "S = %d) plus %.2f GB of partial tiles; %.2f GB of device memory are free next to K and the scratch "
+                 "budget is %.2f GB (S <= 23168)", cbytes / 1073741824.0, T, S, pbytes / 1073741824.0,
+                 have / 1073741824.0, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    if (int e = ensure(ctx, ctx->Cc, (size_t)T * S * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->Asumc, (size_t)T * S * 8)) return e;
+    HIPCHK(hipMemsetAsync(ctx->Cc.p, 0, (size_t)T * S * S * 8, st));
+    HIPCHK(hipMemsetAsync(ctx->Asumc.p, 0, (size_t)T * S * 8, st));
+    ctx->coef_c = c;
+    ctx->coef_active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_finish: data not bound for regression");
+    if (!ctx->coef_active) return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_finish: no coefficient series is open");
+    if (!d_bsum || !d_bsq) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_coef_finish: null output");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const long long n = ctx->coef_n;
+    ctx->coef_active = 0; ctx->coef_n = 0;
+    if (n == 0) return PLSX_OK;
+    // ONE pass over the features: bsum += Xc^T (sum_b A_b), bsq[f][t] += x_f^T C_t x_f
+    const QuadSet qs = coef_set(ctx);
+    return quad_finish(ctx, d_bsum, d_bsq, st, &qs);
+} PLSX_CATCH(ctx)
+
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream)
 try {
     NEED_DATA();
@@ -379,19 +473,25 @@ try {
         double* yl = d_yload + (size_t)off * T * k;
         const double* yst = d_ystack ? d_ystack + (size_t)off * ctx->S * T : nullptr;
         const bool single = simpls_single_pass(ctx);
+        SdArgs sda;                      // the batch's solver state, for an open coefficient series
         if (ctx->quad_active) {
             // quadratic-form route: the aligned dual weights stay in dual space (plsx_boot_finish passes the features)
             if (int e = ensure(ctx, ctx->Vdq, (size_t)ms * k * ctx->S * 8)) return e;
             if (int e = run_simpls_dual(ctx, idx, idx, ms, true, ptr<double>(ctx->spct), yl, ptr<double>(ctx->sc), st, yst,
-                                        true, ptr<double>(ctx->Vdq)))
+                                        true, ptr<double>(ctx->Vdq), nullptr, ctx->coef_active ? &sda : nullptr))
                 return e;
             if (ctx->timing) ctx->timed_units += ms;
             if (int e = quad_accumulate(ctx, ms, st)) return e;
+            if (ctx->coef_active)
+                if (int e = coef_accumulate(ctx, sda, ms, st)) return e;
             continue;
         }
         if (int e = run_simpls_dual(ctx, idx, idx, ms, true, ptr<double>(ctx->spct), yl, ptr<double>(ctx->sc), st, yst,
-                                    single))
+                                    single, nullptr, nullptr, ctx->coef_active ? &sda : nullptr))
             return e;
+        // (the solver state of the batch outlives the feature passes below: they work in buffers of their own)
+        if (ctx->coef_active)
+            if (int e = coef_accumulate(ctx, sda, ms, st)) return e;
         if (single) {
             // ONE feature pass, no R: x_weights = X0_r^T (flip . Wd) accumulated per group in the epilogue
             const int MT = 24, NW = 4, npg_w = (MT * 16) / k;

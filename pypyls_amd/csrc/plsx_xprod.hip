@@ -427,13 +427,16 @@ int launch_xprod_split(plsx_ctx* ctx, int groups, SplitEpi se, hipStream_t st)
 
 // The closing pass of a series: usum += Xc^T Vsum, usq[j][l] += x_j^T C_l x_j.
 template <int MT, int KT>
-int quad_finish_t(plsx_ctx* ctx, double* d_usq, int gpl, hipStream_t st)
+int quad_finish_t(plsx_ctx* ctx, double* d_usq, int gpl, hipStream_t st, const QuadSet* qs)
 {
     constexpr int NW = 8;
-    const int S = ctx->S, L = ctx->method == PLSX_REGRESSION ? ctx->ncomp : ctx->L, B = ctx->B;
+    const int S = ctx->S, L = qs ? qs->L : (ctx->method == PLSX_REGRESSION ? ctx->ncomp : ctx->L), B = ctx->B;
+    const double* Cq = ptr<double>(qs ? *qs->C : ctx->Cq);
     const size_t gstride = (size_t)ctx->nks * MT * 64;
-    ctx->quad_MT = MT; ctx->quad_gpl = gpl;
-    if (ctx->timing) ++ctx->quad_series;
+    if (!qs) {                                    // (the figures plsx_last_timing reports are those of the weights' series)
+        ctx->quad_MT = MT; ctx->quad_gpl = gpl;
+        if (ctx->timing) ++ctx->quad_series;
+    }
     // l's per pass: A operands within 1 GB
     const int lmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)L, (1ULL << 30) / (gstride * 8 * gpl)));
     const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
@@ -447,7 +450,7 @@ int quad_finish_t(plsx_ctx* ctx, double* d_usq, int gpl, hipStream_t st)
         {
             KTimer tm(ctx, KC_BUILD, st);
             hipLaunchKernelGGL(k_pack_afrag, dim3(64, groups), dim3(256), 0, st,
-                               ptr<double>(ctx->Cq) + (size_t)l0 * S * S, S, gpl, MT, ptr<double>(ctx->Afrag_q), gstride);
+                               Cq + (size_t)l0 * S * S, S, gpl, MT, ptr<double>(ctx->Afrag_q), gstride);
             LAUNCHCHK();
         }
         SplitEpi se;
@@ -475,20 +478,20 @@ int quad_finish_t(plsx_ctx* ctx, double* d_usq, int gpl, hipStream_t st)
     return 0;
 }
 
-int quad_finish(plsx_ctx* ctx, double* d_usum, double* d_usq, hipStream_t st)
+int quad_finish(plsx_ctx* ctx, double* d_usum, double* d_usq, hipStream_t st, const QuadSet* qs)
 {
-    const int S = ctx->S, L = ctx->method == PLSX_REGRESSION ? ctx->ncomp : ctx->L, B = ctx->B;
+    const int S = ctx->S, L = qs ? qs->L : (ctx->method == PLSX_REGRESSION ? ctx->ncomp : ctx->L), B = ctx->B;
     {
         KTimer tm(ctx, KC_UROT, st);
         hipLaunchKernelGGL(k_xt_vsum, dim3(ceil_div(B, 256), ceil_div(L, 8)), dim3(256), 0, st, ptr<double>(ctx->Xc),
-                           ctx->Bpad, S, B, ptr<double>(ctx->Vsumq), L, d_usum);
+                           ctx->Bpad, S, B, ptr<double>(qs ? *qs->Vsum : ctx->Vsumq), L, d_usum);
         LAUNCHCHK();
     }
     // the S rows of a C_l in row blocks of 8 tiles (quad_blocks); two k-steps per LDS stage (half the barriers of a
     // block whose pass is only 8 MFMAs long) when every block's contraction is a whole number of stages: the blocks
     // start at multiples of 32 k-steps, so that is when the padded row count is even
-    if (ctx->nks % 2 == 0) return quad_finish_t<8, 2>(ctx, d_usq, quad_blocks(ceil_div(S, 16)), st);
-    return quad_finish_t<8, 1>(ctx, d_usq, quad_blocks(ceil_div(S, 16)), st);
+    if (ctx->nks % 2 == 0) return quad_finish_t<8, 2>(ctx, d_usq, quad_blocks(ceil_div(S, 16)), st, qs);
+    return quad_finish_t<8, 1>(ctx, d_usq, quad_blocks(ceil_div(S, 16)), st, qs);
 }
 
 }  // namespace plsxi

@@ -89,6 +89,8 @@ def _load():
         'plsx_simpls_boot_batch': ([vp, vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_set_row_masks': ([vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_simpls_coef_begin': ([vp, i32, vp], i32),
+        'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_bootsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_permsamp_stream': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp, ctypes.POINTER(i32)], i32),
@@ -124,7 +126,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -747,6 +749,21 @@ class Engine(object):
                 raise ValueError('cross-validation outputs must be contiguous (m, k, T), (m, k, T) and (m, k + 1, T)')
         self._check(self.lib.plsx_simpls_crossval_batch(self.ctx, masks_dev.data_ptr(), m, r_dev.data_ptr(),
                                                         r2_dev.data_ptr(), sse_dev.data_ptr(), self._stream()))
+
+    def simpls_coef_begin(self, c):
+        """Open a coefficient series for the model of the first ``c`` components: until :meth:`simpls_coef_finish`
+        every :meth:`simpls_boot_into` also accumulates the bootstrap's coefficients in dual space
+        (plsx_simpls_coef_begin).  PlsxError (status -2, context still usable) when the T x S x S accumulator does
+        not fit."""
+        self._check(self.lib.plsx_simpls_coef_begin(self.ctx, int(c), self._stream()))
+
+    def simpls_coef_finish(self, bsum, bsq):
+        """Close the series: bsum / bsq (B, T) += sum over the bootstraps of coefs / coefs^2, one pass over the
+        features (plsx_simpls_coef_finish)."""
+        for t in (bsum, bsq):
+            if tuple(t.shape) != (self.B, self.T) or not t.is_contiguous():
+                raise ValueError('coefficient sums must be contiguous ({}, {}) tensors'.format(self.B, self.T))
+        self._check(self.lib.plsx_simpls_coef_finish(self.ctx, bsum.data_ptr(), bsq.data_ptr(), self._stream()))
 
     def simpls_boot_into(self, idx_dev, usum, usq, yl_dev, ystack=None):
         """idx_dev (n, S) int32; usum / usq (B, k) accumulated in place; yl_dev (n, T, k);

@@ -26,6 +26,11 @@ Differences from the reference at this commit, on purpose:
     place of the SVD): SIMPLS with ``n_components`` on the training rows, the test rows predicted by the first
     c = 1 .. n_components components plus the intercept, each prediction scored per behaviour
     (plsx_simpls_crossval_batch; csrc/plsx_simpls.h, k_sd_cv_score).
+  * ``coef_components=c`` returns the fitted model of the first c components, ``Y ~ intercept + X @ coefs`` (simpls
+    computes it as ``beta``, regression.py:149-151, and PLSResults drop it), and bootstraps the coefficients:
+    ``bootres.coefs_stderr`` / ``coefs_normed``, one map per behaviour.  The coefficients depend on neither the signs
+    nor the order of the components, so their bootstrap needs no alignment (plsx_simpls_coef_begin / _finish;
+    csrc/plsx_simpls.h, k_sd_coef).  :func:`predict` applies the model of any ``pls_regression`` result to new rows.
 """
 import numpy as np
 
@@ -90,7 +95,7 @@ def _check_cvsplits(masks, usable, k, B):
 
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
-                   n_proc=None, test_split=0, test_size=0.25, cvsamples=None, **kwargs):
+                   n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -105,7 +110,15 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     ``cvsamples`` (S, test_split) bool, True = training row.  ``cvres`` then holds ``pearson_r`` / ``r_squared``
     (T, test_split) of the full model, ``pearson_r_ncomp`` / ``r_squared_ncomp`` (T, n_components, test_split) of the
     nested models, ``mse`` (n_components + 1, test_split) -- row 0 the intercept-only model -- and ``cvsamples``.
-    Masked rows belong to neither side."""
+    Masked rows belong to neither side.
+
+    Model coefficients: ``coef_components=c`` (1 <= c <= n_components; None, the default: nothing is added) returns
+    ``coefs`` (B, T) ``= x_weights[:, :c] @ y_loadings[:, :c].T`` (with masked rows: simpls' own y_loadings, centred
+    over the rows of the fit) and ``intercept`` (T,) of the c-component model
+    ``Y ~ intercept + X @ coefs`` (means over the rows the fit used; 3-D Y: of the aggregated Y) and, with
+    ``n_boot > 0``, ``bootres.coefs_stderr`` / ``bootres.coefs_normed`` (B, T): the standard error of the coefficients
+    over the bootstraps and the coefficients over it, with the original added back (n = n_boot + 1) as for
+    ``x_weights_normed``.  No random draw is added or moved.  :func:`predict` applies the model to new rows."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -121,6 +134,13 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     if Y.ndim not in (2, 3) or len(X) != len(Y):
         raise ValueError('Provided `X` and `Y` matrices must have the same number of samples. '
                          'Provided matrices differed: X: {}, Y: {}'.format(len(X), len(Y)))
+    if coef_components is not None:                # (validated on the host before any engine is created or looked up)
+        if isinstance(coef_components, bool) or int(coef_components) != coef_components \
+                or not 1 <= int(coef_components) <= n_components:
+            raise ValueError('Provided `coef_components` must be an integer in 1 .. n_components = {}; got {!r}'
+                             .format(n_components, coef_components))
+        coef_components = int(coef_components)
+        kwargs['coef_components'] = coef_components        # (recorded in `inputs` only when asked for)
     S = len(X)
     agg = None
     third = None                                   # (C, n_boot) third-axis resamples for 3-D Y
@@ -262,7 +282,8 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
         if team is not None:
             res = team.run(lambda rank, world, e: _run_device(
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
-                k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv))
+                k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
+                coef_c=coef_components))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -271,7 +292,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 try:
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
-                                      kwargs.get('_emulate'), cv=cv)
+                                      kwargs.get('_emulate'), cv=cv, coef_c=coef_components)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -285,7 +306,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
-                bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None):
+                bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None):
     import time
     import torch
     S = len(X)
@@ -346,7 +367,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
 
     # this rank's shards (permutations contiguous, bootstraps chunk-cyclic), launched chunk by chunk as the index rows arrive; the
     # results stay on the device until the one collective
-    d_perm = d_yl = usum = usq = None
+    d_perm = d_yl = usum = usq = bsum = bsq = None
     n_perm_tot = pstream.n if pstream is not None else 0
     n_boot_tot = bstream.n if bstream is not None else 0
     from .progress import Bar                            # verbose=True: the reference's bars (pyls/utils.py:128-152)
@@ -368,6 +389,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         d_yl = eng._zeros((sum(hi - lo for lo, hi in bchunks), T, k))
         off = 0
         eng.boot_begin(sum(hi - lo for lo, hi in bchunks))     # (plsx_boot_begin: the feature pass may move to boot_finish)
+        if coef_c is not None:
+            # the coefficients of the coef_c-component model ride along every solver batch (plsx_simpls_coef_begin)
+            bsum, bsq = eng._zeros((B, T)), eng._zeros((B, T))
+            eng.simpls_coef_begin(coef_c)
         bars.append(Bar('Running bootstraps', sum(hi - lo for lo, hi in bchunks), show, eng.device))
         # 3-D Y: a (n, S, T) Y stack per chunk, at most 256 of them and at most 256 MB (S = 24 000, T = 20: 69 rows)
         ylim = max(1, min(256, (256 << 20) // (S * T * 8)))
@@ -390,6 +415,9 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             off += hi - lo
         eng.boot_finish(usum, usq)
     tick('bootstraps')
+    if bsum is not None:
+        eng.simpls_coef_finish(bsum, bsq)              # each rank closes its own series: ONE pass over the features
+        tick('coefs_finish')
     permsamp = bootsamp = None
     if pstream is not None and lead:
         permsamp = np.asarray(permsamples) if permsamples is not None else pstream.samples
@@ -427,13 +455,15 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     cyclic = [len(slices) - 1] if d_yl is not None else []
     if d_cv is not None:                                # the cross-validation rows ride in the same buffer: ONE collective
         slices, totals = slices + d_cv, totals + [cv['n']] * 3
-    full, summed = parallel.collect_device(slices, totals, [usum, usq] if usum is not None else [], emulate=emulate,
-                                           cyclic=cyclic, team=team)
+    sums = [t for t in (usum, usq, bsum, bsq) if t is not None]      # (the coefficient sums join the summed part)
+    full, summed = parallel.collect_device(slices, totals, sums, emulate=emulate, cyclic=cyclic, team=team)
     if not lead:
         return None                                     # rank 0 holds everything the ranks computed: it finishes
     full = [t.detach().cpu().numpy() for t in full]
     if usum is not None:
-        usum, usq = summed
+        usum, usq = summed[:2]
+    if bsum is not None:
+        bsum, bsq = summed[2:4]
     tick('collective')
     i = 0
     d_perm = distrib = None
@@ -460,6 +490,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     y_scores[mask] = resid_yscores(x_scores[mask], Yc[mask] @ res['y_loadings'])
     res['y_scores'] = y_scores
     res['x_weights'] = _host_array(h_W)
+    if coef_c is not None:
+        # the model of the first coef_c components (simpls' beta, regression.py:149-151): Y ~ intercept + X @ coefs
+        res['coefs'] = _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_agg, mask, coef_c)
+        res['intercept'] = _model_means(X, Y_agg, mask, res['coefs'])
     if bootsamp is not None:
         # add the original back, n_boot + 1 (regression.py:409-415)
         d_bsr, d_se = eng.boot_rel_dev(d_W, usum, usq, bootsamp.shape[1] + 1, add_orig=True)
@@ -471,6 +505,74 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             y_loadings_boot=distrib,
             y_loadings_ci=np.stack(eng.percentile_ci(distrib, ci=ci), -1),
             bootsamples=bootsamples_out if third is not None else bootsamp))
+        if bsum is not None:
+            d_cn, d_cse = eng.boot_rel_dev(eng._dev(res['coefs'], np.float64), bsum, bsq, bootsamp.shape[1] + 1,
+                                           add_orig=True)
+            eng.sync()
+            res['bootres'].update(dict(coefs_normed=d_cn.cpu().numpy(), coefs_stderr=d_cse.cpu().numpy()))
     res['varexp'] = pctvar                                          # regression.py:425-426
     tick('host_finish')
     return res
+
+
+def _model_coefs(W, Q, x_scores, Y_agg, mask, c):
+    """coefs (B, T) = W[:, :c] @ Q[:, :c].T with Q simpls' y_loadings (regression.py:149-151).  Without masked rows
+    that is the result's own ``y_loadings``.  With rows that are NaN throughout, X and Y are centred over different
+    rows than the fit uses (np.nanmean per matrix, regression.py:395-397), so ``y_loadings`` = Yc^T x_scores carries
+    the product of the two offsets; simpls' own are taken from the scores and Y centred over the rows of the fit."""
+    W, Q = np.asarray(W, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    if not mask.all():
+        t = np.asarray(x_scores, dtype=np.float64)[mask][:, :c]
+        y = np.asarray(Y_agg, dtype=np.float64)[mask]
+        Q = (y - y.mean(axis=0)).T @ (t - t.mean(axis=0))
+    return np.ascontiguousarray(W[:, :c] @ Q[:, :c].T)
+
+
+def _model_means(X, Y_agg, mask, coefs):
+    """intercept (T,) = ybar - xbar @ coefs, means over the rows the fit used."""
+    X, Y_agg = np.asarray(X, dtype=np.float64), np.asarray(Y_agg, dtype=np.float64)
+    if not mask.all():
+        X, Y_agg = X[mask], Y_agg[mask]
+    return Y_agg.mean(axis=0) - X.mean(axis=0) @ coefs
+
+
+def predict(results, X_new, n_components=None):
+    """Predict Y (S_new, T) for new rows ``X_new`` (S_new, B) with the model of the first ``n_components`` SIMPLS
+    components of a ``pls_regression`` result: ``intercept + X_new @ coefs`` with
+    ``coefs = x_weights[:, :c] @ y_loadings[:, :c].T`` (simpls' ``beta``, pyls/types/regression.py:149-151).
+
+    Works on any ``pls_regression`` result, also one read back by ``load_results``: the means come from
+    ``results.inputs`` (X, Y, ``aggfunc``), over the rows the fit used (rows that are NaN throughout are left out).
+    ``n_components=None``: the ``coef_components`` the result was computed with, otherwise all components.
+    Host numpy: one thin product."""
+    inputs = results.get('inputs') if hasattr(results, 'get') else None
+    W, Q = (results.get('x_weights'), results.get('y_loadings')) if inputs is not None else (None, None)
+    if inputs is None or W is None or Q is None or results.get('singvals') is not None \
+            or inputs.get('n_components') is None or inputs.get('X') is None or inputs.get('Y') is None:
+        raise ValueError('`results` is not a pls_regression result (x_weights, y_loadings and the inputs X, Y, '
+                         'n_components are needed)')
+    W, Q = np.asarray(W, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    X, Y = np.asarray(inputs['X'], dtype=np.float64), np.asarray(inputs['Y'], dtype=np.float64)
+    X_new = np.asarray(X_new, dtype=np.float64)
+    if X_new.ndim != 2 or X_new.shape[1] != W.shape[0]:
+        raise ValueError('`X_new` must have shape (S_new, {}); got {}'.format(W.shape[0], X_new.shape))
+    k = W.shape[1]
+    if n_components is None:
+        n_components = inputs.get('coef_components')
+        n_components = k if n_components is None else int(n_components)
+    if isinstance(n_components, bool) or int(n_components) != n_components or not 1 <= int(n_components) <= k:
+        raise ValueError('`n_components` must be an integer in 1 .. {}; got {!r}'.format(k, n_components))
+    c = int(n_components)
+    if Y.ndim == 3:
+        aggfunc = inputs.get('aggfunc')
+        aggfunc = aggfunc.decode() if isinstance(aggfunc, bytes) else aggfunc
+        if not callable(aggfunc) and aggfunc not in _AGGFUNCS:
+            raise ValueError('`results.inputs.aggfunc` must be callable or one of {}'.format(sorted(_AGGFUNCS)))
+        Y = _AGGFUNCS.get(aggfunc, aggfunc)(Y, axis=-1)
+    mask = ~(np.isnan(X).all(axis=1) | np.isnan(Y).all(axis=1))
+    x_scores = results.get('x_scores')
+    if x_scores is None and not mask.all():
+        x_scores = np.full((len(X), k), np.nan)
+        x_scores[mask] = X[mask] @ W
+    coefs = _model_coefs(W, Q, x_scores, Y, mask, c)
+    return _model_means(X, Y, mask, coefs) + X_new @ coefs

@@ -91,6 +91,7 @@ class PLSInputs(KeyedRecord):
         'test_split', 'test_size', 'mean_centering', 'covariance', 'rotate',
         'ci', 'seed', 'verbose', 'n_proc', 'bootsamples', 'permsamples',
         'method', 'n_components', 'aggfunc', 'permindices',
+        'coef_components',                  # pls_regression: component count of the returned model (only when asked for)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
     )
@@ -117,7 +118,10 @@ class PLSInputs(KeyedRecord):
 class PLSBootResults(KeyedRecord):
     allowed = ('x_weights_normed', 'x_weights_stderr', 'bootsamples',
                'y_loadings', 'y_loadings_boot', 'y_loadings_ci',
-               'contrast', 'contrast_boot', 'contrast_ci')
+               'contrast', 'contrast_boot', 'contrast_ci',
+               # pls_regression(coef_components=c): standard error of the model coefficients over the bootstraps and
+               # the coefficients over it, (B, T) -- one map per behaviour
+               'coefs_stderr', 'coefs_normed')
 
 
 class PLSPermResults(KeyedRecord):
@@ -139,7 +143,9 @@ class PLSResults(KeyedRecord):
     """Top-level result object; layout of pyls/structures.py:198-246."""
     allowed = ('x_weights', 'y_weights', 'x_scores', 'y_scores', 'y_loadings',
                'singvals', 'varexp', 'permres', 'bootres', 'splitres', 'cvres',
-               'inputs')
+               'inputs',
+               # pls_regression(coef_components=c): Y ~ intercept (T,) + X @ coefs (B, T)
+               'coefs', 'intercept')
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
