@@ -322,6 +322,45 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           without an open series: PLSX_ERR_STATE.  plsx_set_data
  *                           and plsx_simpls_set_original end an open series.
  *                           Fixed-order reductions: bit-reproducible run to run.
+ *   plsx_simpls_coef_keep / plsx_simpls_coef_ci
+ *                           percentile intervals of the coefficients.  The sums above
+ *                           are quadratic forms; order statistics are not: they need
+ *                           every bootstrap's coefs_b[f][t] = sum_s Xc[s][f] A_b[t][s].
+ *                           _keep (after _begin, before the first batch of the
+ *                           series): every bootstrap the open series sees is also
+ *                           kept, appended in submission order to the caller's
+ *                           d_A, `capacity` bootstraps of T S doubles, layout
+ *                           [bootstrap][T][S] (bootstrap-major, so that shards of
+ *                           several contexts concatenate; k_sd_coef writes each
+ *                           A_b there instead of into scratch, the sums keep their
+ *                           bits).  A plsx_simpls_boot_batch whose bootstraps no
+ *                           longer fit returns PLSX_ERR_ARG before it computes
+ *                           anything; _keep without an open series:
+ *                           PLSX_ERR_STATE; _finish, plsx_set_data,
+ *                           plsx_simpls_set_original and _begin end the keeping
+ *                           with the series (the buffer stays the caller's).
+ *                           _ci is stateless with respect to the series: for ANY
+ *                           stack d_A [n][T][S] and the bound, centred features it
+ *                           writes d_lo, d_hi (B, T): the two interpolated order
+ *                           statistics -- virtual indices (i, g) as for
+ *                           plsx_percentile_ci -- of { coefs_b[f][t] : b < n }.
+ *                           Features go in chunks of whole 128-feature blocks;
+ *                           per chunk kernel k_coef_prod (fp64 MFMA, M = features,
+ *                           N = bootstraps of one behaviour, K = subjects) writes
+ *                           the series [f][t][n] contiguous and the selection
+ *                           kernels of plsx_percentile_ci reduce them (option
+ *                           percentile_sort applies): the (B, T, n) array never
+ *                           exists whole.  A chunk is at most 2 GB and, with the
+ *                           stack, stays inside the scratch budget
+ *                           (plsx_set_scratch) and free device memory.  Every
+ *                           entry is one block's contraction in ascending s: the
+ *                           same bits run to run and whatever the chunking.
+ *                           Limits: PLSX_ERR_UNSUPPORTED (context still usable,
+ *                           sizes in the message) for n > 16384 or when the stack
+ *                           plus the smallest chunk (min(B, 128) features,
+ *                           8 T n bytes each) does not fit; PLSX_ERR_ARG for
+ *                           n < 1, an index outside 0 .. n - 1, a null pointer;
+ *                           PLSX_ERR_STATE without bound regression data.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -334,6 +373,9 @@ int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, dou
                                double* d_sse, void* stream);
 int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream);
 int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* stream);
+int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity);
+int plsx_simpls_coef_ci(plsx_ctx* ctx, const double* d_A, long long n, int i_lo, double g_lo, int i_hi, double g_hi,
+                        double* d_lo, double* d_hi, void* stream);
 
 /* Bootstrap ratios -- compute.boot_rel (pyls/compute.py:212-237), elementwise
  * on (B, L) arrays: se = sqrt(|usq - usum^2/n| / (n-1)), bsr = orig / se.
@@ -389,7 +431,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
 /* Summed duration (ms) and launch count of one kernel class since timing was
  * enabled: 0 k_xprod (cross-product), 1 k_gram / k_gram4 (+ partial reduce),
  * 2 k_small / k_small_ql (eigen-solve + Procrustes), 3 k_urot (+ split add), 4 k_nt_gemm
- * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved.
+ * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 11 k_coef_prod (the feature pass of
+ * plsx_simpls_coef_ci), 12 k_percentile (selection / sort of plsx_percentile_ci and plsx_simpls_coef_ci).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

@@ -8,7 +8,7 @@ namespace plsxi {
 
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
-                                                 "k_sd_cv_score", "k_sd_coef"};
+                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -362,7 +362,7 @@ try {
                    &ctx->Xn, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
-                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->Zcv, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
+                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->Zcv, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     delete ctx;
@@ -479,7 +479,7 @@ try {
         return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
     }
     ctx->has_data = ctx->has_orig = false;
-    ctx->coef_active = 0; ctx->coef_n = 0;             // (an open coefficient series ends with the binding it belonged to)
+    coef_close(ctx);                                   // (an open coefficient series ends with the binding it belonged to)
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;
     HIPCHK(hipMemsetAsync(ctx->status.p, 0, 4 * sizeof(int), st));
@@ -990,6 +990,36 @@ int boot_single_pass(plsx_ctx* ctx, const int32_t* d_boot_idx, int n, double* d_
 
 }  // namespace plsxi
 
+namespace plsxi {
+
+// One block per series (n <= 16384 values, contiguous; nseries < 2^31).  Long series with both ranks in the tails (the
+// 95 % interval of 10 000 bootstraps): selection instead of a full sort; the few series it cannot settle (pathological
+// pivots) fall through to the sort.  Callers: plsx_percentile_ci, plsx_simpls_coef_ci (once per chunk of features).
+int run_percentile(plsx_ctx* ctx, const double* d_data, long long nseries, int n, int i_lo, double g_lo, int i_hi,
+                   double g_hi, double* d_lo, double* d_hi, hipStream_t st)
+{
+    int p2 = 1;
+    while (p2 < n) p2 <<= 1;
+    const size_t lds = (size_t)p2 * 8;
+    HIPCHK(set_lds(k_percentile2, lds));
+    const int* only = nullptr;
+    KTimer tm(ctx, KC_PCTL, st);
+    if (n >= 4096 && std::min(i_lo + 1, n - 1) + 1 <= PSEL_CAP / 2 && n - i_hi <= PSEL_CAP / 2 &&
+        !ctx->opt[OPT_PERCENTILE_SORT]) {
+        if (int e = ensure(ctx, ctx->pflags, (size_t)nseries * sizeof(int))) return e;
+        hipLaunchKernelGGL(k_percentile_sel, dim3((unsigned)nseries), dim3(256), 0, st, d_data, n, i_lo, g_lo, i_hi,
+                           g_hi, d_lo, d_hi, ptr<int>(ctx->pflags));
+        LAUNCHCHK();
+        only = ptr<int>(ctx->pflags);
+    }
+    hipLaunchKernelGGL(k_percentile2, dim3((unsigned)nseries), dim3(256), lds, st,
+                       d_data, n, p2, i_lo, g_lo, i_hi, g_hi, d_lo, d_hi, only);
+    LAUNCHCHK();
+    return 0;
+}
+
+}  // namespace plsxi
+
 extern "C" {
 
 int plsx_boot_batch(plsx_ctx* ctx, const int32_t* d_boot_idx, int n, double* d_usum, double* d_usq,
@@ -1196,28 +1226,9 @@ try {
     if (!ctx) return PLSX_ERR_ARG;
     if (!d_data || !d_lo || !d_hi || nseries < 1 || n < 1 || i_lo < 0 || i_hi < 0 || i_lo >= n || i_hi >= n)
         return fail(ctx, PLSX_ERR_ARG, "plsx_percentile_ci: bad arguments");
-    int p2 = 1;
-    while (p2 < n) p2 <<= 1;
-    if (p2 > 16384) return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_percentile_ci: more than 16384 values per series");
+    if (n > 16384) return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_percentile_ci: more than 16384 values per series");
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t lds = (size_t)p2 * 8;
-    HIPCHK(set_lds(k_percentile2, lds));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int* only = nullptr;
-    // long series with both ranks in the tails (the 95 % interval of 10 000 bootstraps): selection instead of a
-    // full sort; the few series it cannot settle (pathological pivots) fall through to the sort below
-    if (n >= 4096 && std::min(i_lo + 1, n - 1) + 1 <= PSEL_CAP / 2 && n - i_hi <= PSEL_CAP / 2 &&
-        !ctx->opt[OPT_PERCENTILE_SORT]) {
-        if (int e = ensure(ctx, ctx->pflags, (size_t)nseries * sizeof(int))) return e;
-        hipLaunchKernelGGL(k_percentile_sel, dim3((unsigned)nseries), dim3(256), 0, st, d_data, n, i_lo, g_lo, i_hi,
-                           g_hi, d_lo, d_hi, ptr<int>(ctx->pflags));
-        LAUNCHCHK();
-        only = ptr<int>(ctx->pflags);
-    }
-    hipLaunchKernelGGL(k_percentile2, dim3((unsigned)nseries), dim3(256), lds, st,
-                       d_data, n, p2, i_lo, g_lo, i_hi, g_hi, d_lo, d_hi, only);
-    LAUNCHCHK();
-    return PLSX_OK;
+    return run_percentile(ctx, d_data, nseries, n, i_lo, g_lo, i_hi, g_hi, d_lo, d_hi, static_cast<hipStream_t>(stream));
 } PLSX_CATCH(ctx)
 
 int plsx_set_scratch(plsx_ctx* ctx, double max_gb, int fixed)

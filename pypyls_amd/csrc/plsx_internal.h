@@ -122,6 +122,10 @@ struct plsx_ctx {
     Buf Cc, Asumc, Adc, Qc;
     int coef_active = 0, coef_c = 0;                    // 1: a coefficient series is open; its component count
     long long coef_n = 0;                               // bootstraps accumulated in it
+    // plsx_simpls_coef_keep: the open series also keeps every A_b, appended [keep_n][T][S] to the caller's buffer
+    double* keepA = nullptr;
+    long long keep_cap = 0, keep_n = 0;
+    Buf cichunk;                                        // plsx_simpls_coef_ci: one chunk of features' series [fc][T][n]
     bool has_okx = false, has_oky = false;
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
     int ncomp = 0;
@@ -221,7 +225,8 @@ hipError_t set_lds(F* fn, size_t bytes)
 }
 
 // kernel classes of plsx_kernel_timing()
-enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COUNT };
+enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
+       KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -299,6 +304,15 @@ int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st);
 struct QuadSet { Buf* C; Buf* Vsum; const double* Vd; int L; };
 int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st, const QuadSet* qs = nullptr);
 bool quad_applicable(const plsx_ctx* ctx);
+// the two interpolated order statistics of nseries contiguous series of n values (plsx_percentile_ci's body)
+int run_percentile(plsx_ctx* ctx, const double* d_data, long long nseries, int n, int i_lo, double g_lo, int i_hi,
+                   double g_hi, double* d_lo, double* d_hi, hipStream_t st);
+// an open coefficient series ends: with it what it was told to keep
+inline void coef_close(plsx_ctx* ctx)
+{
+    ctx->coef_active = 0; ctx->coef_n = 0;
+    ctx->keepA = nullptr; ctx->keep_cap = 0; ctx->keep_n = 0;
+}
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);
 int launch_xprod_acc(plsx_ctx* ctx, const double* Afrag, size_t gstride, int groups, int L, hipStream_t st);

@@ -219,21 +219,30 @@ bool simpls_single_pass(const plsx_ctx* ctx)
 // dense, in chunks of at most 1 GB, and each chunk goes through quad_accumulate on the series' own accumulator set.
 // `a`: the state run_simpls_dual just left (args_out).  The solver batches themselves are what they are without a
 // series, so everything else a call computes keeps its bits.
-static QuadSet coef_set(plsx_ctx* ctx) { return QuadSet{&ctx->Cc, &ctx->Asumc, ptr<double>(ctx->Adc), ctx->T}; }
+static QuadSet coef_set(plsx_ctx* ctx, const double* Ad = nullptr)
+{
+    return QuadSet{&ctx->Cc, &ctx->Asumc, Ad ? Ad : ptr<double>(ctx->Adc), ctx->T};
+}
 
 static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 {
     const int S = ctx->S, T = ctx->T, cc = ctx->coef_c;
     const bool gl = simpls_global(ctx);
     const int chunk = (int)std::max<long long>(1, std::min<long long>(ms, (1LL << 30) / ((long long)T * S * 8)));
-    if (int e = ensure(ctx, ctx->Adc, (size_t)chunk * T * S * 8)) return e;
+    // (a series that keeps its A_b -- plsx_simpls_coef_keep -- has every chunk written where it stays, in the caller's
+    // buffer, and accumulated from there: the same values through the same kernels, so the sums keep their bits)
+    if (ctx->keepA && ctx->keep_n + ms > ctx->keep_cap)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_boot_batch: the kept coefficient stack is full");
+    if (!ctx->keepA)
+        if (int e = ensure(ctx, ctx->Adc, (size_t)chunk * T * S * 8)) return e;
     if (int e = ensure(ctx, ctx->Qc, (size_t)chunk * cc * T * 8)) return e;
     const size_t per_wave = ((size_t)cc + (gl ? 0 : (size_t)S)) * 8;
     const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / per_wave));
     const size_t lds = (size_t)wpb * per_wave;
-    a.cfA = ptr<double>(ctx->Adc); a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
+    a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
     for (int r0 = 0; r0 < ms; r0 += chunk) {
         const int mc = std::min(chunk, ms - r0);
+        a.cfA = ctx->keepA ? ctx->keepA + (size_t)(ctx->keep_n + r0) * T * S : ptr<double>(ctx->Adc);
         a.cf_r0 = r0; a.cf_n = mc;
         {
             KTimer tm(ctx, KC_COEF, st);
@@ -243,10 +252,11 @@ static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
             hipLaunchKernelGGL(coef_kernel, dim3(ceil_div(mc, wpb)), dim3(wpb * 64), lds, st, a);
             LAUNCHCHK();
         }
-        const QuadSet qs = coef_set(ctx);
+        const QuadSet qs = coef_set(ctx, a.cfA);
         if (int e = quad_accumulate(ctx, mc, st, &qs)) return e;
     }
     ctx->coef_n += ms;
+    if (ctx->keepA) ctx->keep_n += ms;
     return 0;
 }
 
@@ -287,7 +297,7 @@ try {
                        nullptr, 0, 0, 0, ctx->B, 1, ptr<double>(ctx->Qs), 0, ctx->ncomp, nullptr, 0, 0, st))
         return e;
     ctx->has_orig = true; ctx->quad_active = 0;
-    ctx->coef_active = 0; ctx->coef_n = 0;
+    coef_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -369,7 +379,7 @@ try {
     if (ctx->method != PLSX_REGRESSION)
         return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_begin: data not bound for regression");
     if (!ctx->has_orig) return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_begin: plsx_simpls_set_original has not been called");
-    ctx->coef_active = 0; ctx->coef_n = 0;
+    coef_close(ctx);
     if (c < 1 || c > ctx->ncomp) {
         char msg[120];
         snprintf(msg, sizeof msg, "plsx_simpls_coef_begin: c = %d outside 1 .. n_components = %d", c, ctx->ncomp);
@@ -413,11 +423,82 @@ try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const long long n = ctx->coef_n;
-    ctx->coef_active = 0; ctx->coef_n = 0;
+    coef_close(ctx);
     if (n == 0) return PLSX_OK;
     // ONE pass over the features: bsum += Xc^T (sum_b A_b), bsq[f][t] += x_f^T C_t x_f
     const QuadSet qs = coef_set(ctx);
     return quad_finish(ctx, d_bsum, d_bsq, st, &qs);
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_keep: data not bound for regression");
+    if (!ctx->coef_active) return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_keep: no coefficient series is open");
+    if (!d_A || capacity < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_coef_keep: null buffer or capacity < 1");
+    ctx->keepA = d_A; ctx->keep_cap = capacity; ctx->keep_n = 0;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_coef_ci(plsx_ctx* ctx, const double* d_A, long long n, int i_lo, double g_lo, int i_hi, double g_hi,
+                        double* d_lo, double* d_hi, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_ci: data not bound for regression");
+    if (!d_A || !d_lo || !d_hi || n < 1 || i_lo < 0 || i_hi < 0 || i_lo >= n || i_hi >= n)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_coef_ci: null pointer, n < 1 or an index outside 0 .. n - 1");
+    const int S = ctx->S, T = ctx->T, B = ctx->B;
+    char msg[400];
+    if (n > 16384) {
+        snprintf(msg, sizeof msg, "plsx_simpls_coef_ci: n = %lld bootstraps per series; the percentile kernels take at "
+                 "most 16384 (B = %d, T = %d: %.1f GB of series, which no host path forms either)", n, B, T,
+                 8.0 * B * T * (double)n / 1073741824.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    // Features go in chunks of whole 128-feature blocks: a chunk's series, fc T n doubles, next to the stack inside the
+    // scratch budget and in free device memory (what an earlier pass left allocated counts as free), 2 GB at most --
+    // the series are written once and read once, a larger chunk buys nothing
+    const double stack = 8.0 * (double)n * T * S, per_feat = 8.0 * T * (double)n;
+    const int unit = std::min(B, 128);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const double have = (double)free_b + (double)ctx->cichunk.bytes;
+    const double budget = ctx->scratch_gb * 1073741824.0;
+    const double room = std::min(budget - stack, have);
+    if (room < unit * per_feat) {
+        snprintf(msg, sizeof msg, "plsx_simpls_coef_ci: the stack of n = %lld bootstraps (8 n T S = %.3f GB for T = %d, "
+                 "S = %d) and the series of the smallest chunk of %d features (%.3f GB) need %.3f GB; the scratch budget "
+                 "is %.3f GB and %.3f GB of device memory are free", n, stack / 1073741824.0, T, S, unit,
+                 unit * per_feat / 1073741824.0, (stack + unit * per_feat) / 1073741824.0, ctx->scratch_gb,
+                 have / 1073741824.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    long long fc = (long long)(std::min(room, 2147483648.0) / per_feat);
+    fc = std::max<long long>(unit, fc / 128 * 128);
+    if (fc >= B) fc = B;
+    if (fc * T > 2147483647LL)                         // (series per selection launch: one block each, grid x)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_simpls_coef_ci: more than 2^31 series in one chunk");
+    if (int e = ensure(ctx, ctx->cichunk, (size_t)fc * T * (size_t)n * 8)) return e;
+    CoefProdArgs a;
+    a.Xc = ptr<double>(ctx->Xc); a.ldx = ctx->Bpad;
+    a.A = d_A; a.S = S; a.T = T; a.n = (int)n; a.B = B;
+    a.out = ptr<double>(ctx->cichunk);
+    for (long long f0 = 0; f0 < B; f0 += fc) {
+        a.f0 = (int)f0; a.fc = (int)std::min<long long>(fc, B - f0);
+        {
+            KTimer tm(ctx, KC_COEFPROD, st);
+            hipLaunchKernelGGL(k_coef_prod, dim3(ceil_div(a.fc, 128), ceil_div(a.n, 64), T), dim3(256), 0, st, a);
+            LAUNCHCHK();
+        }
+        if (int e = run_percentile(ctx, a.out, (long long)a.fc * T, a.n, i_lo, g_lo, i_hi, g_hi,
+                                   d_lo + (size_t)f0 * T, d_hi + (size_t)f0 * T, st))
+            return e;
+    }
+    return PLSX_OK;
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream)
@@ -448,6 +529,13 @@ try {
     if (ctx->method != PLSX_REGRESSION) return fail(ctx, PLSX_ERR_STATE, "data not bound for regression");
     if (!d_boot_idx || !d_usum || !d_usq || !d_yload || n < 1)
         return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_boot_batch: bad arguments");
+    // (a kept coefficient stack that cannot take the call's bootstraps: refused before anything is computed)
+    if (ctx->coef_active && ctx->keepA && ctx->keep_n + n > ctx->keep_cap) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "plsx_simpls_boot_batch: the kept coefficient stack holds %lld of %lld bootstraps, "
+                 "%d more do not fit (plsx_simpls_coef_keep)", ctx->keep_n, ctx->keep_cap, n);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int k = ctx->ncomp, T = ctx->T;

@@ -91,6 +91,8 @@ def _load():
         'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_coef_begin': ([vp, i32, vp], i32),
         'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
+        'plsx_simpls_coef_keep': ([vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_coef_ci': ([vp, vp, ctypes.c_longlong, i32, c_d, i32, c_d, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_bootsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_permsamp_stream': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp, ctypes.POINTER(i32)], i32),
@@ -126,7 +128,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -138,6 +140,17 @@ def exported_symbols():
 def _torch():
     import torch
     return torch
+
+
+def _virtual_indices(n, ci):
+    """numpy's virtual indices (floor, fraction) of the two quantiles of a ``ci`` % interval over n values."""
+    low = (100 - ci) / 2
+    idx = []
+    for q in (low, 100 - low):
+        vi = (n - 1) * np.true_divide(q, 100)
+        prev = np.floor(vi)
+        idx.append((int(prev), float(vi - prev)))
+    return idx
 
 
 def option_names():
@@ -764,6 +777,35 @@ class Engine(object):
             if tuple(t.shape) != (self.B, self.T) or not t.is_contiguous():
                 raise ValueError('coefficient sums must be contiguous ({}, {}) tensors'.format(self.B, self.T))
         self._check(self.lib.plsx_simpls_coef_finish(self.ctx, bsum.data_ptr(), bsq.data_ptr(), self._stream()))
+
+    def simpls_coef_keep(self, stack):
+        """Have the open coefficient series keep every bootstrap's A_b: ``stack`` (capacity, T, S), a contiguous
+        float64 tensor on this device, is filled in submission order by the :meth:`simpls_boot_into` calls that
+        follow (plsx_simpls_coef_keep).  PlsxError: status -4 without an open series, -1 from the batch that would
+        overflow the stack."""
+        torch = _torch()
+        if stack.dim() != 3 or tuple(stack.shape[1:]) != (self.T, self.S) or stack.dtype != torch.float64 \
+                or not stack.is_contiguous():
+            raise ValueError('the kept stack must be a contiguous (capacity, {}, {}) float64 tensor'.format(self.T, self.S))
+        self._check(self.lib.plsx_simpls_coef_keep(self.ctx, stack.data_ptr(), int(stack.shape[0])))
+
+    def simpls_coef_ci(self, stack, ci=95):
+        """Percentile interval of the coefficients over the bootstraps of ``stack`` (n, T, S) -- a kept stack, the
+        gathered stacks of several ranks, or any contiguous float64 device tensor of that shape: (lo, hi) device
+        tensors (B, T), ``np.percentile(coefs_boot, [(100 - ci) / 2, 100 - (100 - ci) / 2], axis=-1)`` of
+        ``coefs_boot[f, t, b] = (Xc.T @ stack[b].T)[f, t]`` without that array ever existing (plsx_simpls_coef_ci).  No
+        sync.  PlsxError status -2 (context still usable) for n > 16384 or a stack that does not fit the scratch
+        budget."""
+        torch = _torch()
+        if stack.dim() != 3 or tuple(stack.shape[1:]) != (self.T, self.S) or stack.dtype != torch.float64 \
+                or not stack.is_contiguous():
+            raise ValueError('the stack must be a contiguous (n, {}, {}) float64 tensor'.format(self.T, self.S))
+        n = int(stack.shape[0])
+        idx = _virtual_indices(max(n, 1), ci)
+        lo, hi = self._empty((self.B, self.T)), self._empty((self.B, self.T))
+        self._check(self.lib.plsx_simpls_coef_ci(self.ctx, stack.data_ptr(), n, idx[0][0], idx[0][1], idx[1][0],
+                                                 idx[1][1], lo.data_ptr(), hi.data_ptr(), self._stream()))
+        return lo, hi
 
     def simpls_boot_into(self, idx_dev, usum, usq, yl_dev, ystack=None):
         """idx_dev (n, S) int32; usum / usq (B, k) accumulated in place; yl_dev (n, T, k);

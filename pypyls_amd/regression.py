@@ -31,6 +31,9 @@ Differences from the reference at this commit, on purpose:
     ``bootres.coefs_stderr`` / ``coefs_normed``, one map per behaviour.  The coefficients depend on neither the signs
     nor the order of the components, so their bootstrap needs no alignment (plsx_simpls_coef_begin / _finish;
     csrc/plsx_simpls.h, k_sd_coef).  :func:`predict` applies the model of any ``pls_regression`` result to new rows.
+    ``coef_ci=True`` adds ``bootres.coefs_ci``, the percentile interval of every coefficient over the bootstraps: the
+    series keeps every bootstrap's coefficients in subject space and one closing pass over the features forms and
+    reduces their series chunk by chunk (plsx_simpls_coef_keep / plsx_simpls_coef_ci; csrc/plsx_k_coefci.h).
 """
 import numpy as np
 
@@ -95,7 +98,8 @@ def _check_cvsplits(masks, usable, k, B):
 
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
-                   n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, **kwargs):
+                   n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
+                   **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -118,7 +122,14 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     ``Y ~ intercept + X @ coefs`` (means over the rows the fit used; 3-D Y: of the aggregated Y) and, with
     ``n_boot > 0``, ``bootres.coefs_stderr`` / ``bootres.coefs_normed`` (B, T): the standard error of the coefficients
     over the bootstraps and the coefficients over it, with the original added back (n = n_boot + 1) as for
-    ``x_weights_normed``.  No random draw is added or moved.  :func:`predict` applies the model to new rows."""
+    ``x_weights_normed``.  No random draw is added or moved.  :func:`predict` applies the model to new rows.
+
+    ``coef_ci=True`` (needs ``coef_components`` and ``n_boot > 0``; False, the default: nothing is added and no memory
+    is taken) adds ``bootres.coefs_ci`` (B, T, 2), ``[..., 0]`` the lower and ``[..., 1]`` the upper bound of the
+    ``ci`` % percentile interval of every coefficient over the ``n_boot`` bootstraps (numpy's linear interpolation;
+    as for ``y_loadings_ci`` the original fit is not added to the series).  The (B, T, n_boot) coefficients exist on the
+    device only, one chunk of features at a time; what is kept is 8 T S n_boot bytes (on every GPU of a team: the
+    closing pass runs on the first).  ``n_boot`` <= 16384.  Every other array of the call keeps its bits."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -141,6 +152,22 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              .format(n_components, coef_components))
         coef_components = int(coef_components)
         kwargs['coef_components'] = coef_components        # (recorded in `inputs` only when asked for)
+    if isinstance(coef_ci, (bool, np.bool_)):
+        coef_ci = bool(coef_ci)
+    else:
+        raise ValueError('Provided `coef_ci` must be True or False; got {!r}'.format(coef_ci))
+    if coef_ci:                                    # (as above: on the host, before any engine)
+        if coef_components is None:
+            raise ValueError('`coef_ci` needs `coef_components`: the intervals are those of the coefficients of the '
+                             'model of that many components')
+        if not n_boot or n_boot < 1:
+            raise ValueError('`coef_ci` needs bootstraps: n_boot = {!r}'.format(n_boot))
+        if n_boot > 16384:
+            raise ValueError('`coef_ci` takes n_boot <= 16384, the bound of the device\'s percentile kernels; got {}.  '
+                             'There is no host fallback: the (B, T, n_boot) coefficients ({:.1f} GB here) exist on the '
+                             'device only, one chunk of features at a time'
+                             .format(n_boot, 8.0 * X.shape[1] * Y.shape[1] * n_boot / 2 ** 30))
+        kwargs['coef_ci'] = True                   # (recorded in `inputs` only when asked for)
     S = len(X)
     agg = None
     third = None                                   # (C, n_boot) third-axis resamples for 3-D Y
@@ -283,7 +310,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             res = team.run(lambda rank, world, e: _run_device(
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
                 k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
-                coef_c=coef_components))
+                coef_c=coef_components, coef_ci=coef_ci))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -292,7 +319,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 try:
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
-                                      kwargs.get('_emulate'), cv=cv, coef_c=coef_components)
+                                      kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -306,7 +333,8 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
-                bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None):
+                bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None,
+                coef_ci=False):
     import time
     import torch
     S = len(X)
@@ -367,7 +395,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
 
     # this rank's shards (permutations contiguous, bootstraps chunk-cyclic), launched chunk by chunk as the index rows arrive; the
     # results stay on the device until the one collective
-    d_perm = d_yl = usum = usq = bsum = bsq = None
+    d_perm = d_yl = usum = usq = bsum = bsq = d_keep = None
     n_perm_tot = pstream.n if pstream is not None else 0
     n_boot_tot = bstream.n if bstream is not None else 0
     from .progress import Bar                            # verbose=True: the reference's bars (pyls/utils.py:128-152)
@@ -393,6 +421,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             # the coefficients of the coef_c-component model ride along every solver batch (plsx_simpls_coef_begin)
             bsum, bsq = eng._zeros((B, T)), eng._zeros((B, T))
             eng.simpls_coef_begin(coef_c)
+            if coef_ci:
+                # ... and the series keeps every A_b of this rank's share, (n_local, T, S): the source of the intervals
+                d_keep = eng._empty((sum(hi - lo for lo, hi in bchunks), T, S))
+                if d_keep.shape[0]:
+                    eng.simpls_coef_keep(d_keep)
         bars.append(Bar('Running bootstraps', sum(hi - lo for lo, hi in bchunks), show, eng.device))
         # 3-D Y: a (n, S, T) Y stack per chunk, at most 256 of them and at most 256 MB (S = 24 000, T = 20: 69 rows)
         ylim = max(1, min(256, (256 << 20) // (S * T * 8)))
@@ -455,16 +488,26 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     cyclic = [len(slices) - 1] if d_yl is not None else []
     if d_cv is not None:                                # the cross-validation rows ride in the same buffer: ONE collective
         slices, totals = slices + d_cv, totals + [cv['n']] * 3
+    if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
+        slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
+        cyclic = cyclic + [len(slices) - 1]
     sums = [t for t in (usum, usq, bsum, bsq) if t is not None]      # (the coefficient sums join the summed part)
     full, summed = parallel.collect_device(slices, totals, sums, emulate=emulate, cyclic=cyclic, team=team)
     if not lead:
         return None                                     # rank 0 holds everything the ranks computed: it finishes
+    d_stack = full.pop() if d_keep is not None else None           # (stays on the device)
+    d_keep = None
     full = [t.detach().cpu().numpy() for t in full]
     if usum is not None:
         usum, usq = summed[:2]
     if bsum is not None:
         bsum, bsq = summed[2:4]
     tick('collective')
+    d_cci = None
+    if d_stack is not None:
+        # the closing pass over the features, on the lead rank, over the gathered stack (plsx_simpls_coef_ci)
+        d_cci = eng.simpls_coef_ci(d_stack.contiguous(), ci=ci)
+        tick('coefs_ci')
     i = 0
     d_perm = distrib = None
     if pstream is not None:
@@ -510,6 +553,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                                            add_orig=True)
             eng.sync()
             res['bootres'].update(dict(coefs_normed=d_cn.cpu().numpy(), coefs_stderr=d_cse.cpu().numpy()))
+        if d_cci is not None:
+            res['bootres']['coefs_ci'] = np.stack([d_cci[0].cpu().numpy(), d_cci[1].cpu().numpy()], -1)
     res['varexp'] = pctvar                                          # regression.py:425-426
     tick('host_finish')
     return res

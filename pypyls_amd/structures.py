@@ -92,6 +92,7 @@ class PLSInputs(KeyedRecord):
         'ci', 'seed', 'verbose', 'n_proc', 'bootsamples', 'permsamples',
         'method', 'n_components', 'aggfunc', 'permindices',
         'coef_components',                  # pls_regression: component count of the returned model (only when asked for)
+        'coef_ci',                          # pls_regression: percentile intervals of its coefficients (only when asked for)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
     )
@@ -121,7 +122,10 @@ class PLSBootResults(KeyedRecord):
                'contrast', 'contrast_boot', 'contrast_ci',
                # pls_regression(coef_components=c): standard error of the model coefficients over the bootstraps and
                # the coefficients over it, (B, T) -- one map per behaviour
-               'coefs_stderr', 'coefs_normed')
+               'coefs_stderr', 'coefs_normed',
+               # pls_regression(coef_components=c, coef_ci=True): (B, T, 2) lower / upper percentile bound of the
+               # coefficients over the n_boot bootstraps (the original is not added to the series, as for y_loadings_ci)
+               'coefs_ci')
 
 
 class PLSPermResults(KeyedRecord):
