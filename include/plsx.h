@@ -294,6 +294,38 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           regression data; PLSX_ERR_STATE otherwise.  Every split
  *                           needs >= 2 usable test rows and k <= n_train - 1 (the
  *                           caller checks).  Bit-reproducible run to run.
+ *   plsx_simpls_crossval_perm_batch  the null of that cross-validation under
+ *                           permuted Y: for each of m permutations and each of the
+ *                           SAME n splits, SIMPLS with k components on the training
+ *                           positions of (X, Y[perm]) -- X keeps its rows, position
+ *                           p takes row perm[p] of Y, as plsx_simpls_perm_batch --
+ *                           the test positions predicted and scored exactly as
+ *                           plsx_simpls_crossval_batch scores them, against the
+ *                           permuted Y; then the PLAIN MEAN over the n splits.
+ *                           d_masks (n, S) uint8, 1 = training row; d_perm_idx
+ *                           (m, S) int32, one permutation of 0 .. S-1 per row.
+ *                           d_r, d_r2 (m, k, T) out: mean over the splits of the
+ *                           test-row Pearson r / R^2 of the c-component model;
+ *                           d_mse (m, k + 1) out: mean over the splits of
+ *                           sum_t sse / n_test, row 0 = intercept only.  With row
+ *                           masks a position is usable iff okx[p] and oky[perm[p]]
+ *                           (get_mask(X, Y[perm])), so n_test belongs to the
+ *                           (permutation, split) pair and the division is done
+ *                           here; a pair with fewer than two usable test rows
+ *                           gives NaN.  The m n fits (counted in 64 bits) run in
+ *                           solver batches sized like plsx_simpls_crossval_batch's;
+ *                           their Y sources and masks are expanded on the device
+ *                           (k_sd_cvp_expand), scored by k_sd_cv_score<., true>
+ *                           and reduced by k_sd_cvp_reduce: split by split in
+ *                           ascending order, the running sum carried in the output
+ *                           across solver batches, divided by n after the last --
+ *                           no floating-point atomics, the same bits whatever the
+ *                           batch size or the scratch budget (plsx_set_scratch) and
+ *                           however the permutations are spread over contexts.
+ *                           Per-fit scores exist in scratch of one batch only.
+ *                           No bound on m beyond the outputs.  PLSX_ERR_STATE
+ *                           without bound regression data; PLSX_ERR_ARG for a null
+ *                           pointer, n < 1 or m < 1.
  *   plsx_simpls_coef_begin / plsx_simpls_coef_finish
  *                           a coefficient series that rides along the bootstrap
  *                           batches: the model of the first c components,
@@ -371,6 +403,8 @@ int plsx_simpls_boot_batch(plsx_ctx* ctx, const int32_t* d_boot_idx, const doubl
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream);
 int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2,
                                double* d_sse, void* stream);
+int plsx_simpls_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                                    double* d_r, double* d_r2, double* d_mse, void* stream);
 int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream);
 int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* stream);
 int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity);
@@ -431,7 +465,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
 /* Summed duration (ms) and launch count of one kernel class since timing was
  * enabled: 0 k_xprod (cross-product), 1 k_gram / k_gram4 (+ partial reduce),
  * 2 k_small / k_small_ql (eigen-solve + Procrustes), 3 k_urot (+ split add), 4 k_nt_gemm
- * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 11 k_coef_prod (the feature pass of
+ * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 9 k_sd_cv_score (with the pair expansion and the
+ * reduction over the splits of plsx_simpls_crossval_perm_batch), ..., 11 k_coef_prod (the feature pass of
  * plsx_simpls_coef_ci), 12 k_percentile (selection / sort of plsx_percentile_ci and plsx_simpls_coef_ci).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */

@@ -94,6 +94,10 @@ struct plsx_ctx {
     Buf Xn, out_row_f, mom_idx_f;                       // fixed-X fast path
     Buf Kd, Ad, Wd;                                     // dual permutation path (S x S kernel)
     Buf Zcv;                                            // SIMPLS cross-validation: Z = Vd . K, the scores of a batch of splits [n][k][S]
+    // SIMPLS cross-validation under permuted Y (plsx_simpls_crossval_perm_batch): the (permutation, split) fits of a solver
+    // batch -- their Y sources [n][S] int32 and training masks [n][S] bytes, expanded on the device -- and their scores
+    // r, R^2 [n][k][T], sse [n][k + 1][T], usable test rows [n]
+    Buf cvpsrc, cvpfit;
     Buf Qs;                                             // SIMPLS: Xc . W0c^T (S x k), sign alignment of the bootstrap in dual space
     Buf ScT, out_row_w;                                 // single-pass bootstrap (unscaled modes): scores^T (L x S), row -> l map
     int npg_w = 0;                                      // resamples per group of the W operand (MT * 16 / L)

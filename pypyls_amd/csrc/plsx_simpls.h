@@ -116,6 +116,7 @@ struct SdArgs {
     double* cvr;                // [nres][k][T] Pearson r of the nested predictions on the test rows
     double* cvr2;               // [nres][k][T] R^2
     double* cvsse;              // [nres][k + 1][T] squared error summed over the test rows (row 0: intercept only)
+    double* cvnte;              // [nres] usable test rows of the fit (k_sd_cv_score<RC, true> only: they depend on the permutation)
     // coefficient series (plsx_simpls_coef_begin): k_sd_coef runs on resamples cf_r0 .. cf_r0 + cf_n - 1 of the batch
     double* cfA;                // [cf_n][T][S] A_b = sum_{j < cf_c} wd_j q_j^T scattered to subject space (every entry written), or nullptr
     double* cfq;                // [cf_n][cf_c][T] q_j = Y0^T t_j (simpls y_loadings of the resample)
@@ -1276,7 +1277,13 @@ void k_sd_final(SdArgs a)
 // of the scores), reductions are wave_sum4 in fixed order.  One wavefront per split, lanes over positions; no LDS on
 // either route: the running prediction lives in the split's `va` (idle once the solver is through), every position
 // of every S-long vector is only ever touched by the lane that owns it.  Four components at a time.
-template <int RC>
+//
+// PERM (plsx_simpls_crossval_perm_batch): the fit ran on (X, Y[ysrc]); the observed row of position p is row ys[p] of Y
+// and the position is usable iff okx[p] and oky[ys[p]] -- get_mask(X, Y[perm]).  The loads of Y go through the fit's
+// `ys` (a gather of rows of T doubles); everything else, the order of every reduction included, is the identity
+// variant's, whose instantiations are what they were.  The usable test rows of the fit go out too (cvnte): under a
+// permutation they are not the split's own.
+template <int RC, bool PERM = false>
 static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SD_WPE)))
 void k_sd_cv_score(SdArgs a)
 {
@@ -1288,6 +1295,8 @@ void k_sd_cv_score(SdArgs a)
     const double* Y0 = a.Y0 + (size_t)r * S * T;
     const double* ym = a.ymean + (size_t)r * T;
     const double* Yc = a.Yc;                               // identity sources: the observed row of position p is row p
+    const int* ysp = a.ys + (size_t)r * S;                 // (PERM: ... is row ys[p])
+    auto yrow = [&](int p) { if constexpr (PERM) return ysp[p]; else return p; };
     double* Z = a.cvZ + (size_t)r * k * S;
     double* yh = a.va + (size_t)r * S;
     double* out_r = a.cvr + (size_t)r * k * T;
@@ -1295,7 +1304,7 @@ void k_sd_cv_score(SdArgs a)
     double* out_sse = a.cvsse + (size_t)r * (k + 1) * T;
     const double ninc = a.scal[(size_t)r * 4];
     // usable test position: outside the training mask and not a masked (all-NaN) row
-    auto is_test = [&](int p) { return !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[p]); };
+    auto is_test = [&](int p) { return !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[yrow(p)]); };
     // ---- scores of every position, centred by their training mean (in place)
     for (int j0 = 0; j0 < k; j0 += 4) {
         double* z0 = Z + (size_t)min(j0, k - 1) * S;
@@ -1330,16 +1339,18 @@ void k_sd_cv_score(SdArgs a)
     double cnt = 0.0;
     for (int p = lane; p < S; p += 64) cnt += is_test(p) ? 1.0 : 0.0;
     const double nte = wave_sum(cnt);
+    if constexpr (PERM)
+        if (lane == 0) a.cvnte[r] = nte;
     for (int t = 0; t < T; ++t) {
         const double ymt = ym[t];
         // observed test values: mean, then the sums of squares about it and about the training mean
         double sy = 0.0;
-        for (int p = lane; p < S; p += 64) sy += is_test(p) ? Yc[(size_t)p * T + t] : 0.0;
+        for (int p = lane; p < S; p += 64) sy += is_test(p) ? Yc[(size_t)yrow(p) * T + t] : 0.0;
         const double ybar = wave_sum(sy) / nte;
         double syy = 0.0, se0 = 0.0;
         for (int p = lane; p < S; p += 64) {
             const bool te = is_test(p);
-            const double y = Yc[(size_t)p * T + t];
+            const double y = Yc[(size_t)yrow(p) * T + t];
             const double d = y - ybar, e = y - ymt;
             syy += te ? d * d : 0.0;
             se0 += te ? e * e : 0.0;
@@ -1381,7 +1392,7 @@ void k_sd_cv_score(SdArgs a)
                 SD_TILE_PC(pc, p0);
                 SD_OWN(i) {
                     const bool te = SD_IN(p0, i) && is_test(pc[i]);
-                    const double y = Yc[(size_t)pc[i] * T + t];
+                    const double y = Yc[(size_t)yrow(pc[i]) * T + t];
                     const double zz[4] = {z0[pc[i]], z1[pc[i]], z2[pc[i]], z3[pc[i]]};
                     double pred = c0 == 0 ? ymt : yh[pc[i]];
                     const double dy = y - ybar;
@@ -1407,6 +1418,59 @@ void k_sd_cv_score(SdArgs a)
                     out_sse[(size_t)(c0 + u + 1) * T + t] = se[u];
                 }
         }
+    }
+}
+
+// Cross-validation under permuted Y: the (permutation, split) fits f0 .. f0 + ms - 1 of the pair list, fit f = permutation
+// f / n under split f % n (64-bit: P n overflows an int long before memory does).  The solver's per-fit Y sources and
+// position masks are expanded here from the m permutation rows and the n mask rows, so 5 S bytes per fit never leave
+// the host.  grid (ceil(S / 256), ms).
+static __global__ __launch_bounds__(256)
+void k_sd_cvp_expand(const int* __restrict__ perm, const uint8_t* __restrict__ masks, int S, int n, long long f0,
+                     int* __restrict__ ysrc, uint8_t* __restrict__ pmask)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= S) return;
+    const long long f = f0 + blockIdx.y;
+    const long long pi = f / n, si = f % n;
+    ysrc[(size_t)blockIdx.y * S + p] = perm[(size_t)pi * S + p];
+    pmask[(size_t)blockIdx.y * S + p] = masks[(size_t)si * S + p];
+}
+
+// ... and their reduction over the splits: out_r / out_r2 [.][k][T] and out_mse [.][k + 1] of permutation pi take the
+// scores of its fits in this batch, added ONE BY ONE IN SPLIT ORDER to what the earlier batches left there (the entry
+// starts from zero), and are divided by n once the last split is in.  The running sum is carried through the output
+// itself, so a permutation whose splits straddle solver batches is summed in exactly the association of one that does
+// not: the same bits whatever the batch size.  One thread per output entry, no atomics.  mse of a fit: the squared
+// errors summed over the behaviours in ascending t, over the fit's own usable test rows.  grid (ceil(E / 256), perms
+// touched), E = 2 k T + k + 1; pi0 = f0 / n.
+static __global__ __launch_bounds__(256)
+void k_sd_cvp_reduce(const double* __restrict__ r, const double* __restrict__ r2, const double* __restrict__ sse,
+                     const double* __restrict__ nte, int k, int T, int n, long long f0, int ms,
+                     double* __restrict__ out_r, double* __restrict__ out_r2, double* __restrict__ out_mse)
+{
+    const int kT = k * T, e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 2 * kT + k + 1) return;
+    const long long pi = f0 / n + blockIdx.y;
+    const long long lo = pi * n > f0 ? pi * n : f0, end = (pi + 1) * n < f0 + ms ? (pi + 1) * n : f0 + ms;
+    const bool last = end == (pi + 1) * n;
+    if (e < 2 * kT) {
+        const double* src = e < kT ? r + e : r2 + (e - kT);
+        double* dst = e < kT ? out_r + (size_t)pi * kT + e : out_r2 + (size_t)pi * kT + (e - kT);
+        double acc = *dst;
+        for (long long f = lo; f < end; ++f) acc += src[(size_t)(f - f0) * kT];
+        *dst = last ? acc / n : acc;
+    } else {
+        const int c = e - 2 * kT;
+        double* dst = out_mse + (size_t)pi * (k + 1) + c;
+        double acc = *dst;
+        for (long long f = lo; f < end; ++f) {
+            const double* row = sse + ((size_t)(f - f0) * (k + 1) + c) * T;
+            double s = 0.0;
+            for (int t = 0; t < T; ++t) s += row[t];
+            acc += s / nte[f - f0];
+        }
+        *dst = last ? acc / n : acc;
     }
 }
 

@@ -373,6 +373,85 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+int plsx_simpls_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                                    double* d_r, double* d_r2, double* d_mse, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_crossval_perm_batch: data not bound for regression");
+    if (!d_masks || !d_perm_idx || !d_r || !d_r2 || !d_mse || n < 1 || m < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_crossval_perm_batch: bad arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    const bool gl = simpls_global(ctx);
+    // the pair list: fit f = permutation f / n under split f % n, m n of them (64-bit), cut into solver batches sized
+    // as plsx_simpls_crossval_batch sizes its own; a fit also holds its expanded sources and mask (5 S bytes) and
+    // its scores until the reduction over the splits
+    const long long fits = (long long)m * n;
+    const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T + 1;       // doubles of scores per fit
+    const double extra = 2.0 * k * S * 8.0 + 5.0 * S + 8.0 * per_fit;
+    int nb = (int)std::min<long long>(fits, sd_batch(ctx, 8192, 1, extra));
+    // a tail of less than an eighth of a batch is a whole latency chain for a handful of fits (8200 fits: 8 of them
+    // cost a sixth of the 8192 before): spread it over the batches before it where the budget allows -- the bits do not
+    // depend on where a batch ends (k_sd_cvp_reduce)
+    if (fits > nb && fits % nb != 0 && fits % nb < nb / 8) {
+        const long long full = fits / nb, bs = (fits + full - 1) / full;
+        if (sd_batch(ctx, (int)bs, 1, extra) == (int)bs) nb = (int)bs;
+    }
+    if (int e = ensure(ctx, ctx->spct, (size_t)nb * (T + 1) * k * 8)) return e;     // pctvar [nb][k], y-loadings [nb][T][k]
+    if (int e = ensure(ctx, ctx->sc, (size_t)nb * T * k * 8)) return e;
+    if (int e = ensure(ctx, ctx->Vdq, (size_t)nb * k * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->Zcv, (size_t)nb * k * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->cvpsrc, (size_t)nb * S * 5)) return e;
+    if (int e = ensure(ctx, ctx->cvpfit, (size_t)nb * per_fit * 8)) return e;
+    const double* K = ptr<double>(ctx->Kmat);
+    double* Vd = ptr<double>(ctx->Vdq);
+    double* Z = ptr<double>(ctx->Zcv);
+    int* ysrc = ptr<int>(ctx->cvpsrc);
+    uint8_t* pmask = reinterpret_cast<uint8_t*>(ysrc + (size_t)nb * S);
+    double* fr = ptr<double>(ctx->cvpfit);
+    double* fr2 = fr + (size_t)nb * kT;
+    double* fsse = fr2 + (size_t)nb * kT;
+    double* fnte = fsse + (size_t)nb * (k + 1) * T;
+    // the running sums over the splits live in the outputs (k_sd_cvp_reduce)
+    HIPCHK(hipMemsetAsync(d_r, 0, (size_t)m * kT * 8, st));
+    HIPCHK(hipMemsetAsync(d_r2, 0, (size_t)m * kT * 8, st));
+    HIPCHK(hipMemsetAsync(d_mse, 0, (size_t)m * (k + 1) * 8, st));
+    for (long long f0 = 0; f0 < fits; f0 += nb) {
+        const int ms = (int)std::min<long long>(nb, fits - f0);
+        {
+            KTimer tm(ctx, KC_CVSCORE, st);
+            hipLaunchKernelGGL(k_sd_cvp_expand, dim3(ceil_div(S, 256), ms), dim3(256), 0, st, d_perm_idx, d_masks, S, n, f0,
+                               ysrc, pmask);
+            LAUNCHCHK();
+        }
+        SdArgs a;
+        // the fit on the training positions of (X, Y[perm]): X keeps its rows, Y takes the permutation's (as
+        // plsx_simpls_perm_batch), the test positions are excluded (as plsx_simpls_crossval_batch), weights wanted
+        if (int e = run_simpls_dual(ctx, nullptr, ysrc, ms, true, ptr<double>(ctx->spct),
+                                    ptr<double>(ctx->spct) + (size_t)nb * k, ptr<double>(ctx->sc), st, nullptr, false, Vd,
+                                    pmask, &a))
+            return e;
+        // ONE product with K: the scores of all k nested models at every row, training and test
+        if (gl) {
+            if (int e = nt_strips(ctx, Vd, S, ms * k, K, S, S, S, Z, S, st)) return e;
+        } else if (int e = run_nt(ctx, Vd, 0, S, ms * k, K, 0, S, S, nullptr, 0, 0, 0, S, 1, Z, 0, S, nullptr, 0, 0, st))
+            return e;
+        a.cvZ = Z;
+        a.cvr = fr; a.cvr2 = fr2; a.cvsse = fsse; a.cvnte = fnte;
+        KTimer tm(ctx, KC_CVSCORE, st);
+        void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8, true> : k_sd_cv_score<16, true>;
+        hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+        LAUNCHCHK();
+        const int touched = (int)((f0 + ms - 1) / n - f0 / n) + 1;
+        hipLaunchKernelGGL(k_sd_cvp_reduce, dim3(ceil_div((int)(2 * kT) + k + 1, 256), touched), dim3(256), 0, st,
+                           fr, fr2, fsse, fnte, k, T, n, f0, ms, d_r, d_r2, d_mse);
+        LAUNCHCHK();
+    }
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
 int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream)
 try {
     NEED_DATA();

@@ -89,6 +89,7 @@ def _load():
         'plsx_simpls_boot_batch': ([vp, vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_set_row_masks': ([vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_simpls_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_coef_begin': ([vp, i32, vp], i32),
         'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
         'plsx_simpls_coef_keep': ([vp, vp, ctypes.c_longlong], i32),
@@ -128,7 +129,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -762,6 +763,25 @@ class Engine(object):
                 raise ValueError('cross-validation outputs must be contiguous (m, k, T), (m, k, T) and (m, k + 1, T)')
         self._check(self.lib.plsx_simpls_crossval_batch(self.ctx, masks_dev.data_ptr(), m, r_dev.data_ptr(),
                                                         r2_dev.data_ptr(), sse_dev.data_ptr(), self._stream()))
+
+    def simpls_crossval_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev, mse_dev):
+        """masks_dev (n, S) uint8, 1 = training row: the observed splits; idx_dev (m, S) int32, one permutation of the
+        rows of Y per row.  r_dev / r2_dev (m, k, T): per permutation the mean over the n splits of the test-row Pearson
+        r and R^2 of the first c = 1 .. k components; mse_dev (m, k + 1): the mean over the splits of the squared error
+        per usable test row, row 0 the intercept-only model (plsx_simpls_crossval_perm_batch)."""
+        torch = _torch()
+        n, m = masks_dev.shape[0], idx_dev.shape[0]
+        if tuple(masks_dev.shape) != (n, self.S) or masks_dev.dtype != torch.uint8 or not masks_dev.is_contiguous():
+            raise ValueError('split masks must be a contiguous (n, {}) uint8 tensor'.format(self.S))
+        if tuple(idx_dev.shape) != (m, self.S) or idx_dev.dtype != torch.int32 or not idx_dev.is_contiguous():
+            raise ValueError('permutations must be a contiguous (m, {}) int32 tensor'.format(self.S))
+        for t, shape in ((r_dev, (m, self.k, self.T)), (r2_dev, (m, self.k, self.T)), (mse_dev, (m, self.k + 1))):
+            if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('permuted cross-validation outputs must be contiguous float64 (m, k, T), (m, k, T) and '
+                                 '(m, k + 1)')
+        self._check(self.lib.plsx_simpls_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
+                                                             r_dev.data_ptr(), r2_dev.data_ptr(), mse_dev.data_ptr(),
+                                                             self._stream()))
 
     def simpls_coef_begin(self, c):
         """Open a coefficient series for the model of the first ``c`` components: until :meth:`simpls_coef_finish`

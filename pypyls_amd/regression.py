@@ -34,6 +34,10 @@ Differences from the reference at this commit, on purpose:
     ``coef_ci=True`` adds ``bootres.coefs_ci``, the percentile interval of every coefficient over the bootstraps: the
     series keeps every bootstrap's coefficients in subject space and one closing pass over the features forms and
     reduces their series chunk by chunk (plsx_simpls_coef_keep / plsx_simpls_coef_ci; csrc/plsx_k_coefci.h).
+  * ``cv_perm=P`` tests the cross-validated scores against chance: the whole cross-validation, the same splits, on
+    ``(X, Y[perm])`` for P permutations; the (permutation, split) fits are formed, scored against the permuted Y and
+    averaged over the splits in a fixed order on the device (plsx_simpls_crossval_perm_batch; csrc/plsx_simpls.h,
+    k_sd_cvp_expand / k_sd_cv_score<RC, true> / k_sd_cvp_reduce).
 """
 import numpy as np
 
@@ -99,7 +103,7 @@ def _check_cvsplits(masks, usable, k, B):
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
-                   **kwargs):
+                   cv_perm=0, cvpermsamples=None, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -129,7 +133,20 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     ``ci`` % percentile interval of every coefficient over the ``n_boot`` bootstraps (numpy's linear interpolation;
     as for ``y_loadings_ci`` the original fit is not added to the series).  The (B, T, n_boot) coefficients exist on the
     device only, one chunk of features at a time; what is kept is 8 T S n_boot bytes (on every GPU of a team: the
-    closing pass runs on the first).  ``n_boot`` <= 16384.  Every other array of the call keeps its bits."""
+    closing pass runs on the first).  ``n_boot`` <= 16384.  Every other array of the call keeps its bits.
+
+    Permutation test of the cross-validation: ``cv_perm=P`` (needs cross-validation; 0, the default: nothing is added,
+    no memory is taken) repeats the whole cross-validation -- the SAME splits -- on ``(X, Y[perm])`` for P permutations
+    of the rows of Y (3-D Y: of the aggregated Y), drawn with ``gen_permsamp([S], 1, P)`` after everything else the call
+    draws, the split masks included, or given as ``cvpermsamples`` (S, P), one permutation of 0 .. S-1 per column.  The
+    null statistic of a permutation is the plain mean over the splits.  ``cvres`` gains ``perm_pearson_r`` /
+    ``perm_r_squared`` (T, n_components, P), ``perm_mse`` (n_components + 1, P), ``pearson_r_pvals`` /
+    ``r_squared_pvals`` (T, n_components) = (#{null > observed split-mean} + 1) / (P + 1), ``mse_pvals``
+    (n_components + 1,) = (#{null < observed} + 1) / (P + 1) -- smaller is better -- and ``cvpermsamples``.  With rows
+    that are NaN throughout, position p is usable under a permutation iff row p of X and row perm[p] of Y are; a
+    (permutation, split) pair with fewer than two usable test rows gives NaN.  The P x test_split fits run and are
+    reduced over the splits on the device (plsx_simpls_crossval_perm_batch); only P rows come back.  Every array the
+    call returned before keeps its bits."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -168,6 +185,15 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              'device only, one chunk of features at a time'
                              .format(n_boot, 8.0 * X.shape[1] * Y.shape[1] * n_boot / 2 ** 30))
         kwargs['coef_ci'] = True                   # (recorded in `inputs` only when asked for)
+    if isinstance(cv_perm, (bool, np.bool_)) or not isinstance(cv_perm, (int, np.integer)) or cv_perm < 0:
+        raise ValueError('Provided `cv_perm` must be a non-negative integer; got {!r}'.format(cv_perm))
+    cv_perm = int(cv_perm)
+    if cv_perm > 0:                                # (as above: on the host, before any engine)
+        if not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+            raise ValueError('`cv_perm` needs cross-validation: it permutes Y under the splits of `test_split` > 0 with '
+                             '`test_size` > 0 (drawn, or given as `cvsamples`); got test_split = {!r}, test_size = {!r}'
+                             .format(test_split, test_size))
+        kwargs['cv_perm'] = cv_perm                # (recorded in `inputs` only when asked for)
     S = len(X)
     agg = None
     third = None                                   # (C, n_boot) third-axis resamples for 3-D Y
@@ -249,6 +275,28 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 raise ValueError('Provided `n_components` cannot be greater than {} when cross-validating: the '
                                  'smallest training set has {} usable rows'
                                  .format(max(min(lo_tr - 1, X.shape[1]), 0), max(lo_tr, 0)))
+    cvperm = None
+    if cv_perm > 0:
+        if cvpermsamples is not None:
+            from .engine import check_index_array as _check_idx
+            cvperm = np.asarray(cvpermsamples)
+            if cvperm.ndim != 2 or cvperm.shape != (S, cv_perm):
+                raise ValueError('Provided `cvpermsamples` must have shape (S, cv_perm) = ({}, {}); got {}'
+                                 .format(S, cv_perm, cvperm.shape))
+            cvperm = _check_idx(cvperm, S)
+            if not np.array_equal(np.sort(cvperm, axis=0), np.broadcast_to(np.arange(S)[:, None], cvperm.shape)):
+                bad = int(np.flatnonzero((np.sort(cvperm, axis=0) != np.arange(S)[:, None]).any(axis=0))[0])
+                raise ValueError('Provided `cvpermsamples` must hold one permutation of 0 .. {} per column; column {} '
+                                 'is not one'.format(S - 1, bad))
+        # rows that are NaN throughout: position p is usable iff row p of X and row perm[p] of Y are, so a permutation
+        # can leave every masked row of X and of Y on the training side of one split
+        ok_y = ~np.isnan(Y_agg).all(axis=1)
+        n_bad_p = int((~_usable_rows(X, np.zeros((S, 1)))).sum()) + int((~ok_y).sum())
+        lo_tr = (int(cvmasks.sum(axis=0).min()) if cvmasks is not None else int(np.floor(S * (1 - test_size)))) - n_bad_p
+        if n_bad_p and n_components > min(lo_tr - 1, X.shape[1]):
+            raise ValueError('Provided `n_components` cannot be greater than {} when permuting the cross-validation: '
+                             'a permutation can leave {} usable training rows'
+                             .format(max(min(lo_tr - 1, X.shape[1]), 0), max(lo_tr, 0)))
     rs = resampling.check_random_state(seed)
     k = n_components
     B, T = X.shape[1], Y_agg.shape[1]
@@ -290,6 +338,14 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             def cv_draw(r):
                 cv['masks'] = resampling.gen_splits([S], 1, n_cv, seed=r, test_size=test_size)
             jobs.append(cv_draw)
+        if cv_perm > 0:
+            # ... and the permutations of the cross-validation one more, behind the split masks
+            if cvperm is None:
+                cv['pstream'] = resampling.IndexStream('perm', [S], 1, cv_perm)
+                jobs.append(cv['pstream'].draw)
+            else:
+                cv['pstream'] = resampling.IndexStream.of_array(cvperm)
+            cv['perm_given'] = cvperm
     from .engine import default_engine, touch_idle_release
     from . import team as _team
     touch_idle_release()                               # (a pending idle release is pushed back before the engine is looked up)
@@ -476,6 +532,27 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 done.poll()
             bars[-1].queued(b - a)
         tick('crossval')
+    # ... and its permutation test: this rank's contiguous shard of the permutations under ALL the splits.  The
+    # (permutation, split) fits are formed, scored and reduced over the splits on the device; a rank keeps three rows
+    # per permutation.  (Calls of about eight solver batches: the bits do not depend on where a call ends.)
+    d_cvp = cvp = None
+    if cv is not None and cv.get('pstream') is not None:
+        cvp = cv['pstream']
+        lo, hi = parallel.shard_bounds(cvp.n, rank, world)
+        d_cvp = [eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k + 1))]
+        bars.append(Bar('Running cross-validation permutations', hi - lo, show, eng.device))
+        dm_all = torch.from_numpy(np.ascontiguousarray(cv['masks'].T, dtype=np.uint8)).to(eng.device)
+        step = max(1, 65536 // cv['n'])
+        for a in range(lo, hi, step):
+            b = min(hi, a + step)
+            cvp.wait(b)
+            eng.simpls_crossval_perm_into(dm_all, eng.rows_tensor(cvp.rows[a:b]), *(t[a - lo:b - lo] for t in d_cvp))
+            for done in bars:
+                done.poll()
+            bars[-1].queued(b - a)
+        if lead and cv.get('perm_given') is None:
+            cvp.warn()
+        tick('crossval_perm')
     for bar in bars:
         bar.watch()
     try:
@@ -488,6 +565,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     cyclic = [len(slices) - 1] if d_yl is not None else []
     if d_cv is not None:                                # the cross-validation rows ride in the same buffer: ONE collective
         slices, totals = slices + d_cv, totals + [cv['n']] * 3
+    if d_cvp is not None:                               # ... and the three rows per permutation of its permutation test
+        slices, totals = slices + d_cvp, totals + [cvp.n] * 3
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
@@ -523,6 +602,20 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             pearson_r=np.ascontiguousarray(cv_r[:, k - 1]), r_squared=np.ascontiguousarray(cv_r2[:, k - 1]),
             pearson_r_ncomp=cv_r, r_squared_ncomp=cv_r2, mse=cv_sse.sum(axis=0) / n_test[None, :],
             cvsamples=np.asarray(cv['masks'], dtype=bool)))
+        if d_cvp is not None:
+            # the null of the split-means: (T, k, P), (T, k, P), (k + 1, P); the observed statistic is the plain mean
+            # over the splits of what cvres holds
+            P = cvp.n
+            null_r, null_r2 = (np.ascontiguousarray(full[i + 3 + j].transpose(2, 1, 0)) for j in range(2))
+            null_mse = np.ascontiguousarray(full[i + 5].T)
+            obs_r, obs_r2 = cv_r.mean(axis=-1), cv_r2.mean(axis=-1)
+            obs_mse = res['cvres']['mse'].mean(axis=-1)
+            res['cvres'].update(dict(
+                perm_pearson_r=null_r, perm_r_squared=null_r2, perm_mse=null_mse,
+                pearson_r_pvals=hostmath.perm_sig(obs_r.ravel(), null_r.reshape(T * k, P)).reshape(T, k),
+                r_squared_pvals=hostmath.perm_sig(obs_r2.ravel(), null_r2.reshape(T * k, P)).reshape(T, k),
+                mse_pvals=hostmath.perm_sig(-obs_mse, -null_mse),          # (smaller is better: #{null < observed})
+                cvpermsamples=np.asarray(cv['perm_given']) if cv.get('perm_given') is not None else cvp.samples))
     if permsamp is not None:
         res['permres']['pvals'] = hostmath.perm_sig(pctvar, d_perm)
         res['permres']['permsamples'] = permsamp

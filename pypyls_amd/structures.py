@@ -93,6 +93,7 @@ class PLSInputs(KeyedRecord):
         'method', 'n_components', 'aggfunc', 'permindices',
         'coef_components',                  # pls_regression: component count of the returned model (only when asked for)
         'coef_ci',                          # pls_regression: percentile intervals of its coefficients (only when asked for)
+        'cv_perm',                          # pls_regression: permutations of the cross-validation (only when asked for)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
     )
@@ -140,7 +141,11 @@ class PLSSplitHalfResults(KeyedRecord):
 class PLSCrossValidationResults(KeyedRecord):
     # pearson_r_ncomp / r_squared_ncomp (T, k, n), mse (k + 1, n), cvsamples (S, n): pls_regression's cross-validation
     # per component count (no counterpart in the reference, which cross-validates behavioral PLS only)
-    allowed = ('pearson_r', 'r_squared', 'pearson_r_ncomp', 'r_squared_ncomp', 'mse', 'cvsamples')
+    # pls_regression(cv_perm=P): the null of the split-means under permuted Y -- perm_pearson_r / perm_r_squared
+    # (T, k, P), perm_mse (k + 1, P) -- its p-values (T, k), (T, k), (k + 1,) and the permutations (S, P)
+    allowed = ('pearson_r', 'r_squared', 'pearson_r_ncomp', 'r_squared_ncomp', 'mse', 'cvsamples',
+               'perm_pearson_r', 'perm_r_squared', 'perm_mse', 'pearson_r_pvals', 'r_squared_pvals', 'mse_pvals',
+               'cvpermsamples')
 
 
 class PLSResults(KeyedRecord):
