@@ -393,6 +393,64 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           8 T n bytes each) does not fit; PLSX_ERR_ARG for
  *                           n < 1, an index outside 0 .. n - 1, a null pointer;
  *                           PLSX_ERR_STATE without bound regression data.
+ *   plsx_simpls_vip_keep / plsx_simpls_vip_ci
+ *                           bootstrap standard errors and percentile intervals of
+ *                           the VIP scores (variable importance in projection) of
+ *                           the c-component model,
+ *                           VIP[f] = sqrt(B sum_a ssq_a w[f][a]^2 / |w_a|^2 / sum_a ssq_a),
+ *                           ssq_a = |y_loadings[:, a]|^2 (simpls' own), a < c.  A
+ *                           square root of a sum of squares over the components:
+ *                           no quadratic form of anything, so its spread needs
+ *                           every bootstrap's value per feature.
+ *                           _keep (after plsx_simpls_set_original): every
+ *                           bootstrap that later plsx_simpls_boot_batch calls
+ *                           solve is appended in submission order to the caller's
+ *                           d_G, `capacity` bootstraps of c S doubles, layout
+ *                           [bootstrap][c][S] (bootstrap-major, so that shards of
+ *                           several contexts concatenate).  Row a of bootstrap b
+ *                           is sqrt(ssq_a / (|w_a|^2 sum_j ssq_j)) a_a, a_a the dual
+ *                           weight of component a scattered to subject space
+ *                           (kernel k_sd_vip, one wavefront per bootstrap after the
+ *                           solver chain; |w_a|^2 = a_a^T K a_a is taken from the
+ *                           solver's own K_r wd_a, 2 S flop per component), so that
+ *                           VIP_b[f]^2 = B sum_a (sum_s Xc[s][f] G_b[a][s])^2.
+ *                           Independent of a coefficient series: both may be open,
+ *                           neither moves the other's bits, and everything else a
+ *                           batch computes keeps its bits on either route of the
+ *                           weights.  A plsx_simpls_boot_batch whose bootstraps no
+ *                           longer fit returns PLSX_ERR_ARG before it computes
+ *                           anything; _keep returns PLSX_ERR_STATE without bound
+ *                           regression data or before plsx_simpls_set_original,
+ *                           PLSX_ERR_ARG for c outside 1 .. k, a null buffer or
+ *                           capacity < 1.  plsx_set_data, plsx_simpls_set_original
+ *                           and a second _keep end the keeping (the buffer stays
+ *                           the caller's).
+ *                           _ci is stateless: for ANY stack d_G [n][c][S] and the
+ *                           bound, centred features it writes, per feature, d_sd
+ *                           (B,): the standard deviation with n - 1 in the
+ *                           denominator (NaN for n = 1), and d_lo, d_hi (B,): the
+ *                           two interpolated order statistics -- virtual indices
+ *                           (i, g) as for plsx_percentile_ci -- of
+ *                           { VIP_b[f] : b < n }.  Features go in chunks of whole
+ *                           128-feature blocks; per chunk kernel k_vip_prod (fp64
+ *                           MFMA, M = features, N = bootstraps, K = subjects, the
+ *                           block loops over the c components and squares each
+ *                           finished contraction into a second register tile)
+ *                           writes the series [f][n] contiguous, k_vip_moments
+ *                           (two passes: mean, then squared deviations) and the
+ *                           selection kernels of plsx_percentile_ci reduce them:
+ *                           the (B, n) array never exists whole.  A chunk is at
+ *                           most 2 GB and, with the stack, stays inside the
+ *                           scratch budget and free device memory.  Every entry
+ *                           is one block's work in ascending s and a, every
+ *                           reduction has one fixed order: the same bits run to
+ *                           run and whatever the chunking.  Limits:
+ *                           PLSX_ERR_UNSUPPORTED (context still usable, sizes in
+ *                           the message) for n > 16384 or when the stack plus the
+ *                           smallest chunk (min(B, 128) features, 8 n bytes each)
+ *                           does not fit; PLSX_ERR_ARG for n < 1, c < 1, an index
+ *                           outside 0 .. n - 1, a null pointer; PLSX_ERR_STATE
+ *                           without bound regression data.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -410,6 +468,9 @@ int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* 
 int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity);
 int plsx_simpls_coef_ci(plsx_ctx* ctx, const double* d_A, long long n, int i_lo, double g_lo, int i_hi, double g_hi,
                         double* d_lo, double* d_hi, void* stream);
+int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity);
+int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
+                       double* d_sd, double* d_lo, double* d_hi, void* stream);
 
 /* Bootstrap ratios -- compute.boot_rel (pyls/compute.py:212-237), elementwise
  * on (B, L) arrays: se = sqrt(|usq - usum^2/n| / (n-1)), bsr = orig / se.
@@ -467,7 +528,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * 2 k_small / k_small_ql (eigen-solve + Procrustes), 3 k_urot (+ split add), 4 k_nt_gemm
  * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 9 k_sd_cv_score (with the pair expansion and the
  * reduction over the splits of plsx_simpls_crossval_perm_batch), ..., 11 k_coef_prod (the feature pass of
- * plsx_simpls_coef_ci), 12 k_percentile (selection / sort of plsx_percentile_ci and plsx_simpls_coef_ci).
+ * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci count here too, k_sd_vip under 10 with
+ * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

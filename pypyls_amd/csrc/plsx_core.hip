@@ -480,6 +480,7 @@ try {
     }
     ctx->has_data = ctx->has_orig = false;
     coef_close(ctx);                                   // (an open coefficient series ends with the binding it belonged to)
+    vip_close(ctx);                                    // (... and so does a kept VIP stack)
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;
     HIPCHK(hipMemsetAsync(ctx->status.p, 0, 4 * sizeof(int), st));

@@ -129,7 +129,12 @@ struct plsx_ctx {
     // plsx_simpls_coef_keep: the open series also keeps every A_b, appended [keep_n][T][S] to the caller's buffer
     double* keepA = nullptr;
     long long keep_cap = 0, keep_n = 0;
-    Buf cichunk;                                        // plsx_simpls_coef_ci: one chunk of features' series [fc][T][n]
+    Buf cichunk;                                        // plsx_simpls_coef_ci / plsx_simpls_vip_ci: one chunk of features' series [fc][T][n] / [fc][n]
+    // plsx_simpls_vip_keep: every bootstrap a batch solves also leaves its scaled dual weights, appended [vip_n][vip_c][S]
+    // to the caller's buffer (k_sd_vip); independent of the coefficient series
+    double* vipG = nullptr;
+    long long vip_cap = 0, vip_n = 0;
+    int vip_c = 0;
     bool has_okx = false, has_oky = false;
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
     int ncomp = 0;
@@ -316,6 +321,11 @@ inline void coef_close(plsx_ctx* ctx)
 {
     ctx->coef_active = 0; ctx->coef_n = 0;
     ctx->keepA = nullptr; ctx->keep_cap = 0; ctx->keep_n = 0;
+}
+// a kept VIP stack ends (plsx_set_data, plsx_simpls_set_original, a second plsx_simpls_vip_keep)
+inline void vip_close(plsx_ctx* ctx)
+{
+    ctx->vipG = nullptr; ctx->vip_cap = 0; ctx->vip_n = 0; ctx->vip_c = 0;
 }
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);

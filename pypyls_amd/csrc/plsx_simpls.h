@@ -38,6 +38,7 @@
 //   k_sd_init -> [GEMM 0] -> k_sd_post0 -> { k_sd_step(c) -> [GEMM c] } x k -> k_sd_final
 //   cross-validation appends:  k_sd_final (dual weights dense, Vd) -> [Z = Vd . K] -> k_sd_cv_score
 //   an open coefficient series appends to a bootstrap batch:  k_sd_coef (A_b = sum_{j <= c} wd_j q_j^T, dense)
+//   a kept VIP stack appends to a bootstrap batch:  k_sd_vip (the scaled dual weights of the first c components, dense)
 // k_sd_step(c) finishes component c - 1 (what follows its K beta product: basis pair,
 // deflation coefficients, H -= g g^T) and opens component c (leading eigenpair of H, scores,
 // dual weights, new basis vector scattered for GEMM c); the last component needs no
@@ -121,6 +122,9 @@ struct SdArgs {
     double* cfA;                // [cf_n][T][S] A_b = sum_{j < cf_c} wd_j q_j^T scattered to subject space (every entry written), or nullptr
     double* cfq;                // [cf_n][cf_c][T] q_j = Y0^T t_j (simpls y_loadings of the resample)
     int cf_c, cf_r0, cf_n;
+    // VIP stack (plsx_simpls_vip_keep): k_sd_vip runs on every resample of the batch
+    double* vpG;                // [nres][vp_c][S] row a = sqrt(ssq_a / (|w_a|^2 sum_j ssq_j)) . wd_a scattered to subject space (every entry written), or nullptr
+    int vp_c;
 };
 
 // doubles of LDS one wave of k_sd_step needs (on-chip route: the last S of them are the scatter buffer)
@@ -1561,6 +1565,49 @@ void k_sd_coef(SdArgs a)
         else
             sd_scatter(qt + cc, xs, S, lane, A + (size_t)t * S, value);
         wave_sync();
+    }
+}
+
+// VIP stack of one bootstrap (plsx_simpls_vip_keep), after the solver chain of its batch.  With wd_a the dual weights
+// (position space, centred over the included positions, zero elsewhere), w_a = X0_r^T wd_a = Xc^T scatter(wd_a) the
+// x_weights and t_a = X0_r w_a = K_r wd_a the unit-norm scores,
+//     |w_a|^2 = wd_a^T K_r wd_a = a_a^T K a_a = sum_p WD[a][p] XW[a][p]     (a_a = scatter(wd_a); XW = t_a plus a constant,
+//                                                                          which the centred wd_a does not see)
+//     ssq_a   = |q_a|^2 = |Y0^T t_a|^2 = pctvar[a] . sum Y0^2               (k_sd_step left it; the common factor
+//                                                                          sum Y0^2 cancels in ssq_a / sum_j ssq_j)
+//     G[a]    = sqrt(ssq_a / (|w_a|^2 sum_{j < c} ssq_j)) . a_a,    VIP[f]^2 = B sum_a (Xc[:, f]^T G[a])^2
+// -- the quadratic form with K costs 2 S flop per component here because the solver already holds K_r wd_a; no pass over
+// K, no product.  Squares of w_a and q_a: the signs and the order of the components do not matter, no alignment.  A
+// model without explained variance or a component of zero weight norm gives 0 / 0 = NaN rows, as numpy's formula
+// does.  Reductions are wave_sum in fixed order; the scatter is sd_scatter / sd_scatter_g (a subject drawn more than
+// once receives bit-identical addends, both routes write the same bits).  One wavefront per resample; dynamic LDS per
+// wave: S doubles (the scatter buffer; GL: none).
+template <bool GL>
+static __global__ __launch_bounds__(256)
+void k_sd_vip(SdArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm_sd[];
+    const int S = a.S, k = a.k, cc = a.vp_c, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
+    const int r = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (r >= a.nres) return;
+    const int* xs = a.xs + (size_t)r * S;
+    const double* XW = a.XW + (size_t)r * k * S;
+    const double* WD = a.WD + (size_t)r * k * S;
+    const double* pv = a.pctvar + (size_t)r * k;
+    double* G = a.vpG + (size_t)r * cc * S;
+    double tot = 0.0;
+    for (int j = 0; j < cc; ++j) tot += pv[j];
+    for (int j = 0; j < cc; ++j) {
+        const double* wd = WD + (size_t)j * S;
+        const double* xw = XW + (size_t)j * S;
+        double s = 0.0;
+        for (int p = lane; p < S; p += 64) s += (xs[p] >= 0) ? wd[p] * xw[p] : 0.0;
+        const double f = sqrt(pv[j] / (wave_sum(s) * tot));
+        auto value = [&](int p) { return f * wd[p]; };
+        if constexpr (GL)
+            sd_scatter_g(a.sfirst + (size_t)r * S, a.scnt + (size_t)r * S, S, lane, G + (size_t)j * S, value);
+        else
+            sd_scatter(sm_sd + (size_t)wave * S, xs, S, lane, G + (size_t)j * S, value);
     }
 }
 

@@ -261,6 +261,31 @@ static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 }
 
 
+// The VIP stack's share of a solver batch (plsx_simpls_vip_keep): k_sd_vip writes the c scaled dual-weight rows of each
+// of the batch's `ms` bootstraps where they stay, in the caller's buffer.  `a`: the state run_simpls_dual just left
+// (args_out).  Nothing else reads or writes what it touches, so everything else a call computes keeps its bits.
+static int vip_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
+{
+    const int S = ctx->S, cc = ctx->vip_c;
+    const bool gl = simpls_global(ctx);
+    if (ctx->vip_n + ms > ctx->vip_cap)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_boot_batch: the kept VIP stack is full");
+    const size_t per_wave = gl ? 0 : (size_t)S * 8;
+    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / std::max<size_t>(per_wave, 1)));
+    const size_t lds = (size_t)wpb * per_wave;
+    a.vpG = ctx->vipG + (size_t)ctx->vip_n * cc * S; a.vp_c = cc;
+    {
+        KTimer tm(ctx, KC_COEF, st);
+        void (*vip_kernel)(SdArgs) = gl ? k_sd_vip<true> : k_sd_vip<false>;
+        HIPCHK(set_lds(vip_kernel, lds));
+        hipLaunchKernelGGL(vip_kernel, dim3(ceil_div(ms, wpb)), dim3(wpb * 64), lds, st, a);
+        LAUNCHCHK();
+    }
+    ctx->vip_n += ms;
+    return 0;
+}
+
+
 }  // namespace plsxi
 
 extern "C" {
@@ -298,6 +323,7 @@ try {
         return e;
     ctx->has_orig = true; ctx->quad_active = 0;
     coef_close(ctx);
+    vip_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -580,6 +606,84 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_vip_keep: data not bound for regression");
+    if (!ctx->has_orig) return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_vip_keep: plsx_simpls_set_original has not been called");
+    vip_close(ctx);
+    if (c < 1 || c > ctx->ncomp) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "plsx_simpls_vip_keep: c = %d outside 1 .. n_components = %d", c, ctx->ncomp);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (!d_G || capacity < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_vip_keep: null buffer or capacity < 1");
+    ctx->vipG = d_G; ctx->vip_cap = capacity; ctx->vip_n = 0; ctx->vip_c = c;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
+                       double* d_sd, double* d_lo, double* d_hi, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_vip_ci: data not bound for regression");
+    if (!d_G || !d_sd || !d_lo || !d_hi || n < 1 || c < 1 || i_lo < 0 || i_hi < 0 || i_lo >= n || i_hi >= n)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_vip_ci: null pointer, n < 1, c < 1 or an index outside 0 .. n - 1");
+    const int S = ctx->S, B = ctx->B;
+    char msg[400];
+    if (n > 16384) {
+        snprintf(msg, sizeof msg, "plsx_simpls_vip_ci: n = %lld bootstraps per series; the percentile kernels take at "
+                 "most 16384 (B = %d: %.1f GB of series, which no host path forms either)", n, B,
+                 8.0 * B * (double)n / 1073741824.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    // Features go in chunks of whole 128-feature blocks, by the rule of plsx_simpls_coef_ci with 8 n bytes per feature:
+    // a chunk's series, fc n doubles, next to the stack inside the scratch budget and in free device memory (what an
+    // earlier pass left allocated counts as free), 2 GB at most
+    const double stack = 8.0 * (double)n * c * S, per_feat = 8.0 * (double)n;
+    const int unit = std::min(B, 128);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const double have = (double)free_b + (double)ctx->cichunk.bytes;
+    const double budget = ctx->scratch_gb * 1073741824.0;
+    const double room = std::min(budget - stack, have);
+    if (room < unit * per_feat) {
+        snprintf(msg, sizeof msg, "plsx_simpls_vip_ci: the stack of n = %lld bootstraps (8 n c S = %.3f GB for c = %d, "
+                 "S = %d) and the series of the smallest chunk of %d features (%.3f GB) need %.3f GB; the scratch budget "
+                 "is %.3f GB and %.3f GB of device memory are free", n, stack / 1073741824.0, c, S, unit,
+                 unit * per_feat / 1073741824.0, (stack + unit * per_feat) / 1073741824.0, ctx->scratch_gb,
+                 have / 1073741824.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    long long fc = (long long)(std::min(room, 2147483648.0) / per_feat);
+    fc = std::max<long long>(unit, fc / 128 * 128);
+    if (fc >= B) fc = B;
+    if (int e = ensure(ctx, ctx->cichunk, (size_t)fc * (size_t)n * 8)) return e;
+    VipProdArgs a;
+    a.Xc = ptr<double>(ctx->Xc); a.ldx = ctx->Bpad;
+    a.G = d_G; a.S = S; a.c = c; a.n = (int)n; a.B = B;
+    a.out = ptr<double>(ctx->cichunk);
+    for (long long f0 = 0; f0 < B; f0 += fc) {
+        a.f0 = (int)f0; a.fc = (int)std::min<long long>(fc, B - f0);
+        {
+            KTimer tm(ctx, KC_COEFPROD, st);
+            hipLaunchKernelGGL(k_vip_prod, dim3(ceil_div(a.fc, 128), ceil_div(a.n, 64)), dim3(256), 0, st, a);
+            LAUNCHCHK();
+            // (the moments read the series the product just wrote: they count with it)
+            hipLaunchKernelGGL(k_vip_moments, dim3(a.fc), dim3(256), 0, st, a.out, a.n, d_sd + (size_t)f0);
+            LAUNCHCHK();
+        }
+        if (int e = run_percentile(ctx, a.out, (long long)a.fc, a.n, i_lo, g_lo, i_hi, g_hi, d_lo + (size_t)f0,
+                                   d_hi + (size_t)f0, st))
+            return e;
+    }
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream)
 try {
     NEED_DATA();
@@ -615,6 +719,12 @@ try {
                  "%d more do not fit (plsx_simpls_coef_keep)", ctx->keep_n, ctx->keep_cap, n);
         return fail(ctx, PLSX_ERR_ARG, msg);
     }
+    if (ctx->vipG && ctx->vip_n + n > ctx->vip_cap) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "plsx_simpls_boot_batch: the kept VIP stack holds %lld of %lld bootstraps, "
+                 "%d more do not fit (plsx_simpls_vip_keep)", ctx->vip_n, ctx->vip_cap, n);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int k = ctx->ncomp, T = ctx->T;
@@ -640,25 +750,30 @@ try {
         double* yl = d_yload + (size_t)off * T * k;
         const double* yst = d_ystack ? d_ystack + (size_t)off * ctx->S * T : nullptr;
         const bool single = simpls_single_pass(ctx);
-        SdArgs sda;                      // the batch's solver state, for an open coefficient series
+        SdArgs sda;                      // the batch's solver state, for an open coefficient series or a kept VIP stack
+        const bool want_state = ctx->coef_active || ctx->vipG;
         if (ctx->quad_active) {
             // quadratic-form route: the aligned dual weights stay in dual space (plsx_boot_finish passes the features)
             if (int e = ensure(ctx, ctx->Vdq, (size_t)ms * k * ctx->S * 8)) return e;
             if (int e = run_simpls_dual(ctx, idx, idx, ms, true, ptr<double>(ctx->spct), yl, ptr<double>(ctx->sc), st, yst,
-                                        true, ptr<double>(ctx->Vdq), nullptr, ctx->coef_active ? &sda : nullptr))
+                                        true, ptr<double>(ctx->Vdq), nullptr, want_state ? &sda : nullptr))
                 return e;
             if (ctx->timing) ctx->timed_units += ms;
             if (int e = quad_accumulate(ctx, ms, st)) return e;
             if (ctx->coef_active)
                 if (int e = coef_accumulate(ctx, sda, ms, st)) return e;
+            if (ctx->vipG)
+                if (int e = vip_append(ctx, sda, ms, st)) return e;
             continue;
         }
         if (int e = run_simpls_dual(ctx, idx, idx, ms, true, ptr<double>(ctx->spct), yl, ptr<double>(ctx->sc), st, yst,
-                                    single, nullptr, nullptr, ctx->coef_active ? &sda : nullptr))
+                                    single, nullptr, nullptr, want_state ? &sda : nullptr))
             return e;
         // (the solver state of the batch outlives the feature passes below: they work in buffers of their own)
         if (ctx->coef_active)
             if (int e = coef_accumulate(ctx, sda, ms, st)) return e;
+        if (ctx->vipG)
+            if (int e = vip_append(ctx, sda, ms, st)) return e;
         if (single) {
             // ONE feature pass, no R: x_weights = X0_r^T (flip . Wd) accumulated per group in the epilogue
             const int MT = 24, NW = 4, npg_w = (MT * 16) / k;

@@ -94,6 +94,8 @@ def _load():
         'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
         'plsx_simpls_coef_keep': ([vp, vp, ctypes.c_longlong], i32),
         'plsx_simpls_coef_ci': ([vp, vp, ctypes.c_longlong, i32, c_d, i32, c_d, vp, vp, vp], i32),
+        'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_vip_ci': ([vp, vp, ctypes.c_longlong, i32, i32, c_d, i32, c_d, vp, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_bootsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_permsamp_stream': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp, ctypes.POINTER(i32)], i32),
@@ -129,7 +131,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -826,6 +828,34 @@ class Engine(object):
         self._check(self.lib.plsx_simpls_coef_ci(self.ctx, stack.data_ptr(), n, idx[0][0], idx[0][1], idx[1][0],
                                                  idx[1][1], lo.data_ptr(), hi.data_ptr(), self._stream()))
         return lo, hi
+
+    def simpls_vip_keep(self, stack):
+        """Keep the VIP stack of every bootstrap the :meth:`simpls_boot_into` calls that follow solve: ``stack``
+        (capacity, c, S), a contiguous float64 tensor on this device, is filled in submission order with the scaled dual
+        weights of the first c components (plsx_simpls_vip_keep); ``VIP_b[f]**2 = B * ((Xc.T @ stack[b].T)**2).sum(-1)[f]``.
+        Independent of a coefficient series.  PlsxError: status -4 before the original fit is set, -1 for c outside
+        1 .. k and from the batch that would overflow the stack."""
+        torch = _torch()
+        if stack.dim() != 3 or stack.shape[2] != self.S or stack.dtype != torch.float64 or not stack.is_contiguous():
+            raise ValueError('the kept VIP stack must be a contiguous (capacity, c, {}) float64 tensor'.format(self.S))
+        self._check(self.lib.plsx_simpls_vip_keep(self.ctx, int(stack.shape[1]), stack.data_ptr(), int(stack.shape[0])))
+
+    def simpls_vip_ci(self, stack, ci=95):
+        """Standard deviation (ddof = 1) and percentile interval of the VIP scores over the bootstraps of ``stack``
+        (n, c, S) -- a kept stack, the gathered stacks of several ranks, or any contiguous float64 device tensor of that
+        shape: (sd, lo, hi) device tensors (B,), ``np.std(vip_boot, ddof=1, axis=-1)`` and ``np.percentile(vip_boot,
+        [(100 - ci) / 2, 100 - (100 - ci) / 2], axis=-1)`` of ``vip_boot[f, b] = sqrt(B * ((Xc.T @ stack[b].T)**2).sum(-1))[f]``
+        without that array ever existing (plsx_simpls_vip_ci).  No sync.  PlsxError status -2 (context still usable) for
+        n > 16384 or a stack that does not fit the scratch budget."""
+        torch = _torch()
+        if stack.dim() != 3 or stack.shape[2] != self.S or stack.dtype != torch.float64 or not stack.is_contiguous():
+            raise ValueError('the stack must be a contiguous (n, c, {}) float64 tensor'.format(self.S))
+        n, c = int(stack.shape[0]), int(stack.shape[1])
+        idx = _virtual_indices(max(n, 1), ci)
+        sd, lo, hi = self._empty((self.B,)), self._empty((self.B,)), self._empty((self.B,))
+        self._check(self.lib.plsx_simpls_vip_ci(self.ctx, stack.data_ptr(), n, c, idx[0][0], idx[0][1], idx[1][0],
+                                                idx[1][1], sd.data_ptr(), lo.data_ptr(), hi.data_ptr(), self._stream()))
+        return sd, lo, hi
 
     def simpls_boot_into(self, idx_dev, usum, usq, yl_dev, ystack=None):
         """idx_dev (n, S) int32; usum / usq (B, k) accumulated in place; yl_dev (n, T, k);

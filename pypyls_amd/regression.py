@@ -38,6 +38,12 @@ Differences from the reference at this commit, on purpose:
     ``(X, Y[perm])`` for P permutations; the (permutation, split) fits are formed, scored against the permuted Y and
     averaged over the splits in a fixed order on the device (plsx_simpls_crossval_perm_batch; csrc/plsx_simpls.h,
     k_sd_cvp_expand / k_sd_cv_score<RC, true> / k_sd_cvp_reduce).
+  * ``vip_components=c`` returns the VIP scores (variable importance in projection, the formula of MATLAB's
+    ``plsregress`` documentation) of the c-component model, one map per model, and bootstraps them:
+    ``bootres.vip_stderr`` / ``vip_ci``.  VIP is a square root of a sum of squares over the components, so every
+    bootstrap's scaled dual weights are kept in subject space and one closing pass over the features forms and reduces
+    the series chunk by chunk (plsx_simpls_vip_keep / plsx_simpls_vip_ci; csrc/plsx_simpls.h, k_sd_vip;
+    csrc/plsx_k_vip.h).  :func:`vip` computes the scores of any ``pls_regression`` result.
 """
 import numpy as np
 
@@ -103,7 +109,7 @@ def _check_cvsplits(masks, usable, k, B):
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
-                   cv_perm=0, cvpermsamples=None, **kwargs):
+                   cv_perm=0, cvpermsamples=None, vip_components=None, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -146,7 +152,18 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     that are NaN throughout, position p is usable under a permutation iff row p of X and row perm[p] of Y are; a
     (permutation, split) pair with fewer than two usable test rows gives NaN.  The P x test_split fits run and are
     reduced over the splits on the device (plsx_simpls_crossval_perm_batch); only P rows come back.  Every array the
-    call returned before keeps its bits."""
+    call returned before keeps its bits.
+
+    VIP scores: ``vip_components=c`` (1 <= c <= n_components, independent of ``coef_components``; None, the default:
+    nothing is added, no memory is taken) returns ``vip`` (B,), the variable importance in projection of the
+    c-component model, ``sqrt(B * sum_a ssq_a * x_weights[f, a]**2 / |x_weights[:, a]|**2 / sum_a ssq_a)`` with
+    ``ssq_a = |y_loadings[:, a]|**2`` of simpls (:func:`vip`); ``sum(vip**2) == B``.  With ``n_boot > 0`` also
+    ``bootres.vip_stderr`` (B,), ``np.std(..., ddof=1)`` of the VIP scores of the ``n_boot`` bootstrap fits (NaN for
+    ``n_boot = 1``), and ``bootres.vip_ci`` (B, 2), their ``ci`` % percentile interval (numpy's linear interpolation);
+    as for ``coefs_ci`` the original fit is not part of the series.  VIP depends on neither the signs nor the order of
+    the components: no alignment.  The (B, n_boot) scores exist on the device only, one chunk of features at a time;
+    what is kept is 8 c S n_boot bytes (on every GPU of a team: the closing pass runs on the first).
+    ``n_boot`` <= 16384.  Every other array of the call keeps its bits."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -185,6 +202,18 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              'device only, one chunk of features at a time'
                              .format(n_boot, 8.0 * X.shape[1] * Y.shape[1] * n_boot / 2 ** 30))
         kwargs['coef_ci'] = True                   # (recorded in `inputs` only when asked for)
+    if vip_components is not None:                 # (as above: on the host, before any engine)
+        if isinstance(vip_components, bool) or int(vip_components) != vip_components \
+                or not 1 <= int(vip_components) <= n_components:
+            raise ValueError('Provided `vip_components` must be an integer in 1 .. n_components = {}; got {!r}'
+                             .format(n_components, vip_components))
+        vip_components = int(vip_components)
+        if n_boot and n_boot > 16384:
+            raise ValueError('`vip_components` takes n_boot <= 16384, the bound of the device\'s percentile kernels; got '
+                             '{}.  There is no host fallback: the (B, n_boot) VIP scores ({:.1f} GB here) exist on the '
+                             'device only, one chunk of features at a time'
+                             .format(n_boot, 8.0 * X.shape[1] * n_boot / 2 ** 30))
+        kwargs['vip_components'] = vip_components          # (recorded in `inputs` only when asked for)
     if isinstance(cv_perm, (bool, np.bool_)) or not isinstance(cv_perm, (int, np.integer)) or cv_perm < 0:
         raise ValueError('Provided `cv_perm` must be a non-negative integer; got {!r}'.format(cv_perm))
     cv_perm = int(cv_perm)
@@ -366,7 +395,8 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             res = team.run(lambda rank, world, e: _run_device(
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
                 k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
-                coef_c=coef_components, coef_ci=coef_ci))
+                coef_c=coef_components, coef_ci=coef_ci,
+                vip_c=vip_components))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -375,7 +405,8 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 try:
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
-                                      kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci)
+                                      kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci,
+                vip_c=vip_components)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -390,7 +421,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
                 bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None,
-                coef_ci=False):
+                coef_ci=False, vip_c=None):
     import time
     import torch
     S = len(X)
@@ -451,7 +482,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
 
     # this rank's shards (permutations contiguous, bootstraps chunk-cyclic), launched chunk by chunk as the index rows arrive; the
     # results stay on the device until the one collective
-    d_perm = d_yl = usum = usq = bsum = bsq = d_keep = None
+    d_perm = d_yl = usum = usq = bsum = bsq = d_keep = d_vkeep = None
     n_perm_tot = pstream.n if pstream is not None else 0
     n_boot_tot = bstream.n if bstream is not None else 0
     from .progress import Bar                            # verbose=True: the reference's bars (pyls/utils.py:128-152)
@@ -482,6 +513,12 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 d_keep = eng._empty((sum(hi - lo for lo, hi in bchunks), T, S))
                 if d_keep.shape[0]:
                     eng.simpls_coef_keep(d_keep)
+        if vip_c is not None:
+            # the scaled dual weights of the first vip_c components of this rank's share, (n_local, vip_c, S): the source
+            # of the VIP series (plsx_simpls_vip_keep; independent of the coefficient series)
+            d_vkeep = eng._empty((sum(hi - lo for lo, hi in bchunks), vip_c, S))
+            if d_vkeep.shape[0]:
+                eng.simpls_vip_keep(d_vkeep)
         bars.append(Bar('Running bootstraps', sum(hi - lo for lo, hi in bchunks), show, eng.device))
         # 3-D Y: a (n, S, T) Y stack per chunk, at most 256 of them and at most 256 MB (S = 24 000, T = 20: 69 rows)
         ylim = max(1, min(256, (256 << 20) // (S * T * 8)))
@@ -570,12 +607,16 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
+    if d_vkeep is not None:                             # ... and the kept VIP stack, the same way
+        slices, totals = slices + [d_vkeep], totals + [n_boot_tot]
+        cyclic = cyclic + [len(slices) - 1]
     sums = [t for t in (usum, usq, bsum, bsq) if t is not None]      # (the coefficient sums join the summed part)
     full, summed = parallel.collect_device(slices, totals, sums, emulate=emulate, cyclic=cyclic, team=team)
     if not lead:
         return None                                     # rank 0 holds everything the ranks computed: it finishes
-    d_stack = full.pop() if d_keep is not None else None           # (stays on the device)
-    d_keep = None
+    d_vstack = full.pop() if d_vkeep is not None else None         # (stay on the device)
+    d_stack = full.pop() if d_keep is not None else None
+    d_keep = d_vkeep = None
     full = [t.detach().cpu().numpy() for t in full]
     if usum is not None:
         usum, usq = summed[:2]
@@ -587,6 +628,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         # the closing pass over the features, on the lead rank, over the gathered stack (plsx_simpls_coef_ci)
         d_cci = eng.simpls_coef_ci(d_stack.contiguous(), ci=ci)
         tick('coefs_ci')
+    d_vci = None
+    if d_vstack is not None:
+        # the same for the VIP scores (plsx_simpls_vip_ci): standard deviation and interval of every feature's series
+        d_vci = eng.simpls_vip_ci(d_vstack.contiguous(), ci=ci)
+        tick('vip_ci')
     i = 0
     d_perm = distrib = None
     if pstream is not None:
@@ -630,6 +676,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         # the model of the first coef_c components (simpls' beta, regression.py:149-151): Y ~ intercept + X @ coefs
         res['coefs'] = _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_agg, mask, coef_c)
         res['intercept'] = _model_means(X, Y_agg, mask, res['coefs'])
+    if vip_c is not None:
+        res['vip'] = _vip_scores(res['x_weights'], _fit_yloadings(res['y_loadings'], x_scores, Y_agg, mask, vip_c), vip_c)
     if bootsamp is not None:
         # add the original back, n_boot + 1 (regression.py:409-415)
         d_bsr, d_se = eng.boot_rel_dev(d_W, usum, usq, bootsamp.shape[1] + 1, add_orig=True)
@@ -648,22 +696,41 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             res['bootres'].update(dict(coefs_normed=d_cn.cpu().numpy(), coefs_stderr=d_cse.cpu().numpy()))
         if d_cci is not None:
             res['bootres']['coefs_ci'] = np.stack([d_cci[0].cpu().numpy(), d_cci[1].cpu().numpy()], -1)
+        if d_vci is not None:
+            res['bootres'].update(dict(vip_stderr=d_vci[0].cpu().numpy(),
+                                       vip_ci=np.stack([d_vci[1].cpu().numpy(), d_vci[2].cpu().numpy()], -1)))
     res['varexp'] = pctvar                                          # regression.py:425-426
     tick('host_finish')
     return res
 
 
-def _model_coefs(W, Q, x_scores, Y_agg, mask, c):
-    """coefs (B, T) = W[:, :c] @ Q[:, :c].T with Q simpls' y_loadings (regression.py:149-151).  Without masked rows
-    that is the result's own ``y_loadings``.  With rows that are NaN throughout, X and Y are centred over different
-    rows than the fit uses (np.nanmean per matrix, regression.py:395-397), so ``y_loadings`` = Yc^T x_scores carries
-    the product of the two offsets; simpls' own are taken from the scores and Y centred over the rows of the fit."""
-    W, Q = np.asarray(W, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+def _fit_yloadings(Q, x_scores, Y_agg, mask, c):
+    """simpls' own y_loadings (T, c) of the first c components.  Without masked rows that is the result's own
+    ``y_loadings``.  With rows that are NaN throughout, X and Y are centred over different rows than the fit uses
+    (np.nanmean per matrix, regression.py:395-397), so ``y_loadings`` = Yc^T x_scores carries the product of the two
+    offsets; simpls' own are taken from the scores and Y centred over the rows of the fit."""
+    Q = np.asarray(Q, dtype=np.float64)
     if not mask.all():
         t = np.asarray(x_scores, dtype=np.float64)[mask][:, :c]
         y = np.asarray(Y_agg, dtype=np.float64)[mask]
         Q = (y - y.mean(axis=0)).T @ (t - t.mean(axis=0))
-    return np.ascontiguousarray(W[:, :c] @ Q[:, :c].T)
+    return Q[:, :c]
+
+
+def _model_coefs(W, Q, x_scores, Y_agg, mask, c):
+    """coefs (B, T) = W[:, :c] @ Q[:, :c].T with Q simpls' y_loadings (regression.py:149-151; :func:`_fit_yloadings`)."""
+    W = np.asarray(W, dtype=np.float64)
+    return np.ascontiguousarray(W[:, :c] @ _fit_yloadings(Q, x_scores, Y_agg, mask, c).T)
+
+
+def _vip_scores(W, Q, c):
+    """VIP (B,) of the first c components from x_weights W (B, k) and simpls' y_loadings Q (T, >= c): the formula of
+    MATLAB's ``plsregress`` documentation with unit-norm x_scores.  A model that explains nothing or a component of
+    zero weight norm gives NaN (0 / 0)."""
+    W, Q = np.asarray(W, dtype=np.float64)[:, :c], np.asarray(Q, dtype=np.float64)[:, :c]
+    ssq = (Q ** 2).sum(axis=0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.sqrt(W.shape[0] * ((W ** 2 / (W ** 2).sum(axis=0)) @ ssq) / ssq.sum())
 
 
 def _model_means(X, Y_agg, mask, coefs):
@@ -674,15 +741,10 @@ def _model_means(X, Y_agg, mask, coefs):
     return Y_agg.mean(axis=0) - X.mean(axis=0) @ coefs
 
 
-def predict(results, X_new, n_components=None):
-    """Predict Y (S_new, T) for new rows ``X_new`` (S_new, B) with the model of the first ``n_components`` SIMPLS
-    components of a ``pls_regression`` result: ``intercept + X_new @ coefs`` with
-    ``coefs = x_weights[:, :c] @ y_loadings[:, :c].T`` (simpls' ``beta``, pyls/types/regression.py:149-151).
-
-    Works on any ``pls_regression`` result, also one read back by ``load_results``: the means come from
-    ``results.inputs`` (X, Y, ``aggfunc``), over the rows the fit used (rows that are NaN throughout are left out).
-    ``n_components=None``: the ``coef_components`` the result was computed with, otherwise all components.
-    Host numpy: one thin product."""
+def _fit_of(results, n_components, default_key, X_new=None):
+    """What predict / vip need of a ``pls_regression`` result: W, Q, X, Y aggregated, the mask of the rows of the fit,
+    the scores and the component count (``n_components=None``: ``inputs[default_key]``, otherwise all components).
+    ``X_new``: new rows, checked against W."""
     inputs = results.get('inputs') if hasattr(results, 'get') else None
     W, Q = (results.get('x_weights'), results.get('y_loadings')) if inputs is not None else (None, None)
     if inputs is None or W is None or Q is None or results.get('singvals') is not None \
@@ -691,12 +753,11 @@ def predict(results, X_new, n_components=None):
                          'n_components are needed)')
     W, Q = np.asarray(W, dtype=np.float64), np.asarray(Q, dtype=np.float64)
     X, Y = np.asarray(inputs['X'], dtype=np.float64), np.asarray(inputs['Y'], dtype=np.float64)
-    X_new = np.asarray(X_new, dtype=np.float64)
-    if X_new.ndim != 2 or X_new.shape[1] != W.shape[0]:
+    if X_new is not None and (X_new.ndim != 2 or X_new.shape[1] != W.shape[0]):
         raise ValueError('`X_new` must have shape (S_new, {}); got {}'.format(W.shape[0], X_new.shape))
     k = W.shape[1]
     if n_components is None:
-        n_components = inputs.get('coef_components')
+        n_components = inputs.get(default_key)
         n_components = k if n_components is None else int(n_components)
     if isinstance(n_components, bool) or int(n_components) != n_components or not 1 <= int(n_components) <= k:
         raise ValueError('`n_components` must be an integer in 1 .. {}; got {!r}'.format(k, n_components))
@@ -712,5 +773,36 @@ def predict(results, X_new, n_components=None):
     if x_scores is None and not mask.all():
         x_scores = np.full((len(X), k), np.nan)
         x_scores[mask] = X[mask] @ W
+    return W, Q, X, Y, mask, x_scores, c
+
+
+def predict(results, X_new, n_components=None):
+    """Predict Y (S_new, T) for new rows ``X_new`` (S_new, B) with the model of the first ``n_components`` SIMPLS
+    components of a ``pls_regression`` result: ``intercept + X_new @ coefs`` with
+    ``coefs = x_weights[:, :c] @ y_loadings[:, :c].T`` (simpls' ``beta``, pyls/types/regression.py:149-151).
+
+    Works on any ``pls_regression`` result, also one read back by ``load_results``: the means come from
+    ``results.inputs`` (X, Y, ``aggfunc``), over the rows the fit used (rows that are NaN throughout are left out).
+    ``n_components=None``: the ``coef_components`` the result was computed with, otherwise all components.
+    Host numpy: one thin product."""
+    X_new = np.asarray(X_new, dtype=np.float64)
+    W, Q, X, Y, mask, x_scores, c = _fit_of(results, n_components, 'coef_components', X_new)
     coefs = _model_coefs(W, Q, x_scores, Y, mask, c)
     return _model_means(X, Y, mask, coefs) + X_new @ coefs
+
+
+def vip(results, n_components=None):
+    """VIP scores (B,), variable importance in projection, of the model of the first ``n_components`` SIMPLS components
+    of a ``pls_regression`` result -- the formula of MATLAB's ``plsregress`` documentation with unit-norm x_scores:
+
+        ssq_a  = |y_loadings[:, a]|**2                                                    a = 0 .. c - 1
+        vip[f] = sqrt(B * sum_a ssq_a * x_weights[f, a]**2 / |x_weights[:, a]|**2 / sum_a ssq_a)
+
+    so that ``sum(vip**2) == B``; independent of the signs and the order of the components.  The models are nested: a
+    k-component fit serves every c <= k.  Works on any ``pls_regression`` result, also one read back by
+    ``load_results``; with rows that are NaN throughout the y_loadings are simpls' own, centred over the rows of the
+    fit (as for :func:`predict`).  ``n_components=None``: the ``vip_components`` the result was computed with,
+    otherwise all components.  ``results.vip`` of ``pls_regression(vip_components=c)`` is this function's value.  Host
+    numpy."""
+    W, Q, X, Y, mask, x_scores, c = _fit_of(results, n_components, 'vip_components')
+    return _vip_scores(W, _fit_yloadings(Q, x_scores, Y, mask, c), c)

@@ -94,6 +94,7 @@ class PLSInputs(KeyedRecord):
         'coef_components',                  # pls_regression: component count of the returned model (only when asked for)
         'coef_ci',                          # pls_regression: percentile intervals of its coefficients (only when asked for)
         'cv_perm',                          # pls_regression: permutations of the cross-validation (only when asked for)
+        'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
     )
@@ -126,7 +127,10 @@ class PLSBootResults(KeyedRecord):
                'coefs_stderr', 'coefs_normed',
                # pls_regression(coef_components=c, coef_ci=True): (B, T, 2) lower / upper percentile bound of the
                # coefficients over the n_boot bootstraps (the original is not added to the series, as for y_loadings_ci)
-               'coefs_ci')
+               'coefs_ci',
+               # pls_regression(vip_components=c): (B,) standard deviation (ddof = 1) and (B, 2) lower / upper percentile
+               # bound of the VIP scores over the n_boot bootstraps (the original is not added to the series)
+               'vip_stderr', 'vip_ci')
 
 
 class PLSPermResults(KeyedRecord):
@@ -154,7 +158,9 @@ class PLSResults(KeyedRecord):
                'singvals', 'varexp', 'permres', 'bootres', 'splitres', 'cvres',
                'inputs',
                # pls_regression(coef_components=c): Y ~ intercept (T,) + X @ coefs (B, T)
-               'coefs', 'intercept')
+               'coefs', 'intercept',
+               # pls_regression(vip_components=c): (B,) variable importance in projection of the c-component model
+               'vip')
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
