@@ -451,6 +451,60 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           does not fit; PLSX_ERR_ARG for n < 1, c < 1, an index
  *                           outside 0 .. n - 1, a null pointer; PLSX_ERR_STATE
  *                           without bound regression data.
+ *   plsx_simpls_coef_perm_test / plsx_simpls_coef_perm_begin / plsx_simpls_coef_perm_end
+ *                           permutation test of the coefficients of the c-component
+ *                           model: per (feature, behaviour) the number of
+ *                           permutations whose coefficient is at least as large in
+ *                           magnitude as the observed one, and per (permutation,
+ *                           behaviour) the maximum over the features of the
+ *                           standardised magnitude (the null of the single-step
+ *                           maxT statistic of Westfall & Young).  Counts add over
+ *                           permutations and a maximum over features belongs to one
+ *                           permutation: no coefficient is ever stored.
+ *                           _test is stateless: for ANY stack d_A [n][T][S] and the
+ *                           bound, centred features, with
+ *                           coef_b[f][t] = sum_s Xc[s][f] A[b][t][s] (contracted in
+ *                           ascending s) and s_f = sqrt(sum_s Xc[s][f]^2 / (n_x - 1))
+ *                           (n_x the usable rows of X) when `standardise` is set,
+ *                           else 1: d_count (B, T) int32 += #{b < n :
+ *                           s_f |coef_b[f][t]| >= s_f |d_obs[f][t]|} (>=, so that a
+ *                           feature without variance counts every permutation),
+ *                           d_max (n, T) = max_f s_f |coef_b[f][t]|.  Kernel
+ *                           k_coef_perm_prod has k_coef_prod's tiling (fp64 MFMA,
+ *                           M = 128 features, N = 64 permutations of one behaviour,
+ *                           K = subjects); a block walks all the tiles of its
+ *                           (128 features, t), counts in registers and stores the
+ *                           per-tile maxima of its 128 features; k_coef_perm_max
+ *                           reduces them over the feature blocks.  The stack goes
+ *                           in pieces of at most 16384 permutations, the features
+ *                           in chunks of whole 128-feature blocks whose partial
+ *                           maxima (8 T n bytes per block) fit 2 GB and, next to
+ *                           the stack, the scratch budget (plsx_set_scratch) and
+ *                           free device memory.  Integer counts, maxima, one owner
+ *                           per (f, t), no atomics: the same bits run to run and
+ *                           whatever the chunking.  No bound on n beyond the
+ *                           outputs.  PLSX_ERR_ARG for a null pointer or n < 1,
+ *                           PLSX_ERR_STATE without bound regression data,
+ *                           PLSX_ERR_UNSUPPORTED (context still usable) when not
+ *                           even one block of 64 permutations fits.
+ *                           _begin (after plsx_simpls_set_original) opens a series
+ *                           that rides along plsx_simpls_perm_batch: every solver
+ *                           batch runs with the dual weights on (they stay in the
+ *                           batch's state; d_out keeps its bits), k_sd_coef writes
+ *                           A_p = sum_{j < c} wd_j q_j^T of its permutations into
+ *                           scratch (T S doubles each, counted in the batch's share
+ *                           of the scratch budget: the batch shrinks, the scratch
+ *                           does not grow), the test above runs on that piece
+ *                           against d_obs, adds to d_count and appends the maxima
+ *                           to d_max (capacity, T) in submission order.  s_f is
+ *                           computed once, in _begin.  A batch that would pass
+ *                           `capacity` returns PLSX_ERR_ARG before it computes
+ *                           anything.  _end, plsx_set_data,
+ *                           plsx_simpls_set_original and a second _begin end the
+ *                           series (the buffers stay the caller's).  _begin:
+ *                           PLSX_ERR_ARG for c outside 1 .. k, a null pointer or
+ *                           capacity < 1; PLSX_ERR_STATE without bound regression
+ *                           data or before plsx_simpls_set_original.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -468,6 +522,11 @@ int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* 
 int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity);
 int plsx_simpls_coef_ci(plsx_ctx* ctx, const double* d_A, long long n, int i_lo, double g_lo, int i_hi, double g_hi,
                         double* d_lo, double* d_hi, void* stream);
+int plsx_simpls_coef_perm_test(plsx_ctx* ctx, const double* d_A, long long n, const double* d_obs, int standardise,
+                               int32_t* d_count, double* d_max, void* stream);
+int plsx_simpls_coef_perm_begin(plsx_ctx* ctx, int c, const double* d_obs, int standardise, int32_t* d_count,
+                                double* d_max, long long capacity);
+int plsx_simpls_coef_perm_end(plsx_ctx* ctx);
 int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity);
 int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
                        double* d_sd, double* d_lo, double* d_hi, void* stream);
@@ -528,7 +587,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * 2 k_small / k_small_ql (eigen-solve + Procrustes), 3 k_urot (+ split add), 4 k_nt_gemm
  * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 9 k_sd_cv_score (with the pair expansion and the
  * reduction over the splits of plsx_simpls_crossval_perm_batch), ..., 11 k_coef_prod (the feature pass of
- * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci count here too, k_sd_vip under 10 with
+ * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
+ * k_col_sd of plsx_simpls_coef_perm_test count here too, k_sd_vip under 10 with
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */

@@ -135,7 +135,17 @@ struct plsx_ctx {
     double* vipG = nullptr;
     long long vip_cap = 0, vip_n = 0;
     int vip_c = 0;
+    // plsx_simpls_coef_perm_begin: a permutation series of the coefficients rides along plsx_simpls_perm_batch -- the
+    // caller's observed coefficients (B, T), counts (B, T) and maxima [cperm_n][T] (appended), the batch's A_p dense
+    // [m][T][S] (cpA), the partial maxima of a chunk of feature blocks (cppart), the feature scale s_f (colsd)
+    int cperm_active = 0, cperm_c = 0, cperm_std = 0;
+    const double* cperm_obs = nullptr;
+    int* cperm_count = nullptr;
+    double* cperm_max = nullptr;
+    long long cperm_cap = 0, cperm_n = 0;
+    Buf cpA, cppart, colsd;
     bool has_okx = false, has_oky = false;
+    int n_okx = 0;                                      // usable rows of X under the row masks (has_okx)
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
     int ncomp = 0;
     // per-kernel-class timing (HIP events on the launch stream)
@@ -326,6 +336,14 @@ inline void coef_close(plsx_ctx* ctx)
 inline void vip_close(plsx_ctx* ctx)
 {
     ctx->vipG = nullptr; ctx->vip_cap = 0; ctx->vip_n = 0; ctx->vip_c = 0;
+}
+// an open permutation series of the coefficients ends (plsx_set_data, plsx_simpls_set_original, a second
+// plsx_simpls_coef_perm_begin, plsx_simpls_coef_perm_end); the buffers stay the caller's
+inline void cperm_close(plsx_ctx* ctx)
+{
+    ctx->cperm_active = 0; ctx->cperm_c = 0; ctx->cperm_std = 0;
+    ctx->cperm_obs = nullptr; ctx->cperm_count = nullptr; ctx->cperm_max = nullptr;
+    ctx->cperm_cap = 0; ctx->cperm_n = 0;
 }
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);

@@ -58,8 +58,10 @@ int simpls_form_K(plsx_ctx* ctx, hipStream_t st)
 int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, bool scatter,
                     double* pctvar, double* yload, double* cvec, hipStream_t st,
                     const double* ystack = nullptr, bool align_signs = false, double* Vd = nullptr,
-                    const uint8_t* pmask = nullptr, SdArgs* args_out = nullptr)
+                    const uint8_t* pmask = nullptr, SdArgs* args_out = nullptr, bool weights_only = false)
 {
+    // weights_only (without scatter): k_sd_step keeps the dual weights WD in the batch's state (a.weights), nothing
+    // leaves the solver but pctvar -- k_sd_final does not run (the permutation test of the coefficients reads the state)
     // Vd (with scatter): the dual weights go out dense, [nres][k][S] (k_sd_final writes every entry), not into the A operand
     // pmask: [nres][S] positions a resample keeps (cross-validation: its training rows); args_out: the carved-out
     // state of the batch, for a kernel that runs after the chain (valid until the next call)
@@ -69,7 +71,7 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     SdArgs a;
     memset(&a, 0, sizeof(a));
     a.jacobi_eig = ctx->opt[OPT_SIMPLS_JACOBI] ? 1 : 0;
-    a.weights = scatter ? 1 : 0;
+    a.weights = (scatter || weights_only) ? 1 : 0;
     a.S = S; a.T = T; a.k = k; a.nres = nres;
     a.Yc = ystack ? ystack : ptr<double>(ctx->Y);
     a.y_stride = ystack ? (long long)S * T : 0;
@@ -286,6 +288,94 @@ static int vip_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 }
 
 
+// s_f of every bound feature into ctx->colsd (k_col_sd): the standard deviation over the usable rows of X
+static int col_sd(plsx_ctx* ctx, hipStream_t st)
+{
+    if (int e = ensure(ctx, ctx->colsd, (size_t)ctx->Bpad * 8)) return e;
+    const double nx = ctx->has_okx ? (double)ctx->n_okx : (double)ctx->S;
+    KTimer tm(ctx, KC_COEFPROD, st);
+    hipLaunchKernelGGL(k_col_sd, dim3(ceil_div(ctx->Bpad, 256)), dim3(256), 0, st, ptr<double>(ctx->Xc), ctx->Bpad, ctx->S,
+                       ctx->B, nx, ptr<double>(ctx->colsd));
+    LAUNCHCHK();
+    return 0;
+}
+
+// The permutation statistics of a stack A [n][T][S] against `obs` (plsx_simpls_coef_perm_test and the open series of
+// plsx_simpls_coef_perm_begin): count (B, T) += exceedances, dmax (n, T) = maxima over the features.  The stack goes in
+// pieces of at most 16384 permutations, the features of a piece in chunks of whole 128-feature blocks whose partial
+// maxima, 8 T n bytes per block, fit `room` bytes and 2 GB.  Counts are integers and a maximum has no order: the
+// result depends on neither.
+static int coef_perm_run(plsx_ctx* ctx, const double* A, long long n, const double* obs, const double* sd, int* count,
+                         double* dmax, double room, const char* who, hipStream_t st)
+{
+    const int S = ctx->S, T = ctx->T, B = ctx->B;
+    room = std::min(room, 2147483648.0);
+    long long piece = std::min<long long>(n, 16384);
+    if (room < 8.0 * T * (double)piece) piece = (long long)(room / (8.0 * T)) / 64 * 64;
+    if (piece < 1) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "%s: the partial maxima of one 128-feature block and 64 permutations (8 T n = %.0f "
+                 "bytes for T = %d) do not fit next to the stack: the scratch budget is %.6f GB", who, 8.0 * T * 64, T,
+                 ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    const int nfb_all = ceil_div(B, 128);
+    const int nfb = (int)std::max<long long>(1, std::min<long long>(nfb_all, (long long)(room / (8.0 * T * (double)piece))));
+    if (int e = ensure(ctx, ctx->cppart, (size_t)nfb * T * (size_t)piece * 8)) return e;
+    CoefPermArgs a;
+    a.Xc = ptr<double>(ctx->Xc); a.ldx = ctx->Bpad;
+    a.S = S; a.T = T; a.B = B;
+    a.obs = obs; a.sd = sd; a.count = count; a.pmax = ptr<double>(ctx->cppart);
+    for (long long p0 = 0; p0 < n; p0 += piece) {
+        a.n = (int)std::min<long long>(piece, n - p0);
+        a.A = A + (size_t)p0 * T * S;
+        for (int fb0 = 0; fb0 < nfb_all; fb0 += nfb) {
+            const int nb = std::min(nfb, nfb_all - fb0);
+            a.f0 = fb0 * 128; a.fc = std::min(nb * 128, B - a.f0);
+            KTimer tm(ctx, KC_COEFPROD, st);
+            hipLaunchKernelGGL(k_coef_perm_prod, dim3(nb, T), dim3(256), 0, st, a);
+            LAUNCHCHK();
+            hipLaunchKernelGGL(k_coef_perm_max, dim3((unsigned)(((long long)T * a.n + 255) / 256)), dim3(256), 0, st,
+                               a.pmax, nb, T, a.n, fb0 == 0 ? 1 : 0, dmax + (size_t)p0 * T);
+            LAUNCHCHK();
+        }
+    }
+    return 0;
+}
+
+// The open permutation series' share of a solver batch (plsx_simpls_coef_perm_begin): k_sd_coef writes A_p of the
+// batch's `ms` permutations dense into scratch, the test above runs on that piece and appends its maxima.  `a`: the
+// state run_simpls_dual just left (args_out; weights on).
+static int coef_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
+{
+    const int S = ctx->S, T = ctx->T, cc = ctx->cperm_c;
+    const bool gl = simpls_global(ctx);
+    if (int e = ensure(ctx, ctx->cpA, (size_t)ms * T * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->Qc, (size_t)ms * cc * T * 8)) return e;
+    const size_t per_wave = ((size_t)cc + (gl ? 0 : (size_t)S)) * 8;
+    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / per_wave));
+    const size_t lds = (size_t)wpb * per_wave;
+    a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
+    a.cfA = ptr<double>(ctx->cpA); a.cf_r0 = 0; a.cf_n = ms;
+    {
+        KTimer tm(ctx, KC_COEF, st);
+        void (*coef_kernel)(SdArgs) = gl ? k_sd_coef<16, true> : (ms > 2048 ? k_sd_coef<8, false> : k_sd_coef<16, false>);
+        HIPCHK(set_lds(coef_kernel, lds));
+        hipLaunchKernelGGL(coef_kernel, dim3(ceil_div(ms, wpb)), dim3(wpb * 64), lds, st, a);
+        LAUNCHCHK();
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const double room = std::min(0.25 * ctx->scratch_gb * 1073741824.0, (double)free_b + (double)ctx->cppart.bytes);
+    if (int e = coef_perm_run(ctx, a.cfA, ms, ctx->cperm_obs, ctx->cperm_std ? ptr<double>(ctx->colsd) : nullptr,
+                              ctx->cperm_count, ctx->cperm_max + (size_t)ctx->cperm_n * T, room,
+                              "plsx_simpls_perm_batch", st))
+        return e;
+    ctx->cperm_n += ms;
+    return 0;
+}
+
+
 }  // namespace plsxi
 
 extern "C" {
@@ -324,6 +414,7 @@ try {
     ctx->has_orig = true; ctx->quad_active = 0;
     coef_close(ctx);
     vip_close(ctx);
+    cperm_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -334,19 +425,32 @@ try {
     if (!d_perm_idx || !d_out || n < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_perm_batch: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
+    // (an open permutation series of the coefficients that cannot take the call: refused before anything is computed)
+    const bool series = ctx->cperm_active != 0;
+    if (series && ctx->cperm_n + n > ctx->cperm_cap) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "plsx_simpls_perm_batch: the open coefficient series holds %lld of %lld permutations, "
+                 "%d more do not fit (plsx_simpls_coef_perm_begin)", ctx->cperm_n, ctx->cperm_cap, n);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
     // solver batches are as large as the call: a launch of the component step lasts as long as one
     // wave's latency chain whatever the batch (one wave per resample, up to 8 per SIMD)
-    // (8192, or fewer where the solver state of 8192 resamples would exceed half the scratch budget: sd_batch)
-    const int nb = sd_batch(ctx, 8192, 1, 0.0);
+    // (8192, or fewer where the solver state of 8192 resamples would exceed half the scratch budget: sd_batch; an open
+    // series adds a permutation's A_p, T S doubles, and its y-loadings to that state)
+    const int nb = sd_batch(ctx, 8192, 1, series ? 8.0 * ctx->T * ((double)ctx->S + ctx->cperm_c) : 0.0);
     if (int e = ensure(ctx, ctx->spct, (size_t)nb * ctx->T * ctx->ncomp * 8)) return e;
     if (int e = ensure(ctx, ctx->sc, (size_t)nb * ctx->T * ctx->ncomp * 8)) return e;
     for (int off = 0; off < n; off += nb) {
         const int m = std::min(nb, n - off);
+        SdArgs sda;
         // Y is permuted, X is not (BasePLS.make_permutation, base.py:599)
         if (int e = run_simpls_dual(ctx, nullptr, d_perm_idx + (size_t)off * ctx->S, m, false,
                                     d_out + (size_t)off * ctx->ncomp, ptr<double>(ctx->spct),
-                                    ptr<double>(ctx->sc), st))
+                                    ptr<double>(ctx->sc), st, nullptr, false, nullptr, nullptr, series ? &sda : nullptr,
+                                    series))
             return e;
+        if (series)
+            if (int e = coef_perm_append(ctx, sda, m, st)) return e;
     }
     return PLSX_OK;
 } PLSX_CATCH(ctx)
@@ -606,6 +710,63 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+int plsx_simpls_coef_perm_test(plsx_ctx* ctx, const double* d_A, long long n, const double* d_obs, int standardise,
+                               int32_t* d_count, double* d_max, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_perm_test: data not bound for regression");
+    if (!d_A || !d_obs || !d_count || !d_max || n < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_coef_perm_test: null pointer or n < 1");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (standardise)
+        if (int e = col_sd(ctx, st)) return e;
+    // the partial maxima stay next to the caller's stack inside the scratch budget and in free device memory (what an
+    // earlier pass left allocated counts as free)
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const double stack = 8.0 * (double)n * ctx->T * ctx->S;
+    const double room = std::min(ctx->scratch_gb * 1073741824.0 - stack, (double)free_b + (double)ctx->cppart.bytes);
+    return coef_perm_run(ctx, d_A, n, d_obs, standardise ? ptr<double>(ctx->colsd) : nullptr, d_count, d_max, room,
+                         "plsx_simpls_coef_perm_test", st);
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_coef_perm_begin(plsx_ctx* ctx, int c, const double* d_obs, int standardise, int32_t* d_count,
+                                double* d_max, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_perm_begin: data not bound for regression");
+    if (!ctx->has_orig)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_coef_perm_begin: plsx_simpls_set_original has not been called");
+    cperm_close(ctx);
+    if (c < 1 || c > ctx->ncomp) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "plsx_simpls_coef_perm_begin: c = %d outside 1 .. n_components = %d", c, ctx->ncomp);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (!d_obs || !d_count || !d_max || capacity < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_coef_perm_begin: null pointer or capacity < 1");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (standardise) {                                 // once per series; the entry takes no stream: fenced both ways
+        HIPCHK(hipDeviceSynchronize());
+        if (int e = col_sd(ctx, nullptr)) return e;
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    ctx->cperm_c = c; ctx->cperm_obs = d_obs; ctx->cperm_std = standardise ? 1 : 0;
+    ctx->cperm_count = d_count; ctx->cperm_max = d_max; ctx->cperm_cap = capacity; ctx->cperm_n = 0;
+    ctx->cperm_active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_coef_perm_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    cperm_close(ctx);
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
 int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity)
 try {
     NEED_DATA();
@@ -695,6 +856,12 @@ try {
         if (int e = ensure(ctx, ctx->okx, ctx->S)) return e;
         HIPCHK(hipMemcpyAsync(ctx->okx.p, d_okx, ctx->S, hipMemcpyDeviceToDevice, st));
         ctx->has_okx = true;
+        // the number of usable rows of X: the denominator of the feature scale (k_col_sd)
+        std::vector<uint8_t> h(ctx->S);
+        HIPCHK(hipMemcpyAsync(h.data(), d_okx, ctx->S, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ctx->n_okx = 0;
+        for (uint8_t v : h) ctx->n_okx += v ? 1 : 0;
     }
     if (d_oky) {
         if (int e = ensure(ctx, ctx->oky, ctx->S)) return e;

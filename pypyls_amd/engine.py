@@ -94,6 +94,9 @@ def _load():
         'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
         'plsx_simpls_coef_keep': ([vp, vp, ctypes.c_longlong], i32),
         'plsx_simpls_coef_ci': ([vp, vp, ctypes.c_longlong, i32, c_d, i32, c_d, vp, vp, vp], i32),
+        'plsx_simpls_coef_perm_test': ([vp, vp, ctypes.c_longlong, vp, i32, vp, vp, vp], i32),
+        'plsx_simpls_coef_perm_begin': ([vp, i32, vp, i32, vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_coef_perm_end': ([vp], i32),
         'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
         'plsx_simpls_vip_ci': ([vp, vp, ctypes.c_longlong, i32, i32, c_d, i32, c_d, vp, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
@@ -131,7 +134,8 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
+             'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -828,6 +832,46 @@ class Engine(object):
         self._check(self.lib.plsx_simpls_coef_ci(self.ctx, stack.data_ptr(), n, idx[0][0], idx[0][1], idx[1][0],
                                                  idx[1][1], lo.data_ptr(), hi.data_ptr(), self._stream()))
         return lo, hi
+
+    def simpls_coef_perm_test(self, stack, obs, count, dmax, standardise=True):
+        """The permutation statistics of ``stack`` (n, T, S) -- any contiguous float64 device tensor -- against the
+        observed coefficients ``obs`` (B, T): ``count`` (B, T) int32 += the number of b with
+        ``s_f |(Xc.T @ stack[b].T)[f, t]| >= s_f |obs[f, t]|``, ``dmax`` (n, T) = the maximum over the features of the
+        left side; s_f the standard deviation of feature f when ``standardise``, else 1
+        (plsx_simpls_coef_perm_test).  No sync."""
+        torch = _torch()
+        if stack.dim() != 3 or tuple(stack.shape[1:]) != (self.T, self.S) or stack.dtype != torch.float64 \
+                or not stack.is_contiguous():
+            raise ValueError('the stack must be a contiguous (n, {}, {}) float64 tensor'.format(self.T, self.S))
+        n = int(stack.shape[0])
+        self._check_coef_perm(obs, count, dmax, n)
+        self._check(self.lib.plsx_simpls_coef_perm_test(self.ctx, stack.data_ptr(), n, obs.data_ptr(),
+                                                        1 if standardise else 0, count.data_ptr(), dmax.data_ptr(),
+                                                        self._stream()))
+
+    def _check_coef_perm(self, obs, count, dmax, n):
+        torch = _torch()
+        if tuple(obs.shape) != (self.B, self.T) or obs.dtype != torch.float64 or not obs.is_contiguous():
+            raise ValueError('the observed coefficients must be a contiguous ({}, {}) float64 tensor'.format(self.B, self.T))
+        if tuple(count.shape) != (self.B, self.T) or count.dtype != torch.int32 or not count.is_contiguous():
+            raise ValueError('the counts must be a contiguous ({}, {}) int32 tensor'.format(self.B, self.T))
+        if tuple(dmax.shape) != (n, self.T) or dmax.dtype != torch.float64 or not dmax.is_contiguous():
+            raise ValueError('the maxima must be a contiguous ({}, {}) float64 tensor'.format(n, self.T))
+
+    def simpls_coef_perm_begin(self, c, obs, count, dmax, standardise=True):
+        """Open a permutation series of the coefficients of the ``c``-component model: until
+        :meth:`simpls_coef_perm_end` every :meth:`simpls_perm_into` also forms its permutations' coefficients tile by
+        tile, adds their exceedances of ``obs`` (B, T) to ``count`` (B, T) int32 and appends their maxima over the
+        features to ``dmax`` (capacity, T) in submission order (plsx_simpls_coef_perm_begin).  The three tensors must
+        stay alive until the series ends.  PlsxError: status -1 for c outside 1 .. k and from the batch that would
+        pass the capacity, -4 before the original fit is set."""
+        self._check_coef_perm(obs, count, dmax, int(dmax.shape[0]))
+        self._check(self.lib.plsx_simpls_coef_perm_begin(self.ctx, int(c), obs.data_ptr(), 1 if standardise else 0,
+                                                         count.data_ptr(), dmax.data_ptr(), int(dmax.shape[0])))
+
+    def simpls_coef_perm_end(self):
+        """Close the permutation series of the coefficients (plsx_simpls_coef_perm_end)."""
+        self._check(self.lib.plsx_simpls_coef_perm_end(self.ctx))
 
     def simpls_vip_keep(self, stack):
         """Keep the VIP stack of every bootstrap the :meth:`simpls_boot_into` calls that follow solve: ``stack``

@@ -109,7 +109,7 @@ def _check_cvsplits(masks, usable, k, B):
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
-                   cv_perm=0, cvpermsamples=None, vip_components=None, **kwargs):
+                   cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -140,6 +140,20 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     as for ``y_loadings_ci`` the original fit is not added to the series).  The (B, T, n_boot) coefficients exist on the
     device only, one chunk of features at a time; what is kept is 8 T S n_boot bytes (on every GPU of a team: the
     closing pass runs on the first).  ``n_boot`` <= 16384.  Every other array of the call keeps its bits.
+
+    ``coef_perm=True`` (needs ``coef_components`` and ``n_perm > 0``; False, the default: nothing is added) tests the
+    coefficients against permuted behaviour.  The c-component model is fitted on ``(X, Y[perm_p])`` for the SAME
+    permutations as ``permres.permsamples`` (3-D Y: the aggregated Y is permuted; rows that are NaN throughout: position
+    p is usable iff row p of X and row perm[p] of Y are), giving coefficients ``b_p`` (B, T) that exist on the device
+    only, one tile at a time.  ``permres`` gains ``coefs_pvals`` (B, T), the uncorrected two-sided p-value
+    ``(#{p : |b_p[f, t]| >= |coefs[f, t]|} + 1) / (n_perm + 1)``; ``coefs_max`` (T, n_perm), the null of the single-step
+    max statistic per behaviour, ``max_f s_f |b_p[f, t]|`` with ``s_f`` the standard deviation of feature f over the
+    usable rows of X (so the maximum runs over standardised coefficients); and ``coefs_pvals_fwe`` (B, T) =
+    ``(#{p : coefs_max[t, p] >= s_f |coefs[f, t]|} + 1) / (n_perm + 1)``, the maxT p-value of Westfall & Young,
+    family-wise over the features of one behaviour (for a family that spans the behaviours too, compare against
+    ``coefs_max.max(axis=0)``).  The comparison is ``>=``, not the strict ``>`` of ``permres.pvals``: a feature without
+    variance has ``coefs = b_p = 0`` exactly and comes out at p = 1, not 1 / (n_perm + 1); everywhere else an exact
+    tie has probability zero.  Every other array of the call keeps its bits.
 
     Permutation test of the cross-validation: ``cv_perm=P`` (needs cross-validation; 0, the default: nothing is added,
     no memory is taken) repeats the whole cross-validation -- the SAME splits -- on ``(X, Y[perm])`` for P permutations
@@ -202,6 +216,17 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              'device only, one chunk of features at a time'
                              .format(n_boot, 8.0 * X.shape[1] * Y.shape[1] * n_boot / 2 ** 30))
         kwargs['coef_ci'] = True                   # (recorded in `inputs` only when asked for)
+    if isinstance(coef_perm, (bool, np.bool_)):
+        coef_perm = bool(coef_perm)
+    else:
+        raise ValueError('Provided `coef_perm` must be True or False; got {!r}'.format(coef_perm))
+    if coef_perm:                                  # (as above: on the host, before any engine)
+        if coef_components is None:
+            raise ValueError('`coef_perm` needs `coef_components`: the p-values are those of the coefficients of the '
+                             'model of that many components')
+        if not n_perm or n_perm < 1:
+            raise ValueError('`coef_perm` needs permutations: n_perm = {!r}'.format(n_perm))
+        kwargs['coef_perm'] = True                 # (recorded in `inputs` only when asked for)
     if vip_components is not None:                 # (as above: on the host, before any engine)
         if isinstance(vip_components, bool) or int(vip_components) != vip_components \
                 or not 1 <= int(vip_components) <= n_components:
@@ -396,7 +421,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
                 k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
                 coef_c=coef_components, coef_ci=coef_ci,
-                vip_c=vip_components))
+                vip_c=vip_components, coef_perm=coef_perm))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -406,7 +431,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
                                       kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci,
-                vip_c=vip_components)
+                                      vip_c=vip_components, coef_perm=coef_perm)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -421,7 +446,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
                 bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None,
-                coef_ci=False, vip_c=None):
+                coef_ci=False, vip_c=None, coef_perm=False):
     import time
     import torch
     S = len(X)
@@ -482,7 +507,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
 
     # this rank's shards (permutations contiguous, bootstraps chunk-cyclic), launched chunk by chunk as the index rows arrive; the
     # results stay on the device until the one collective
-    d_perm = d_yl = usum = usq = bsum = bsq = d_keep = d_vkeep = None
+    d_perm = d_yl = usum = usq = bsum = bsq = d_keep = d_vkeep = d_cmax = d_ccnt = coefs_obs = None
     n_perm_tot = pstream.n if pstream is not None else 0
     n_boot_tot = bstream.n if bstream is not None else 0
     from .progress import Bar                            # verbose=True: the reference's bars (pyls/utils.py:128-152)
@@ -491,12 +516,26 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     if pstream is not None:
         lo, hi = parallel.shard_bounds(n_perm_tot, rank, world)
         d_perm = eng._zeros((hi - lo, k))
+        if coef_perm:
+            # the observed coefficients, from the decomposition, uploaded once; each rank opens a series over its own
+            # shard: the permutations' coefficients are formed tile by tile along the solver batches, counted against the
+            # observed ones and reduced to their maxima over the features (plsx_simpls_coef_perm_begin)
+            eng.sync()                                  # (the x_weights are on the host)
+            coefs_obs = _model_coefs(_host_array(h_W), Yc[mask].T @ x_scores[mask], x_scores, Y_agg, mask, coef_c)
+            d_cobs = eng._dev(coefs_obs, np.float64)
+            d_ccnt = torch.zeros((B, T), dtype=torch.int32, device=eng.device)
+            d_cmax = eng._zeros((hi - lo, T))
+            if hi > lo:
+                eng.simpls_coef_perm_begin(coef_c, d_cobs, d_ccnt, d_cmax)
+            tick('coefs_perm')                          # (the set-up; the series itself runs inside 'permutations')
         bars.append(Bar('Running permutations', hi - lo, show, eng.device))
         # (a solver batch is a latency chain of ~3 k launches whatever its size: few, large chunks -- the first 2048 rows
         # are drawn in 5 ms)
         for a, b in pstream.chunks(lo, hi, first=2048):
             eng.simpls_perm_into(eng.rows_tensor(pstream.rows[a:b]), d_perm[a - lo:b - lo])
             bars[-1].queued(b - a)
+        if d_cmax is not None:
+            eng.simpls_coef_perm_end()
     tick('permutations')
     if bstream is not None:
         bchunks = parallel.shard_chunks(n_boot_tot, rank, world)     # chunk-cyclic share of the bootstraps
@@ -597,8 +636,9 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     finally:
         for bar in bars:
             bar.close()
-    slices = [t for t in (d_perm, d_yl) if t is not None]
-    totals = [n for t, n in ((d_perm, n_perm_tot), (d_yl, n_boot_tot)) if t is not None]
+    # (the maxima of the coefficient series ride next to d_perm, a contiguous slice like it)
+    slices = [t for t in (d_perm, d_cmax, d_yl) if t is not None]
+    totals = [n for t, n in ((d_perm, n_perm_tot), (d_cmax, n_perm_tot), (d_yl, n_boot_tot)) if t is not None]
     cyclic = [len(slices) - 1] if d_yl is not None else []
     if d_cv is not None:                                # the cross-validation rows ride in the same buffer: ONE collective
         slices, totals = slices + d_cv, totals + [cv['n']] * 3
@@ -611,6 +651,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         slices, totals = slices + [d_vkeep], totals + [n_boot_tot]
         cyclic = cyclic + [len(slices) - 1]
     sums = [t for t in (usum, usq, bsum, bsq) if t is not None]      # (the coefficient sums join the summed part)
+    if d_ccnt is not None:                              # ... and the exceedance counts, as float64: they are exact
+        sums = sums + [d_ccnt.to(torch.float64)]
     full, summed = parallel.collect_device(slices, totals, sums, emulate=emulate, cyclic=cyclic, team=team)
     if not lead:
         return None                                     # rank 0 holds everything the ranks computed: it finishes
@@ -638,6 +680,9 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     if pstream is not None:
         d_perm = np.ascontiguousarray(full[i].T)                    # (k, n_perm)
         i += 1
+        if d_cmax is not None:
+            coefs_max = np.ascontiguousarray(full[i].T)             # (T, n_perm)
+            i += 1
     if bstream is not None:
         distrib = np.ascontiguousarray(np.moveaxis(full[i], 0, -1))  # (T, k, n_boot)
         i += 1
@@ -666,6 +711,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         res['permres']['pvals'] = hostmath.perm_sig(pctvar, d_perm)
         res['permres']['permsamples'] = permsamp
         res['permres']['perm_singval'] = d_perm
+        if d_cmax is not None:
+            cnt = np.rint(summed[-1].detach().cpu().numpy()).astype(np.int64)
+            res['permres'].update(_coef_perm_pvals(coefs_obs, cnt, coefs_max,
+                                                   _feature_scale(X, okx, None if clean else Xc)))
 
     res['y_loadings'] = Yc[mask].T @ x_scores[mask]                # regression.py:401
     y_scores = np.full((S, k), np.nan)
@@ -674,7 +723,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     res['x_weights'] = _host_array(h_W)
     if coef_c is not None:
         # the model of the first coef_c components (simpls' beta, regression.py:149-151): Y ~ intercept + X @ coefs
-        res['coefs'] = _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_agg, mask, coef_c)
+        res['coefs'] = coefs_obs if coefs_obs is not None else \
+            _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_agg, mask, coef_c)
         res['intercept'] = _model_means(X, Y_agg, mask, res['coefs'])
     if vip_c is not None:
         res['vip'] = _vip_scores(res['x_weights'], _fit_yloadings(res['y_loadings'], x_scores, Y_agg, mask, vip_c), vip_c)
@@ -702,6 +752,35 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     res['varexp'] = pctvar                                          # regression.py:425-426
     tick('host_finish')
     return res
+
+
+def _feature_scale(X, okx, Xc=None):
+    """s_f (B,): the standard deviation (n - 1) of every feature over the usable rows of X -- the scale of the
+    standardised coefficients of ``coef_perm``.  Xc: the centred X where the caller already holds it (masked rows NaN or
+    zero); otherwise X is centred here, a block of columns at a time."""
+    S, B = X.shape
+    n_x = int(np.sum(okx))
+    ss = np.empty(B)
+    step = max(1, (32 << 20) // (8 * S))
+    for lo in range(0, B, step):
+        blk = (Xc if Xc is not None else X)[:, lo:lo + step][okx].astype(np.float64)
+        if Xc is None:
+            blk = blk - blk.mean(axis=0, keepdims=True)
+        ss[lo:lo + step] = np.einsum('sf,sf->f', blk, blk)
+    return np.sqrt(ss / (n_x - 1))
+
+
+def _coef_perm_pvals(coefs, count, coefs_max, scale):
+    """The three arrays ``coef_perm`` adds to permres.  coefs (B, T) observed; count (B, T) = #{p : |b_p| >= |coefs|};
+    coefs_max (T, n_perm) = max_f s_f |b_p[f, t]|; scale (B,) = s_f.  The maxT p-value counts, per behaviour, the
+    maxima at or above the observed standardised magnitude: one sort and one searchsorted per behaviour."""
+    n_perm = coefs_max.shape[1]
+    obs = scale[:, None] * np.abs(coefs)
+    fwe = np.empty(coefs.shape)
+    for t in range(coefs.shape[1]):
+        null = np.sort(coefs_max[t])
+        fwe[:, t] = (n_perm - np.searchsorted(null, obs[:, t], side='left') + 1) / (n_perm + 1)
+    return dict(coefs_pvals=(count + 1) / (n_perm + 1), coefs_max=coefs_max, coefs_pvals_fwe=fwe)
 
 
 def _fit_yloadings(Q, x_scores, Y_agg, mask, c):

@@ -94,6 +94,7 @@ class PLSInputs(KeyedRecord):
         'coef_components',                  # pls_regression: component count of the returned model (only when asked for)
         'coef_ci',                          # pls_regression: percentile intervals of its coefficients (only when asked for)
         'cv_perm',                          # pls_regression: permutations of the cross-validation (only when asked for)
+        'coef_perm',                        # pls_regression: permutation p-values of its coefficients (only when asked for)
         'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
@@ -134,7 +135,10 @@ class PLSBootResults(KeyedRecord):
 
 
 class PLSPermResults(KeyedRecord):
-    allowed = ('pvals', 'permsamples', 'perm_singval')
+    # pls_regression(coef_components=c, coef_perm=True): coefs_pvals (B, T) uncorrected two-sided p-values of the
+    # coefficients, coefs_max (T, n_perm) the null of the max statistic over standardised coefficients per behaviour,
+    # coefs_pvals_fwe (B, T) the maxT p-values (family-wise over the features of one behaviour)
+    allowed = ('pvals', 'permsamples', 'perm_singval', 'coefs_pvals', 'coefs_max', 'coefs_pvals_fwe')
 
 
 class PLSSplitHalfResults(KeyedRecord):
