@@ -10,6 +10,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 #define PLSX_MAX_TP 1280        // largest stacked dimension T' (rows of one resample; sliced over blocks above 352)
 #define PLSX_BLOCK_TP 352       // largest T' whose rows fit ONE cross-product block (22 data tiles + moments)
+#define PLSX_MAX_BPAD 16000000  // largest padded feature count plsx_set_data binds (32-bit offsets along a row of features)
 #define PLSX_MAX_CELLS 352      // largest number of group x condition cells
 #define PLSX_JACOBI_TP 64       // largest T' of the LDS Jacobi small solver; above it Householder + QL (plsx_symeig.h)
 #define PLSX_UROT_KC 20         // k-steps (of 4 rows of T') per LDS stage of the rotation operand when it is staged in pieces

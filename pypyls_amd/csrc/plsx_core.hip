@@ -465,7 +465,7 @@ try {
     // to kernels that would have read zeros.  (Columns alone: a 4-row k-step of X, 32 Bpad bytes, fits up to 67 million.)
     {
         const long long tpp = ((long long)Tp + 3) / 4 * 4, bpad = ((long long)B + std::min(Tp, B) + 127) / 128 * 128;
-        if (tpp * bpad * 8 >= (1LL << 31) || bpad > 16000000LL) {
+        if (tpp * bpad * 8 >= (1LL << 31) || bpad > (long long)PLSX_MAX_BPAD) {
             char msg[256];
             snprintf(msg, sizeof msg, "T' x B too large: one cross-covariance matrix (%lld x %lld doubles = %.2f GB) must "
                      "stay below 2 GB, and B below 16,000,000 (32-bit buffer offsets)", tpp, bpad, tpp * bpad * 8 / 1073741824.0);

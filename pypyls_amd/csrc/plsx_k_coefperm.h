@@ -26,11 +26,11 @@ void k_col_sd(const double* __restrict__ Xc, int ldx, int S, int B, double nx, d
 
 // ---------------------------------------------------------------------------
 // The test statistics of one piece of n permutations (or any stack A [n][T][S]) against the observed coefficients,
-// without storing a product.  coef_b[f][t] = sum_s Xc[s][f] . A[b][t][s] is k_coef_prod's product -- the same staging,
-// pitches, fragment maps and ascending-s contraction, so the same bits -- but a block owns 128 features of ONE
-// behaviour and walks ALL the 64-permutation tiles of the piece.  Its lanes keep, per row of their accumulators
-// (D[m = (l >> 4) + 4 i][n = l & 15]: 8 rows per lane), the scale s_f, the observed statistic s_f |obs[f][t]| and an
-// integer count.  After each tile:
+// without storing a product.  coef_b[f][t] = sum_s Xc[s][f] . A[b][t][s] is k_coef_prod's product through k_coef_prod's
+// own contraction (cp_contract of plsx_k_coefci.h, which describes the tile), so the same bits -- but a block owns 128
+// features of ONE behaviour and walks ALL the 64-permutation tiles of the piece.  Its lanes keep, per row of their
+// accumulators (cp_feature: 8 rows per lane), the scale s_f, the observed statistic s_f |obs[f][t]| and an integer
+// count.  After each tile:
 //   * v = s_f |coef_b[f][t]|; count += (v >= observed) for the tile's valid (f, b);
 //   * the tile's per-permutation maximum over the block's 128 features: over the lane's 8 rows in registers, over the
 //     four row groups of a wave with __shfl_xor 16 / 32, over the four waves through LDS; stored to the partial
@@ -58,10 +58,8 @@ void k_coef_perm_prod(CoefPermArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fb = a.f0 + blockIdx.x * 128;         // (fb + 127 < ldx: both multiples of 128, fb < B <= ldx)
     const int t = blockIdx.y;
-    const int S = a.S;
     const int fend = min(a.B, a.f0 + a.fc);
-    // pairs of doubles of a stack row are 16-byte aligned when S is even and the stack itself is
-    const bool al2 = (S & 1) == 0 && (reinterpret_cast<size_t>(a.A) & 15) == 0;
+    const bool al2 = cp_aligned(a.A, a.S);
 
     // the lane's 8 rows: scale, observed statistic, count
     double sf[2][4], ob[2][4];
@@ -70,67 +68,20 @@ void k_coef_perm_prod(CoefPermArgs a)
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int f = fb + wave * 32 + r * 16 + (lane >> 4) + 4 * i;
-            const bool ok = f < fend;
-            sf[r][i] = ok ? (a.sd ? a.sd[f] : 1.0) : 0.0;
-            ob[r][i] = ok ? sf[r][i] * fabs(a.obs[(size_t)f * a.T + t]) : 0.0;
+            const int f = cp_feature(fb, fend, r, i);
+            sf[r][i] = f >= 0 ? (a.sd ? a.sd[f] : 1.0) : 0.0;
+            ob[r][i] = f >= 0 ? sf[r][i] * fabs(a.obs[(size_t)f * a.T + t]) : 0.0;
             cnt[r][i] = 0;
         }
 
-    const int xcol = (tid & 63) * 2, xrow = tid >> 6;       // feature stage: row xrow + 4 i, one d2 of the 128 features
-    const int seg = tid & 15, rbase = tid >> 4;             // stack stage: permutation rbase + 16 i, d2 slot seg of 32 subjects
     double* pm = a.pmax + ((size_t)blockIdx.x * a.T + t) * a.n;
+    const double* At = a.A + (size_t)t * a.S;       // row t of permutation 0; a permutation further on is T S doubles on
+    const size_t pitch = (size_t)a.T * a.S;
     for (int b0 = 0; b0 < a.n; b0 += 64) {
         d4 acc[2][4];
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[r][i] = (d4){0, 0, 0, 0};
-        d2 rx[8], ra[4];
-        auto fetch = [&](int kk) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int s = kk + xrow + 4 * i;
-                d2 v = (d2){0, 0};
-                if (s < S) v = *reinterpret_cast<const d2*>(a.Xc + (size_t)s * a.ldx + fb + xcol);
-                rx[i] = v;
-            }
-            const int c = kk + seg * 2;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int b = b0 + rbase + 16 * i;
-                d2 v = (d2){0, 0};
-                if (b < a.n) {
-                    const double* p = a.A + ((size_t)b * a.T + t) * S + c;
-                    if (c + 1 < S) v = al2 ? *reinterpret_cast<const d2*>(p) : (d2){p[0], p[1]};
-                    else if (c < S) v = (d2){p[0], 0.0};
-                }
-                ra[i] = v;
-            }
-        };
-        fetch(0);
-        for (int kk = 0; kk < S; kk += CP_KB) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) *reinterpret_cast<d2*>(&sX[(xrow + 4 * i) * CP_XLD + xcol]) = rx[i];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) *reinterpret_cast<d2*>(&sA[(rbase + 16 * i) * CP_ALD + seg * 2]) = ra[i];
-            __syncthreads();
-            if (kk + CP_KB < S) fetch(kk + CP_KB);
-#pragma unroll
-            for (int ks = 0; ks < CP_KB / 4; ++ks) {
-                const int kr = ks * 4 + (lane >> 4);
-                double fx[2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r) fx[r] = sX[kr * CP_XLD + wave * 32 + r * 16 + (lane & 15)];
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    const double fa = sA[(nt * 16 + (lane & 15)) * CP_ALD + kr];
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) acc[r][nt] = mfma_f64(fx[r], fa, acc[r][nt]);
-                }
-            }
-            __syncthreads();
-        }
+        cp_clear(acc);
+        cp_contract(CpTile{a.Xc, a.ldx, a.S, a.n, fb, b0, al2},
+                    [&](int b) { return At + b * pitch; }, sX, sA, acc);
         // compare and count; the tile's maximum over the lane's rows (rows f >= fend carry s_f = 0: the identity of a
         // maximum of magnitudes)
 #pragma unroll
@@ -164,8 +115,8 @@ void k_coef_perm_prod(CoefPermArgs a)
             c += __shfl_xor(c, 2);
             c += __shfl_xor(c, 4);
             c += __shfl_xor(c, 8);
-            const int f = fb + wave * 32 + r * 16 + (lane >> 4) + 4 * i;
-            if ((lane & 15) == 0 && f < fend) a.count[(size_t)f * a.T + t] += c;
+            const int f = cp_feature(fb, fend, r, i);
+            if ((lane & 15) == 0 && f >= 0) a.count[(size_t)f * a.T + t] += c;
         }
 }
 

@@ -9,9 +9,8 @@
 // one contiguous series of n bootstraps per feature -- what the selection kernels and k_vip_moments read.  G is the
 // kept stack of plsx_simpls_vip_keep: row a of bootstrap b is the dual weight of component a in subject space, scaled
 // by sqrt(ssq_a / (|w_a|^2 sum ssq)), so that the contraction of a row is the share of component a in VIP_b[f]^2 / B.
-// The square root of a sum of squares over the components is no quadratic form of the stack: the block keeps k_coef_prod's tile,
-// staging, pitches and prefetch (128 features x 64 bootstraps, a wave 32 x 64, v_mfma_f64_16x16x4_f64; see
-// plsx_k_coefci.h) and loops over the c components itself:
+// The square root of a sum of squares over the components is no quadratic form of the stack: the block contracts
+// k_coef_prod's tile (the cp_* pieces of plsx_k_coefci.h, which describes it) once per component, in one loop of its own:
 //   * per component the accumulator tile (32 doubles per lane) takes the full contraction over s in ascending order;
 //     it is then squared into a second register tile (32 more doubles per lane) and cleared;
 //   * the first stage of the next component is fetched while the last stage of the current one is multiplied;
@@ -33,79 +32,37 @@ void k_vip_prod(VipProdArgs a)
 {
     __shared__ __attribute__((aligned(16))) double sX[CP_KB * CP_XLD];
     __shared__ __attribute__((aligned(16))) double sA[64 * CP_ALD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63;
     const int fb = a.f0 + blockIdx.x * 128;         // (fb + 127 < ldx: both multiples of 128, fb < B <= ldx)
     const int b0 = blockIdx.y * 64;
     const int S = a.S, nc = a.c;
-    // pairs of doubles of a stack row are 16-byte aligned when S is even and the stack itself is
-    const bool al2 = (S & 1) == 0 && (reinterpret_cast<size_t>(a.G) & 15) == 0;
+    const CpTile tl{a.Xc, a.ldx, S, a.n, fb, b0, cp_aligned(a.G, S)};
+    auto row = [&](int comp) { return [&a, comp](int b) { return a.G + ((size_t)b * a.c + comp) * a.S; }; };
 
     d4 acc[2][4], sq[2][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { acc[r][i] = (d4){0, 0, 0, 0}; sq[r][i] = (d4){0, 0, 0, 0}; }
-
-    const int xcol = (tid & 63) * 2, xrow = tid >> 6;       // feature stage: row xrow + 4 i, one d2 of the 128 features
-    const int seg = tid & 15, rbase = tid >> 4;             // stack stage: bootstrap rbase + 16 i, d2 slot seg of 32 subjects
-    d2 rx[8], ra[4];
-    auto fetch = [&](int comp, int kk) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int s = kk + xrow + 4 * i;
-            d2 v = (d2){0, 0};
-            if (s < S) v = *reinterpret_cast<const d2*>(a.Xc + (size_t)s * a.ldx + fb + xcol);
-            rx[i] = v;
-        }
-        const int c = kk + seg * 2;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + rbase + 16 * i;
-            d2 v = (d2){0, 0};
-            if (b < a.n) {
-                const double* p = a.G + ((size_t)b * nc + comp) * S + c;
-                if (c + 1 < S) v = al2 ? *reinterpret_cast<const d2*>(p) : (d2){p[0], p[1]};
-                else if (c < S) v = (d2){p[0], 0.0};
-            }
-            ra[i] = v;
-        }
-    };
-    fetch(0, 0);
+    cp_clear(acc);
+    cp_clear(sq);
+    CpStage g;
+    cp_fetch(g, tl, 0, row(0));
     // one loop over the (component, stage) pairs: a single fetch site, whose next pair is the next stage of the
     // component or the first stage of the next one
     int comp = 0, kk = 0;
     while (comp < nc) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<d2*>(&sX[(xrow + 4 * i) * CP_XLD + xcol]) = rx[i];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<d2*>(&sA[(rbase + 16 * i) * CP_ALD + seg * 2]) = ra[i];
+        cp_store(g, sX, sA);
         __syncthreads();
         const bool last = kk + CP_KB >= S;
         const int ncomp = last ? comp + 1 : comp, nkk = last ? 0 : kk + CP_KB;
-        if (ncomp < nc) fetch(ncomp, nkk);
-#pragma unroll
-        for (int ks = 0; ks < CP_KB / 4; ++ks) {
-            const int kr = ks * 4 + (lane >> 4);
-            double fx[2];
-#pragma unroll
-            for (int r = 0; r < 2; ++r) fx[r] = sX[kr * CP_XLD + wave * 32 + r * 16 + (lane & 15)];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const double fa = sA[(nt * 16 + (lane & 15)) * CP_ALD + kr];
-#pragma unroll
-                for (int r = 0; r < 2; ++r) acc[r][nt] = mfma_f64(fx[r], fa, acc[r][nt]);
-            }
-        }
+        if (ncomp < nc) cp_fetch(g, tl, nkk, row(ncomp));
+        cp_mma(sX, sA, acc);
         __syncthreads();
         if (last) {
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
+                for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) sq[r][nt][i] += acc[r][nt][i] * acc[r][nt][i];
-                    acc[r][nt] = (d4){0, 0, 0, 0};
-                }
+            cp_clear(acc);
         }
         comp = ncomp; kk = nkk;
     }
@@ -115,13 +72,13 @@ void k_vip_prod(VipProdArgs a)
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int f = fb + wave * 32 + r * 16 + (lane >> 4) + 4 * i;
-            if (f >= fend) continue;
-            double* row = a.out + (size_t)(f - a.f0) * a.n;
+            const int f = cp_feature(fb, fend, r, i);
+            if (f < 0) continue;
+            double* row_out = a.out + (size_t)(f - a.f0) * a.n;
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 const int b = b0 + nt * 16 + (lane & 15);
-                if (b < a.n) row[b] = sqrt(nfeat * sq[r][nt][i]);
+                if (b < a.n) row_out[b] = sqrt(nfeat * sq[r][nt][i]);
             }
         }
 }

@@ -38,7 +38,7 @@
 //   plsx_k_urot.h      the rotation kernel k_urot
 //   plsx_k_misc.h      small helpers, dual-space products of one wave (k_dual_gp), the quadratic-form route of the bootstrap sums, sign flip / scaling / transposition kernels
 //   plsx_k_finish.h    split-half projections and finishing (k_ucorr_partial, k_split_final), cross-validation, percentile intervals
-//   plsx_k_coefci.h    percentile intervals of the SIMPLS model coefficients: the feature pass k_coef_prod
+//   plsx_k_coefci.h    percentile intervals of the SIMPLS model coefficients: the feature pass k_coef_prod, and the tile contraction (cp_fetch / cp_store / cp_mma / cp_contract / cp_feature) it shares with k_coef_perm_prod and k_vip_prod
 //   plsx_k_coefperm.h  permutation test of the SIMPLS model coefficients: the feature pass k_coef_perm_prod (counts and maxima, no product stored), k_coef_perm_max, the feature scale k_col_sd
 //   plsx_k_vip.h       VIP scores of the SIMPLS bootstraps: the feature pass k_vip_prod, the moments of its series (k_vip_moments)
 #pragma once

@@ -217,6 +217,44 @@ bool simpls_single_pass(const plsx_ctx* ctx)
 }
 
 
+// Free device bytes, with what an earlier pass left allocated in `own` -- the buffer the caller is about to size --
+// counting as free.
+static int free_bytes(plsx_ctx* ctx, const Buf& own, double* have)
+{
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    *have = (double)free_b + (double)own.bytes;
+    return 0;
+}
+
+// Feature chunks of a closing pass over a kept stack of n resamples (plsx_simpls_coef_ci, plsx_simpls_vip_ci): whole
+// 128-feature blocks whose series, `per_feat` bytes a feature, stay next to the stack (`stack` bytes) inside the scratch
+// budget and in free device memory, 2 GB at most -- the series are written once and read once, a larger chunk buys
+// nothing.  Sets *fc (the caller sizes ctx->cichunk for it, fc . per_feat bytes, after its own checks); refuses when not
+// even the smallest chunk fits.  `dim`, `dimv`: the name and value of the stack's middle dimension ("T" or "c") in the
+// refusal.
+static int ci_chunk(plsx_ctx* ctx, const char* who, long long n, double stack, double per_feat, const char* dim,
+                    int dimv, long long* fc)
+{
+    const int B = ctx->B, unit = std::min(B, 128);
+    double have;
+    if (int e = free_bytes(ctx, ctx->cichunk, &have)) return e;
+    const double room = std::min(ctx->scratch_gb * 1073741824.0 - stack, have);
+    if (room < unit * per_feat) {
+        char msg[400];
+        snprintf(msg, sizeof msg, "%s: the stack of n = %lld bootstraps (8 n %s S = %.3f GB for %s = %d, "
+                 "S = %d) and the series of the smallest chunk of %d features (%.3f GB) need %.3f GB; the scratch budget "
+                 "is %.3f GB and %.3f GB of device memory are free", who, n, dim, stack / 1073741824.0, dim, dimv,
+                 ctx->S, unit, unit * per_feat / 1073741824.0, (stack + unit * per_feat) / 1073741824.0, ctx->scratch_gb,
+                 have / 1073741824.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    *fc = (long long)(std::min(room, 2147483648.0) / per_feat);
+    *fc = std::max<long long>(unit, *fc / 128 * 128);
+    if (*fc >= B) *fc = B;
+    return 0;
+}
+
 // The coefficient series' share of a solver batch (plsx_simpls_coef_begin): k_sd_coef writes A_b of `ms` bootstraps
 // dense, in chunks of at most 1 GB, and each chunk goes through quad_accumulate on the series' own accumulator set.
 // `a`: the state run_simpls_dual just left (args_out).  The solver batches themselves are what they are without a
@@ -226,10 +264,38 @@ static QuadSet coef_set(plsx_ctx* ctx, const double* Ad = nullptr)
     return QuadSet{&ctx->Cc, &ctx->Asumc, Ad ? Ad : ptr<double>(ctx->Adc), ctx->T};
 }
 
+// Waves per block and dynamic LDS of a kernel that gives each wave `per_wave` bytes (k_sd_coef, k_sd_vip): up to four
+// waves inside 64 KB.
+static int sd_waves(size_t per_wave, size_t* lds)
+{
+    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / std::max<size_t>(per_wave, 1)));
+    *lds = (size_t)wpb * per_wave;
+    return wpb;
+}
+
+// k_sd_coef on the state `a` run_simpls_dual just left for a batch of `ms` resamples: A_r of resamples r0 .. r0 + mc - 1
+// with cc components, dense into Ad [mc][T][S]; Q in ctx->Qc.  The kernel variant goes by the batch, not by mc.
+static int sd_coef_launch(plsx_ctx* ctx, SdArgs a, int cc, int ms, int r0, int mc, double* Ad, hipStream_t st)
+{
+    const bool gl = simpls_global(ctx);
+    // (a batch's first chunk is its largest and ensure() never shrinks: Qc is sized once per batch)
+    if (int e = ensure(ctx, ctx->Qc, (size_t)mc * cc * ctx->T * 8)) return e;
+    size_t lds;
+    const int wpb = sd_waves(((size_t)cc + (gl ? 0 : (size_t)ctx->S)) * 8, &lds);
+    a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
+    a.cfA = Ad; a.cf_r0 = r0; a.cf_n = mc;
+    KTimer tm(ctx, KC_COEF, st);
+    // (more waves than two per SIMD of the chip: the short position tiles, as in the solver)
+    void (*coef_kernel)(SdArgs) = gl ? k_sd_coef<16, true> : (ms > 2048 ? k_sd_coef<8, false> : k_sd_coef<16, false>);
+    HIPCHK(set_lds(coef_kernel, lds));
+    hipLaunchKernelGGL(coef_kernel, dim3(ceil_div(mc, wpb)), dim3(wpb * 64), lds, st, a);
+    LAUNCHCHK();
+    return 0;
+}
+
 static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 {
     const int S = ctx->S, T = ctx->T, cc = ctx->coef_c;
-    const bool gl = simpls_global(ctx);
     const int chunk = (int)std::max<long long>(1, std::min<long long>(ms, (1LL << 30) / ((long long)T * S * 8)));
     // (a series that keeps its A_b -- plsx_simpls_coef_keep -- has every chunk written where it stays, in the caller's
     // buffer, and accumulated from there: the same values through the same kernels, so the sums keep their bits)
@@ -237,24 +303,11 @@ static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
         return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_boot_batch: the kept coefficient stack is full");
     if (!ctx->keepA)
         if (int e = ensure(ctx, ctx->Adc, (size_t)chunk * T * S * 8)) return e;
-    if (int e = ensure(ctx, ctx->Qc, (size_t)chunk * cc * T * 8)) return e;
-    const size_t per_wave = ((size_t)cc + (gl ? 0 : (size_t)S)) * 8;
-    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / per_wave));
-    const size_t lds = (size_t)wpb * per_wave;
-    a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
     for (int r0 = 0; r0 < ms; r0 += chunk) {
         const int mc = std::min(chunk, ms - r0);
-        a.cfA = ctx->keepA ? ctx->keepA + (size_t)(ctx->keep_n + r0) * T * S : ptr<double>(ctx->Adc);
-        a.cf_r0 = r0; a.cf_n = mc;
-        {
-            KTimer tm(ctx, KC_COEF, st);
-            // (more waves than two per SIMD of the chip: the short position tiles, as in the solver)
-            void (*coef_kernel)(SdArgs) = gl ? k_sd_coef<16, true> : (ms > 2048 ? k_sd_coef<8, false> : k_sd_coef<16, false>);
-            HIPCHK(set_lds(coef_kernel, lds));
-            hipLaunchKernelGGL(coef_kernel, dim3(ceil_div(mc, wpb)), dim3(wpb * 64), lds, st, a);
-            LAUNCHCHK();
-        }
-        const QuadSet qs = coef_set(ctx, a.cfA);
+        double* Ad = ctx->keepA ? ctx->keepA + (size_t)(ctx->keep_n + r0) * T * S : ptr<double>(ctx->Adc);
+        if (int e = sd_coef_launch(ctx, a, cc, ms, r0, mc, Ad, st)) return e;
+        const QuadSet qs = coef_set(ctx, Ad);
         if (int e = quad_accumulate(ctx, mc, st, &qs)) return e;
     }
     ctx->coef_n += ms;
@@ -272,9 +325,8 @@ static int vip_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
     const bool gl = simpls_global(ctx);
     if (ctx->vip_n + ms > ctx->vip_cap)
         return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_boot_batch: the kept VIP stack is full");
-    const size_t per_wave = gl ? 0 : (size_t)S * 8;
-    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / std::max<size_t>(per_wave, 1)));
-    const size_t lds = (size_t)wpb * per_wave;
+    size_t lds;
+    const int wpb = sd_waves(gl ? 0 : (size_t)S * 8, &lds);
     a.vpG = ctx->vipG + (size_t)ctx->vip_n * cc * S; a.vp_c = cc;
     {
         KTimer tm(ctx, KC_COEF, st);
@@ -348,26 +400,13 @@ static int coef_perm_run(plsx_ctx* ctx, const double* A, long long n, const doub
 // state run_simpls_dual just left (args_out; weights on).
 static int coef_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 {
-    const int S = ctx->S, T = ctx->T, cc = ctx->cperm_c;
-    const bool gl = simpls_global(ctx);
+    const int S = ctx->S, T = ctx->T;
     if (int e = ensure(ctx, ctx->cpA, (size_t)ms * T * S * 8)) return e;
-    if (int e = ensure(ctx, ctx->Qc, (size_t)ms * cc * T * 8)) return e;
-    const size_t per_wave = ((size_t)cc + (gl ? 0 : (size_t)S)) * 8;
-    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / per_wave));
-    const size_t lds = (size_t)wpb * per_wave;
-    a.cfq = ptr<double>(ctx->Qc); a.cf_c = cc;
-    a.cfA = ptr<double>(ctx->cpA); a.cf_r0 = 0; a.cf_n = ms;
-    {
-        KTimer tm(ctx, KC_COEF, st);
-        void (*coef_kernel)(SdArgs) = gl ? k_sd_coef<16, true> : (ms > 2048 ? k_sd_coef<8, false> : k_sd_coef<16, false>);
-        HIPCHK(set_lds(coef_kernel, lds));
-        hipLaunchKernelGGL(coef_kernel, dim3(ceil_div(ms, wpb)), dim3(wpb * 64), lds, st, a);
-        LAUNCHCHK();
-    }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const double room = std::min(0.25 * ctx->scratch_gb * 1073741824.0, (double)free_b + (double)ctx->cppart.bytes);
-    if (int e = coef_perm_run(ctx, a.cfA, ms, ctx->cperm_obs, ctx->cperm_std ? ptr<double>(ctx->colsd) : nullptr,
+    if (int e = sd_coef_launch(ctx, a, ctx->cperm_c, ms, 0, ms, ptr<double>(ctx->cpA), st)) return e;
+    double have;
+    if (int e = free_bytes(ctx, ctx->cppart, &have)) return e;
+    const double room = std::min(0.25 * ctx->scratch_gb * 1073741824.0, have);
+    if (int e = coef_perm_run(ctx, ptr<double>(ctx->cpA), ms, ctx->cperm_obs, ctx->cperm_std ? ptr<double>(ctx->colsd) : nullptr,
                               ctx->cperm_count, ctx->cperm_max + (size_t)ctx->cperm_n * T, room,
                               "plsx_simpls_perm_batch", st))
         return e;
@@ -668,27 +707,9 @@ try {
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
-    // Features go in chunks of whole 128-feature blocks: a chunk's series, fc T n doubles, next to the stack inside the
-    // scratch budget and in free device memory (what an earlier pass left allocated counts as free), 2 GB at most --
-    // the series are written once and read once, a larger chunk buys nothing
-    const double stack = 8.0 * (double)n * T * S, per_feat = 8.0 * T * (double)n;
-    const int unit = std::min(B, 128);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const double have = (double)free_b + (double)ctx->cichunk.bytes;
-    const double budget = ctx->scratch_gb * 1073741824.0;
-    const double room = std::min(budget - stack, have);
-    if (room < unit * per_feat) {
-        snprintf(msg, sizeof msg, "plsx_simpls_coef_ci: the stack of n = %lld bootstraps (8 n T S = %.3f GB for T = %d, "
-                 "S = %d) and the series of the smallest chunk of %d features (%.3f GB) need %.3f GB; the scratch budget "
-                 "is %.3f GB and %.3f GB of device memory are free", n, stack / 1073741824.0, T, S, unit,
-                 unit * per_feat / 1073741824.0, (stack + unit * per_feat) / 1073741824.0, ctx->scratch_gb,
-                 have / 1073741824.0);
-        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
-    }
-    long long fc = (long long)(std::min(room, 2147483648.0) / per_feat);
-    fc = std::max<long long>(unit, fc / 128 * 128);
-    if (fc >= B) fc = B;
+    long long fc;
+    if (int e = ci_chunk(ctx, "plsx_simpls_coef_ci", n, 8.0 * (double)n * T * S, 8.0 * T * (double)n, "T", T, &fc))
+        return e;
     if (fc * T > 2147483647LL)                         // (series per selection launch: one block each, grid x)
         return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_simpls_coef_ci: more than 2^31 series in one chunk");
     if (int e = ensure(ctx, ctx->cichunk, (size_t)fc * T * (size_t)n * 8)) return e;
@@ -724,10 +745,10 @@ try {
         if (int e = col_sd(ctx, st)) return e;
     // the partial maxima stay next to the caller's stack inside the scratch budget and in free device memory (what an
     // earlier pass left allocated counts as free)
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    double have;
+    if (int e = free_bytes(ctx, ctx->cppart, &have)) return e;
     const double stack = 8.0 * (double)n * ctx->T * ctx->S;
-    const double room = std::min(ctx->scratch_gb * 1073741824.0 - stack, (double)free_b + (double)ctx->cppart.bytes);
+    const double room = std::min(ctx->scratch_gb * 1073741824.0 - stack, have);
     return coef_perm_run(ctx, d_A, n, d_obs, standardise ? ptr<double>(ctx->colsd) : nullptr, d_count, d_max, room,
                          "plsx_simpls_coef_perm_test", st);
 } PLSX_CATCH(ctx)
@@ -802,27 +823,9 @@ try {
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
-    // Features go in chunks of whole 128-feature blocks, by the rule of plsx_simpls_coef_ci with 8 n bytes per feature:
-    // a chunk's series, fc n doubles, next to the stack inside the scratch budget and in free device memory (what an
-    // earlier pass left allocated counts as free), 2 GB at most
-    const double stack = 8.0 * (double)n * c * S, per_feat = 8.0 * (double)n;
-    const int unit = std::min(B, 128);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const double have = (double)free_b + (double)ctx->cichunk.bytes;
-    const double budget = ctx->scratch_gb * 1073741824.0;
-    const double room = std::min(budget - stack, have);
-    if (room < unit * per_feat) {
-        snprintf(msg, sizeof msg, "plsx_simpls_vip_ci: the stack of n = %lld bootstraps (8 n c S = %.3f GB for c = %d, "
-                 "S = %d) and the series of the smallest chunk of %d features (%.3f GB) need %.3f GB; the scratch budget "
-                 "is %.3f GB and %.3f GB of device memory are free", n, stack / 1073741824.0, c, S, unit,
-                 unit * per_feat / 1073741824.0, (stack + unit * per_feat) / 1073741824.0, ctx->scratch_gb,
-                 have / 1073741824.0);
-        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
-    }
-    long long fc = (long long)(std::min(room, 2147483648.0) / per_feat);
-    fc = std::max<long long>(unit, fc / 128 * 128);
-    if (fc >= B) fc = B;
+    long long fc;
+    if (int e = ci_chunk(ctx, "plsx_simpls_vip_ci", n, 8.0 * (double)n * c * S, 8.0 * (double)n, "c", c, &fc))
+        return e;
     if (int e = ensure(ctx, ctx->cichunk, (size_t)fc * (size_t)n * 8)) return e;
     VipProdArgs a;
     a.Xc = ptr<double>(ctx->Xc); a.ldx = ctx->Bpad;

@@ -109,6 +109,51 @@ def test_stateless_entry_gives_the_same_bits_when_the_features_go_in_chunks():
     assert np.array_equal(got['default'][1], got['three chunks'][1])
 
 
+@pytest.mark.parametrize('S', [37, 64])
+def test_the_three_feature_passes_share_one_contraction_bit_for_bit(S):
+    """k_coef_prod, k_coef_perm_prod and k_vip_prod contract the same tile through the same pieces (plsx_k_coefci.h), so
+    a product is the same bits whichever of them forms it and wherever its resample sits in a tile.  S = 37: unaligned
+    pair loads, the odd tail, a partial stage; S = 64: the aligned path, two full stages; B = 150: a partial second
+    feature block; n = 70: a partial second resample tile.  P[b] (B, T) comes from plsx_simpls_coef_ci on the
+    one-resample stack stack[b:b+1] (a series of one value: lo = hi = the product).  The permutation pass over the whole
+    stack must then give max_f |P[b][f, t]| and sum_b (|P[b]| >= |obs|) exactly, and plsx_simpls_vip_ci on the
+    one-component, one-resample stack stack[b:b+1, t:t+1] must give sqrt(B . P[b][:, t]^2) bit-equal to numpy's.
+    That is what the three separate kernels gave before they shared their code (0 ulp at every b tried, both S), and
+    what the number formats promise: the device's fp64 multiply and sqrt are correctly rounded (0 + p p, fused or not,
+    is the rounded product), and numpy rounds in the same order -- p p first, then the product with B, then the root.
+    The largest distance in ulp is printed before it is asserted to be zero."""
+    import torch
+    B, T, n, t_vip = 150, 3, 70, 1
+    eng = _engine()
+    try:
+        _, rs = _bind(eng, S, B, T, 1, seed=S)
+        stack, obs = rs.randn(n, T, S), rs.randn(B, T) * np.sqrt(S)
+        d_stack = eng._dev(stack, np.float64)
+        P = np.empty((n, B, T))
+        for b in range(n):
+            lo, hi = eng.simpls_coef_ci(d_stack[b:b + 1])
+            assert torch.equal(lo, hi)
+            P[b] = lo.cpu().numpy()
+        assert np.all(np.isfinite(P)) and np.abs(P).min() > 0.0
+        count, dmax = _stateless(eng, stack, obs, 0)
+        want_count = (np.abs(P) >= np.abs(obs)[None]).sum(axis=0)
+        differing = int((dmax != np.abs(P).max(axis=1)).sum())
+        print('S={}: maxima differing in any bit {} of {}, counts differing {}'.format(
+            S, differing, dmax.size, int((count.cpu().numpy() != want_count).sum())))
+        assert np.array_equal(dmax, np.abs(P).max(axis=1))
+        assert np.array_equal(count.cpu().numpy(), want_count)
+        for b in (0, 63, 64, n - 1):
+            sd, lo, hi = eng.simpls_vip_ci(d_stack[b:b + 1, t_vip:t_vip + 1].contiguous())
+            want = np.sqrt(B * (P[b][:, t_vip] * P[b][:, t_vip]))
+            got = lo.cpu().numpy()
+            ulp = np.max(np.abs(got - want) / np.spacing(want))
+            print('S={} b={}: VIP differs from numpy by at most {} ulp'.format(S, b, ulp))
+            assert torch.equal(lo, hi)
+            assert np.array_equal(got, want)
+    finally:
+        eng.close()
+
+
 def _series_setup(eng, S, B, T, k, c, seed, n):
     import torch
     Xc, rs = _bind(eng, S, B, T, k, seed)
