@@ -83,6 +83,60 @@ int launch_xprod_acc(plsx_ctx* ctx, const double* Afrag, size_t gstride, int gro
     return 0;
 }
 
+// k-steps per LDS stage of the dense blocks that choose at launch: the main loop of k_xprod runs whole stages, so
+// the largest of 3, 2, 1 that divides the padded k-step count.  plsx_set_data pads the contraction to a multiple of
+// eight rows (Kpad), so nks is even today and the answer is 3 or 2; 1 guards a future change of that padding (a
+// stage that does not divide nks would drop k-steps without a word).
+static int stage_ksteps(int nks) { return nks % 3 == 0 ? 3 : (nks % 2 == 0 ? 2 : 1); }
+
+// Moment-only blocks (MT / 2 weight tiles against X, the same against X^2; EPI 4 or 6) over `groups` groups of the
+// operand Afrag_m, `stride` doubles apart.  The caller holds the timer.
+template <int MT, int NW, int KT, int EPI>
+int launch_moments_t(plsx_ctx* ctx, size_t stride, int groups, SplitEpi se, hipStream_t st)
+{
+    const size_t lds = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
+    HIPCHK(set_lds(k_xprod<MT, NW, KT, MT / 2, EPI>, lds));
+    const int ncolblk = ceil_div(ctx->Bpad, NW * 16);
+    hipLaunchKernelGGL((k_xprod<MT, NW, KT, MT / 2, EPI>), dim3(ncolblk * round_up(groups, 8)), dim3(NW * 64), lds, st,
+                       ptr<double>(ctx->Afrag_m), stride, ptr<double>(ctx->Xc), ctx->Bpad, ctx->nks,
+                       (double*)nullptr, ctx->Bpad, 0, (const int*)nullptr, (const int*)nullptr,
+                       ptr<double>(ctx->momn_m), 0, groups, ncolblk, (double*)nullptr, se, 1);
+    LAUNCHCHK();
+    return 0;
+}
+
+template <int MT, int NW, int EPI>
+int launch_moments(plsx_ctx* ctx, size_t stride, int groups, SplitEpi se, hipStream_t st)
+{
+    // The raw-moment blocks of the split-half passes (EPI 6, 4 waves) stay at one k-step per stage: at three the
+    // 24-tile instantiation spills and the 16-tile one loses its third resident block (170 VGPRs).
+    if constexpr (EPI == 4) {
+        const int kt = stage_ksteps(ctx->nks);
+        if (kt == 3) return launch_moments_t<MT, NW, 3, EPI>(ctx, stride, groups, se, st);
+        if (kt == 2) return launch_moments_t<MT, NW, 2, EPI>(ctx, stride, groups, se, st);
+    }
+    return launch_moments_t<MT, NW, 1, EPI>(ctx, stride, groups, se, st);
+}
+
+template <int KT>
+int launch_xprod_fixed_t(plsx_ctx* ctx, int groups, hipStream_t st)
+{
+    constexpr int MT = 25, NW = 4;                      // (8-wave blocks measured: no gain here, A = 1.6 MB stays in L2)
+    const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
+    const size_t lds = std::max(stage, (size_t)2 * MT * 16 * 4);
+    HIPCHK(set_lds(k_xprod<MT, NW, KT, 0>, lds));
+    const int ncolblk = ctx->Bpad / (NW * 16);
+    dim3 grid(ncolblk * round_up(groups, 8)), block(NW * 64);
+    KTimer tm(ctx, KC_XPROD, st);
+    hipLaunchKernelGGL((k_xprod<MT, NW, KT, 0>), grid, block, lds, st,
+                       ptr<double>(ctx->Afrag), ctx->group_stride_f, ptr<double>(ctx->Xn), ctx->Bpad,
+                       ctx->nks, ptr<double>(ctx->R), ctx->Bpad, ctx->npgf * ctx->Tpp,
+                       ptr<int>(ctx->out_row_f), ptr<int>(ctx->mom_idx_f), ptr<double>(ctx->mom_n), 0,
+                       groups, ncolblk, (double*)nullptr, SplitEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}, 1);
+    LAUNCHCHK();
+    return 0;
+}
+
 // Fixed-X fast path: A = z-scored (permuted) Y only, X pre-scaled per cell, no
 // moment tiles, 25 M-tiles = 8 resamples of T' = 50 with no padding.
 int run_xprod_fixed(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, const double* ystack)
@@ -104,20 +158,11 @@ int run_xprod_fixed(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, co
                            0, 0, ptr<double>(ctx->Afrag), ctx->group_stride_f, ptr<double>(ctx->mom_n), 16);
         LAUNCHCHK();
     }
-    constexpr int MT = 25, NW = 4, KT = 1;              // (8-wave blocks measured: no gain here, A = 1.6 MB stays in L2)
-    const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
-    const size_t lds = std::max(stage, (size_t)2 * MT * 16 * 4);
-    HIPCHK(set_lds(k_xprod<MT, NW, KT, 0>, lds));
-    const int ncolblk = ctx->Bpad / (NW * 16);
-    dim3 grid(ncolblk * round_up(groups, 8)), block(NW * 64);
-    KTimer tm(ctx, KC_XPROD, st);
-    hipLaunchKernelGGL((k_xprod<MT, NW, KT, 0>), grid, block, lds, st,
-                       ptr<double>(ctx->Afrag), ctx->group_stride_f, ptr<double>(ctx->Xn), ctx->Bpad,
-                       ctx->nks, ptr<double>(ctx->R), ctx->Bpad, ctx->npgf * ctx->Tpp,
-                       ptr<int>(ctx->out_row_f), ptr<int>(ctx->mom_idx_f), ptr<double>(ctx->mom_n), 0,
-                       groups, ncolblk, (double*)nullptr, SplitEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}, 1);
-    LAUNCHCHK();
-    return 0;
+    switch (stage_ksteps(ctx->nks)) {
+        case 3: return launch_xprod_fixed_t<3>(ctx, groups, st);
+        case 2: return launch_xprod_fixed_t<2>(ctx, groups, st);
+        default: return launch_xprod_fixed_t<1>(ctx, groups, st);
+    }
 }
 
 // Correlation mode, separate-moments layout: data-only blocks (MTd tiles, npg_d resamples) scaled by
@@ -170,18 +215,10 @@ int run_xprod_sepmom(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, 
     memset(&se, 0, sizeof(se));
     se.scale = ptr<double>(ctx->scale);
     {
-        // moment-only blocks: 12 weight tiles against X, the same 12 against X^2
-        constexpr int NW = 8;     // (moment-only blocks of 8 waves: half the A traffic per flop)
-        const size_t lds = (size_t)2 * (((size_t)24 * 64 + 127) / 128) * 128 * 8;
-        HIPCHK(set_lds(k_xprod<24, NW, 1, 12, 4>, lds));
-        const int ncolblk = ceil_div(ctx->Bpad, NW * 16);
+        // moment-only blocks: 12 weight tiles against X, the same 12 against X^2 (8 waves: half the A traffic per flop)
         se.npairs = npairs;
         KTimer tm(ctx, KC_MOM, st);
-        hipLaunchKernelGGL((k_xprod<24, NW, 1, 12, 4>), dim3(ncolblk * round_up(groups_m, 8)), dim3(NW * 64), lds, st,
-                           ptr<double>(ctx->Afrag_m), mstride, ptr<double>(ctx->Xc), ctx->Bpad, ctx->nks,
-                           (double*)nullptr, ctx->Bpad, 0, (const int*)nullptr, (const int*)nullptr,
-                           ptr<double>(ctx->momn_m), 0, groups_m, ncolblk, (double*)nullptr, se, 1);
-        LAUNCHCHK();
+        if (int e = launch_moments<24, 8, 4>(ctx, mstride, groups_m, se, st)) return e;
     }
     se.npairs = ctx->npg_d * ctx->J;
     se.accB = nres * ctx->Tpp;
@@ -210,25 +247,9 @@ template <int EPI>
 int launch_moment_blocks(plsx_ctx* ctx, const MomLayout& ml, SplitEpi se, hipStream_t st)
 {
     constexpr int NW = (EPI == 4) ? 8 : 4;
-    const int ncolblk = ceil_div(ctx->Bpad, NW * 16);
     KTimer tm(ctx, KC_MOM, st);
-    if (ml.mt == 24) {
-        const size_t lds = (size_t)2 * (((size_t)24 * 64 + 127) / 128) * 128 * 8;
-        HIPCHK(set_lds(k_xprod<24, NW, 1, 12, EPI>, lds));
-        hipLaunchKernelGGL((k_xprod<24, NW, 1, 12, EPI>), dim3(ncolblk * round_up(ml.groups, 8)), dim3(NW * 64), lds, st,
-                           ptr<double>(ctx->Afrag_m), ml.stride, ptr<double>(ctx->Xc), ctx->Bpad, ctx->nks,
-                           (double*)nullptr, ctx->Bpad, 0, (const int*)nullptr, (const int*)nullptr,
-                           ptr<double>(ctx->momn_m), 0, ml.groups, ncolblk, (double*)nullptr, se, 1);
-    } else {
-        const size_t lds = (size_t)2 * (((size_t)16 * 64 + 127) / 128) * 128 * 8;
-        HIPCHK(set_lds(k_xprod<16, NW, 1, 8, EPI>, lds));
-        hipLaunchKernelGGL((k_xprod<16, NW, 1, 8, EPI>), dim3(ncolblk * round_up(ml.groups, 8)), dim3(NW * 64), lds, st,
-                           ptr<double>(ctx->Afrag_m), ml.stride, ptr<double>(ctx->Xc), ctx->Bpad, ctx->nks,
-                           (double*)nullptr, ctx->Bpad, 0, (const int*)nullptr, (const int*)nullptr,
-                           ptr<double>(ctx->momn_m), 0, ml.groups, ncolblk, (double*)nullptr, se, 1);
-    }
-    LAUNCHCHK();
-    return 0;
+    if (ml.mt == 24) return launch_moments<24, NW, EPI>(ctx, ml.stride, ml.groups, se, st);
+    return launch_moments<16, NW, EPI>(ctx, ml.stride, ml.groups, se, st);
 }
 
 // Row maps of a compact block (one resample / split per group): data row t -> R row t, moment index = its cell.
