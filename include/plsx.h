@@ -565,6 +565,18 @@ int plsx_mfma_f64_peak(plsx_ctx* ctx, double* tflops);
  * (k_nt_gemm), [9] bootstrap series closed on the quadratic-form route
  * (plsx_boot_finish) since timing was switched on, [10] / [11] tile rows of a
  * block / blocks per latent variable of the last closing pass.
+ * [12..18] say how the last rotation pass (k_urot) and the last Gram pass were
+ * launched; they are recorded whether or not timing is on (0 before the first
+ * such launch): [12] waves per block of the rotation kernel (4 or 8), [13] its
+ * resample splits (grid y; more than 1: partial sums added by k_add_splits),
+ * [14] resamples per split, [15] its variant: the compiled-in k-step count
+ * 1..16, plus 100 when the last tile of L ran on the 4x4x4 shape (TAIL); 0 the
+ * generic variant with the whole operand in LDS, -1 the generic variant staged
+ * in pieces -- of the launch of the first chunk of L tiles, [16] column chunks
+ * of the last k_gram4 / k_gram / k_gram_lds launch, [17] as [15] for the last
+ * chunk of L tiles (equal to [15] unless L is cut into several launches),
+ * [18] the Gram kernel: row blocks NB of k_gram4 (1..13), 0 k_gram (16x16x4),
+ * -1 k_gram_lds.
  * Returns the number written. */
 int plsx_last_timing(const plsx_ctx* ctx, double* out, int cap);
 /* Scratch budget of the resampling super-batches (default 48 GB; the R block

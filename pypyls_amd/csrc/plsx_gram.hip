@@ -134,6 +134,8 @@ int launch_gram4(plsx_ctx* ctx, int nres, const double* E, int Erows, double* Po
     nchunk = std::min(nchunk, maxchunk);
     const int cols = round_up(ceil_div(ctx->B, nchunk), 8);
     nchunk = ceil_div(ctx->B, cols);
+    ctx->gram_chunks_l = nchunk;
+    ctx->gram_kind_l = NB;
     if (int e = ensure(ctx, ctx->part, (size_t)nchunk * nres * 2 * 4096 * 8)) return e;
     double* part = ptr<double>(ctx->part);
     constexpr size_t lds = (size_t)2 * (NB + (NLB + 3) / 4) * 128 * 8;
@@ -191,6 +193,8 @@ int run_gram_ex(plsx_ctx* ctx, int nres, int mode, const double* E, int Erows, d
         nchunk = std::min(nchunk, maxchunk);
         const int cols = round_up(ceil_div(ctx->B, nchunk), 16);
         nchunk = ceil_div(ctx->B, cols);
+        ctx->gram_chunks_l = nchunk;
+        ctx->gram_kind_l = -1;
         if (int e = ensure(ctx, ctx->part, (size_t)nchunk * nres * 2 * tiles * 4096 * 8)) return e;
         double* part = ptr<double>(ctx->part);
         KTimer tm(ctx, KC_GRAM, st);
@@ -252,6 +256,8 @@ int run_gram_ex(plsx_ctx* ctx, int nres, int mode, const double* E, int Erows, d
     nchunk = std::min(nchunk, maxchunk);
     const int cols = round_up(ceil_div(ctx->B, nchunk), 16);
     nchunk = ceil_div(ctx->B, cols);
+    ctx->gram_chunks_l = nchunk;
+    ctx->gram_kind_l = 0;
     if (int e = ensure(ctx, ctx->part, (size_t)nchunk * nres * 2 * 4096 * 8)) return e;
     double* part = ptr<double>(ctx->part);
     dim3 grid(nchunk, nres), block(256);

@@ -156,6 +156,10 @@ struct plsx_ctx {
     double nt_flops = 0.0;                              // flop of the timed k_nt_gemm launches (products issued, symmetric ones by half)
     int quad_MT = 0, quad_gpl = 0, quad_series = 0;     // block height / blocks per LV of the last closing pass; series closed on that route while timing
     int last_compact_n = 0, last_compact_ktot = 0;   // compact launch behind the last run_xprod (0: none)
+    // how the last run_urot / Gram pass was launched (plsx_last_timing [12..18]; recorded whether or not timing is on)
+    int urot_waves_l = 0, urot_splits_l = 0, urot_rps_l = 0;   // waves per block, resample splits, resamples per split
+    int urot_nks_first = 0, urot_nks_last = 0, urot_tail_l = 0; // NKS template argument of the first / last L chunk's launch, TAIL
+    int gram_chunks_l = 0, gram_kind_l = 0;             // column chunks; NB of k_gram4 (1..13), 0: k_gram, -1: k_gram_lds
     double scratch_gb = 48.0;                           // super-batch scratch budget
     long long R_geom[6] = {0, 0, 0, 0, 0, 0};           // (T', T'pp, Bpad, B, L, method) the R scratch was last zeroed under
     size_t R_zeroed_bytes = 0;

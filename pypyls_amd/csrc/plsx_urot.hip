@@ -30,6 +30,10 @@ int launch_urot(plsx_ctx* ctx, int nres, int lt0, int nsplit, int rps, double* u
                        ctx->strideR, ctx->Bpad, ctx->nks_t, M, (size_t)ctx->nks_t * ctx->LT * 64, nres, ctx->B,
                        ctx->L, lt0 * 16, usum, usq, out, rps, ps, pq);
     LAUNCHCHK();
+    // the path taken, for plsx_last_timing
+    ctx->urot_waves_l = nw;
+    if (lt0 == 0) { ctx->urot_nks_first = NKS; ctx->urot_tail_l = TAIL ? 1 : 0; }
+    ctx->urot_nks_last = NKS;
     return 0;
 }
 
@@ -64,6 +68,8 @@ int run_urot(plsx_ctx* ctx, int nres, double* usum, double* usq, double* out, hi
     }
     const int rps = ceil_div(nres, std::max(nsplit, 1));
     nsplit = ceil_div(nres, rps);
+    ctx->urot_splits_l = nsplit;
+    ctx->urot_rps_l = rps;
     double *ps = nullptr, *pq = nullptr;
     if (nsplit > 1) {
         const size_t bytes = (size_t)nsplit * ctx->B * ctx->L * 8;

@@ -26,6 +26,8 @@ import pytest
 
 from conftest import assert_close, assert_close_per_lv
 from oracle import cpu_ref as ref
+from replica_expect import slot_map as _slot_map, rel_per_column as _rel_per_column, \
+    assert_replicas as _assert_replicas, synth as _synth
 
 pytestmark = pytest.mark.gpu
 
@@ -44,14 +46,6 @@ C2_PERM_FEATURE = dict(dual_perm=0, xprod_launches=1, xprod_resamples=5000, comp
 C2_BOOT = dict(xprod_launches=2, xprod_resamples=5000, resamples_per_group=32, superbatch=4096, quad_series=0,
                compact_row_fraction=0)
 C2_BOOT_ROUTE = 0
-
-
-def _synth(S, B, T, seed=0):
-    """bench.py synth(): the data of the bench's headline and c2 records."""
-    rs = np.random.RandomState(seed)
-    X = rs.randn(S, B)
-    Y = rs.randn(S, T) + 0.3 * X[:, :T]
-    return X, Y
 
 
 def _assert_geometry(got, pinned, what):
@@ -115,44 +109,6 @@ def _other_perm_route(eng, perms):
     eng.set_timing(False)
     eng.set_perm_path(dual)
     return out.cpu().numpy(), tm
-
-
-def _slot_map(n, nd, boundaries, seed):
-    """slot -> distinct resample: seeded random, every distinct one used, and different resamples on the two sides
-    of every boundary b (slots b - 1 and b) and in the first and last slot."""
-    rs = np.random.RandomState(seed)
-    which = rs.randint(nd, size=n)
-    which[:nd] = rs.permutation(nd)                     # (every distinct resample at least once)
-    rs.shuffle(which)
-    for b in sorted(set(boundaries) | {n - 1}):
-        if 0 < b < n and which[b] == which[b - 1]:
-            taken = {which[b - 1]} | ({which[b + 1]} if b + 1 < n else set())
-            which[b] = min(set(range(nd)) - taken)
-    assert which[0] != which[-1] and len(np.unique(which)) == nd
-    for b in boundaries:
-        assert which[b] != which[b - 1], b
-    return which
-
-
-def _rel_per_column(a, b):
-    """max |a - b| / max |b| of every trailing-axis column."""
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    axes = tuple(range(a.ndim - 1))
-    return np.max(np.abs(a - b), axis=axes) / np.max(np.abs(b), axis=axes)
-
-
-def _assert_replicas(vals, which, rtol, what):
-    """vals (n, ...): slots that hold the same resample agree to rtol of that resample's own scale (per LV when the
-    last axis is the LV axis)."""
-    for d in np.unique(which):
-        slots = np.flatnonzero(which == d)
-        v = vals[slots]
-        err = np.max(np.abs(v - v[:1]), axis=tuple(range(v.ndim - 1)))
-        scale = np.max(np.abs(v[0]), axis=tuple(range(v.ndim - 2))) if v.ndim > 2 else np.abs(v[0])
-        bad = err > rtol * scale
-        assert not np.any(bad), '{}: resample {} differs between its slots {} (LVs {}, max rel err {:.3e})'.format(
-            what, d, slots[np.argmax(np.max(np.abs(v - v[:1]).reshape(len(slots), -1), axis=1))],
-            np.flatnonzero(bad), float(np.max(err / scale)))
 
 
 # ----------------------------------------------------------------------------------------------------------------
