@@ -326,6 +326,36 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           No bound on m beyond the outputs.  PLSX_ERR_STATE
  *                           without bound regression data; PLSX_ERR_ARG for a null
  *                           pointer, n < 1 or m < 1.
+ *   plsx_simpls_split_half_batch  split-half reliability of the SIMPLS components
+ *                           (BasePLS.split_half, pyls/base.py:366-397, with SIMPLS
+ *                           in place of the SVD): for each of np arrangements
+ *                           (X, Y[perm]) -- d_perm_idx (np, S) int32, or NULL: the
+ *                           identity, the observed data, for every arrangement --
+ *                           SIMPLS with k components on all usable
+ *                           rows gives W (B, k) and Q = y_loadings (T, k); each of
+ *                           the arrangement's ns masks, d_masks (np, ns, S) uint8,
+ *                           1 = first half, splits the usable rows into halves with
+ *                           D_h = (Y_h - ybar_h)^T (X_h - xbar_h), and
+ *                           d_ucorr[p][s][c] = efficient_corr(D_1^T q_c, D_2^T q_c)
+ *                           over the B features, d_vcorr[p][s][c] =
+ *                           efficient_corr(D_1 w_c, D_2 w_c) over the T behaviours
+ *                           ((np, ns, k) each, the layout plsx_split_half_batch
+ *                           writes; plsx_mean_splits averages them).  Nothing
+ *                           B-sized is formed: D_h^T q_c = Xc^T g_{h,c} with g the
+ *                           half-centred Y q_c, so ucorr follows from g_1^T K g_2,
+ *                           g_h^T K g_h and g_h^T r (K = Xc Xc^T, r = Xc 1_B), two
+ *                           products with K per (split, component), 4 S^2 k flop
+ *                           per split.  With row masks a position is usable iff
+ *                           okx[p] and oky[perm[p]]; unusable rows are in neither
+ *                           half.  A side without variance gives NaN (T = 1:
+ *                           vcorr).  Arrangements run in solver batches; the splits
+ *                           of an arrangement go in groups where they do not fit
+ *                           half the scratch budget (plsx_set_scratch) at once;
+ *                           PLSX_ERR_UNSUPPORTED when one split does not.  Every
+ *                           (arrangement, split) is computed on its own, in fixed
+ *                           order, without atomics.  PLSX_ERR_STATE without bound
+ *                           regression data; PLSX_ERR_ARG for a null pointer,
+ *                           np < 1 or ns < 1.
  *   plsx_simpls_coef_begin / plsx_simpls_coef_finish
  *                           a coefficient series that rides along the bootstrap
  *                           batches: the model of the first c components,
@@ -517,6 +547,8 @@ int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, dou
                                double* d_sse, void* stream);
 int plsx_simpls_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
                                     double* d_r, double* d_r2, double* d_mse, void* stream);
+int plsx_simpls_split_half_batch(plsx_ctx* ctx, const int32_t* d_perm_idx, int np, const uint8_t* d_masks, int ns,
+                                 double* d_ucorr, double* d_vcorr, void* stream);
 int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream);
 int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* stream);
 int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity);
@@ -598,7 +630,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * enabled: 0 k_xprod (cross-product), 1 k_gram / k_gram4 (+ partial reduce),
  * 2 k_small / k_small_ql (eigen-solve + Procrustes), 3 k_urot (+ split add), 4 k_nt_gemm
  * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 9 k_sd_cv_score (with the pair expansion and the
- * reduction over the splits of plsx_simpls_crossval_perm_batch), ..., 11 k_coef_prod (the feature pass of
+ * reduction over the splits of plsx_simpls_crossval_perm_batch, and k_row_sum / k_sd_sh_prep / k_sd_sh_expand /
+ * k_sd_sh_score of plsx_simpls_split_half_batch), ..., 11 k_coef_prod (the feature pass of
  * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
  * k_col_sd of plsx_simpls_coef_perm_test count here too, k_sd_vip under 10 with
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci).

@@ -362,7 +362,7 @@ try {
                    &ctx->Xn, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
-                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
+                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     delete ctx;
@@ -486,6 +486,7 @@ try {
     ctx->n_refined = ctx->n_unrefined = 0;
     HIPCHK(hipMemsetAsync(ctx->status.p, 0, 4 * sizeof(int), st));
     ctx->has_Kd = 0;
+    ctx->has_shrsum = 0;
     ctx->npg_w = 0;                                    // the row -> LV map of the accumulating epilogue follows L
     ctx->has_compact_maps = 0;
     // a re-bound context keeps its scratch: the padding rows (t >= T') of every R slot must

@@ -11,9 +11,11 @@ int run_nt(plsx_ctx* ctx, const double* A, long long strideA, int lda, int Ma,
            const double* B1, long long strideB1, int ldb1, int N1,
            const double* B2, long long strideB2, int ldb2, int N2, int K, int batch,
            double* C1, long long strideC1, int ldc1, double* C2, long long strideC2, int ldc2,
-           hipStream_t st, bool sym, bool accumulate)
+           hipStream_t st, bool sym, bool accumulate, bool one_chunk)
 {
     // sym: B1 is A itself (K = X X^T): only the blocks on and above the diagonal are multiplied
+    // one_chunk: never split the contraction, however few tiles the call has -- every output entry is one block's full
+    // contraction in fixed order, so its bits do not depend on how many rows the call holds
     NtArgs a;
     a.sym = (sym && !B2 && A == B1 && Ma == N1) ? 1 : 0;
     a.A = A; a.strideA = strideA; a.lda = lda; a.Ma = Ma;
@@ -25,6 +27,7 @@ int run_nt(plsx_ctx* ctx, const double* A, long long strideA, int lda, int Ma,
     const int tiles = a.mtiles * a.ntiles;
     int nchunk = std::max(1, ceil_div(2048, batch * tiles));
     nchunk = std::min(nchunk, std::max(1, K / 256));
+    if (one_chunk) nchunk = 1;
     a.kchunk = round_up(ceil_div(K, nchunk), NT_KB);
     nchunk = ceil_div(K, a.kchunk);
     const bool direct = nchunk == 1 && !B2 && !a.sym && !accumulate;
@@ -68,14 +71,14 @@ bool nt_sym_fits(int S)
 
 // C = A Bm^T (A: Ma x Kc, Bm: N x Kc, row-major) on the direct path of run_nt, in strips of rows that keep the grid of
 // k_nt_gemm below 65536 blocks in y.  Each output entry is one block's full contraction wherever a strip covers the
-// chip (a strip of a few tiles on a small chip-wide grid falls back to run_nt's split contraction).
+// chip (a strip of a few tiles on a small chip-wide grid falls back to run_nt's split contraction, unless one_chunk).
 int nt_strips(plsx_ctx* ctx, const double* A, int lda, int Ma, const double* Bm, int ldb, int N, int Kc,
-              double* C, int ldc, hipStream_t st)
+              double* C, int ldc, hipStream_t st, bool one_chunk)
 {
     const int rows = std::max(2, 2 * (65535 / ceil_div(N, 64))) * 64;
     for (int m0 = 0; m0 < Ma; m0 += rows)
         if (int e = run_nt(ctx, A + (size_t)m0 * lda, 0, lda, std::min(rows, Ma - m0), Bm, 0, ldb, N, nullptr, 0, 0, 0,
-                           Kc, 1, C + (size_t)m0 * ldc, 0, ldc, nullptr, 0, 0, st))
+                           Kc, 1, C + (size_t)m0 * ldc, 0, ldc, nullptr, 0, 0, st, false, false, one_chunk))
             return e;
     return 0;
 }

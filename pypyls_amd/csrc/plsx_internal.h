@@ -98,6 +98,11 @@ struct plsx_ctx {
     // batch -- their Y sources [n][S] int32 and training masks [n][S] bytes, expanded on the device -- and their scores
     // r, R^2 [n][k][T], sse [n][k + 1][T], usable test rows [n]
     Buf cvpsrc, cvpfit;
+    // SIMPLS split-half reliability (plsx_simpls_split_half_batch): r = Xc 1_B [S] of the bound data (formed by the first
+    // call after a binding), the y-loadings and yq = Y0 q of a solver batch ([n][k][T] + [n][k][S]), the half vectors of
+    // a group of splits [n nsg][k][2][S] and their products with K
+    Buf shrsum, shq, shG, shKG;
+    int has_shrsum = 0;
     Buf Qs;                                             // SIMPLS: Xc . W0c^T (S x k), sign alignment of the bootstrap in dual space
     Buf ScT, out_row_w;                                 // single-pass bootstrap (unscaled modes): scores^T (L x S), row -> l map
     int npg_w = 0;                                      // resamples per group of the W operand (MT * 16 / L)
@@ -374,10 +379,10 @@ int run_nt(plsx_ctx* ctx, const double* A, long long strideA, int lda, int Ma,
            const double* B1, long long strideB1, int ldb1, int N1,
            const double* B2, long long strideB2, int ldb2, int N2, int K, int batch,
            double* C1, long long strideC1, int ldc1, double* C2, long long strideC2, int ldc2,
-           hipStream_t st, bool sym = false, bool accumulate = false);
+           hipStream_t st, bool sym = false, bool accumulate = false, bool one_chunk = false);
 bool nt_sym_fits(int S);
 int nt_strips(plsx_ctx* ctx, const double* A, int lda, int Ma, const double* Bm, int ldb, int N, int Kc,
-              double* C, int ldc, hipStream_t st);
+              double* C, int ldc, hipStream_t st, bool one_chunk = false);
 int form_gram_K(plsx_ctx* ctx, const double* X, int ldx, int S, int Kc, double* K, int ldk, hipStream_t st);
 int run_dual_gp(plsx_ctx* ctx, int m, int Sd, const double* ScT, int L, hipStream_t st);
 int run_gram_ex(plsx_ctx* ctx, int nres, int mode, const double* E, int Erows, double* Pout,

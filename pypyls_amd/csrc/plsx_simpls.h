@@ -37,6 +37,7 @@
 // memory traffic):
 //   k_sd_init -> [GEMM 0] -> k_sd_post0 -> { k_sd_step(c) -> [GEMM c] } x k -> k_sd_final
 //   cross-validation appends:  k_sd_final (dual weights dense, Vd) -> [Z = Vd . K] -> k_sd_cv_score
+//   split-half appends:  k_sd_sh_prep -> { k_sd_sh_expand -> [KG = G . K] -> k_sd_sh_score } per group of splits
 //   an open coefficient series appends to a bootstrap batch:  k_sd_coef (A_b = sum_{j <= c} wd_j q_j^T, dense)
 //   a kept VIP stack appends to a bootstrap batch:  k_sd_vip (the scaled dual weights of the first c components, dense)
 // k_sd_step(c) finishes component c - 1 (what follows its K beta product: basis pair,
@@ -1475,6 +1476,211 @@ void k_sd_cvp_reduce(const double* __restrict__ r, const double* __restrict__ r2
             acc += s / nte[f - f0];
         }
         *dst = last ? acc / n : acc;
+    }
+}
+
+// Split-half reliability of the SIMPLS components (plsx_simpls_split_half_batch), after the solver ran on ALL usable
+// rows of an arrangement (X, Y[ysrc]).  With t_c the scores (XW, which carries them plus a constant), q_c = Y0^T t_c the
+// y-loadings, K = Xc Xc^T and r = Xc 1_B of the bound data, a split into halves H1 / H2 of the usable positions gives
+//     g_{h,c}[p] = sum_t (Y[ys_p][t] - ybar_h[t]) q_c[t] = yq_c[p] - mean_{H_h} yq_c     on H_h, 0 elsewhere,
+//                  yq_c[p] = sum_t Y0[t][p] q_c[t]        (the centring of the fit drops out with the half mean)
+//     D_h^T q_c  = Xc^T g_{h,c}                            (B-long: never formed)
+//     ucorr[c]   = corr_f(D_1^T q_c, D_2^T q_c)            from g1^T K g2, g1^T K g1, g2^T K g2 and g_h^T r:
+//                  sum_f u1 u2 - (sum_f u1)(sum_f u2) / B = g1^T K g2 - (g1^T r)(g2^T r) / B
+//     D_h w_c    = sum_{p in H_h} Y0[.][p] (t_c[p] - mean_{H_h} t_c)                  (T-long)
+//     vcorr[c]   = corr_t(D_1 w_c, D_2 w_c)
+// -- compute.efficient_corr of both pairs, clipped to [-1, 1]; a side without variance gives the NaN numpy gives.  A
+// position is usable iff the solver kept it (xs >= 0: okx[p] and oky[ys_p]); unusable rows belong to neither half.
+struct ShArgs {
+    int S, T, k, B;
+    int nres;                   // arrangements of the solver batch
+    int ns, s0, nsg;            // splits per arrangement; first split and number of splits of this group
+    long long a0;               // the batch's first arrangement in the call's list
+    const int* xs;              // [nres][S] solver state
+    const double* Y0;           // [nres][T][S]
+    const double* XW;           // [nres][k][S]
+    const uint8_t* masks;       // (np, ns, S) 1 = first half
+    const double* rsum;         // [S] row sums of Xc over the B features
+    double* q;                  // [nres][k][T]
+    double* yq;                 // [nres][k][S]
+    double* G;                  // [nres nsg][k][2][S] half vectors g_{1,c}, g_{2,c}
+    const double* KG;           // [nres nsg][k][2][S] their products with K
+    double* ucorr;              // (np, ns, k)
+    double* vcorr;
+};
+
+// r = Xc 1_B: one wavefront per row, fixed order.
+static __global__ __launch_bounds__(256)
+void k_row_sum(const double* __restrict__ Xc, int ldx, int S, int B, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, p = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= S) return;
+    const double* row = Xc + (size_t)p * ldx;
+    double s = 0.0;
+    for (int f = lane; f < B; f += 64) s += row[f];
+    s = wave_sum(s);
+    if (lane == 0) out[p] = s;
+}
+
+// q_c = Y0^T XW_c (Y0 sums to zero over the usable positions and is zero elsewhere: the constant XW carries drops
+// out) and yq_c = Y0 q_c of one arrangement.  One wavefront per arrangement, four components per reduction.
+static __global__ __launch_bounds__(256)
+void k_sd_sh_prep(ShArgs a)
+{
+    const int S = a.S, T = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (r >= a.nres) return;
+    const double* Y0 = a.Y0 + (size_t)r * S * T;
+    const double* XW = a.XW + (size_t)r * k * S;
+    double* q = a.q + (size_t)r * k * T;
+    double* yq = a.yq + (size_t)r * k * S;
+    for (int t = 0; t < T; ++t) {
+        const double* y0t = Y0 + (size_t)t * S;
+        for (int c0 = 0; c0 < k; c0 += 4) {
+            const double *w0 = XW + (size_t)min(c0, k - 1) * S, *w1 = XW + (size_t)min(c0 + 1, k - 1) * S,
+                         *w2 = XW + (size_t)min(c0 + 2, k - 1) * S, *w3 = XW + (size_t)min(c0 + 3, k - 1) * S;
+            double s4[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int p = lane; p < S; p += 64) {
+                const double y = y0t[p];
+                s4[0] += y * w0[p]; s4[1] += y * w1[p]; s4[2] += y * w2[p]; s4[3] += y * w3[p];
+            }
+            wave_sum4(s4[0], s4[1], s4[2], s4[3]);
+            if (lane == 0)
+                for (int u = 0; u < 4 && c0 + u < k; ++u) q[(size_t)(c0 + u) * T + t] = s4[u];
+        }
+    }
+    wave_global_sync();                        // q, as lane 0 wrote it
+    for (int c = 0; c < k; ++c) {
+        const double* qc = q + (size_t)c * T;
+        for (int p = lane; p < S; p += 64) {
+            double s = 0.0;
+            for (int t = 0; t < T; ++t) s += Y0[(size_t)t * S + p] * qc[t];
+            yq[(size_t)c * S + p] = s;
+        }
+    }
+}
+
+// The half vectors of one (arrangement, split): G[c][h][p] = yq_c[p] - mean_{H_h} yq_c on H_h, zero elsewhere (every
+// entry written).  One wavefront per (arrangement, split) of the group, two components per reduction.
+static __global__ __launch_bounds__(256)
+void k_sd_sh_expand(ShArgs a)
+{
+    const int S = a.S, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (w >= (long long)a.nres * a.nsg) return;
+    const int r = (int)(w / a.nsg), s = (int)(w % a.nsg);
+    const int* xs = a.xs + (size_t)r * S;
+    const uint8_t* m = a.masks + ((size_t)(a.a0 + r) * a.ns + a.s0 + s) * S;
+    const double* yq = a.yq + (size_t)r * k * S;
+    double* G = a.G + (size_t)w * k * 2 * S;
+    double c1 = 0.0, c2 = 0.0;
+    for (int p = lane; p < S; p += 64) {
+        const bool ok = xs[p] >= 0;
+        c1 += (ok && m[p]) ? 1.0 : 0.0;
+        c2 += (ok && !m[p]) ? 1.0 : 0.0;
+    }
+    const double n1 = wave_sum(c1), n2 = wave_sum(c2);
+    for (int c0 = 0; c0 < k; c0 += 2) {
+        const int cb = min(c0 + 1, k - 1);
+        const double *ya = yq + (size_t)c0 * S, *yb = yq + (size_t)cb * S;
+        double s4[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int p = lane; p < S; p += 64) {
+            const bool ok = xs[p] >= 0, h1 = ok && m[p], h2 = ok && !m[p];
+            const double va = ya[p], vb = yb[p];
+            s4[0] += h1 ? va : 0.0; s4[1] += h2 ? va : 0.0; s4[2] += h1 ? vb : 0.0; s4[3] += h2 ? vb : 0.0;
+        }
+        wave_sum4(s4[0], s4[1], s4[2], s4[3]);
+        const double ma1 = s4[0] / n1, ma2 = s4[1] / n2, mb1 = s4[2] / n1, mb2 = s4[3] / n2;
+        double* ga = G + (size_t)c0 * 2 * S;
+        double* gb = G + (size_t)cb * 2 * S;
+        for (int p = lane; p < S; p += 64) {
+            const bool ok = xs[p] >= 0, h1 = ok && m[p], h2 = ok && !m[p];
+            const double va = ya[p], vb = yb[p];
+            ga[p] = h1 ? va - ma1 : 0.0;
+            ga[S + p] = h2 ? va - ma2 : 0.0;
+            if (cb != c0) {
+                gb[p] = h1 ? vb - mb1 : 0.0;
+                gb[S + p] = h2 ? vb - mb2 : 0.0;
+            }
+        }
+    }
+}
+
+// ucorr and vcorr of one (arrangement, split) from G, KG = G . K, r and the fit's Y0 / XW.  One wavefront per
+// (arrangement, split); reductions are wave_sum / wave_sum4 in fixed order, no atomics, no LDS.  The T-vectors D_h w_c
+// are formed twice (their means over t first, then the centred sums): T S flop per half and component, nothing kept.
+static __global__ __launch_bounds__(256)
+void k_sd_sh_score(ShArgs a)
+{
+    const int S = a.S, T = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (w >= (long long)a.nres * a.nsg) return;
+    const int r = (int)(w / a.nsg), s = (int)(w % a.nsg);
+    const int* xs = a.xs + (size_t)r * S;
+    const uint8_t* m = a.masks + ((size_t)(a.a0 + r) * a.ns + a.s0 + s) * S;
+    const double* Y0 = a.Y0 + (size_t)r * S * T;
+    const double* XW = a.XW + (size_t)r * k * S;
+    const double* G = a.G + (size_t)w * k * 2 * S;
+    const double* KG = a.KG + (size_t)w * k * 2 * S;
+    double* out_u = a.ucorr + ((size_t)(a.a0 + r) * a.ns + a.s0 + s) * k;
+    double* out_v = a.vcorr + ((size_t)(a.a0 + r) * a.ns + a.s0 + s) * k;
+    const double nB = (double)a.B;
+    auto clip = [](double v) { return v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v); };      // (NaN stays NaN)
+    double c1 = 0.0, c2 = 0.0;
+    for (int p = lane; p < S; p += 64) {
+        const bool ok = xs[p] >= 0;
+        c1 += (ok && m[p]) ? 1.0 : 0.0;
+        c2 += (ok && !m[p]) ? 1.0 : 0.0;
+    }
+    const double n1 = wave_sum(c1), n2 = wave_sum(c2);
+    for (int c = 0; c < k; ++c) {
+        const double *g1 = G + (size_t)c * 2 * S, *g2 = g1 + S, *k1 = KG + (size_t)c * 2 * S, *k2 = k1 + S;
+        double s11 = 0.0, s22 = 0.0, s12 = 0.0, r1 = 0.0, r2 = 0.0;
+        for (int p = lane; p < S; p += 64) {
+            const double u = g1[p], v = g2[p], rs = a.rsum[p];
+            s11 += u * k1[p]; s22 += v * k2[p]; s12 += u * k2[p];
+            r1 += u * rs; r2 += v * rs;
+        }
+        wave_sum4(s11, s22, s12, r1);
+        r2 = wave_sum(r2);
+        const double v11 = s11 - r1 * r1 / nB, v22 = s22 - r2 * r2 / nB, v12 = s12 - r1 * r2 / nB;
+        if (lane == 0) out_u[c] = clip(v12 / sqrt(v11 * v22));
+        // the scores' half means, then D_h w_c[t] = sum_{p in H_h} Y0[t][p] (t_c[p] - mean_h)
+        const double* xw = XW + (size_t)c * S;
+        double x1 = 0.0, x2 = 0.0;
+        for (int p = lane; p < S; p += 64) {
+            const bool ok = xs[p] >= 0;
+            const double x = xw[p];
+            x1 += (ok && m[p]) ? x : 0.0;
+            x2 += (ok && !m[p]) ? x : 0.0;
+        }
+        const double mx1 = wave_sum(x1) / n1, mx2 = wave_sum(x2) / n2;
+        auto dw = [&](int t, double& d1, double& d2) {
+            const double* y0t = Y0 + (size_t)t * S;
+            double e1 = 0.0, e2 = 0.0;
+            for (int p = lane; p < S; p += 64) {
+                const bool ok = xs[p] >= 0;
+                const double y = y0t[p], x = xw[p];
+                e1 += (ok && m[p]) ? y * (x - mx1) : 0.0;
+                e2 += (ok && !m[p]) ? y * (x - mx2) : 0.0;
+            }
+            d1 = wave_sum(e1); d2 = wave_sum(e2);
+        };
+        double sa1 = 0.0, sa2 = 0.0;
+        for (int t = 0; t < T; ++t) {
+            double d1, d2;
+            dw(t, d1, d2);
+            sa1 += d1; sa2 += d2;
+        }
+        const double m1 = sa1 / T, m2 = sa2 / T;
+        double q11 = 0.0, q22 = 0.0, q12 = 0.0;
+        for (int t = 0; t < T; ++t) {
+            double d1, d2;
+            dw(t, d1, d2);
+            d1 -= m1; d2 -= m2;
+            q11 += d1 * d1; q22 += d2 * d2; q12 += d1 * d2;
+        }
+        if (lane == 0) out_v[c] = clip(q12 / sqrt(q11 * q22));
     }
 }
 

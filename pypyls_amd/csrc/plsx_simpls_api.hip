@@ -621,6 +621,97 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+int plsx_simpls_split_half_batch(plsx_ctx* ctx, const int32_t* d_perm_idx, int np, const uint8_t* d_masks, int ns,
+                                 double* d_ucorr, double* d_vcorr, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_split_half_batch: data not bound for regression");
+    if (!d_masks || !d_ucorr || !d_vcorr || np < 1 || ns < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_split_half_batch: bad arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    // Solver batches as for the permutations.  An arrangement also holds its y-loadings and yq (8 k (T + S) bytes) and,
+    // per split, the two stacks of half vectors: G and G . K, 2 . 8 . 2 k S bytes.  Where all the splits of even one
+    // arrangement do not fit half the scratch budget next to its solver state they go in groups; only a single split
+    // that does not fit is refused.  (Rows of one product stay below 2^30.)
+    const double per_arr = 8.0 * (double)sd_scratch_doubles(S, T, k, simpls_global(ctx)) + 8.0 * k * ((double)T + S);
+    const double per_split = 32.0 * k * (double)S;
+    const double budget = 0.5 * ctx->scratch_gb * 1073741824.0;
+    if (per_arr + per_split > budget) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "plsx_simpls_split_half_batch: the solver state of one arrangement (%.0f bytes) and the "
+                 "half vectors of one split with their products (32 k S = %.0f bytes for S = %d, k = %d) do not fit half "
+                 "the scratch budget of %.6f GB", per_arr, per_split, S, k, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    const long long max_rows = 1LL << 30;
+    const int nsg = (int)std::min<long long>(std::min<long long>(ns, (long long)((budget - per_arr) / per_split)),
+                                             std::max<long long>(1, max_rows / (2 * k)));
+    int nb = 1;
+    if (nsg == ns) {
+        nb = std::min(np, sd_batch(ctx, 8192, 1, 8.0 * k * ((double)T + S) + ns * per_split));
+        nb = (int)std::max<long long>(1, std::min<long long>(nb, max_rows / (2LL * k * ns)));
+    }
+    if (int e = ensure(ctx, ctx->spct, (size_t)nb * (T + 1) * k * 8)) return e;     // pctvar [nb][k], y-loadings [nb][T][k]
+    if (int e = ensure(ctx, ctx->sc, (size_t)nb * T * k * 8)) return e;
+    if (int e = ensure(ctx, ctx->shq, (size_t)nb * k * ((size_t)T + S) * 8)) return e;
+    if (int e = ensure(ctx, ctx->shG, (size_t)nb * nsg * k * 2 * S * 8)) return e;
+    if (int e = ensure(ctx, ctx->shKG, (size_t)nb * nsg * k * 2 * S * 8)) return e;
+    if (!ctx->has_shrsum) {
+        if (int e = ensure(ctx, ctx->shrsum, (size_t)S * 8)) return e;
+        KTimer tm(ctx, KC_CVSCORE, st);
+        hipLaunchKernelGGL(k_row_sum, dim3(ceil_div(S, 4)), dim3(256), 0, st, ptr<double>(ctx->Xc), ctx->Bpad, S, ctx->B,
+                           ptr<double>(ctx->shrsum));
+        LAUNCHCHK();
+        ctx->has_shrsum = 1;
+    }
+    ShArgs h;
+    memset(&h, 0, sizeof(h));
+    h.S = S; h.T = T; h.k = k; h.B = ctx->B; h.ns = ns;
+    h.masks = d_masks; h.rsum = ptr<double>(ctx->shrsum);
+    h.q = ptr<double>(ctx->shq); h.yq = h.q + (size_t)nb * k * T;
+    h.G = ptr<double>(ctx->shG); h.KG = ptr<double>(ctx->shKG);
+    h.ucorr = d_ucorr; h.vcorr = d_vcorr;
+    const double* K = ptr<double>(ctx->Kmat);
+    for (int off = 0; off < np; off += nb) {
+        const int ms = std::min(nb, np - off);
+        SdArgs a;
+        // the fit on all usable rows of (X, Y[perm]): X keeps its rows, Y takes the permutation's (as
+        // plsx_simpls_perm_batch; nullptr: the observed arrangement); the scores stay in the batch's state
+        if (int e = run_simpls_dual(ctx, nullptr, d_perm_idx ? d_perm_idx + (size_t)off * S : nullptr, ms, false,
+                                    ptr<double>(ctx->spct), ptr<double>(ctx->spct) + (size_t)nb * k, ptr<double>(ctx->sc),
+                                    st, nullptr, false, nullptr, nullptr, &a))
+            return e;
+        h.nres = ms; h.a0 = off;
+        h.xs = a.xs; h.Y0 = a.Y0; h.XW = a.XW;
+        {
+            KTimer tm(ctx, KC_CVSCORE, st);
+            hipLaunchKernelGGL(k_sd_sh_prep, dim3(ceil_div(ms, 4)), dim3(256), 0, st, h);
+            LAUNCHCHK();
+        }
+        for (int s0 = 0; s0 < ns; s0 += nsg) {
+            h.s0 = s0; h.nsg = std::min(nsg, ns - s0);
+            const long long waves = (long long)ms * h.nsg;
+            const dim3 grid((unsigned)((waves + 3) / 4));
+            {
+                KTimer tm(ctx, KC_CVSCORE, st);
+                hipLaunchKernelGGL(k_sd_sh_expand, grid, dim3(256), 0, st, h);
+                LAUNCHCHK();
+            }
+            // both half vectors of every (arrangement, split, component) against K (symmetric): 4 S^2 k flop per split;
+            // never a split contraction: the bits of a row do not depend on how many rows ride with it
+            if (int e = nt_strips(ctx, h.G, S, (int)(waves * k * 2), K, S, S, S, ptr<double>(ctx->shKG), S, st, true))
+                return e;
+            KTimer tm(ctx, KC_CVSCORE, st);
+            hipLaunchKernelGGL(k_sd_sh_score, grid, dim3(256), 0, st, h);
+            LAUNCHCHK();
+        }
+    }
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
 int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream)
 try {
     NEED_DATA();

@@ -90,6 +90,7 @@ def _load():
         'plsx_simpls_set_row_masks': ([vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_simpls_split_half_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
         'plsx_simpls_coef_begin': ([vp, i32, vp], i32),
         'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
         'plsx_simpls_coef_keep': ([vp, vp, ctypes.c_longlong], i32),
@@ -134,7 +135,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
@@ -788,6 +789,29 @@ class Engine(object):
         self._check(self.lib.plsx_simpls_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
                                                              r_dev.data_ptr(), r2_dev.data_ptr(), mse_dev.data_ptr(),
                                                              self._stream()))
+
+    def simpls_split_half_into(self, perm_dev, masks_dev, uc_dev, vc_dev):
+        """Split-half reliability of the SIMPLS components.  perm_dev (n, S) int32, one permutation of the rows of Y per
+        arrangement, or None: the observed arrangement (n = masks_dev.shape[0]); masks_dev (n, ns, S) uint8, 1 = first
+        half, the arrangement's own splits.  uc_dev / vc_dev (n, ns, k): per split the correlation between the halves of
+        the projections D_h^T q_c over the features and D_h w_c over the behaviours (plsx_simpls_split_half_batch);
+        :meth:`mean_splits_into` averages them."""
+        torch = _torch()
+        if masks_dev.dim() != 3:
+            raise ValueError('split masks must be a contiguous (n, ns, {}) uint8 tensor'.format(self.S))
+        n, ns = masks_dev.shape[0], masks_dev.shape[1]
+        if tuple(masks_dev.shape) != (n, ns, self.S) or masks_dev.dtype != torch.uint8 or not masks_dev.is_contiguous() \
+                or n < 1 or ns < 1:
+            raise ValueError('split masks must be a contiguous (n, ns, {}) uint8 tensor'.format(self.S))
+        if perm_dev is not None and (tuple(perm_dev.shape) != (n, self.S) or perm_dev.dtype != torch.int32
+                                     or not perm_dev.is_contiguous()):
+            raise ValueError('permutations must be a contiguous (n, {}) int32 tensor, one per arrangement'.format(self.S))
+        for t in (uc_dev, vc_dev):
+            if tuple(t.shape) != (n, ns, self.k) or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('split-half outputs must be contiguous float64 (n, ns, k)')
+        self._check(self.lib.plsx_simpls_split_half_batch(
+            self.ctx, None if perm_dev is None else perm_dev.data_ptr(), n, masks_dev.data_ptr(), ns,
+            uc_dev.data_ptr(), vc_dev.data_ptr(), self._stream()))
 
     def simpls_coef_begin(self, c):
         """Open a coefficient series for the model of the first ``c`` components: until :meth:`simpls_coef_finish`

@@ -44,7 +44,14 @@ Differences from the reference at this commit, on purpose:
     bootstrap's scaled dual weights are kept in subject space and one closing pass over the features forms and reduces
     the series chunk by chunk (plsx_simpls_vip_keep / plsx_simpls_vip_ci; csrc/plsx_simpls.h, k_sd_vip;
     csrc/plsx_k_vip.h).  :func:`vip` computes the scores of any ``pls_regression`` result.
+  * ``n_split=n`` runs the split-half reliability of the components (the reference forces ``n_split=0``: "not
+    implemented for PLSRegression", regression.py:237-238): BasePLS.split_half (base.py:366-397, 704-770) with the
+    x_weights and y_loadings of SIMPLS in place of the singular vectors, for the observed data and for every
+    permutation, in dual space -- no pass over the features (plsx_simpls_split_half_batch; csrc/plsx_simpls.h,
+    k_sd_sh_prep / k_sd_sh_expand / k_sd_sh_score).
 """
+import warnings
+
 import numpy as np
 
 from . import hostmath, parallel, resampling
@@ -109,7 +116,7 @@ def _check_cvsplits(masks, usable, k, B):
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
-                   cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, **kwargs):
+                   cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, n_split=0, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -177,7 +184,24 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     as for ``coefs_ci`` the original fit is not part of the series.  VIP depends on neither the signs nor the order of
     the components: no alignment.  The (B, n_boot) scores exist on the device only, one chunk of features at a time;
     what is kept is 8 c S n_boot bytes (on every GPU of a team: the closing pass runs on the first).
-    ``n_boot`` <= 16384.  Every other array of the call keeps its bits."""
+    ``n_boot`` <= 16384.  Every other array of the call keeps its bits.
+
+    Split-half reliability: ``n_split=n`` (0 or None, the default: nothing is added, nothing is drawn) asks whether the
+    components replicate between two halves of the cohort, as ``behavioral_pls(n_split=n)`` does (BasePLS.split_half,
+    pyls/base.py:366-397, with SIMPLS in place of the SVD).  The k-component fit on all usable rows of an arrangement
+    ``(X, Y[perm])`` gives W = x_weights (B, k) and Q = simpls' y_loadings (T, k); each of n random halvings (``gen_splits``
+    with ``test_size=0.5``) gives ``D_h = (Y_h - ybar_h).T @ (X_h - xbar_h)`` per half, and
+    ``ucorr[c] = efficient_corr(D_1.T @ Q, D_2.T @ Q)[c]`` over the features, ``vcorr[c] = efficient_corr(D_1 @ W,
+    D_2 @ W)[c]`` over the behaviours, averaged over the n splits.  ``splitres`` holds the reference's keys with k
+    components: ``ucorr`` / ``vcorr`` (k,) of the observed data, ``ucorr_pvals`` / ``vcorr_pvals`` against the same
+    statistic of the ``n_perm`` permutations of ``permres.permsamples`` (permutation i halves with the masks of a fresh
+    ``RandomState(i)``), and ``*_lolim`` / ``*_uplim``, the ``ci`` % interval of the permuted means.  With ``n_perm = 0``
+    only ``ucorr`` and ``vcorr`` are filled (the reference fills nothing then).  3-D Y: the aggregated Y is split.  Rows
+    that are NaN throughout belong to neither half (under a permutation: position p is usable iff row p of X and row
+    perm[p] of Y are); every half must keep at least 2 usable rows.  With one behaviour (T = 1) ``vcorr`` is NaN, as
+    numpy's correlation of single values is.  The observed data's masks are drawn after everything else the call
+    draws: every other array of the call keeps its bits.  Per split the device forms two S-long vectors per component
+    and multiplies them with K = Xc Xc^T: 4 S^2 k flop, nothing B-sized (plsx_simpls_split_half_batch)."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -248,6 +272,11 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              '`test_size` > 0 (drawn, or given as `cvsamples`); got test_split = {!r}, test_size = {!r}'
                              .format(test_split, test_size))
         kwargs['cv_perm'] = cv_perm                # (recorded in `inputs` only when asked for)
+    if n_split is None:
+        n_split = 0
+    if isinstance(n_split, (bool, np.bool_)) or not isinstance(n_split, (int, np.integer)) or n_split < 0:
+        raise ValueError('Provided `n_split` must be a non-negative integer; got {!r}'.format(n_split))
+    n_split = int(n_split)
     S = len(X)
     agg = None
     third = None                                   # (C, n_boot) third-axis resamples for 3-D Y
@@ -296,7 +325,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     else:
         Y_agg = Y
         bootsamples_out = None
-    kwargs.update(n_split=0)                       # regression.py:238 (test_split is NOT forced to 0 here)
+    kwargs.update(n_split=n_split)                 # (the reference forces 0, regression.py:238; so does test_split there)
     kwargs.setdefault('permindices', True)
     test_split = int(test_split or 0)
     inputs = PLSInputs(X=X, Y=Y, groups=[S], n_cond=1, n_components=n_components, n_perm=n_perm,
@@ -351,6 +380,43 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             raise ValueError('Provided `n_components` cannot be greater than {} when permuting the cross-validation: '
                              'a permutation can leave {} usable training rows'
                              .format(max(min(lo_tr - 1, X.shape[1]), 0), max(lo_tr, 0)))
+    # ---- split-half: validated on the host before any engine is created or looked up
+    sh = None
+    if n_split > 0:
+        sh = dict(n=n_split, masks=None, perm_given=None)
+        usable = _usable_rows(X, Y_agg)
+        # under a permutation position p is usable iff row p of X and row perm[p] of Y are: a permutation can put every
+        # masked row of X and of Y into one half
+        n_bad = int((~usable).sum())
+        n_bad_p = int((~_usable_rows(X, np.zeros((S, 1)))).sum()) + int(np.isnan(Y_agg).all(axis=1).sum())
+        worst = n_bad_p if (n_perm or 0) > 0 else n_bad
+        given = kwargs.get('_splitsamples')
+        if given is not None:
+            given = np.asarray(given)
+            if given.ndim != 2 or given.shape != (S, n_split):
+                raise ValueError('Provided `_splitsamples` must have shape (S, n_split) = ({}, {}); got {}'
+                                 .format(S, n_split, given.shape))
+            given = given.astype(bool)
+            halves = np.minimum((given & usable[:, None]).sum(axis=0), (~given & usable[:, None]).sum(axis=0))
+            if int(halves.min()) < 2:
+                raise ValueError('Every split half needs at least 2 usable rows; split {} leaves {} ({} of {} rows are '
+                                 'NaN throughout)'.format(int(halves.argmin()), int(halves.min()), n_bad, S))
+            sh['masks'] = given
+        pgiven = kwargs.get('_perm_splitsamples')
+        if pgiven is not None and (n_perm or 0) > 0:
+            pgiven = np.asarray(pgiven)
+            if pgiven.ndim != 3 or pgiven.shape != (n_perm, S, n_split):
+                raise ValueError('Provided `_perm_splitsamples` must have shape (n_perm, S, n_split) = ({}, {}, {}); '
+                                 'got {}'.format(n_perm, S, n_split, pgiven.shape))
+            sh['perm_given'] = pgiven = pgiven.astype(bool)
+            lo_half = int(min(pgiven.sum(axis=1).min(), (~pgiven).sum(axis=1).min())) - n_bad_p
+            if given is None:
+                lo_half = min(lo_half, S // 2 - n_bad)
+        else:
+            lo_half = S // 2 - worst                   # gen_splits keeps ceil or floor of S / 2 rows in the first half
+        if (given is None or (n_perm or 0) > 0) and lo_half < 2:
+            raise ValueError('Every split half needs at least 2 usable rows; a split can leave {} of {} ({} rows of X or '
+                             'Y are NaN throughout)'.format(max(lo_half, 0), S, worst))
     rs = resampling.check_random_state(seed)
     k = n_components
     B, T = X.shape[1], Y_agg.shape[1]
@@ -400,6 +466,12 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             else:
                 cv['pstream'] = resampling.IndexStream.of_array(cvperm)
             cv['perm_given'] = cvperm
+    if sh is not None and sh['masks'] is None:
+        # the observed data's split masks: one more job at the END of the list, behind the cross-validation's draws
+        # (permutation i takes its masks from a fresh RandomState(i), base.py:705-708: nothing of the call's stream)
+        def sh_draw(r):
+            sh['masks'] = resampling.gen_splits([S], 1, n_split, seed=r, test_size=0.5)
+        jobs.append(sh_draw)
     from .engine import default_engine, touch_idle_release
     from . import team as _team
     touch_idle_release()                               # (a pending idle release is pushed back before the engine is looked up)
@@ -421,7 +493,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
                 k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
                 coef_c=coef_components, coef_ci=coef_ci,
-                vip_c=vip_components, coef_perm=coef_perm))
+                vip_c=vip_components, coef_perm=coef_perm, sh=sh))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -431,7 +503,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
                                       kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci,
-                                      vip_c=vip_components, coef_perm=coef_perm)
+                                      vip_c=vip_components, coef_perm=coef_perm, sh=sh)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -446,7 +518,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
                 bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None,
-                coef_ci=False, vip_c=None, coef_perm=False):
+                coef_ci=False, vip_c=None, coef_perm=False, sh=None):
     import time
     import torch
     S = len(X)
@@ -629,6 +701,40 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         if lead and cv.get('perm_given') is None:
             cvp.warn()
         tick('crossval_perm')
+    # split-half reliability: this rank's contiguous shard of the permutations, block by block as their masks arrive
+    # (permutation i: RandomState(i)), the mean over the splits taken on the device in fixed order; the observed
+    # arrangement runs on the lead rank.  Per-split values exist in scratch of one block only.
+    d_sh = d_sh0 = None
+    if sh is not None:
+        ns = sh['n']
+        if pstream is not None:
+            lo, hi = parallel.shard_bounds(n_perm_tot, rank, world)
+            d_sh = [eng._zeros((hi - lo, k)), eng._zeros((hi - lo, k))]
+            if hi > lo:
+                bars.append(Bar('Running split-half resampling of the permutations', hi - lo, show, eng.device))
+                mstream = resampling.MaskStream([S], 1, ns, lo, hi, block=128, given=sh['perm_given'])
+                try:
+                    for a, b, masks in mstream:
+                        dm = torch.from_numpy(masks).to(eng.device)
+                        uc, vc = eng._empty((b - a, ns, k)), eng._empty((b - a, ns, k))
+                        eng.simpls_split_half_into(eng.rows_tensor(pstream.rows[a:b]), dm, uc, vc)
+                        eng.mean_splits_into(uc, d_sh[0][a - lo:b - lo])
+                        eng.mean_splits_into(vc, d_sh[1][a - lo:b - lo])
+                        for done in bars:
+                            done.poll()
+                        bars[-1].queued(b - a)
+                finally:
+                    mstream.close()
+                if mstream.duplicates and lead:
+                    warnings.warn('WARNING: Duplicate split halves used.')
+        if lead:
+            dm = torch.from_numpy(np.ascontiguousarray(sh['masks'].T[None], dtype=np.uint8)).to(eng.device)
+            uc, vc = eng._empty((1, ns, k)), eng._empty((1, ns, k))
+            eng.simpls_split_half_into(None, dm, uc, vc)
+            d_sh0 = [eng._zeros((1, k)), eng._zeros((1, k))]
+            eng.mean_splits_into(uc, d_sh0[0])
+            eng.mean_splits_into(vc, d_sh0[1])
+        tick('split_half')
     for bar in bars:
         bar.watch()
     try:
@@ -644,6 +750,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         slices, totals = slices + d_cv, totals + [cv['n']] * 3
     if d_cvp is not None:                               # ... and the three rows per permutation of its permutation test
         slices, totals = slices + d_cvp, totals + [cvp.n] * 3
+    if d_sh is not None:                                # ... and the two rows per permutation of the split-half means
+        slices, totals = slices + d_sh, totals + [n_perm_tot] * 2
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
@@ -707,6 +815,17 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 r_squared_pvals=hostmath.perm_sig(obs_r2.ravel(), null_r2.reshape(T * k, P)).reshape(T, k),
                 mse_pvals=hostmath.perm_sig(-obs_mse, -null_mse),          # (smaller is better: #{null < observed})
                 cvpermsamples=np.asarray(cv['perm_given']) if cv.get('perm_given') is not None else cvp.samples))
+    if d_sh0 is not None:
+        orig_uc, orig_vc = (t.cpu().numpy()[0] for t in d_sh0)
+        res['splitres'].update(dict(ucorr=orig_uc, vcorr=orig_vc))
+        if d_sh is not None:
+            j = i + (3 if d_cv is not None else 0) + (3 if d_cvp is not None else 0)
+            ucorrs, vcorrs = np.ascontiguousarray(full[j].T), np.ascontiguousarray(full[j + 1].T)      # (k, n_perm)
+            ull, uul = hostmath.boot_ci(ucorrs, ci=ci)
+            vll, vul = hostmath.boot_ci(vcorrs, ci=ci)
+            res['splitres'].update(dict(
+                ucorr_pvals=hostmath.perm_sig(orig_uc, ucorrs), vcorr_pvals=hostmath.perm_sig(orig_vc, vcorrs),
+                ucorr_lolim=ull, vcorr_lolim=vll, ucorr_uplim=uul, vcorr_uplim=vul))
     if permsamp is not None:
         res['permres']['pvals'] = hostmath.perm_sig(pctvar, d_perm)
         res['permres']['permsamples'] = permsamp
