@@ -609,6 +609,12 @@ int plsx_mfma_f64_peak(plsx_ctx* ctx, double* tflops);
  * chunk of L tiles (equal to [15] unless L is cut into several launches),
  * [18] the Gram kernel: row blocks NB of k_gram4 (1..13), 0 k_gram (16x16x4),
  * -1 k_gram_lds.
+ * [19] / [20] say how the last pass of plsx_split_half_batch ran: [19] its
+ * cross-product blocks -- 0 both halves as resamples of the plain blocks (no
+ * fused epilogue), 1 the dense fused blocks (several splits per block), 5 / 8
+ * compact blocks, one split each, with the fused epilogue 5 / the raw first-half
+ * sums of epilogue 8; [20] the one-pass reader behind epilogue 8 -- 0 none, else
+ * its waves per block (12 or 8), plus 100 with the wave kinds in runs of four.
  * Returns the number written. */
 int plsx_last_timing(const plsx_ctx* ctx, double* out, int cap);
 /* Scratch budget of the resampling super-batches (default 48 GB; the R block
@@ -661,7 +667,9 @@ int plsx_set_perm_path(plsx_ctx* ctx, int dual);
  *   layout-time (before plsx_set_data): "min_batch" (resamples per super-batch aimed for, default 4096),
  *     "inblock_moments", "no_fixed_x", "no_dual_perm"
  *   any time: "no_refine" (graded spectra: skip the refinement on R), "two_pass_boot", "no_compact_boot",
- *     "compact_boot_always", "sepmom_always", "no_split_fuse" (split halves: two passes), "split_two_readers"
+ *     "compact_boot_always", "crosscov_sparse" (plsx_crosscov_batch treats its resamples as bootstraps: the compact
+ *     blocks wherever plsx_boot_batch would take them, so that tests can read R of a compact launch),
+ *     "sepmom_always", "no_split_fuse" (split halves: two passes), "split_two_readers"
  *     (fused split blocks read by the Gram and the projection kernel instead of the one-pass reader),
  *     "split_reader8" (bit 0: the one-pass reader as the round-5 8-wave block whose matrix waves build the tiles
  *     themselves, instead of the 12-wave block with dedicated construction waves; bit 1: wave kinds in runs of

@@ -82,14 +82,15 @@ int launch_csplit(plsx_ctx* ctx, int m, int nks_c, SplitEpi se, hipStream_t st, 
     // (a last tile of <= 4 live rows -- T' = 50: rows 48, 49 -- runs on the 4x4x4 shape)
     const bool tail = ctx->Tp - (MTc - 1) * 16 <= 4;
     if (raw) {
-        // raw first-half sums for the one-pass reader (T' = 17 .. 52)
+        // raw first-half sums for the one-pass reader (T' = 17 .. 52).  Four tiles are T' = 49 .. 52 here, a last tile
+        // of at most 4 rows: always the tail form, there is no <4, ., false, 8> instantiation
         switch (MTc) {
             case 2: return tail ? launch_xprod_compact<2, 6, true, 8>(ctx, m, nks_c, se, st)
                                 : launch_xprod_compact<2, 6, false, 8>(ctx, m, nks_c, se, st);
             case 3: return tail ? launch_xprod_compact<3, 4, true, 8>(ctx, m, nks_c, se, st)
                                 : launch_xprod_compact<3, 4, false, 8>(ctx, m, nks_c, se, st);
-            case 4: return tail ? launch_xprod_compact<4, PLSX_CKT, true, 8>(ctx, m, nks_c, se, st)
-                                : launch_xprod_compact<4, PLSX_CKT, false, 8>(ctx, m, nks_c, se, st);
+            case 4: if (tail) return launch_xprod_compact<4, PLSX_CKT, true, 8>(ctx, m, nks_c, se, st);
+                    [[fallthrough]];
             default: return fail(ctx, PLSX_ERR_STATE, "raw compact split blocks: T' outside 17..52");
         }
     }

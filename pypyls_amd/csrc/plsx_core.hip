@@ -626,7 +626,8 @@ try {
         const int m = std::min(nb, n - off);
         const int* xs = d_xsrc ? d_xsrc + (size_t)off * ctx->S : nullptr;
         const int* ys = d_ysrc ? d_ysrc + (size_t)off * ctx->S : nullptr;
-        if (int e = run_xprod(ctx, xs, ys, m, st)) return e;
+        // option crosscov_sparse (tests): the resamples are bootstraps -- compact blocks where plsx_boot_batch takes them
+        if (int e = run_xprod(ctx, xs, ys, m, st, false, nullptr, -1, ctx->opt[OPT_CROSSCOV_SPARSE] != 0)) return e;
         dim3 g(ceil_div(ctx->Tp * ctx->B, 256), m);
         hipLaunchKernelGGL(k_gather_cols, g, dim3(256), 0, st, ptr<double>(ctx->R), ctx->strideR,
                            ctx->Bpad, 0, ctx->Tp, ctx->B, d_R + (size_t)off * ctx->Tp * ctx->B);
@@ -1283,14 +1284,14 @@ try {
     const bool cmp = ctx->last_compact_n > 0;
     // [12..18]: the path of the last rotation / Gram launch (include/plsx.h); the tail flag rides on the variant
     const auto uvar = [&](int nks) { return (double)(nks > 0 && ctx->urot_tail_l ? nks + 100 : nks); };
-    double vals[19] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
+    double vals[21] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
                        (double)(cmp ? ceil_div(ctx->Tp, 16) : (ctx->sepmom_used ? ctx->MTd : ctx->MT)),
                        (double)ctx->Gcap * ctx->npg, (double)ctx->timed_units, (double)use_dual(ctx), crows,
                        ctx->nt_flops, (double)ctx->quad_series, (double)ctx->quad_MT, (double)ctx->quad_gpl,
                        (double)ctx->urot_waves_l, (double)ctx->urot_splits_l, (double)ctx->urot_rps_l,
                        uvar(ctx->urot_nks_first), (double)ctx->gram_chunks_l, uvar(ctx->urot_nks_last),
-                       (double)ctx->gram_kind_l};
-    int n = std::min(cap, 19);
+                       (double)ctx->gram_kind_l, (double)ctx->split_blocks_l, (double)ctx->split_reader_l};
+    int n = std::min(cap, 21);
     for (int i = 0; i < n; ++i) out[i] = vals[i];
     return n;
 } PLSX_CATCH(const_cast<plsx_ctx*>(cctx))

@@ -40,13 +40,15 @@ enum {
     OPT_NO_REFINE = 0, OPT_MIN_BATCH, OPT_INBLOCK_MOMENTS, OPT_NO_COMPACT_BOOT, OPT_COMPACT_BOOT_ALWAYS,
     OPT_SEPMOM_ALWAYS, OPT_NO_GRAM4, OPT_UROT_GENERIC, OPT_UROT_NO_TAIL4, OPT_NO_FIXED_X, OPT_NO_DUAL_PERM,
     OPT_TWO_PASS_BOOT, OPT_SPLIT_INBLOCK, OPT_NO_SPLIT_FUSE, OPT_SPLIT_TWO_READERS, OPT_EXPECT_RESAMPLES,
-    OPT_SIMPLS_JACOBI, OPT_PERCENTILE_SORT, OPT_QUAD_SUMS, OPT_SPLIT_READER8, OPT_SIMPLS_GLOBAL, OPT_COUNT
+    OPT_SIMPLS_JACOBI, OPT_PERCENTILE_SORT, OPT_QUAD_SUMS, OPT_SPLIT_READER8, OPT_SIMPLS_GLOBAL,
+    OPT_CROSSCOV_SPARSE, OPT_COUNT
 };
 static const char* const kOptionNames[OPT_COUNT] = {
     "no_refine", "min_batch", "inblock_moments", "no_compact_boot", "compact_boot_always",
     "sepmom_always", "no_gram4", "urot_generic", "urot_no_tail4", "no_fixed_x", "no_dual_perm",
     "two_pass_boot", "split_inblock", "no_split_fuse", "split_two_readers", "expect_resamples",
-    "simpls_jacobi", "percentile_sort", "quad_sums", "split_reader8", "simpls_global"};
+    "simpls_jacobi", "percentile_sort", "quad_sums", "split_reader8", "simpls_global",
+    "crosscov_sparse"};
 
 // k-steps per LDS stage of the 4-tile compact cross-product blocks (T' = 49 .. 64: the headline shape).  A/B lever of
 // tools/ckt_probe.sh (measured: profiles/r06_compact_kt.txt); other tile counts keep 12 / MT.
@@ -115,6 +117,7 @@ struct plsx_ctx {
     long long n_refined = 0, n_unrefined = 0;           // host copies of status[1], status[2] since the last plsx_numeric_report
     Buf cellS, rowc, out_row_s;                         // fused split-half: cell moments of X, row constants, row map
     Buf ccon, sFt;                                      // one-pass split reader: column constants [pair][4][Bpad], cell std [J][Bpad]
+    int split_blocks_l = 0, split_reader_l = 0;         // the last split-half pass, as plsx_last_timing [19] / [20] report it
     int has_sFt = 0, split_raw = 0;                     // split_raw: the last compact split pass left raw first-half sums (one slot per split)
     int has_cellS = 0;
     int dual = 0, dual_ok = 0, has_Kd = 0;              // has_Kd: the S x S kernel of the bound data is current

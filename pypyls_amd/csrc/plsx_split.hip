@@ -21,6 +21,7 @@ int run_split_compact(plsx_ctx* ctx, const int* perm, const uint8_t* masks, int 
 {
     const bool raw = split_reader_ok(ctx);
     ctx->split_raw = raw ? 1 : 0;
+    ctx->split_blocks_l = raw ? 8 : 5;
     const int J = ctx->J, S = ctx->S, MTc = ceil_div(ctx->Tp, 16), KT = MTc == 4 ? PLSX_CKT : 12 / MTc, rows = MTc * 16;
     ctx->last_compact_n = 0;                            // (the row tables are about to hold this pass's splits)
     if (!ctx->has_cellS) {
@@ -162,6 +163,7 @@ int run_split_reader(plsx_ctx* ctx, int m, const double* Rfull, const double* Mv
         // 12-wave block with dedicated construction waves (round 6); option "split_reader8": the round-5 block whose
         // matrix waves build the tiles themselves (the A/B, and the same results to the last bit: same products, same order)
         const bool twelve = (ctx->opt[OPT_SPLIT_READER8] & 1) == 0;
+        ctx->split_reader_l = (twelve ? 12 : 8) + (a.wmap ? 0 : 100);
         switch (NB) {
 #define SFCASE(N) case N: rc = twelve ? launch_split_fused12<N>(ctx, a, blocks, lds, st) : launch_split_fused<N>(ctx, a, blocks, lds, st); break;
             SFCASE(5) SFCASE(6) SFCASE(7) SFCASE(8) SFCASE(9) SFCASE(10) SFCASE(11) SFCASE(12) SFCASE(13)
@@ -188,6 +190,7 @@ int run_split_fused(plsx_ctx* ctx, const int* perm, const uint8_t* masks, int m,
         !ctx->opt[OPT_SPLIT_INBLOCK])
         return run_split_compact(ctx, perm, masks, m, Rfull, st, Yarr);
     const int J = ctx->J, S = ctx->S, rows = ctx->MT * 16;
+    ctx->split_blocks_l = 1;
     if (ctx->has_cellS != 1) {
         if (int e = ensure(ctx, ctx->cellS, (size_t)2 * J * ctx->Bpad * 8, true)) return e;
         hipLaunchKernelGGL(k_cell_moments, dim3(ceil_div(ctx->B, 256)), dim3(256), 0, st, ptr<double>(ctx->Xc),
@@ -293,7 +296,7 @@ try {
             const double* Yarr = d_ystack ? d_ystack + (size_t)p * ysz : nullptr;     // this arrangement's Y
             for (int off = 0; off < ns; off += spp) {
                 const int m = std::min(spp, ns - off);               // splits in this pass
-                ctx->split_raw = 0;
+                ctx->split_raw = 0; ctx->split_blocks_l = 0; ctx->split_reader_l = 0;
                 if (fused) {
                     if (int e = run_split_fused(ctx, perm, d_masks + ((size_t)p * ns + off) * S, m, Rfull, st, Yarr))
                         return e;

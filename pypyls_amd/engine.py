@@ -1021,14 +1021,15 @@ class Engine(object):
         return bool(rc)
 
     def last_timing(self):
-        """include/plsx.h, plsx_last_timing.  The last seven keys say how the last rotation (k_urot) and Gram pass
-        were launched; they are recorded whether or not timing is on."""
-        buf = (ctypes.c_double * 19)()
-        n = self.lib.plsx_last_timing(self.ctx, buf, 19)
+        """include/plsx.h, plsx_last_timing.  ``urot_waves`` .. ``gram_kernel`` say how the last rotation (k_urot) and Gram pass
+        were launched, ``split_blocks`` / ``split_reader`` how the last split-half pass ran; they are recorded whether or
+        not timing is on."""
+        buf = (ctypes.c_double * 21)()
+        n = self.lib.plsx_last_timing(self.ctx, buf, 21)
         keys = ['xprod_ms', 'xprod_launches', 'resamples_per_group', 'm_tiles', 'superbatch',
                 'xprod_resamples', 'dual_perm', 'compact_row_fraction', 'nt_flops', 'quad_series', 'quad_m_tiles',
                 'quad_blocks_per_lv', 'urot_waves', 'urot_splits', 'urot_res_per_split', 'urot_variant',
-                'gram_chunks', 'urot_variant_last', 'gram_kernel']
+                'gram_chunks', 'urot_variant_last', 'gram_kernel', 'split_blocks', 'split_reader']
         return {k: buf[i] for i, k in enumerate(keys[:max(n, 0)])}
 
 

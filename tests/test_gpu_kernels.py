@@ -354,6 +354,7 @@ def test_compact_blocks_equal_dense_blocks(shape):
     (PLSX_SPLIT_INBLOCK = the 7-per-block fused layout) against the dense layouts: bootstrap sums, distrib,
     split-half correlations.  Every tile count 1..4, with and without the tail, J = 1..16 cells (16 cells:
     compact bootstraps, but the split-half epilogue's column tables no longer fit: dense fused layout).
+    tests/test_gpu_compact_blocks.py runs every compiled variant at every stage edge against the oracle.
     Own processes (historical: the switches used to be read once per process)."""
     import json
     import os
