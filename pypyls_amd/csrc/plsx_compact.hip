@@ -14,9 +14,7 @@ namespace plsxi {
 template <int MT, int KT, bool TAIL = false>
 int launch_xprod_cboot(plsx_ctx* ctx, int nres, int nks_c, SplitEpi se, hipStream_t st)
 {
-    const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8 + (size_t)nks_c * 4 * sizeof(int);
-    const size_t epi = (size_t)se.npairs * 128 * 8 + (size_t)2 * MT * 16 * 4;
-    const size_t lds = std::max(stage, epi);
+    const size_t lds = compact_lds_bytes(MT, KT, 3, nks_c, se.npairs);
     HIPCHK(set_lds(k_xprod_compact<MT, KT, 3, TAIL>, lds));
     const int ncolblk = ceil_div(ctx->Bpad, 128);
     KTimer tm(ctx, KC_XPROD, st);
@@ -60,10 +58,8 @@ template <int MT, int KT, bool TAIL = false, int EPI = 5>
 int launch_xprod_compact(plsx_ctx* ctx, int m, int nks_c, SplitEpi se, hipStream_t st)
 {
     const int J = ctx->J;
-    const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8 + (size_t)nks_c * 4 * sizeof(int);
-    // EPI 8 (raw first-half sums, one R slot per split): the epilogue needs the row map only
-    const size_t epi = EPI == 8 ? (size_t)MT * 16 * 4 : (size_t)5 * J * 128 * 8 + (size_t)2 * MT * 16 * 4 + (size_t)MT * 16 * 5 * 8;
-    const size_t lds = std::max(stage, epi);
+    // (EPI 8, raw first-half sums, one R slot per split: the epilogue needs the row map only)
+    const size_t lds = compact_lds_bytes(MT, KT, EPI, nks_c, J);
     se.off_pre = 0;
     HIPCHK(set_lds(k_xprod_compact<MT, KT, EPI, TAIL>, lds));
     const int ncolblk = ceil_div(ctx->Bpad, 128);

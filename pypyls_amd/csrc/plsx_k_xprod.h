@@ -514,6 +514,10 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
 //        tiles (T' <= 208) at 3 or 2 waves per SIMD.
 // EPI 5: fused split-half (both halves from the first half's raw sums and the arrangement's full-sample R:
 //        se.Rfull, se.rowc, se.scale / scale2 = raw first-half moments, se.cellS1 / S2, se.cell_len).
+// EPI 8: the raw first-half sums of one split per block (the one-pass reader k_split_fused rebuilds both halves).
+// A block is short (~80 k-steps at the headline shape, 788 k blocks per launch), so what it does outside its loop is
+// kept to ONE barrier and two dependent round trips in front of the loop and to stores behind it (epilogues 3, 8):
+// the kernel body says how.
 // TAIL: the last tile holds <= 4 live rows and runs on the 4x4x4 shape (16 instead of 64 pipe cycles;
 //       A = the tile's rows 0..3 for every block, B = the X fragment as it is, the result lands where
 //       register 0 of the 16x16 tile would).
@@ -523,8 +527,34 @@ __device__ __forceinline__ d2 load_x2_buf(const double* base, int voff)
     return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
 }
 
+// LDS of a block, in doubles from smem: the row maps (2 x MT * 16 ints, filled once in the prologue and read by the
+// epilogue: an area of their own, nothing is staged after the loop), the two A stages, the row table (byte offsets
+// of the block's X rows), and for epilogue 3 with more cells than a lane keeps in registers the 1 / std table.
+// plsx_compact.hip sizes the launch with the same three functions.
+__host__ __device__ constexpr int compact_stage_lds(int MT, int KT) { return ((KT * MT * 64 + 127) / 128) * 128; }
+// cells whose 1 / std (16 bytes per lane and cell) a lane of epilogue 3 holds in registers: they arrive in the
+// registers that hold the next stage's X fragments in every pass but the last, so as many as a stage has k-steps;
+// four at the most (the store loop selects among them with compares)
+__host__ __device__ constexpr int compact_scale_regs(int KT) { return KT < 4 ? KT : 4; }
+__host__ __device__ constexpr size_t compact_lds_bytes(int MT, int KT, int EPI, int nks, int J)
+{
+    const size_t loop = (size_t)MT * 16 * 8 + (size_t)2 * compact_stage_lds(MT, KT) * 8 + (size_t)nks * 4 * 4;
+    if (EPI == 3) return loop + (J > compact_scale_regs(KT) ? (size_t)J * 128 * 8 : 0);
+    // epilogue 5: u1, v1, u2, v2, sF : [5][J][128] and the row constants [MT * 16][5] over the stages and the table
+    const size_t epi5 = (size_t)MT * 16 * 8 + (size_t)5 * J * 128 * 8 + (size_t)MT * 16 * 5 * 8;
+    return EPI == 5 && epi5 > loop ? epi5 : loop;
+}
+
+// waves per SIMD the register allocation is held to: what each variant runs at (epilogue 3: 5 at four tiles with the
+// tail -- the headline --, 4 up to six tiles, 3 up to nine and at ten with the tail, 2 beyond)
+__host__ __device__ constexpr int compact_waves(int MT, int EPI, bool TAIL)
+{
+    if (EPI == 3) return MT > 10 ? 2 : MT == 10 ? (TAIL ? 3 : 2) : MT > 6 ? 3 : MT > 4 ? 4 : (MT == 4 && TAIL) ? 5 : 4;
+    return (EPI == 5 && MT == 4 && !TAIL) ? 3 : 4;
+}
+
 template <int MT, int KT, int EPI, bool TAIL>
-__global__ __launch_bounds__(256, MT > 6 ? 2 : ((MT > 4 || (EPI == 5 && MT == 4 && !TAIL)) ? 3 : 4))
+__global__ __launch_bounds__(256, compact_waves(MT, EPI, TAIL))
 void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
                      const double* __restrict__ X, int ldx, int nks,
                      double* __restrict__ R, int ldr, int rows_per_group,
@@ -535,64 +565,116 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NW = 4, NT = NW * 64, BC = NW * 32;       // threads, columns of a block
     constexpr int STAGE = KT * MT * 64;
-    constexpr int STAGE_LDS = ((STAGE + 127) / 128) * 128;
+    constexpr int STAGE_LDS = compact_stage_lds(MT, KT);
     constexpr int PASSES = (STAGE + NT * 2 - 1) / (NT * 2);
     constexpr bool EVEN = (STAGE % (NT * 2)) == 0;
     constexpr int MF = TAIL ? MT - 1 : MT;                   // tiles on the 16x16x4 shape
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int NSCR = compact_scale_regs(KT);
+    static_assert(MT * 16 <= NT, "the row maps are staged by one thread per row");
     const int ncb = (ncolblk + 7) & ~7;
     const int sweep = blockIdx.x / (8 * ncb);
     const int within = blockIdx.x - sweep * (8 * ncb);
     const int slot = within >> 3;
     const int grp = sweep * 8 + (slot & 7);
     const int colblk = (slot >> 3) * 8 + (within & 7);
-    if (grp >= n_groups || colblk >= ncolblk) return;
-    const int kq = lane >> 4;
-    const int cw = wave * 32 + 2 * (lane & 15);              // this lane's (even) column inside the block
-    const int col = colblk * BC + cw;
-    const bool live = col < ldr;                             // (ldr is a multiple of 64: whole waves)
-    const int lcol = live ? col : 0;
+    if (grp >= n_groups || colblk >= ncolblk) return;         // (the whole block: before its only barrier outside the loop)
     const double* Ag = Afrag + (size_t)grp * group_stride;
-    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    const int swave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 
     d4 acc0[MF > 0 ? MF : 1], acc1[MF > 0 ? MF : 1];
 #pragma unroll
     for (int m = 0; m < MF; ++m) { acc0[m] = (d4){0.0, 0.0, 0.0, 0.0}; acc1[m] = (d4){0.0, 0.0, 0.0, 0.0}; }
     double tl0 = 0.0, tl1 = 0.0;
+
+    int* s_out = reinterpret_cast<int*>(smem);
+    int* s_mom = s_out + MT * 16;
+    double* sStage = smem + MT * 16;
+    int* s_tab = reinterpret_cast<int*>(sStage + 2 * STAGE_LDS);
+    const int J3 = se.npairs;                                 // (epilogue 3: cells)
+    double* sW = reinterpret_cast<double*>(s_tab + nks * 4) + swave * (J3 * 32);   // [J3][32]: 1 / std, this wave's columns
+    d2 scr[NSCR];                                             // ... or per cell in registers
+    {   // ---- prologue and main loop (a scope of their own: the epilogue declares its lane constants again) ------
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kq = lane >> 4;
+    const int cw = wave * 32 + 2 * (lane & 15);              // this lane's (even) column inside the block
+    const int col = colblk * BC + cw;
+    const bool live = col < ldr;                             // (ldr is a multiple of 64: whole waves)
+    const int lcol8 = (live ? col : 0) * 8;                  // byte offset of the lane's columns in a row of X (0: beyond ldr)
     const int toff = (lane & 48) + (lane & 3) - lane;        // TAIL: lane 16 k + 4 blk + i -> fragment position 16 k + i
 
+    // ---- prologue: everything the block needs besides its A stages and X rows, behind ONE barrier ----------------
+    // Every lane fetches the table entries of stage 0 for itself, so its first X loads wait for one round trip, not
+    // for the table's way through LDS; the A stage-0 copy, the row maps and the table are in flight meanwhile.
+    // The table holds rows; its LDS copy holds their byte offsets in X (row * ldx * 8, the 32-bit range x_off always
+    // had), multiplied here once per entry instead of once per lane, k-step and pass.
+    // Padding entries (the table is zero beyond the block's rows: row 0 against zero A columns) come along as they are.
+    const int* tabg = se.row_tab + (size_t)grp * nks * 4;
+    const int ldx8 = ldx * 8;
+    int row0[KT];
+#pragma unroll
+    for (int s = 0; s < KT; ++s) row0[s] = tabg[s * 4 + kq];
+    stage_copy_buf<NT, PASSES, EVEN, STAGE>(Ag, sStage, tid, swave);
+    int orw = -1, mix = -1;
+    if (tid < MT * 16) {
+        orw = out_row[tid];
+        if (EPI != 8) mix = mom_idx[tid];
+    }
     // any mask / index list is legal: the tables are sized for S rows, the block contracts over its own count
     const int ksteps = max(1, (se.row_cnt[grp] + 3) >> 2);
     const int nkt = (ksteps + KT - 1) / KT;
-    int* s_tab = reinterpret_cast<int*>(smem + 2 * STAGE_LDS);
-    for (int i = tid; i < nks * 4; i += NT) s_tab[i] = se.row_tab[(size_t)grp * nks * 4 + i];
+    const int ntab = nkt * KT * 4;                            // live entries, whole stages (<= nks * 4)
+    // four entries per thread and trip, all four loads issued before the first is waited for
+    auto tab_load = [&](int i0, int (&v)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = tabg[min(i0 + u * NT + tid, ntab - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(v[u]));    // (or hipcc sinks a load into its guarded store)
+    };
+    auto tab_store = [&](int i0, const int (&v)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u * NT + tid < ntab) s_tab[i0 + u * NT + tid] = v[u] * ldx8;
+    };
+    int tv[4];
+    tab_load(0, tv);
+    d2 xa[KT], xb[KT];
+#pragma unroll
+    for (int s = 0; s < KT; ++s) xa[s] = load_x2_buf(X, row0[s] * ldx8 + lcol8);
+    tab_store(0, tv);
+    for (int i0 = 4 * NT; i0 < ntab; i0 += 4 * NT) { tab_load(i0, tv); tab_store(i0, tv); }
+    if (tid < MT * 16) {
+        if constexpr (EPI == 3) {
+            // one word per row: the R row and the row's cell + 1; rows of resamples beyond the launch's last one (the
+            // last group may hold fewer than its block has room for: zero A rows, no scale) are not stored
+            const int rows_valid = min(rows_per_group, se.accB - grp * rows_per_group);
+            s_out[tid] = (orw < 0 || orw >= rows_valid) ? -1 : (orw | ((mix + 1) << 16));
+        } else if constexpr (EPI == 5) {
+            // the R row inside the arrangement (orow mod 2 Tpp) rides in the upper half of the word so the store
+            // loop does no integer division
+            s_out[tid] = orw < 0 ? -1 : (orw | ((orw % (2 * se.Tpp)) << 20));
+            s_mom[tid] = mix;
+        } else {
+            s_out[tid] = orw;
+        }
+    }
+    // (first X fragments resident before the loop: a load still pending at the loop header makes hipcc place a
+    // near-draining s_waitcnt right after the next stage's loads are issued)
+#pragma unroll
+    for (int s = 0; s < KT; ++s) asm volatile("" : "+v"(xa[s]));
     __syncthreads();
-    auto x_off = [&](int kstep) -> int { return (s_tab[kstep * 4 + kq] * ldx + lcol) * 8; };
 
-    stage_copy_buf<NT, PASSES, EVEN, STAGE>(Ag, smem, tid, swave);
-    d2 xb[KT];
-#pragma unroll
-    for (int s = 0; s < KT; ++s) xb[s] = load_x2_buf(X, x_off(s));
-#pragma unroll
-    for (int s = 0; s < KT; ++s) asm volatile("" : "+v"(xb[s]));
-    __syncthreads();
-
-    // one pass of the main loop; FULL: every k-step of the stage is live -- the passes before the last run without the
-    // test for a partial stage in their body (a loop of their own, as in k_xprod's EPI 7)
-    auto pass = [&](int kt, auto full) {
-        const int cur = kt & 1;
-        const int kn = min(kt + 1, nkt - 1);
-        d2 xn[KT];
-        stage_copy_buf<NT, PASSES, EVEN, STAGE>(Ag + (size_t)kn * STAGE, smem + (cur ^ 1) * STAGE_LDS, tid, swave);
-#pragma unroll
-        for (int s = 0; s < KT; ++s) xn[s] = load_x2_buf(X, x_off(kn * KT + s));
-        const double* sA = smem + cur * STAGE_LDS + lane;
+    // ---- main loop --------------------------------------------------------------------------------------------------
+    // the MFMAs of one stage: buffer CUR, X fragments xc; the first `nlive` k-steps when the stage may be partial
+    const double* sA0 = sStage + lane;                       // this lane's word of a fragment, buffer 0
+    const double* sT0 = sA0 + toff;                          // ... of the tail tile's fragment
+    auto contract = [&](auto curc, const d2 (&xc)[KT], auto full, int nlive) {
+        const int cur = curc;
+        const double* sA = sA0 + cur * STAGE_LDS;
+        const double* sT = sT0 + cur * STAGE_LDS;
 #pragma unroll
         for (int s = 0; s < KT; ++s) {
-            if constexpr (!decltype(full)::value) {
-                if (kt * KT + s >= ksteps) break;           // (the last stage may be partial)
-            }
-            const double b0 = xb[s].x, b1 = xb[s].y;
+            if (!decltype(full)::value && s >= nlive) continue;    // (no break: the loop must unroll, xc[s] is a register)
+            const double b0 = xc[s].x, b1 = xc[s].y;
 #pragma unroll
             for (int m = 0; m < MF; ++m) {
                 const double a = sA[(s * MT + m) * 64];
@@ -600,20 +682,80 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
                 acc1[m] = mfma_f64(a, b1, acc1[m]);
             }
             if constexpr (TAIL) {
-                const double a = sA[(s * MT + MT - 1) * 64 + toff];
+                const double a = sT[(s * MT + MT - 1) * 64];
                 tl0 = mfma_f64_4x4(a, b0, tl0);
                 tl1 = mfma_f64_4x4(a, b1, tl1);
             }
         }
-#pragma unroll
-        for (int s = 0; s < KT; ++s) xb[s] = xn[s];
-        __syncthreads();
     };
-    const int nfull = ksteps / KT;                           // stages whose KT k-steps are all live
-    int kt_main = 0;
-    for (; kt_main < nfull; ++kt_main) pass(kt_main, std::integral_constant<bool, true>());
-    for (; kt_main < nkt; ++kt_main) pass(kt_main, std::integral_constant<bool, false>());
+    // One pass before the last: stage kt + 1 of A by LDS-DMA into the other buffer and its X fragments into the OTHER
+    // register set, then the MFMAs of stage kt.  The loop runs two passes per trip, so the buffer is a constant and the
+    // register sets swap by name (no moves); the table's LDS address and the A source step by one stage per pass, and
+    // the X offset of a k-step is its table entry plus the lane's column bytes: one add.
+    const int* tp = s_tab + KT * 4 + kq;
+    const double* An = Ag + STAGE;
+    auto pass = [&](auto curc, const d2 (&xc)[KT], d2 (&xn)[KT]) {
+        constexpr int CUR = decltype(curc)::value;
+        stage_copy_buf<NT, PASSES, EVEN, STAGE>(An, sStage + (CUR ^ 1) * STAGE_LDS, tid, swave);
+#pragma unroll
+        for (int s = 0; s < KT; ++s) xn[s] = load_x2_buf(X, tp[s * 4] + lcol8);
+        An += STAGE;
+        tp += KT * 4;
+        contract(curc, xc, std::true_type(), KT);
+        __syncthreads();             // (drains the DMA issued in this pass, then barrier)
+    };
+    // The last pass fetches no further stage.  Epilogue 3 issues its only loads here instead, so that they land
+    // under the last MFMAs and the epilogue is stores only: the block's 1 / std per cell, 16 bytes per lane and cell
+    // into registers (up to NSCR cells), or each wave's own 32 columns of the table by LDS-DMA into its part of an
+    // LDS area of its own -- read back by that wave alone, so its wait for the copy is all the ordering it needs.
+    auto last = [&](int cur, const d2 (&xc)[KT]) {
+#pragma unroll
+        for (int j = 0; j < NSCR; ++j) scr[j] = (d2){1.0, 1.0};
+        if constexpr (EPI == 3) {
+            if (J3 <= NSCR) {
+#pragma unroll
+                for (int j = 0; j < NSCR; ++j)
+                    if (j < J3)                                // (lcol8: the loop's own register, not lcol kept beside it)
+                        scr[j] = *reinterpret_cast<const d2*>(
+                            reinterpret_cast<const char*>(se.scale + ((size_t)grp * J3 + j) * ldr) + lcol8);
+            } else if (live) {
+                // one piece per cell: the wave's 256 bytes of the cell's table row, 4 bytes per lane (whole pieces of
+                // 16 bytes per lane would hold four cells: with lanes beyond the last cell clamped onto it the copies came
+                // out wrong whenever the cells were no multiple of four)
+                __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                    (void*)(se.scale + (size_t)grp * J3 * ldr + colblk * BC + swave * 32), (short)0, 0x7fffffff, PLSX_RSRC_FLAGS);
+                const int ln4 = __lane_id() * 4;              // (not `lane`: that would be one more register across the loop)
+                for (int j = 0; j < J3; ++j)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                        rs, (__attribute__((address_space(3))) void*)(sW + j * 32), 4, ln4, j * ldr * 8, 0, 0);
+            }
+        }
+        contract(cur, xc, std::false_type(), ksteps - (nkt - 1) * KT);
+        if constexpr (EPI == 5) __syncthreads();   // (its epilogue builds tables over the stages)
+    };
+    {
+        std::integral_constant<int, 0> c0;
+        std::integral_constant<int, 1> c1;
+        int kt = 0, cur = 0;
+        for (; kt + 2 < nkt; kt += 2) { pass(c0, xa, xb); pass(c1, xb, xa); }
+        if (kt + 1 < nkt) {
+            pass(c0, xa, xb);
+#pragma unroll
+            for (int s = 0; s < KT; ++s) xa[s] = xb[s];      // (once per block)
+            cur = 1;
+        }
+        last(cur, xa);
+    }
+    }
 
+    // ---- epilogue: stores -----------------------------------------------------------------------------------------
+    // The lane's constants are derived again from the thread id, opaque to the compiler: carried across the loop they
+    // took <4,3,3,true> past 96 VGPRs (5 -> 4 waves per SIMD).
+    int tid16 = threadIdx.x * 16;                             // (the value the loop's LDS-DMA offset already holds)
+    if constexpr (EPI != 5) asm volatile("" : "+v"(tid16));   // (epilogue 5 spills two registers more with it than without)
+    const int tid = tid16 >> 4, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
+    const int cw = wave * 32 + 2 * (lane & 15), col = colblk * BC + cw;
+    const bool live = col < ldr;
     // value of (tile m, register i), column 0 / 1 of the lane; the tail tile has register 0 only
     auto val0 = [&](int m, int i) -> double { return (TAIL && m == MT - 1) ? tl0 : acc0[m < MF ? m : 0][i]; };
     auto val1 = [&](int m, int i) -> double { return (TAIL && m == MT - 1) ? tl1 : acc1[m < MF ? m : 0][i]; };
@@ -622,9 +764,6 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
         // raw first-half sums C_1 = A_1 . X of ONE split per block, stored once (slot = split): the fused reader
         // (k_split_fused) rebuilds both z-scored halves from them and the arrangement's full-sample cross-product,
         // so this leg writes half the bytes of epilogue 5 and spends no arithmetic on them
-        int* s_out = reinterpret_cast<int*>(smem);
-        for (int i = tid; i < MT * 16; i += NT) s_out[i] = out_row[i];
-        __syncthreads();
         if (!live) return;
         double* Rg = R + (size_t)grp * rows_per_group * ldr + col;
 #pragma unroll
@@ -638,45 +777,32 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
             }
         return;
     } else if constexpr (EPI == 3) {
-        const int nmu = se.npairs;
-        double* sS3 = smem;                                  // [nmu][BC]
-        int* s_out = reinterpret_cast<int*>(smem + (size_t)nmu * BC);
-        int* s_mom = s_out + MT * 16;
-        const double* sc0 = se.scale + (size_t)grp * nmu * ldr + colblk * BC;
-        for (int idx = tid; idx < nmu * BC; idx += NT) {
-            const int mi = idx / BC, c = idx - mi * BC;
-            sS3[idx] = (colblk * BC + c < ldr) ? sc0[(size_t)mi * ldr + c] : 0.0;
-        }
-        for (int i = tid; i < MT * 16; i += NT) { s_out[i] = out_row[i]; s_mom[i] = mom_idx[i]; }
-        __syncthreads();
         if (!live) return;
+        if (J3 > NSCR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wave's own copy of its scales)
         double* Rg = R + (size_t)grp * rows_per_group * ldr + col;
-        const int rows_valid = min(rows_per_group, se.accB - grp * rows_per_group);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (TAIL && m == MT - 1 && i > 0) break;
-                const int row = m * 16 + kq + 4 * i;
-                const int orow = s_out[row], mi = s_mom[row];
-                if (orow < 0 || orow >= rows_valid) continue;
+                const int packed = s_out[m * 16 + kq + 4 * i];
+                if (packed < 0) continue;
+                const int orow = packed & 0xffff, mi = (packed >> 16) - 1;
                 d2 sc = (d2){1.0, 1.0};
-                if (mi >= 0) sc = *reinterpret_cast<const d2*>(&sS3[mi * BC + cw]);
+                if (J3 > NSCR) {
+                    if (mi >= 0) sc = *reinterpret_cast<const d2*>(&sW[mi * 32 + 2 * (lane & 15)]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NSCR; ++j)
+                        if (mi == j) sc = scr[j];
+                }
                 *reinterpret_cast<d2*>(&Rg[(size_t)orow * ldr]) = (d2){val0(m, i) * sc.x, val1(m, i) * sc.y};
             }
         return;
     } else {
         const int J = se.J;
-        double* w5 = smem;                                   // u1, v1, u2, v2, sF : [5][J][BC]
-        int* s_out = reinterpret_cast<int*>(smem + (size_t)5 * J * BC);
-        int* s_mom = s_out + MT * 16;
-        double* s_rc = reinterpret_cast<double*>(s_mom + MT * 16);
-        const int pitch2 = 2 * se.Tpp;
-        for (int i = tid; i < MT * 16; i += NT) {
-            const int orw = out_row[i];
-            s_out[i] = orw < 0 ? -1 : (orw | ((orw % pitch2) << 20));
-            s_mom[i] = mom_idx[i];
-        }
+        double* w5 = sStage;                                 // u1, v1, u2, v2, sF : [5][J][BC] (the stages and the table are dead)
+        double* s_rc = w5 + (size_t)5 * J * BC;
         for (int i = tid; i < MT * 16 * 5; i += NT) s_rc[i] = se.rowc[(size_t)grp * MT * 16 * 5 + i];
         const int cb0 = colblk * BC;
         for (int idx = tid; idx < J * BC; idx += NT) {
