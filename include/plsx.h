@@ -113,6 +113,27 @@ int plsx_crosscov_batch(plsx_ctx* ctx, const int32_t* d_xsrc, const int32_t* d_y
  */
 int plsx_decompose(plsx_ctx* ctx, double* d_xw, double* d_sv, double* d_yw, void* stream);
 
+/*
+ * Non-rotated PLS: the effects are the caller's contrasts over the rows of R (cell-major: group, then condition, then
+ * behaviour -- the row order of y_weights), nothing is decomposed and nothing is rotated.  Called after plsx_set_data;
+ * plsx_decompose / plsx_set_original follow as usual.
+ *   d_C  (T', Lc) fp64, unit columns (the host normalises); copied before the call returns
+ *   Lc   1 .. min(T', B).  Lc = 0 or d_C = NULL returns the context to SVD mode; so does plsx_set_data.
+ * Internally C is zero-padded to the context's L = min(T', B) columns: every layout stays as it is, the columns >= Lc
+ * of every result are zero and the host slices [:Lc].  While contrasts are set, with V = C:
+ *   plsx_decompose         Z = R^T V (B, L); d_sv[l] = ||Z[:, l]||; d_xw[:, l] = Z[:, l] / d_sv[l] (0 where the norm
+ *                          is 0); d_yw = V.  The contrast fixes the sign: plsx_svd_flip is not called.
+ *   plsx_perm_batch[_y]    d_out_sv[p][l] = ||R_p^T v_l||; `rotate` is ignored.  Feature pass: one pass over R_p
+ *                          (k_contrast_norms: fixed chunking of the features, fixed summation order -- the same bits
+ *                          whatever the batch size, the scratch budget or the team); dual route: v_l^T G_p v_l.
+ *   plsx_boot_batch        accumulates U_b = R_b^T V and its squares (with plsx_boot_begin / _finish as usual);
+ *                          d_distrib as usual.
+ *   plsx_split_half_batch[_y], plsx_crossval_batch   PLSX_ERR_UNSUPPORTED.
+ * A contrast whose singular value lies below 1e-3 of the largest takes the binding off the dual-space routes, as a
+ * graded spectrum does (plsx_set_original).  PLSX_ERR_ARG for data bound for regression or Lc out of range.
+ */
+int plsx_set_contrasts(plsx_ctx* ctx, const double* d_C, int Lc, void* stream);
+
 /* Fix the original decomposition used for Procrustes alignment
  * (`original=` of _single_perm / _single_boot, pyls/base.py:505,648). */
 int plsx_set_original(plsx_ctx* ctx, const double* d_xw, const double* d_sv,
@@ -640,7 +661,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * k_sd_sh_score of plsx_simpls_split_half_batch), ..., 11 k_coef_prod (the feature pass of
  * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
  * k_col_sd of plsx_simpls_coef_perm_test count here too, k_sd_vip under 10 with
- * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci).
+ * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci),
+ * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

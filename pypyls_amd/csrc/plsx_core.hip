@@ -8,7 +8,7 @@ namespace plsxi {
 
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
-                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile"};
+                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -315,6 +315,51 @@ int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st)
     return 0;
 }
 
+// Non-rotated PLS, feature pass: s_l = || R_r^T v_l || of the nres resamples in the cross-product scratch -- where
+// run_gram + run_small(SMALL_PERM) stand.  Chunks of feature tiles: at least 32 tiles, at most 64 chunks -- a function
+// of B alone (the bits of a resample do not follow the batch size, the scratch budget or the team).
+int run_contrast_norms(plsx_ctx* ctx, int nres, double* out_sv, hipStream_t st)
+{
+    const int ntiles = ceil_div(ctx->B, 16);
+    const int tpc = std::max(32, round_up(ceil_div(ntiles, 64), 4));
+    const int nchunk = ceil_div(ntiles, tpc);
+    const int LTl = ceil_div(ctx->nc, 16);                    // tiles of L that hold a live contrast
+    if (int e = ensure(ctx, ctx->cpart, (size_t)nres * nchunk * ctx->L * 8)) return e;
+    KTimer tm(ctx, KC_CONTRAST, st);
+    for (int lt0 = 0; lt0 < LTl; lt0 += 4) {
+        const int ltc = std::min(4, LTl - lt0);
+        const size_t lds = (size_t)ctx->nks_t * ltc * 512;
+        const bool vlds = lds <= 64 * 1024;
+#define CN_ARGS ptr<double>(ctx->R), ctx->strideR, ctx->Bpad, ctx->nks_t, ptr<double>(ctx->Cfrag), ctx->LT, lt0, ctx->B, \
+                tpc, ctx->L, ptr<double>(ctx->cpart)
+#define CN_CASE(N) case N: \
+            if (vlds) { HIPCHK(set_lds((k_contrast_norms<N, true>), lds)); \
+                        hipLaunchKernelGGL((k_contrast_norms<N, true>), dim3(nchunk, nres), dim3(256), lds, st, CN_ARGS); } \
+            else hipLaunchKernelGGL((k_contrast_norms<N, false>), dim3(nchunk, nres), dim3(256), 0, st, CN_ARGS); \
+            break;
+        switch (ltc) { CN_CASE(1) CN_CASE(2) CN_CASE(3) default: CN_CASE(4) }
+#undef CN_CASE
+#undef CN_ARGS
+        LAUNCHCHK();
+    }
+    const long long count = (long long)nres * ctx->L;
+    hipLaunchKernelGGL(k_contrast_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
+                       ptr<double>(ctx->cpart), nchunk, nres, ctx->L, ctx->nc, out_sv);
+    LAUNCHCHK();
+    return 0;
+}
+
+// ... and V as the rotation operand of every resample of a batch -- where run_small(SMALL_BOOT / SMALL_DECOMP) stands.
+int run_contrast_fill(plsx_ctx* ctx, int nres, hipStream_t st)
+{
+    const int tot = ctx->nks_t * ctx->LT * 64;
+    KTimer tm(ctx, KC_CONTRAST, st);
+    hipLaunchKernelGGL(k_contrast_fill, dim3(ceil_div(tot, 256), nres), dim3(256), 0, st, ptr<double>(ctx->Cfrag), tot,
+                       ptr<double>(ctx->Mfrag));
+    LAUNCHCHK();
+    return 0;
+}
+
 bool quad_applicable(const plsx_ctx* ctx)
 {
     if (!ctx->has_orig) return false;
@@ -362,7 +407,8 @@ try {
                    &ctx->Xn, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
-                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot})
+                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
+                   &ctx->Cv, &ctx->Cfrag, &ctx->cpart})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     delete ctx;
@@ -479,6 +525,7 @@ try {
         return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
     }
     ctx->has_data = ctx->has_orig = false;
+    ctx->nc = 0;                                       // (a new binding is in SVD mode until plsx_set_contrasts)
     coef_close(ctx);                                   // (an open coefficient series ends with the binding it belonged to)
     vip_close(ctx);                                    // (... and so does a kept VIP stack)
     cperm_close(ctx);                                  // (... and an open permutation series of the coefficients)
@@ -643,6 +690,18 @@ try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     if (int e = run_xprod(ctx, nullptr, nullptr, 1, st)) return e;
+    if (ctx->nc > 0) {
+        // non-rotated: Z = R^T V, singvals = its column norms, x_weights = Z / singvals, y_weights = V
+        if (int e = run_contrast_fill(ctx, 1, st)) return e;
+        if (int e = run_urot(ctx, 1, nullptr, nullptr, d_xw, st)) return e;
+        if (int e = run_contrast_norms(ctx, 1, d_sv, st)) return e;
+        const long long count = (long long)ctx->B * ctx->L;
+        hipLaunchKernelGGL(k_contrast_scale, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, d_xw, count, ctx->L,
+                           d_sv);
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(d_yw, ctx->Cv.p, (size_t)ctx->Tp * ctx->L * 8, hipMemcpyDeviceToDevice, st));
+        return note_spectrum(ctx, d_sv, st);
+    }
     if (int e = run_gram(ctx, 1, false, st)) return e;
     SmallArgs a = small_args(ctx, SMALL_DECOMP);
     a.out_V = d_yw; a.out_d = d_sv;
@@ -660,6 +719,29 @@ try {
         LAUNCHCHK();
     }
     return note_spectrum(ctx, d_sv, st);
+} PLSX_CATCH(ctx)
+
+int plsx_set_contrasts(plsx_ctx* ctx, const double* d_C, int Lc, void* stream)
+try {
+    NEED_DATA();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->method == PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_set_contrasts: contrasts belong to behavioral and mean-centred PLS");
+    if (Lc < 0 || Lc > ctx->L) return fail(ctx, PLSX_ERR_ARG, "plsx_set_contrasts: Lc must lie in 0 .. min(T', B)");
+    // the original of the other mode is not this mode's: plsx_decompose / plsx_set_original follow
+    ctx->has_orig = false; ctx->quad_active = 0; ctx->graded = 0;
+    ctx->nc = 0;
+    if (Lc == 0 || !d_C) return PLSX_OK;
+    const int tot = ctx->nks_t * ctx->LT * 64;
+    if (int e = ensure(ctx, ctx->Cv, (size_t)ctx->Tp * ctx->L * 8)) return e;
+    if (int e = ensure(ctx, ctx->Cfrag, (size_t)tot * 8 + 1024)) return e;
+    hipLaunchKernelGGL(k_contrast_pack, dim3(ceil_div(std::max(ctx->Tp * ctx->L, tot), 256)), dim3(256), 0, st, d_C,
+                       ctx->Tp, Lc, ctx->L, ctx->nks_t, ctx->LT, ptr<double>(ctx->Cv), ptr<double>(ctx->Cfrag));
+    LAUNCHCHK();
+    HIPCHK(hipStreamSynchronize(st));                  // (the caller's d_C may go once this returns)
+    ctx->nc = Lc;
+    return PLSX_OK;
 } PLSX_CATCH(ctx)
 
 int plsx_project(plsx_ctx* ctx, const double* d_W, int L, double* d_out, void* stream)
@@ -801,6 +883,13 @@ int perm_dual(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ystack, 
             return e;
         // G_p = W_p A_p^T
         if (int e = run_dual_gp(ctx, m, Sd, nullptr, 0, st)) return e;
+        if (ctx->nc > 0) {
+            KTimer tm(ctx, KC_CONTRAST, st);
+            hipLaunchKernelGGL(k_contrast_quad, dim3(m), dim3(256), 0, st, ptr<double>(ctx->Gm), Tp, ptr<double>(ctx->Cv),
+                               ctx->L, ctx->nc, d_out_sv + (size_t)off * ctx->L);
+            LAUNCHCHK();
+            continue;
+        }
         SmallArgs a = small_args(ctx, SMALL_PERM);
         a.rotate = rotate ? 1 : 0;
         a.out_sv = d_out_sv + (size_t)off * ctx->L;
@@ -827,6 +916,10 @@ int perm_batch_impl(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ys
         if (ctx->fix) {
             if (int e = run_xprod_fixed(ctx, ys, m, st, yst)) return e;
         } else if (int e = run_xprod(ctx, xs, ys, m, st, false, yst)) return e;
+        if (ctx->nc > 0) {
+            if (int e = run_contrast_norms(ctx, m, d_out_sv + (size_t)off * ctx->L, st)) return e;
+            continue;
+        }
         if (int e = run_gram(ctx, m, false, st)) return e;
         SmallArgs a = small_args(ctx, SMALL_PERM);
         a.rotate = rotate ? 1 : 0;
@@ -956,8 +1049,12 @@ int boot_single_pass(plsx_ctx* ctx, const int32_t* d_boot_idx, int n, double* d_
                            nullptr, 0, 0, 0, S, 1, ptr<double>(ctx->Wd), 0, Sd, nullptr, 0, 0, st))
             return e;
         if (int e = run_dual_gp(ctx, m, Sd, ptr<double>(ctx->ScT), L, st)) return e;
-        SmallArgs a = small_args(ctx, SMALL_BOOT);
-        if (int e = run_small(ctx, a, m, st)) return e;
+        if (ctx->nc > 0) {
+            if (int e = run_contrast_fill(ctx, m, st)) return e;
+        } else {
+            SmallArgs a = small_args(ctx, SMALL_BOOT);
+            if (int e = run_small(ctx, a, m, st)) return e;
+        }
         // gen_distrib of a resample is its cross-product with the score columns: P_r itself
         HIPCHK(hipMemcpyAsync(d_distrib + (size_t)off * Tp * L, ctx->Pm.p, (size_t)m * Tp * L * 8,
                               hipMemcpyDeviceToDevice, st));
@@ -1043,10 +1140,14 @@ try {
         const int m = std::min(nb, n - off);
         const int* idx = d_boot_idx + (size_t)off * ctx->S;
         if (int e = run_xprod(ctx, idx, idx, m, st, false, nullptr, -1, true)) return e;
-        if (int e = run_gram(ctx, m, true, st)) return e;
         const double* R = ptr<double>(ctx->R);
-        SmallArgs a = small_args(ctx, SMALL_BOOT);
-        if (int e = run_small(ctx, a, m, st, R)) return e;
+        if (ctx->nc > 0) {
+            if (int e = run_contrast_fill(ctx, m, st)) return e;
+        } else {
+            if (int e = run_gram(ctx, m, true, st)) return e;
+            SmallArgs a = small_args(ctx, SMALL_BOOT);
+            if (int e = run_small(ctx, a, m, st, R)) return e;
+        }
         if (int e = run_urot(ctx, m, d_usum, d_usq, nullptr, st)) return e;
         dim3 g(ceil_div(ctx->Tp * ctx->L, 256), m);
         hipLaunchKernelGGL(k_gather_cols, g, dim3(256), 0, st, R, ctx->strideR, ctx->Bpad, ctx->B, ctx->Tp,

@@ -2,7 +2,7 @@
 // small host helpers and the prototypes of the launch layers.  Nothing here is part of the C ABI (include/plsx.h).
 //
 // Translation units (compiled in parallel by pypyls_amd/_build.py, one code object each):
-//   plsx_core.hip        context, plsx_set_data, options, timing, permutations, PLS-C bootstraps, finishing, generators
+//   plsx_core.hip        context, plsx_set_data, plsx_set_contrasts, options, timing, permutations, PLS-C bootstraps, finishing, generators
 //   plsx_xprod.hip       k_xprod launches (dense blocks, moment blocks, accumulating / quadratic-form epilogues)
 //   plsx_compact.hip     k_xprod_compact launches (one bootstrap / split per block)
 //   plsx_gram.hip        k_nt_gemm, k_dual_gp, k_gram4, k_gram, k_gram_lds
@@ -120,6 +120,10 @@ struct plsx_ctx {
     int split_blocks_l = 0, split_reader_l = 0;         // the last split-half pass, as plsx_last_timing [19] / [20] report it
     int has_sFt = 0, split_raw = 0;                     // split_raw: the last compact split pass left raw first-half sums (one slot per split)
     int has_cellS = 0;
+    // non-rotated PLS (plsx_set_contrasts): nc > 0 live contrasts; V dense (T' x L, zero padded), V in fragment order,
+    // the chunk partials of k_contrast_norms [nres][nchunk][L]
+    int nc = 0;
+    Buf Cv, Cfrag, cpart;
     int dual = 0, dual_ok = 0, has_Kd = 0;              // has_Kd: the S x S kernel of the bound data is current
     Buf okx, oky;                                       // regression: usable-row masks (NaN rows)
     Buf psum, psq;                                      // k_urot resample-split partials
@@ -257,7 +261,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_COUNT };
+       KC_CONTRAST, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -335,6 +339,9 @@ int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st);
 struct QuadSet { Buf* C; Buf* Vsum; const double* Vd; int L; };
 int quad_accumulate(plsx_ctx* ctx, int m, hipStream_t st, const QuadSet* qs = nullptr);
 bool quad_applicable(const plsx_ctx* ctx);
+// non-rotated PLS: out_sv[r][l] = || R_r^T v_l || of the nres resamples in the cross-product scratch; Mfrag[r] = V
+int run_contrast_norms(plsx_ctx* ctx, int nres, double* out_sv, hipStream_t st);
+int run_contrast_fill(plsx_ctx* ctx, int nres, hipStream_t st);
 // the two interpolated order statistics of nseries contiguous series of n values (plsx_percentile_ci's body)
 int run_percentile(plsx_ctx* ctx, const double* d_data, long long nseries, int n, int i_lo, double g_lo, int i_hi,
                    double g_hi, double* d_lo, double* d_hi, hipStream_t st);

@@ -248,6 +248,9 @@ try {
         return fail(ctx, PLSX_ERR_ARG, "plsx_split_half_batch: bad arguments");
     if (d_ystack && ctx->method != PLSX_BEHAVIORAL)
         return fail(ctx, PLSX_ERR_ARG, "plsx_split_half_batch_y: pre-permuted Y stacks need behavioral PLS");
+    if (ctx->nc > 0)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_split_half_batch: split-half resampling is not built for non-rotated PLS "
+                                               "(contrasts are set)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, Tp = ctx->Tp, L = ctx->L;
@@ -374,6 +377,9 @@ try {
     if (ctx->method != PLSX_BEHAVIORAL)
         return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_batch: cross-validation is defined for behavioral PLS");
     if (!d_masks || !d_r || !d_r2 || m < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_batch: bad arguments");
+    if (ctx->nc > 0)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_batch: cross-validation predicts from a fitted decomposition, "
+                                               "which non-rotated PLS (contrasts are set) does not have");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->momrows) return crossval_impl(ctx, d_masks, m, d_r, d_r2, st);

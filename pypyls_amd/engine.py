@@ -54,6 +54,7 @@ def _load():
         'plsx_crosscov_batch': ([vp, vp, vp, i32, vp, vp], i32),
         'plsx_decompose': ([vp, vp, vp, vp, vp], i32),
         'plsx_set_original': ([vp, vp, vp, vp, vp], i32),
+        'plsx_set_contrasts': ([vp, vp, i32, vp], i32),
         'plsx_project': ([vp, vp, i32, vp, vp], i32),
         'plsx_colmean': ([vp, vp, vp], i32),
         'plsx_perm_batch': ([vp, vp, i32, i32, vp, vp], i32),
@@ -130,7 +131,7 @@ def exported_symbols():
     lib = _load()
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
-             'plsx_crosscov_batch', 'plsx_decompose', 'plsx_set_original', 'plsx_project',
+             'plsx_crosscov_batch', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
              'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
@@ -442,6 +443,19 @@ class Engine(object):
                                             self._stream()))
         self.sync()
         return xw.cpu().numpy(), sv.cpu().numpy(), yw.cpu().numpy()
+
+    def set_contrasts(self, V=None):
+        """Non-rotated PLS (plsx_set_contrasts): V (T', Lc) with unit columns, after :meth:`set_data`; None returns
+        the context to SVD mode.  decompose / set_original follow; results keep L columns, those >= Lc are zero."""
+        if V is None:
+            self._check(self.lib.plsx_set_contrasts(self.ctx, None, 0, self._stream()))
+            return
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != self.Tp or not 1 <= V.shape[1] <= self.L:
+            raise ValueError('contrasts must have shape ({}, Lc) with 1 <= Lc <= {}; got {}'
+                             .format(self.Tp, self.L, V.shape))
+        d = self._dev(V, np.float64)
+        self._check(self.lib.plsx_set_contrasts(self.ctx, d.data_ptr(), int(V.shape[1]), self._stream()))
 
     def _as_dev(self, a):
         """numpy array or device tensor -> contiguous fp64 device tensor."""

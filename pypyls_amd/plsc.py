@@ -76,6 +76,34 @@ def _check_finite(A, name):
         raise ValueError('Input `{}` contains NaN, infinity or a value too large'.format(name))
 
 
+def _check_contrasts(contrasts, Tp, B, n_split):
+    """Non-rotated PLS: the caller's contrasts (T', Lc) -> V = normalize(contrasts), checked on the host before any
+    engine is created or looked up."""
+    C = np.asarray(contrasts)
+    if C.ndim != 2:
+        raise ValueError('Expected 2D array for `contrasts`, got {}D array instead'.format(C.ndim))
+    C = C.astype(np.float64)
+    if C.shape[0] != Tp:
+        raise ValueError('Provided `contrasts` must have one row per row of the cross-covariance matrix (groups x '
+                         'conditions, x behaviours for behavioral PLS).\n    EXPECTED: {}\n    ACTUAL:   {}'
+                         .format(Tp, C.shape[0]))
+    if not 1 <= C.shape[1] <= min(Tp, B):
+        raise ValueError('Provided `contrasts` must have between 1 and min(T\', B) = {} columns; got {}'
+                         .format(min(Tp, B), C.shape[1]))
+    if not np.all(np.isfinite(C)):
+        raise ValueError('Input `contrasts` contains NaN, infinity or a value too large')
+    norms = np.sqrt((C ** 2).sum(axis=0))
+    if np.any(norms == 0):
+        raise ValueError('Provided `contrasts` has a column of zeros (column {})'.format(int(np.argmin(norms != 0))))
+    if n_split:
+        raise ValueError('Split-half resampling (`n_split` > 0) is not available for non-rotated PLS (`contrasts`)')
+    V = C / norms
+    if np.abs(V.T @ V - np.eye(V.shape[1])).max() > 1e-8:
+        warnings.warn('Provided `contrasts` are not orthogonal: the effects are not independent and `varexp` is not '
+                      'a partition of the covariance.', stacklevel=4)
+    return V
+
+
 class _PLSCRun(object):
     """One analysis; the counterpart of BasePLS + subclass (pyls/base.py:232)."""
 
@@ -98,6 +126,17 @@ class _PLSCRun(object):
                              'samples. Provided matrices differed: X: {}, Y: {}'
                              .format(len(X), len(Y)))
         kwargs.setdefault('permindices', True)
+        # non-rotated PLS: V = normalize(contrasts) (T', Lc), or None
+        self.V = None
+        if kwargs.get('contrasts') is not None:
+            Xa, Ya = np.asarray(X), (None if Y is None else np.asarray(Y))
+            if Xa.ndim != 2 or (Ya is not None and Ya.ndim != 2):
+                raise ValueError('Expected 2D arrays for `X` and `Y`')
+            Tp = len(groups) * n_cond * (Ya.shape[1] if Ya is not None else 1)
+            self.V = _check_contrasts(kwargs['contrasts'], Tp, Xa.shape[1], kwargs.get('n_split'))
+            kwargs['contrasts'] = np.asarray(kwargs['contrasts'], dtype=np.float64)
+        else:
+            kwargs.pop('contrasts', None)
         # measurement hooks of bench.py --mode analysis (not inputs of the analysis): a dict that receives
         # per-phase wall times; (rank, world) of a world emulated on one GPU
         self.phases = kwargs.pop('_phases', None)
@@ -174,7 +213,8 @@ class _PLSCRun(object):
                 self.boot_stream = resampling.IndexStream.of_array(check_index_array(bootsamp, S))
                 self.boot_given = bootsamp
         if (self.method == 'behavioral' and inp.get('test_split') is not None
-                and (inp.get('test_size') or 0) > 0):
+                and (inp.get('test_size') or 0) > 0 and self.V is None):
+            # (non-rotated PLS: no fitted decomposition to predict from -- the masks came last, nothing else moves)
             # behavioral.py:219-221, 82-170
             self.cv_splits = inp.get('_cvsplits')
             if self.cv_splits is None:
@@ -275,12 +315,21 @@ class _PLSCRun(object):
             _check_finite(Y, 'Y')
 
         # ---- original decomposition (BasePLS.svd, base.py:362-364), signs and scores on the device -------
-        d_xw, d_sv, d_yw = eng.decompose_dev()
-        eng.svd_flip(d_xw, d_yw)
+        Lc = L                                         # columns of the results (non-rotated PLS: the contrasts')
+        if self.V is not None:
+            # non-rotated PLS: the contrasts stand where the SVD's y_weights stand; they fix the sign
+            eng.set_contrasts(self.V)
+            Lc = self.V.shape[1]
+            d_xw, d_sv, d_yw = eng.decompose_dev()
+        else:
+            d_xw, d_sv, d_yw = eng.decompose_dev()
+            eng.svd_flip(d_xw, d_yw)
         eng.set_original(d_xw, d_sv, d_yw)
         d_scores = eng.project_dev(d_xw)               # (X - mean) @ x_weights; the mean's share is added on the host
         sv = d_sv.cpu().numpy()
         yw = d_yw.cpu().numpy()
+        if Lc != L:
+            sv, yw = sv[:Lc].copy(), np.ascontiguousarray(yw[:, :Lc])
         tick('decompose')
         emulate = self.emulate                         # (rank, world) of an emulated run on one GPU (bench.py)
         if team is not None:
@@ -443,7 +492,7 @@ class _PLSCRun(object):
         if n_perm_tot > 0:
             blk = full[k].cpu().numpy().T                                             # (L or 3 L, n_perm)
             k += 1
-            d_perm = np.ascontiguousarray(blk[:L])
+            d_perm = np.ascontiguousarray(blk[:Lc])
             if orig_splits is not None:
                 ucorrs, vcorrs = np.ascontiguousarray(blk[L:2 * L]), np.ascontiguousarray(blk[2 * L:])
         h_bsr = h_se = h_dist = None
@@ -472,8 +521,11 @@ class _PLSCRun(object):
         eng.sync()
         tick('finish_and_d2h')
         xw = _host_array(h_xw)
+        scores = h_scores.numpy()
+        if Lc != L:
+            xw, scores = np.ascontiguousarray(xw[:, :Lc]), scores[:, :Lc]
         res['x_weights'], res['y_weights'] = xw, yw
-        res['x_scores'] = h_scores.numpy() + (xmean @ xw)[None, :]
+        res['x_scores'] = scores + (xmean @ xw)[None, :]
         if orig_splits is not None and d_perm is not None:
             uc, vc = eng.split_half(orig_splits)
             orig_uc, orig_vc = uc[0].mean(axis=-1), vc[0].mean(axis=-1)
@@ -494,7 +546,7 @@ class _PLSCRun(object):
 
         # ---- scores / loadings (subclass run_pls) --------------------------
         if self.method == 'behavioral':
-            y_scores = np.zeros((len(X), L))
+            y_scores = np.zeros((len(X), Lc))
             T = Y.shape[1]
             for c in range(self.n_cells):
                 m = self.cells == c
@@ -519,6 +571,9 @@ class _PLSCRun(object):
             else:                                       # more than 16384 bootstraps: numpy on the host copy
                 ci_arr = np.stack(hostmath.boot_ci(distrib, ci=inp.get('ci', 95)), -1)
             bsr, se = _host_array(h_bsr), _host_array(h_se)
+            if Lc != L:
+                distrib, ci_arr = np.ascontiguousarray(distrib[:, :Lc]), np.ascontiguousarray(ci_arr[:, :Lc])
+                bsr, se = np.ascontiguousarray(bsr[:, :Lc]), np.ascontiguousarray(se[:, :Lc])
             if self.method == 'behavioral':
                 res['bootres'].update(dict(
                     x_weights_normed=bsr, x_weights_stderr=se,
@@ -539,9 +594,19 @@ class _PLSCRun(object):
 def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_split=0,
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
-                   **kwargs):
+                   contrasts=None, **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
-    shard the resamples over (module docstring); ``device_ids=[...]`` names them."""
+    shard the resamples over (module docstring); ``device_ids=[...]`` names them.
+
+    ``contrasts`` (T', Lc), T' = groups x conditions x behaviours in the row order of ``y_weights`` (group, then
+    condition, then behaviour): non-rotated PLS.  The effects are the normalised columns of ``contrasts`` instead of
+    the singular vectors of the cross-covariance matrix R: ``y_weights = V = normalize(contrasts)``, ``singvals[l] =
+    ||R.T @ V[:, l]||``, ``x_weights`` the normalised ``R.T @ V``; permutations test each contrast (``rotate`` has no
+    meaning), bootstraps give the reliability of each contrast's weights, and every result has Lc columns.  The
+    cross-validation is not run (``cvres`` stays empty) and ``n_split`` > 0 raises.  A seeded call draws the same
+    resampling arrays as the call without contrasts."""
+    if contrasts is not None:
+        kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     run = _PLSCRun('behavioral', np.asarray(X), np.asarray(Y), groups=groups, n_cond=n_cond,
                    n_perm=n_perm, n_boot=n_boot, n_split=n_split, test_size=test_size,
                    test_split=test_split, covariance=covariance, rotate=rotate, ci=ci,
@@ -552,9 +617,14 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
 
 def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000, n_boot=5000,
                      n_split=0, rotate=True, ci=95, permsamples=None, bootsamples=None,
-                     seed=None, verbose=True, n_proc=None, **kwargs):
+                     seed=None, verbose=True, n_proc=None, contrasts=None, **kwargs):
     """Mean-centred PLS of X (S, B) sorted into groups x conditions; see
-    pyls.meancentered_pls (argument checks of pyls/types/meancentered.py:16-38)."""
+    pyls.meancentered_pls (argument checks of pyls/types/meancentered.py:16-38).
+
+    ``contrasts`` (T', Lc), T' = groups x conditions (group-major rows): non-rotated PLS, as for
+    :func:`behavioral_pls`; the bootstrap keeps the mean-centred conventions (no add-back of the original)."""
+    if contrasts is not None:
+        kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     X = np.asarray(X)
     if groups is None:
         if len(X) // n_cond != len(X) / n_cond:

@@ -96,6 +96,7 @@ class PLSInputs(KeyedRecord):
         'cv_perm',                          # pls_regression: permutations of the cross-validation (only when asked for)
         'coef_perm',                        # pls_regression: permutation p-values of its coefficients (only when asked for)
         'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
+        'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
     )
