@@ -636,6 +636,9 @@ int plsx_mfma_f64_peak(plsx_ctx* ctx, double* tflops);
  * compact blocks, one split each, with the fused epilogue 5 / the raw first-half
  * sums of epilogue 8; [20] the one-pass reader behind epilogue 8 -- 0 none, else
  * its waves per block (12 or 8), plus 100 with the wave kinds in runs of four.
+ * [21] 1 when the compact bootstrap blocks of the last launch formed the first
+ * moments of the features in their own padding rows (the moment-only blocks then
+ * contract X^2 alone), 0 on every other route.
  * Returns the number written. */
 int plsx_last_timing(const plsx_ctx* ctx, double* out, int cap);
 /* Scratch budget of the resampling super-batches (default 48 GB; the R block
@@ -691,7 +694,8 @@ int plsx_set_perm_path(plsx_ctx* ctx, int dual);
  *   any time: "no_refine" (graded spectra: skip the refinement on R), "two_pass_boot", "no_compact_boot",
  *     "compact_boot_always", "crosscov_sparse" (plsx_crosscov_batch treats its resamples as bootstraps: the compact
  *     blocks wherever plsx_boot_batch would take them, so that tests can read R of a compact launch),
- *     "sepmom_always", "no_split_fuse" (split halves: two passes), "split_two_readers"
+ *     "sepmom_always", "no_moment_rows" (compact bootstrap blocks: first moments from the moment-only blocks even
+ *     where the padding rows of a block could deliver them), "no_split_fuse" (split halves: two passes), "split_two_readers"
  *     (fused split blocks read by the Gram and the projection kernel instead of the one-pass reader),
  *     "split_reader8" (bit 0: the one-pass reader as the round-5 8-wave block whose matrix waves build the tiles
  *     themselves, instead of the 12-wave block with dedicated construction waves; bit 1: wave kinds in runs of

@@ -14,6 +14,8 @@ namespace plsxi {
 template <int MT, int KT, bool TAIL = false>
 int launch_xprod_cboot(plsx_ctx* ctx, int nres, int nks_c, SplitEpi se, hipStream_t st)
 {
+    // (moment rows only with the scales in registers: the LDS scale table of compact_lds_bytes is never theirs)
+    se.nmu = compact_moment_rows(ctx) ? ctx->Tp : 0;
     const size_t lds = compact_lds_bytes(MT, KT, 3, nks_c, se.npairs);
     HIPCHK(set_lds(k_xprod_compact<MT, KT, 3, TAIL>, lds));
     const int ncolblk = ceil_div(ctx->Bpad, 128);
@@ -21,7 +23,7 @@ int launch_xprod_cboot(plsx_ctx* ctx, int nres, int nks_c, SplitEpi se, hipStrea
     hipLaunchKernelGGL((k_xprod_compact<MT, KT, 3, TAIL>), dim3(round_up(ncolblk, 8) * round_up(nres, 8)), dim3(256),
                        lds, st, ptr<double>(ctx->Afrag_c), (size_t)nks_c * MT * 64, ptr<double>(ctx->Xc), ctx->Bpad, nks_c,
                        ptr<double>(ctx->R), ctx->Bpad, ctx->Tpp, ptr<int>(ctx->out_row_c), ptr<int>(ctx->mom_idx_c),
-                       (const double*)nullptr, nres, ncolblk, se);
+                       ptr<double>(ctx->momn_m), nres, ncolblk, se);
     LAUNCHCHK();
     return 0;
 }

@@ -1385,14 +1385,16 @@ try {
     const bool cmp = ctx->last_compact_n > 0;
     // [12..18]: the path of the last rotation / Gram launch (include/plsx.h); the tail flag rides on the variant
     const auto uvar = [&](int nks) { return (double)(nks > 0 && ctx->urot_tail_l ? nks + 100 : nks); };
-    double vals[21] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
+    // [21]: the compact blocks of the last launch formed the first moments in their padding rows (compact_moment_rows)
+    double vals[22] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
                        (double)(cmp ? ceil_div(ctx->Tp, 16) : (ctx->sepmom_used ? ctx->MTd : ctx->MT)),
                        (double)ctx->Gcap * ctx->npg, (double)ctx->timed_units, (double)use_dual(ctx), crows,
                        ctx->nt_flops, (double)ctx->quad_series, (double)ctx->quad_MT, (double)ctx->quad_gpl,
                        (double)ctx->urot_waves_l, (double)ctx->urot_splits_l, (double)ctx->urot_rps_l,
                        uvar(ctx->urot_nks_first), (double)ctx->gram_chunks_l, uvar(ctx->urot_nks_last),
-                       (double)ctx->gram_kind_l, (double)ctx->split_blocks_l, (double)ctx->split_reader_l};
-    int n = std::min(cap, 21);
+                       (double)ctx->gram_kind_l, (double)ctx->split_blocks_l, (double)ctx->split_reader_l,
+                       (double)(cmp && ctx->last_moment_rows ? 1 : 0)};
+    int n = std::min(cap, 22);
     for (int i = 0; i < n; ++i) out[i] = vals[i];
     return n;
 } PLSX_CATCH(const_cast<plsx_ctx*>(cctx))

@@ -91,7 +91,7 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
                                 double* __restrict__ mom_n, int nmom_pad, int dense_ld = 0,
                                 double* __restrict__ Amom = nullptr, size_t mom_stride = 0,
                                 const int* __restrict__ rank = nullptr, int mom_pairs = PLSX_MOM_PAIRS,
-                                int chain_cap = 0)
+                                int chain_cap = 0, int mom_row0 = -1)
 {
     // chain_cap: how duplicates of a source row inside a cell (bootstraps) are added up.  > 0: that many ints of
     // dynamic LDS behind the 2 T doubles hold, per position of the cell, the NEXT position with the same source row
@@ -107,6 +107,9 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
     // q = r * J + j go to group q / PLSX_MOM_PAIRS of Amom -- moment-only blocks of 24 tiles, rows
     // [0, 192) against X and rows [192, 384) against X^2 -- instead of riding in the data group;
     // mom_n is then indexed by the pair.
+    // mom_row0 >= 0 (compact layout only): the multiplicities of cell j go into row mom_row0 + j of the resample's OWN
+    // block, at the rank -- a padding row of its last tile, whose accumulators then deliver m1 -- and Amom holds
+    // second-moment rows only: mom_pairs = 16 pairs per tile of a block that runs every tile against X^2.
     // dense_ld != 0: write plain row-major (T' x dense_ld) matrices, one per
     // resample, instead of k_xprod's fragment order (dual permutation path)
     extern __shared__ double sm_b[];
@@ -231,12 +234,15 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
     } else if (scaled && Amom) {
         const int pair = r * lay.J + j;
         double* Am = Amom + (size_t)(pair / mom_pairs) * mom_stride;
-        const int mrow = pair % mom_pairs, mmt = mom_pairs / 8;
+        const int mrow = pair % mom_pairs, mmt = mom_row0 >= 0 ? mom_pairs / 16 : mom_pairs / 8;
         for (int pl = tid; pl < len; pl += blockDim.x) {
             int p = start + pl;
             int xi = xs ? xs[p] : p;
             if (xi < 0) continue;
-            put_weight(Am + afrag_off(mrow, xi, mmt), Am + afrag_off(mom_pairs + mrow, xi, mmt), pl);
+            if (mom_row0 >= 0)
+                put_weight(A + afrag_off(mom_row0 + j, rank[(size_t)r * S + xi], lay.MT), Am + afrag_off(mrow, xi, mmt), pl);
+            else
+                put_weight(Am + afrag_off(mrow, xi, mmt), Am + afrag_off(mom_pairs + mrow, xi, mmt), pl);
         }
         if (tid == 0) mom_n[pair] = (double)cnt;
     } else if (scaled) {
@@ -436,7 +442,8 @@ struct SplitEpi {
     const int* cell_len;     // [J]
     const double* rowc;      // [groups][MT*16][5]: Sy1, 1/((n1-1) sy1), Sy2, 1/((n2-1) sy2), (nF-1) syF
     int J, Tpp;
-    int nmu;                 // moment rows in use (splits per group x cells)
+    int nmu;                 // moment rows in use (splits per group x cells); compact bootstrap blocks (k_xprod_compact,
+                             // EPI 3): T' when rows T' + j of a block hold the cells' multiplicities (the table is raw m2), else 0
     int off_pre;             // > 0: doubles offset of the LDS region that receives this block's tile of
                              // Rfull ([Tpp][64]) and its row constants by DMA at kernel start
     // EPI == 2 (accumulating epilogue, see k_xprod): per-group partial sums [group][B][L]

@@ -79,6 +79,9 @@ __device__ __forceinline__ double load_x_buf(const double* rowbase, int voff)
 #define PLSX_ACC_PITCH 80        // LDS pitch of an l-row (64 columns + 16: rows l, l+1 of one MFMA register land in different banks)
 // 6 = moment-only block writing the raw moments m1, m2 (se.scale, se.scale2) -- the first-half feature moments
 //     of the compact fused split-half blocks (k_xprod_compact, EPI 5 there).
+// 9 = second-moment-only block (NSQ == MT: every tile against X^2) writing the RAW m2 of its 16 MT pairs into the
+//     table that holds 1 / std on the other routes (se.scale): the compact bootstrap blocks whose padding rows deliver
+//     m1 (k_xprod_compact, EPI 3 with se.nmu > 0) form 1 / std from the two themselves.
 template <int MT, int NW, int KT, int NSQ, int EPI = 0>
 __global__ __launch_bounds__(NW * 64, 2)
 void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
@@ -225,7 +228,20 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
     // [W0, SQ0), second-moment tiles [SQ0, MT).  Lane (kq, c) reg i of weight
     // tile W0+j holds m1 of moment row j*16 + kq + 4*i and the same lane / reg
     // of tile SQ0+j holds m2 of that row.  The A stages are dead: reuse LDS.
-    constexpr int W0 = MT - 2 * NSQ, SQ0 = MT - NSQ, NMOM = NSQ * 16;
+    constexpr int W0 = (EPI == 9) ? 0 : MT - 2 * NSQ, SQ0 = MT - NSQ, NMOM = NSQ * 16;
+    if constexpr (EPI == 9) {
+        // second-moment-only block: tile j holds the raw m2 of pairs j * 16 .. + 15
+        static_assert(MT == NSQ, "EPI 9 runs every tile against X^2");
+#pragma unroll
+        for (int j = 0; j < MT; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int pair = grp * (MT * 16) + j * 16 + kq + 4 * i;
+                if (pair >= se.npairs || col >= ldr) continue;
+                se.scale[(size_t)pair * ldr + col] = acc[j][i];
+            }
+        return;
+    }
     if constexpr (EPI == 6) {
         // moment-only block writing the RAW first / second moments of its pairs (compact split-half)
         static_assert(MT == 2 * NSQ, "EPI 6 is a moment-only instantiation");
@@ -511,7 +527,9 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
 // (measured: 11.9 GB fetched per 100 splits against 40 GB of row segments requested).
 // The feature moments come from moment-only blocks of k_xprod (EPI 4 / 6) over all (resample, cell) pairs.
 // EPI 3: R = (A . X) scaled by the 1 / std table (bootstraps; se.scale, se.npairs = cells, se.accB); MT up to 13
-//        tiles (T' <= 208) at 3 or 2 waves per SIMD.
+//        tiles (T' <= 208) at 3 or 2 waves per SIMD.  With se.nmu = T' (moment rows, compact_moment_rows) the block's
+//        padding rows T' + j carry the cells' multiplicities: the first moments come out of its own accumulators, the
+//        table holds the raw second moments (k_xprod EPI 9) and 1 / std is formed after the loop.
 // EPI 5: fused split-half (both halves from the first half's raw sums and the arrangement's full-sample R:
 //        se.Rfull, se.rowc, se.scale / scale2 = raw first-half moments, se.cellS1 / S2, se.cell_len).
 // EPI 8: the raw first-half sums of one split per block (the one-pass reader k_split_fused rebuilds both halves).
@@ -545,10 +563,12 @@ __host__ __device__ constexpr size_t compact_lds_bytes(int MT, int KT, int EPI, 
     return EPI == 5 && epi5 > loop ? epi5 : loop;
 }
 
-// waves per SIMD the register allocation is held to: what each variant runs at (epilogue 3: 5 at four tiles with the
-// tail -- the headline --, 4 up to six tiles, 3 up to nine and at ten with the tail, 2 beyond)
+// waves per SIMD the register allocation is held to: what each variant runs at (epilogue 3: 7 / 6 at two tiles with /
+// without the tail, 5 at four tiles with the tail -- the headline --, 4 otherwise up to six tiles, 3 up to nine and at
+// ten with the tail, 2 beyond)
 __host__ __device__ constexpr int compact_waves(int MT, int EPI, bool TAIL)
 {
+    if (EPI == 3 && MT == 2) return TAIL ? 7 : 6;            // (72 / 80 registers: where they stood before they had moment rows to read)
     if (EPI == 3) return MT > 10 ? 2 : MT == 10 ? (TAIL ? 3 : 2) : MT > 6 ? 3 : MT > 4 ? 4 : (MT == 4 && TAIL) ? 5 : 4;
     return (EPI == 5 && MT == 4 && !TAIL) ? 3 : 4;
 }
@@ -593,6 +613,11 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
     const int J3 = se.npairs;                                 // (epilogue 3: cells)
     double* sW = reinterpret_cast<double*>(s_tab + nks * 4) + swave * (J3 * 32);   // [J3][32]: 1 / std, this wave's columns
     d2 scr[NSCR];                                             // ... or per cell in registers
+    // Epilogue 3 with se.nmu = T' > 0 (moment rows): row T' + j of the block -- a padding row of its last tile -- holds the
+    // multiplicities of cell j's drawn rows, so the accumulators of that row are m1 = sum w x of the block's columns;
+    // the table holds the raw m2 (k_xprod EPI 9) and the epilogue forms 1 / std from the two and the cell's count.
+    const int mrow0 = (EPI == 3) ? se.nmu : 0;
+    int cnt_lo[NSCR], cnt_hi[NSCR];                           // draws inside cell j, a double in two scalar registers
     {   // ---- prologue and main loop (a scope of their own: the epilogue declares its lane constants again) ------
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kq = lane >> 4;
@@ -710,9 +735,18 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
     // LDS area of its own -- read back by that wave alone, so its wait for the copy is all the ordering it needs.
     auto last = [&](int cur, const d2 (&xc)[KT]) {
 #pragma unroll
-        for (int j = 0; j < NSCR; ++j) scr[j] = (d2){1.0, 1.0};
+        for (int j = 0; j < NSCR; ++j) { scr[j] = (d2){1.0, 1.0}; cnt_lo[j] = 0; cnt_hi[j] = 0; }
         if constexpr (EPI == 3) {
             if (J3 <= NSCR) {
+                if (mrow0 > 0) {
+#pragma unroll
+                    for (int j = 0; j < NSCR; ++j)
+                        if (j < J3) {
+                            const double v = mom_n[(size_t)grp * J3 + j];
+                            cnt_lo[j] = __builtin_amdgcn_readfirstlane(__double2loint(v));
+                            cnt_hi[j] = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+                        }
+                }
 #pragma unroll
                 for (int j = 0; j < NSCR; ++j)
                     if (j < J3)                                // (lcol8: the loop's own register, not lcol kept beside it)
@@ -746,6 +780,45 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
         }
         last(cur, xa);
     }
+    }
+
+    // ---- moment rows (epilogue 3): 1 / std from the block's own first moments ------------------------------------
+    // scr[j] holds m2 of the lane's two columns; m1 sits in the last tile's accumulators of row r = T' + j: register
+    // (r % 16) / 4 of lane 16 (r % 4) + column (the tail tile has register 0 only).  var and 1 / std as epilogue 4 of
+    // k_xprod forms them.  The four lanes that share a column pair would all form the same two values: the lanes of
+    // the even 16-lane rows form the first column's, those of the odd rows the second's, and neighbouring rows swap --
+    // ONE chain of two divisions and a square root per cell instead of two (vector fp64 work takes issue slots from
+    // the other waves' MFMAs), and few enough temporaries next to the accumulators: with both chains in flight
+    // <10,1,3,true> spilled.  The step stands before the epilogue's lane constants exist, for the same reason; every
+    // wave runs it, live columns or not.
+    if constexpr (EPI == 3) {
+        if (mrow0 > 0 && J3 <= NSCR) {
+            const int ln = __lane_id();
+            const bool second = (ln & 16) != 0;
+#pragma unroll
+            for (int j = 0; j < NSCR; ++j) {
+                if (j >= J3) continue;
+                const int r = mrow0 + j;
+                double a0, a1;
+                if constexpr (TAIL) { a0 = tl0; a1 = tl1; }
+                else {
+                    const int ri = (r & 15) >> 2;
+                    a0 = acc0[MT - 1][0]; a1 = acc1[MT - 1][0];
+#pragma unroll
+                    for (int q = 1; q < 4; ++q)
+                        if (ri == q) { a0 = acc0[MT - 1][q]; a1 = acc1[MT - 1][q]; }
+                }
+                const int src = ((r & 3) << 4) | (ln & 15);
+                const double nn = __hiloint2double(cnt_hi[j], cnt_lo[j]);
+                const double m1x = __shfl(a0, src), m1y = __shfl(a1, src);
+                const double m1 = second ? m1y : m1x, m2 = second ? scr[j].y : scr[j].x;
+                const double var = (m2 - m1 * m1 / nn) / (nn - 1.0);
+                double sc = (var > 0.0) ? sd_rsqrt(var) : 0.0;
+                asm volatile("" : "+v"(sc));
+                const double other = __shfl_xor(sc, 16);
+                scr[j] = second ? (d2){other, sc} : (d2){sc, other};
+            }
+        }
     }
 
     // ---- epilogue: stores -----------------------------------------------------------------------------------------

@@ -89,15 +89,16 @@ int launch_xprod_acc(plsx_ctx* ctx, const double* Afrag, size_t gstride, int gro
 // stage that does not divide nks would drop k-steps without a word).
 static int stage_ksteps(int nks) { return nks % 3 == 0 ? 3 : (nks % 2 == 0 ? 2 : 1); }
 
-// Moment-only blocks (MT / 2 weight tiles against X, the same against X^2; EPI 4 or 6) over `groups` groups of the
+// Moment-only blocks (MT / 2 weight tiles against X, the same against X^2; EPI 4 or 6 -- or MT tiles against X^2, EPI 9) over `groups` groups of the
 // operand Afrag_m, `stride` doubles apart.  The caller holds the timer.
 template <int MT, int NW, int KT, int EPI>
 int launch_moments_t(plsx_ctx* ctx, size_t stride, int groups, SplitEpi se, hipStream_t st)
 {
+    constexpr int NSQ = (EPI == 9) ? MT : MT / 2;       // (EPI 9: every tile against X^2)
     const size_t lds = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
-    HIPCHK(set_lds(k_xprod<MT, NW, KT, MT / 2, EPI>, lds));
+    HIPCHK(set_lds(k_xprod<MT, NW, KT, NSQ, EPI>, lds));
     const int ncolblk = ceil_div(ctx->Bpad, NW * 16);
-    hipLaunchKernelGGL((k_xprod<MT, NW, KT, MT / 2, EPI>), dim3(ncolblk * round_up(groups, 8)), dim3(NW * 64), lds, st,
+    hipLaunchKernelGGL((k_xprod<MT, NW, KT, NSQ, EPI>), dim3(ncolblk * round_up(groups, 8)), dim3(NW * 64), lds, st,
                        ptr<double>(ctx->Afrag_m), stride, ptr<double>(ctx->Xc), ctx->Bpad, ctx->nks,
                        (double*)nullptr, ctx->Bpad, 0, (const int*)nullptr, (const int*)nullptr,
                        ptr<double>(ctx->momn_m), 0, groups, ncolblk, (double*)nullptr, se, 1);
@@ -110,7 +111,7 @@ int launch_moments(plsx_ctx* ctx, size_t stride, int groups, SplitEpi se, hipStr
 {
     // The raw-moment blocks of the split-half passes (EPI 6, 4 waves) stay at one k-step per stage: at three the
     // 24-tile instantiation spills and the 16-tile one loses its third resident block (170 VGPRs).
-    if constexpr (EPI == 4) {
+    if constexpr (EPI == 4 || EPI == 9) {
         const int kt = stage_ksteps(ctx->nks);
         if (kt == 3) return launch_moments_t<MT, NW, 3, EPI>(ctx, stride, groups, se, st);
         if (kt == 2) return launch_moments_t<MT, NW, 2, EPI>(ctx, stride, groups, se, st);
@@ -242,11 +243,27 @@ MomLayout moment_layout(const plsx_ctx* ctx, int npairs)
     return m;
 }
 
-// EPI 4 (1 / std table) or EPI 6 (raw m1, m2) over the layout above; 8-wave blocks for the single table.
+// The X^2-only blocks (EPI 9: every tile holds the second-moment rows of 16 pairs) of a launch whose first moments
+// come out of the compact blocks' padding rows: 384 pairs per block (24 tiles) or 256 (16 tiles), chosen as above --
+// the 16-tile blocks when they issue fewer tiles by a sixth or more.  Up to 256 pairs: one 16-tile block; 257 .. 384:
+// one 24-tile block; 385 .. 512: two 16-tile blocks, the second partly empty (504 pairs: 32 tile passes for 72).
+MomLayout moment2_layout(const plsx_ctx* ctx, int npairs)
+{
+    const int t384 = ceil_div(npairs, 384) * 24, t256 = ceil_div(npairs, 256) * 16;
+    MomLayout m;
+    m.pairs = (t256 * 6 < t384 * 5) ? 256 : 384;
+    m.mt = m.pairs / 16;
+    m.groups = ceil_div(npairs, m.pairs);
+    m.stride = (size_t)ctx->nks * m.mt * 64;
+    return m;
+}
+
+// EPI 4 (1 / std table), EPI 6 (raw m1, m2) or EPI 9 (raw m2, layout of moment2_layout) over the layout above; 8-wave
+// blocks for the single table.
 template <int EPI>
 int launch_moment_blocks(plsx_ctx* ctx, const MomLayout& ml, SplitEpi se, hipStream_t st)
 {
-    constexpr int NW = (EPI == 4) ? 8 : 4;
+    constexpr int NW = (EPI == 6) ? 4 : 8;
     KTimer tm(ctx, KC_MOM, st);
     if (ml.mt == 24) return launch_moments<24, NW, EPI>(ctx, ml.stride, ml.groups, se, st);
     return launch_moments<16, NW, EPI>(ctx, ml.stride, ml.groups, se, st);
@@ -296,13 +313,33 @@ bool compact_boot_ok(const plsx_ctx* ctx)
     return cost_c * 1.1 < (double)mt_dense / npg_dense && npg_dense <= 16;
 }
 
+// k-steps per LDS stage of the compact bootstrap blocks of mt tiles (two column tiles per wave; launch_cboot compiles
+// the same values in)
+int compact_boot_ksteps(int mt) { return mt == 4 ? PLSX_CKT : std::max(1, 12 / mt); }
+
+// Moment rows: a compact bootstrap block issues whole tiles -- 16 mt rows, or 16 (mt - 1) + 4 when its last tile runs
+// on the 4x4x4 shape -- and the rows beyond T' are zero rows of its A operand.  With the multiplicities of cell j's
+// drawn rows in row T' + j the block's own accumulators deliver m1 = sum w x, the moment-only blocks contract X^2
+// alone (k_xprod EPI 9) and the compact epilogue forms 1 / std from the two.  That needs one padding row per cell and
+// the scales of the cells in the lane's registers (compact_scale_regs); every other launch keeps the 1 / std table of
+// the 12 + 12 / 8 + 8 blocks.  run_xprod_cboot and launch_cboot (plsx_compact.hip) both ask here.
+bool compact_moment_rows(const plsx_ctx* ctx)
+{
+    if (ctx->opt[OPT_NO_MOMENT_ROWS]) return false;
+    const int mt = ceil_div(ctx->Tp, 16);
+    const bool tail = mt >= 2 && ctx->Tp - (mt - 1) * 16 <= 4;
+    const int rows = tail ? (mt - 1) * 16 + 4 : mt * 16;
+    return ctx->J <= compact_scale_regs(compact_boot_ksteps(mt)) && rows - ctx->Tp >= ctx->J;
+}
+
 int run_xprod_cboot(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, hipStream_t st,
                     const double* ystack, long long ystride)
 {
-    const int S = ctx->S, J = ctx->J, MTc = ceil_div(ctx->Tp, 16), KT = MTc == 4 ? PLSX_CKT : std::max(1, 12 / MTc);      // (two column tiles per wave)
+    const int S = ctx->S, J = ctx->J, MTc = ceil_div(ctx->Tp, 16), KT = compact_boot_ksteps(MTc);
     const int nks_c = round_up(ceil_div(S, 4), KT);
     const int npairs = nres * J;
-    const MomLayout ml = moment_layout(ctx, npairs);
+    const bool mrows = compact_moment_rows(ctx);
+    const MomLayout ml = mrows ? moment2_layout(ctx, npairs) : moment_layout(ctx, npairs);
     const int groups_m = ml.groups;
     const size_t astride = (size_t)nks_c * MTc * 64, mstride = ml.stride;
     if (int e = ensure_compact_maps(ctx)) return e;
@@ -311,13 +348,13 @@ int run_xprod_cboot(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, h
     if (int e = ensure(ctx, ctx->rank_c, (size_t)nres * S * sizeof(int))) return e;
     if (int e = ensure(ctx, ctx->rowtab_c, ((size_t)nres * nks_c * 4 + nres) * sizeof(int))) return e;
     if (int e = ensure(ctx, ctx->Afrag_m, (size_t)groups_m * mstride * 8 + 4096)) return e;
-    if (int e = ensure(ctx, ctx->momn_m, (size_t)round_up(npairs, 192) * 8)) return e;
+    if (int e = ensure(ctx, ctx->momn_m, (size_t)round_up(npairs, 384) * 8)) return e;
     if (int e = ensure(ctx, ctx->scale, (size_t)round_up(npairs, 8) * ctx->Bpad * 8)) return e;
     HIPCHK(hipMemsetAsync(ctx->Afrag_c.p, 0, (size_t)nres * astride * 8, st));
     HIPCHK(hipMemsetAsync(ctx->Afrag_m.p, 0, (size_t)groups_m * mstride * 8, st));
     HIPCHK(hipMemsetAsync(ctx->mask_c.p, 0, (size_t)nres * S, st));
     int* row_cnt = ptr<int>(ctx->rowtab_c) + (size_t)nres * nks_c * 4;
-    ctx->last_compact_n = nres; ctx->last_compact_ktot = nks_c * 4;
+    ctx->last_compact_n = nres; ctx->last_compact_ktot = nks_c * 4; ctx->last_moment_rows = mrows ? 1 : 0;
     {
         KTimer tm(ctx, KC_BUILD, st);
         hipLaunchKernelGGL(k_drawn_mask, dim3(ceil_div(S, 256), nres), dim3(256), 0, st, xsrc, S, ptr<uint8_t>(ctx->mask_c));
@@ -333,14 +370,14 @@ int run_xprod_cboot(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, h
                            ystack ? ystack : ptr<double>(ctx->Y), ystack ? ystride : 0LL, ctx->T, S,
                            ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), xsrc, ysrc, lay, ctx->cov, 1,
                            ptr<double>(ctx->Afrag_c), astride, ptr<double>(ctx->momn_m), 0, 0,
-                           ptr<double>(ctx->Afrag_m), mstride, ptr<int>(ctx->rank_c), ml.pairs, cap);
+                           ptr<double>(ctx->Afrag_m), mstride, ptr<int>(ctx->rank_c), ml.pairs, cap, mrows ? ctx->Tp : -1);
         LAUNCHCHK();
     }
     SplitEpi se;
     memset(&se, 0, sizeof(se));
     se.scale = ptr<double>(ctx->scale);
     se.npairs = npairs;
-    if (int e = launch_moment_blocks<4>(ctx, ml, se, st)) return e;
+    if (int e = mrows ? launch_moment_blocks<9>(ctx, ml, se, st) : launch_moment_blocks<4>(ctx, ml, se, st)) return e;
     se.npairs = J;
     se.accB = nres * ctx->Tpp;
     se.row_tab = ptr<int>(ctx->rowtab_c);

@@ -1037,13 +1037,15 @@ class Engine(object):
     def last_timing(self):
         """include/plsx.h, plsx_last_timing.  ``urot_waves`` .. ``gram_kernel`` say how the last rotation (k_urot) and Gram pass
         were launched, ``split_blocks`` / ``split_reader`` how the last split-half pass ran; they are recorded whether or
-        not timing is on."""
-        buf = (ctypes.c_double * 21)()
-        n = self.lib.plsx_last_timing(self.ctx, buf, 21)
+        not timing is on.  ``moment_rows``: 1 when the compact bootstrap blocks of the last launch formed the first
+        moments of the features in their padding rows (option ``no_moment_rows`` forces 0)."""
+        buf = (ctypes.c_double * 22)()
+        n = self.lib.plsx_last_timing(self.ctx, buf, 22)
         keys = ['xprod_ms', 'xprod_launches', 'resamples_per_group', 'm_tiles', 'superbatch',
                 'xprod_resamples', 'dual_perm', 'compact_row_fraction', 'nt_flops', 'quad_series', 'quad_m_tiles',
                 'quad_blocks_per_lv', 'urot_waves', 'urot_splits', 'urot_res_per_split', 'urot_variant',
-                'gram_chunks', 'urot_variant_last', 'gram_kernel', 'split_blocks', 'split_reader']
+                'gram_chunks', 'urot_variant_last', 'gram_kernel', 'split_blocks', 'split_reader',
+                'moment_rows']
         return {k: buf[i] for i, k in enumerate(keys[:max(n, 0)])}
 
 
