@@ -43,8 +43,19 @@ enum plsx_status {
 enum plsx_method {
     PLSX_BEHAVIORAL = 0,     /* pyls/types/behavioral.py  (R = stacked per-cell xcorr)   */
     PLSX_MEANCENTERED = 1,   /* pyls/types/meancentered.py (R = cell means - ref. mean)  */
-    PLSX_REGRESSION = 2      /* pyls/types/regression.py (SIMPLS); plsx_set_data takes
+    PLSX_REGRESSION = 2,     /* pyls/types/regression.py (SIMPLS); plsx_set_data takes
                                 globally centred X / Y, n_groups = 1 and n_cond = n_components */
+    PLSX_MULTIBLOCK = 3      /* task and behaviour blocks in one decomposition (no pyls counterpart; the Matlab
+                                toolbox's method 4 in structure): R = [rownorm(R_meancentered); rownorm(R_behavioral)],
+                                T' = J + J T rows -- the J task rows (group-major, then condition), then the behaviour
+                                rows (group, condition, behaviour); rownorm divides a row by its L2 norm over the B
+                                features (a zero row stays zero).  Needs d_Y; takes n_groups, n_cond, mean_centering and
+                                PLSX_FLAG_COVARIANCE.  One resample with the moment rows of its cells must fit one
+                                24-tile cross-product block (ceil(T'/16) + 2 ceil(J/16) <= 24; PLSX_ERR_UNSUPPORTED
+                                otherwise).  plsx_crosscov_batch / plsx_perm_batch: an index array given as d_ysrc alone
+                                (a permutation) also places the rows of X into the cells of the task block; d_xsrc, when
+                                given, does that (bootstraps: both).  plsx_set_contrasts, plsx_split_half_batch[_y],
+                                plsx_crossval_batch and plsx_perm_batch_y: not built (PLSX_ERR_UNSUPPORTED / _ARG) */
 };
 
 /* flags for plsx_set_data */
@@ -55,7 +66,8 @@ int plsx_version(void);
 
 /* Largest stacked-Y dimension T' = J*T of behavioral PLS (rows of one resample;
  * above 352 they are sliced over several cross-product blocks).  Mean-centred
- * PLS (T' = J cells) and SIMPLS (T' = n_components) are limited to 352. */
+ * PLS (T' = J cells) and SIMPLS (T' = n_components) are limited to 352; multiblock
+ * PLS (T' = J + J*T) to one 24-tile block: ceil(T'/16) + 2 ceil(J/16) <= 24. */
 int plsx_max_tprime(void);
 
 /* Create / destroy the per-GPU context (streams, scratch).               */
@@ -68,11 +80,12 @@ int plsx_sync(plsx_ctx* ctx);
  * Bind the data set.  Replaces what BasePLS.__init__ stores in self.inputs /
  * self.dummy (pyls/base.py:254-283).
  *   d_X          (S, B) fp64
- *   d_Y          (S, T) fp64, NULL for PLSX_MEANCENTERED
+ *   d_Y          (S, T) fp64, NULL for PLSX_MEANCENTERED (required for PLSX_MULTIBLOCK)
  *   d_cell_of_row (S,) int32, cell index in [0, J): group-major then condition
  *                (pyls/utils.py:178-197)
  *   n_groups * n_cond == J
- *   mean_centering in {0,1,2} (pyls/compute.py:267-317), ignored for behavioral
+ *   mean_centering in {0,1,2} (pyls/compute.py:267-317), ignored for behavioral;
+ *                the task block of PLSX_MULTIBLOCK uses it
  * The library keeps its own centred, padded copy; the caller may release d_X /
  * d_Y afterwards.
  * PLSX_REGRESSION also forms K = X0 X0^T (S x S doubles) here and refuses
@@ -104,6 +117,14 @@ int plsx_tprime(const plsx_ctx* ctx);
  */
 int plsx_crosscov_batch(plsx_ctx* ctx, const int32_t* d_xsrc, const int32_t* d_ysrc,
                         int n, double* d_R, void* stream);
+
+/*
+ * Test / inspection hook: rows [row0, row0 + nrows) of slot `slot` of the cross-product scratch as the last batch
+ * left them, at their full pitch -- d_out (nrows, Bpad) fp64 with Bpad = (B + L) rounded up to 128: the B features,
+ * the L score columns of gen_distrib, zero padding.  A slot has T' rounded up to 4 rows; those >= T' read zero.
+ * PLSX_ERR_ARG for rows or a slot the scratch does not hold (it is mapped by the first batch after plsx_set_data).
+ */
+int plsx_scratch_read(plsx_ctx* ctx, int slot, int row0, int nrows, double* d_out, void* stream);
 
 /*
  * Decomposition of the un-resampled data -- BasePLS.svd (pyls/base.py:401-437
@@ -665,7 +686,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
  * k_col_sd of plsx_simpls_coef_perm_test count here too, k_sd_vip under 10 with
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci),
- * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill).
+ * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill),
+ * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

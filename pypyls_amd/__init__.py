@@ -14,7 +14,7 @@ from .structures import (PLSInputs, PLSResults, PLSBootResults, PLSPermResults, 
                          PLSSplitHalfResults, PLSCrossValidationResults)
 from .resampling import (gen_permsamp, gen_bootsamp, gen_splits, dummy_code,  # noqa: F401
                          dummy_label, permute_cols)
-from .plsc import behavioral_pls, meancentered_pls  # noqa: F401
+from .plsc import behavioral_pls, meancentered_pls, multiblock_pls  # noqa: F401
 from .regression import pls_regression, predict, vip  # noqa: F401
 from .matlab_io import import_matlab_result  # noqa: F401
 from .io import save_results, load_results  # noqa: F401

@@ -8,16 +8,18 @@ namespace plsxi {
 
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
-                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast"};
+                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
 int plan_groups(plsx_ctx* c)
 {
-    c->scaled = (c->method == PLSX_BEHAVIORAL && !c->cov) ? 1 : 0;   // mean-centred / regression: no feature scaling
+    // mean-centred / regression: no feature scaling; multiblock: its behaviour rows (mom_idx >= 0, upload_rowmaps)
+    const bool mb = c->method == PLSX_MULTIBLOCK;
+    c->scaled = ((c->method == PLSX_BEHAVIORAL || mb) && !c->cov) ? 1 : 0;
     // covariance mode scales nothing: its moment rows only serve cross-validation's zmap and are
     // planned in for the duration of plsx_crossval_batch (cv_mom), not for permutations / bootstraps
-    c->momrows = (c->method == PLSX_BEHAVIORAL && (!c->cov || c->cv_mom)) ? 1 : 0;
+    c->momrows = ((c->method == PLSX_BEHAVIORAL && (!c->cov || c->cv_mom)) || (mb && !c->cov)) ? 1 : 0;
     const int Jw = c->momrows ? c->J : 0;
     c->gps = 0;
     c->h_slice_row0.clear(); c->h_slice_rows.clear(); c->h_slice_cell0.clear(); c->h_slice_ncell.clear();
@@ -38,6 +40,7 @@ int plan_groups(plsx_ctx* c)
         if (b16 >= 1 && (double)b16 / 16.0 > 1.15 * (double)best / 24.0) { c->MT = 16; best = b16; }
     }
     int tw = Jw ? ceil_div(std::max(best, 1) * Jw, 16) : 0;
+    if (best == 0 && mb) return -1;                     // (plain layout only: plsx_set_data refuses the shape by name)
     if (best == 0) {
         // sliced: greedy row ranges [a, b) with their cells' moment rows
         const int Tc = (c->method == PLSX_BEHAVIORAL) ? c->T : 1;      // rows per cell
@@ -117,7 +120,10 @@ int upload_rowmaps(plsx_ctx* ctx)
             for (int t = 0; t < ctx->Tp; ++t) {
                 int row = rr * ctx->Tp + t;
                 out_row[row] = rr * ctx->Tpp + t;
-                if (ctx->scaled) mom_idx[row] = rr * ctx->J + t / ctx->T;
+                if (!ctx->scaled) continue;
+                // multiblock: the J task rows stay unscaled, behaviour row t belongs to cell (t - J) / T
+                if (ctx->method == PLSX_MULTIBLOCK) mom_idx[row] = t < ctx->J ? -1 : rr * ctx->J + (t - ctx->J) / ctx->T;
+                else mom_idx[row] = rr * ctx->J + t / ctx->T;
             }
     }
     if (ensure(ctx, ctx->out_row, out_row.size() * sizeof(int))) return PLSX_ERR_HIP;
@@ -132,7 +138,7 @@ int upload_rowmaps(plsx_ctx* ctx)
 int plan_sepmom(plsx_ctx* ctx)
 {
     ctx->sepmom = 0;
-    if (!ctx->scaled || ctx->gps > 0 || ctx->opt[OPT_INBLOCK_MOMENTS]) return 0;
+    if (!ctx->scaled || ctx->gps > 0 || ctx->opt[OPT_INBLOCK_MOMENTS] || ctx->method != PLSX_BEHAVIORAL) return 0;
     int best_mt = 0, best_n = 0;
     double best_fill = 0.0;
     for (int mt : {24, 22, 16}) {
@@ -408,7 +414,7 @@ try {
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
                    &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
-                   &ctx->Cv, &ctx->Cfrag, &ctx->cpart})
+                   &ctx->Cv, &ctx->Cfrag, &ctx->cpart, &ctx->mbpart})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     delete ctx;
@@ -452,7 +458,7 @@ try {
     HIPCHK(hipSetDevice(ctx->device));
     if (!d_X || !d_cell_of_row || S < 2 || B < 1 || n_groups < 1 || n_cond < 1)
         return fail(ctx, PLSX_ERR_ARG, "plsx_set_data: bad shape or null pointer");
-    if (method != PLSX_BEHAVIORAL && method != PLSX_MEANCENTERED && method != PLSX_REGRESSION)
+    if (method != PLSX_BEHAVIORAL && method != PLSX_MEANCENTERED && method != PLSX_REGRESSION && method != PLSX_MULTIBLOCK)
         return fail(ctx, PLSX_ERR_ARG, "plsx_set_data: unknown method");
     if (method != PLSX_MEANCENTERED && (!d_Y || T < 1))
         return fail(ctx, PLSX_ERR_ARG, "plsx_set_data: this method needs Y");
@@ -466,7 +472,8 @@ try {
     if (mean_centering < 0 || mean_centering > 2)
         return fail(ctx, PLSX_ERR_ARG, "plsx_set_data: mean_centering must be 0, 1 or 2");
     const int J = n_groups * n_cond;
-    const int Tp = (method == PLSX_BEHAVIORAL) ? J * T : (method == PLSX_REGRESSION ? ncomp : J);
+    // multiblock: the J task rows (cell means - reference mean), then the J T behaviour rows
+    const int Tp = (method == PLSX_BEHAVIORAL) ? J * T : (method == PLSX_REGRESSION ? ncomp : (method == PLSX_MULTIBLOCK ? J + J * T : J));
     if (method == PLSX_REGRESSION) {
         // what bounds SIMPLS: the T x T work of a wave's LDS slice (the S-long data leave it for device memory when
         // they do not fit, simpls_global), and K = Xc Xc^T, S^2 doubles of device memory
@@ -488,7 +495,7 @@ try {
         // block pair.  Only a binding that would take those routes (ctx->dual below: the fixed feature matrix exists
         // and no_dual_perm is off) is refused; shapes below 1 GB of K skip the query.
         const bool dual = (method == PLSX_MEANCENTERED || (flags & PLSX_FLAG_COVARIANCE) || !ctx->opt[OPT_NO_FIXED_X]) &&
-                          !ctx->opt[OPT_NO_DUAL_PERM];
+                          !ctx->opt[OPT_NO_DUAL_PERM] && method != PLSX_MULTIBLOCK;
         const double mt = (double)ceil_div(S, 64);
         const double kbytes = (double)S * round_up(S, 8) * 8, pbytes = nt_sym_fits(S) ? mt * mt * 2 * 4096 * 8 : 0.0;
         if (dual && kbytes + pbytes > 1073741824.0) {
@@ -518,6 +525,17 @@ try {
             return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
         }
     }
+    if (method == PLSX_MULTIBLOCK) {
+        // plain block layout only: one resample, data tiles + the two moment tiles of its cells, in a 24-tile block
+        const int td = ceil_div(Tp, 16), tw = (flags & PLSX_FLAG_COVARIANCE) ? 0 : ceil_div(J, 16);
+        if (td + 2 * tw > 24 || tw > 3 || J > PLSX_MAX_CELLS) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "multiblock PLS: one resample of T' = %d rows with the moment rows of its J = %d cells "
+                     "does not fit one 24-tile cross-product block (%d + 2 x %d tiles; the sliced layout is not built for "
+                     "this method)", Tp, J, td, tw);
+            return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+        }
+    }
     if (Tp > PLSX_MAX_TP || J > PLSX_MAX_CELLS || (method != PLSX_BEHAVIORAL && Tp > PLSX_BLOCK_TP)) {
         char msg[200];
         snprintf(msg, sizeof msg, "stacked dimension T' = %d (cells J = %d) exceeds the limit (T' <= %d for "
@@ -541,7 +559,7 @@ try {
     {
         // ... unless the layout of a slot is the one the buffer was last zeroed under (the cached engine of the
         // front-ends re-binding data of the same shape: a 26 GB fill is 8 ms per call)
-        const int Tp_n = (method == PLSX_BEHAVIORAL) ? J * T : (method == PLSX_REGRESSION ? ncomp : J);
+        const int Tp_n = Tp;
         const int L_n = std::min(Tp_n, B);
         // (the key holds everything a slot's padding depends on: rows T'..T'pp, columns B + L..Bpad, and the method --
         // a route of another method may have left other rows / columns of a slot untouched)
@@ -683,6 +701,18 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+int plsx_scratch_read(plsx_ctx* ctx, int slot, int row0, int nrows, double* d_out, void* stream)
+try {
+    NEED_DATA();
+    const long long slots = ctx->strideR > 0 ? (long long)(ctx->R.bytes / ((size_t)ctx->strideR * 8)) : 0;
+    if (!d_out || slot < 0 || slot >= slots || row0 < 0 || nrows < 1 || row0 + nrows > ctx->Tpp)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_scratch_read: no such rows in the cross-product scratch");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(d_out, ptr<double>(ctx->R) + (size_t)slot * ctx->strideR + (size_t)row0 * ctx->Bpad,
+                          (size_t)nrows * ctx->Bpad * 8, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
 int plsx_decompose(plsx_ctx* ctx, double* d_xw, double* d_sv, double* d_yw, void* stream)
 try {
     NEED_DATA();
@@ -728,6 +758,8 @@ try {
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->method == PLSX_REGRESSION)
         return fail(ctx, PLSX_ERR_ARG, "plsx_set_contrasts: contrasts belong to behavioral and mean-centred PLS");
+    if (ctx->method == PLSX_MULTIBLOCK)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_set_contrasts: non-rotated PLS is not built for multiblock PLS");
     if (Lc < 0 || Lc > ctx->L) return fail(ctx, PLSX_ERR_ARG, "plsx_set_contrasts: Lc must lie in 0 .. min(T', B)");
     // the original of the other mode is not this mode's: plsx_decompose / plsx_set_original follow
     ctx->has_orig = false; ctx->quad_active = 0; ctx->graded = 0;
@@ -910,8 +942,11 @@ int perm_batch_impl(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ys
         const int m = std::min(nb, n - off);
         const int* idx = d_perm_idx ? d_perm_idx + (size_t)off * ctx->S : nullptr;
         // behavioral permutes Y (base.py:599), mean-centred permutes X (meancentered.py:125)
-        const int* xs = (ctx->method == PLSX_BEHAVIORAL) ? nullptr : idx;
-        const int* ys = (ctx->method == PLSX_BEHAVIORAL) ? idx : nullptr;
+        // multiblock takes the one index array in both roles: rows of X into the cells of the task block, rows of Y
+        // against the fixed X in the behaviour block (run_xprod)
+        const bool perm_y = ctx->method == PLSX_BEHAVIORAL || ctx->method == PLSX_MULTIBLOCK;
+        const int* xs = perm_y ? nullptr : idx;
+        const int* ys = perm_y ? idx : nullptr;
         const double* yst = d_ystack ? d_ystack + (size_t)off * ctx->S * ctx->T : nullptr;
         if (ctx->fix) {
             if (int e = run_xprod_fixed(ctx, ys, m, st, yst)) return e;

@@ -3,7 +3,7 @@
 //
 // Translation units (compiled in parallel by pypyls_amd/_build.py, one code object each):
 //   plsx_core.hip        context, plsx_set_data, plsx_set_contrasts, options, timing, permutations, PLS-C bootstraps, finishing, generators
-//   plsx_xprod.hip       k_xprod launches (dense blocks, moment blocks, accumulating / quadratic-form epilogues)
+//   plsx_xprod.hip       k_xprod launches (dense blocks, moment blocks, accumulating / quadratic-form epilogues), the row normalisation of multiblock PLS
 //   plsx_compact.hip     k_xprod_compact launches (one bootstrap / split per block)
 //   plsx_gram.hip        k_nt_gemm, k_dual_gp, k_gram4, k_gram, k_gram_lds
 //   plsx_small.hip       k_small, k_refine_gram, k_rotate_rows; plsx_smallql{1,2}.hip: k_small_ql (plsx_smallql.h)
@@ -124,6 +124,7 @@ struct plsx_ctx {
     // the chunk partials of k_contrast_norms [nres][nchunk][L]
     int nc = 0;
     Buf Cv, Cfrag, cpart;
+    Buf mbpart;                                         // multiblock PLS: chunk partials of the row norms [nres][T'][nchunk]
     int dual = 0, dual_ok = 0, has_Kd = 0;              // has_Kd: the S x S kernel of the bound data is current
     Buf okx, oky;                                       // regression: usable-row masks (NaN rows)
     Buf psum, psq;                                      // k_urot resample-split partials
@@ -262,7 +263,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -375,6 +376,8 @@ int compact_boot_ksteps(int mt);                               // k-steps per LD
 bool compact_moment_rows(const plsx_ctx* ctx);                 // the compact bootstrap blocks form m1 in their padding rows
 int launch_moment_blocks_raw(plsx_ctx* ctx, const MomLayout& ml, SplitEpi se, hipStream_t st);   // EPI 6: raw m1, m2
 int ensure_compact_maps(plsx_ctx* ctx);
+// multiblock PLS: every row t < T' of the nres resamples in the cross-product scratch to unit norm over the B features
+int run_mb_rownorm(plsx_ctx* ctx, int nres, hipStream_t st);
 int run_xprod(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, hipStream_t st,
               bool prebuilt = false, const double* ystack = nullptr, long long ystride = -1, bool sparse_rows = false);
 int launch_xprod_split(plsx_ctx* ctx, int groups, SplitEpi se, hipStream_t st);

@@ -91,7 +91,7 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
                                 double* __restrict__ mom_n, int nmom_pad, int dense_ld = 0,
                                 double* __restrict__ Amom = nullptr, size_t mom_stride = 0,
                                 const int* __restrict__ rank = nullptr, int mom_pairs = PLSX_MOM_PAIRS,
-                                int chain_cap = 0, int mom_row0 = -1)
+                                int chain_cap = 0, int mom_row0 = -1, int row0 = 0)
 {
     // chain_cap: how duplicates of a source row inside a cell (bootstraps) are added up.  > 0: that many ints of
     // dynamic LDS behind the 2 T doubles hold, per position of the cell, the NEXT position with the same source row
@@ -110,6 +110,8 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
     // mom_row0 >= 0 (compact layout only): the multiplicities of cell j go into row mom_row0 + j of the resample's OWN
     // block, at the rank -- a padding row of its last tile, whose accumulators then deliver m1 -- and Amom holds
     // second-moment rows only: mom_pairs = 16 pairs per tile of a block that runs every tile against X^2.
+    // row0 (plain fragment layout only): the cell's data rows start at row rr * T' + row0 + j * T of the group -- multiblock
+    // PLS, whose J task rows (k_build_A_mc) come first; 0 everywhere else.
     // dense_ld != 0: write plain row-major (T' x dense_ld) matrices, one per
     // resample, instead of k_xprod's fragment order (dual permutation path)
     extern __shared__ double sm_b[];
@@ -195,7 +197,7 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
             int yi = ys ? ys[p] : p;
             v = (Y[(size_t)yi * T + t] - mean[t]) * rstd[t] * inv_nm1;
         }
-        int row = rr * lay.Tp + j * T + t;
+        int row = rr * lay.Tp + row0 + j * T + t;
         double* dst;
         if (dense_ld) dst = Afrag + ((size_t)r * lay.Tp + j * T + t) * dense_ld + xi;
         else if (sliced) {

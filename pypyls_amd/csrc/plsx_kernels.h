@@ -41,6 +41,7 @@
 //   plsx_k_coefci.h    percentile intervals of the SIMPLS model coefficients: the feature pass k_coef_prod, and the tile contraction (cp_fetch / cp_store / cp_mma / cp_contract / cp_feature) it shares with k_coef_perm_prod and k_vip_prod
 //   plsx_k_coefperm.h  permutation test of the SIMPLS model coefficients: the feature pass k_coef_perm_prod (counts and maxima, no product stored), k_coef_perm_max, the feature scale k_col_sd
 //   plsx_k_contrast.h  non-rotated PLS (plsx_set_contrasts): k_contrast_norms (|| R_r^T v_l || in one pass over R_r), k_contrast_quad (the same from G_p), k_contrast_fill (V as every resample's rotation operand)
+//   plsx_k_multiblock.h  multiblock PLS (PLSX_MULTIBLOCK): the row normalisation of the stacked cross-covariance matrix (k_mb_rownorm, k_mb_rowscale)
 //   plsx_k_vip.h       VIP scores of the SIMPLS bootstraps: the feature pass k_vip_prod, the moments of its series (k_vip_moments)
 #pragma once
 #include "plsx_common.h"
@@ -55,3 +56,4 @@
 #include "plsx_k_coefperm.h"
 #include "plsx_k_vip.h"
 #include "plsx_k_contrast.h"
+#include "plsx_k_multiblock.h"

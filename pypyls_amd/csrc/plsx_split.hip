@@ -248,6 +248,8 @@ try {
         return fail(ctx, PLSX_ERR_ARG, "plsx_split_half_batch: bad arguments");
     if (d_ystack && ctx->method != PLSX_BEHAVIORAL)
         return fail(ctx, PLSX_ERR_ARG, "plsx_split_half_batch_y: pre-permuted Y stacks need behavioral PLS");
+    if (ctx->method == PLSX_MULTIBLOCK)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_split_half_batch: split-half resampling is not built for multiblock PLS");
     if (ctx->nc > 0)
         return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_split_half_batch: split-half resampling is not built for non-rotated PLS "
                                                "(contrasts are set)");
@@ -374,6 +376,8 @@ extern "C" {
 int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, void* stream)
 try {
     NEED_DATA();
+    if (ctx->method == PLSX_MULTIBLOCK)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_batch: cross-validation is not built for multiblock PLS");
     if (ctx->method != PLSX_BEHAVIORAL)
         return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_batch: cross-validation is defined for behavioral PLS");
     if (!d_masks || !d_r || !d_r2 || m < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_batch: bad arguments");

@@ -385,6 +385,27 @@ int run_xprod_cboot(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, h
     return launch_cboot(ctx, nres, nks_c, se, st);
 }
 
+// Multiblock PLS: rows t < T' of the first `nres` slots of the cross-product scratch to unit norm over the B features
+// (k_mb_rownorm, k_mb_rowscale: chunks that follow B alone, one fixed summation order).
+int run_mb_rownorm(plsx_ctx* ctx, int nres, hipStream_t st)
+{
+    const int cols = mb_chunk_cols(ctx->B), nchunk = ceil_div(ctx->B, cols);
+    if (int e = ensure(ctx, ctx->mbpart, (size_t)nres * ctx->Tp * nchunk * 8)) return e;
+    KTimer tm(ctx, KC_ROWNORM, st);
+    for (int r0 = 0; r0 < nres; r0 += 32768) {              // (grid.z)
+        const int m = std::min(32768, nres - r0);
+        double* R = ptr<double>(ctx->R) + (size_t)r0 * ctx->strideR;
+        double* part = ptr<double>(ctx->mbpart) + (size_t)r0 * ctx->Tp * nchunk;
+        hipLaunchKernelGGL(k_mb_rownorm, dim3(nchunk, ctx->Tp, m), dim3(256), 0, st, R, ctx->strideR, ctx->Bpad, ctx->Tp,
+                           ctx->B, cols, part);
+        LAUNCHCHK();
+        hipLaunchKernelGGL(k_mb_rowscale, dim3(ceil_div(ctx->B, 2048), ctx->Tp, m), dim3(256), 0, st, R, ctx->strideR,
+                           ctx->Bpad, ctx->Tp, ctx->B, nchunk, part);
+        LAUNCHCHK();
+    }
+    return 0;
+}
+
 // Build the A operands of `nres` resamples and run the cross-product kernel:
 // afterwards R[r] (r < nres) holds gen_covcorr of resample r in columns
 // [0, B) and its gen_distrib in columns [B, B+L) (once the original is set).
@@ -425,6 +446,26 @@ int run_xprod(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, hipStre
     }
     if (ctx->method == PLSX_REGRESSION) {
         // A (dual weights) was scattered by k_simpls_dual; nothing to build here
+    } else if (ctx->method == PLSX_MULTIBLOCK) {
+        // both blocks of a resample in one group: the J task rows as mean-centred PLS builds them (rows of X into the
+        // cells: the caller's xsrc, or the one index array of a permutation, which arrives as ysrc), then the J T
+        // behaviour rows as behavioral PLS builds them, J rows further down, with their weight and moment rows
+        ctx->sepmom_used = 0;
+        int cap = 0;
+        const size_t lds_t = build_lds_mc(ctx, &cap);
+        hipLaunchKernelGGL(k_build_A_mc, dim3(nres), dim3(256), lds_t, st, ctx->S, ctx->J, ctx->n_cond, ctx->mc,
+                           ptr<int>(ctx->cell_of_row), xsrc ? xsrc : ysrc, lay, ptr<double>(ctx->Afrag),
+                           ctx->group_stride, 0, cap);
+        LAUNCHCHK();
+        const size_t lds_b = build_lds_behav(ctx, &cap);
+        hipLaunchKernelGGL(k_build_A_behav, dim3(nres, ctx->J), dim3(256), lds_b, st, ptr<double>(ctx->Y), 0LL, ctx->T,
+                           ctx->S, ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), xsrc, ysrc, lay,
+                           ctx->cov, ctx->momrows, ptr<double>(ctx->Afrag), ctx->group_stride,
+                           ptr<double>(ctx->mom_n), std::max(ctx->nmom_pad, 16), 0, (double*)nullptr, (size_t)0,
+                           (const int*)nullptr, PLSX_MOM_PAIRS, cap, -1, ctx->J);
+        LAUNCHCHK();
+        if (int e = launch_xprod(ctx, pgroups, st)) return e;
+        return run_mb_rownorm(ctx, nres, st);
     } else if (ctx->method == PLSX_BEHAVIORAL) {
         dim3 grid(nres, ctx->J), block(256);
         int cap = 0;

@@ -53,6 +53,7 @@ def _load():
         'plsx_tprime': ([vp], i32),
         'plsx_crosscov_batch': ([vp, vp, vp, i32, vp, vp], i32),
         'plsx_decompose': ([vp, vp, vp, vp, vp], i32),
+        'plsx_scratch_read': ([vp, i32, i32, i32, vp, vp], i32),
         'plsx_set_original': ([vp, vp, vp, vp, vp], i32),
         'plsx_set_contrasts': ([vp, vp, i32, vp], i32),
         'plsx_project': ([vp, vp, i32, vp, vp], i32),
@@ -131,7 +132,7 @@ def exported_symbols():
     lib = _load()
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
-             'plsx_crosscov_batch', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
+             'plsx_crosscov_batch', 'plsx_scratch_read', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
              'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
@@ -144,6 +145,11 @@ def exported_symbols():
              'plsx_comm_load', 'plsx_comm_unique_id', 'plsx_comm_init', 'plsx_comm_rank', 'plsx_allgather',
              'plsx_comm_destroy', 'plsx_comm_init_all', 'plsx_comm_transport', 'plsx_allgather_all']
     return [n for n in names if hasattr(lib, n)]
+
+
+def max_tprime():
+    """Largest stacked dimension T' the library binds (plsx_max_tprime); no context, no device."""
+    return int(_load().plsx_max_tprime())
 
 
 def _torch():
@@ -433,6 +439,17 @@ class Engine(object):
         self._check(self.lib.plsx_crosscov_batch(
             self.ctx, None if dx is None else dx.data_ptr(), None if dy is None else dy.data_ptr(),
             int(n), out.data_ptr(), self._stream()))
+        self.sync()
+        return out.cpu().numpy()
+
+    def scratch_rows(self, slot, row0=0, nrows=None):
+        """Rows of one resample's slot of the cross-product scratch as the last batch left them (plsx_scratch_read;
+        tests): (nrows, Bpad) with the B features, the L score columns, zero padding; T' rounded up to 4 rows."""
+        tpp, bpad = -(-self.Tp // 4) * 4, -(-(self.B + self.L) // 128) * 128
+        nrows = tpp - row0 if nrows is None else nrows
+        out = self._empty((nrows, bpad))
+        self._check(self.lib.plsx_scratch_read(self.ctx, int(slot), int(row0), int(nrows), out.data_ptr(),
+                                               self._stream()))
         self.sync()
         return out.cpu().numpy()
 

@@ -57,3 +57,23 @@ def cellwise_xcorr(scores, Y, cell_of_row, n_cells, covariance=False):
         a, b = zscore_cols(scores[m], covariance), zscore_cols(Y[m], covariance)
         out.append(b.T @ a / (m.sum() - 1))
     return np.vstack(out)
+
+
+def cell_means_centered(scores, cell_of_row, n_groups, n_cond, mean_centering=0):
+    """Cell means of ``scores`` (S, L) minus the reference mean of ``mean_centering`` (pyls/compute.py:267-357 with
+    means=True) -> (J, L): the (S, L)-sized use of the mean-centred gen_covcorr (the task rows of multiblock
+    PLS's ``y_loadings``).  0: the mean of the cell's group over all its rows, 1: the mean over the groups of the
+    condition's cell means, 2: the grand mean of the rows."""
+    scores = np.asarray(scores, dtype=float)
+    J = n_groups * n_cond
+    means = np.vstack([scores[cell_of_row == c].mean(axis=0) for c in range(J)])
+    if mean_centering == 0:
+        ref = np.vstack([scores[(cell_of_row // n_cond) == c // n_cond].mean(axis=0) for c in range(J)])
+    elif mean_centering == 1:
+        cond = means.reshape(n_groups, n_cond, -1).mean(axis=0)
+        ref = np.tile(cond, (n_groups, 1))
+    elif mean_centering == 2:
+        ref = np.repeat(scores.mean(axis=0)[None], J, axis=0)
+    else:
+        raise ValueError('Mean centering type must be in [0, 1, 2].')
+    return means - ref

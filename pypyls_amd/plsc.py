@@ -1,7 +1,9 @@
 """
 Front-ends ``behavioral_pls`` / ``meancentered_pls`` with the keyword surface
 and ``PLSResults`` layout of the reference (pyls/types/behavioral.py:231-242,
-pyls/types/meancentered.py:182-192), driving the MI355X engine.
+pyls/types/meancentered.py:182-192), driving the MI355X engine, and
+``multiblock_pls`` (no counterpart in the reference: both blocks in one
+decomposition, on the same driver).
 
 Host code here mirrors the ORCHESTRATION of BasePLS.run_pls
 (pyls/base.py:341-399) and the subclass ``run_pls`` bodies; every
@@ -31,7 +33,7 @@ import numpy as np
 from . import hostmath, parallel, resampling
 from .structures import PLSInputs, PLSResults
 
-_METHOD_CODE = {'behavioral': 0, 'meancentered': 1}
+_METHOD_CODE = {'behavioral': 0, 'meancentered': 1, 'multiblock': 3}
 
 # The B- and n_boot-sized result arrays (x_weights, bootstrap ratios / standard errors, the (T', L, n_boot)
 # distributions: 440 MB at the headline shape) LAND in page-locked memory (57 GB/s instead of 8 - 10 pageable) that is
@@ -143,6 +145,8 @@ class _PLSCRun(object):
         self.emulate = kwargs.pop('_emulate', None)
         self.device_ids = kwargs.pop('device_ids', None)
         self.transport = kwargs.pop('_transport', 'auto')
+        if method == 'multiblock':
+            kwargs['method'] = method                  # (the two reference front-ends record none)
         self.inputs = PLSInputs(X=X, Y=Y, groups=groups, n_cond=n_cond, **kwargs)
         # under torch.distributed every rank must draw the same index arrays
         self.rs = resampling.check_random_state(parallel.shared_seed(self.inputs.get('seed')))
@@ -229,6 +233,8 @@ class _PLSCRun(object):
         X = _as_float_array(inp.X, 'X')
         Y = None if self.method == 'meancentered' else _as_float_array(inp.Y, 'Y')
         Tp = self.n_cells * Y.shape[1] if Y is not None else self.n_cells
+        if self.method == 'multiblock':
+            Tp += self.n_cells                         # the task rows come first
         self.perm_given = self.boot_given = None
         from .engine import default_engine, touch_idle_release
         from . import team as _team
@@ -503,7 +509,7 @@ class _PLSCRun(object):
             lo_hi = eng.percentile_ci_dev(d_series, ci=inp.get('ci', 95))
             h_dist = eng.to_host_async(d_series, pin['dist'])
             d_bs = eng.scale_columns(d_xw, d_sv)                                       # x_weights @ singvals
-            if self.method == 'behavioral':
+            if self.method in ('behavioral', 'multiblock'):
                 # add the original back, n_boot + 1 (behavioral.py:201-207)
                 d_bsr, d_se = eng.boot_rel_dev(d_bs, usum, usq, n_boot_tot + 1, add_orig=True)
             else:
@@ -545,15 +551,21 @@ class _PLSCRun(object):
             res['permres']['perm_singval'] = d_perm
 
         # ---- scores / loadings (subclass run_pls) --------------------------
-        if self.method == 'behavioral':
+        if self.method in ('behavioral', 'multiblock'):
             y_scores = np.zeros((len(X), Lc))
             T = Y.shape[1]
+            row0 = self.n_cells if self.method == 'multiblock' else 0      # (multiblock: the behaviour rows of y_weights)
             for c in range(self.n_cells):
                 m = self.cells == c
-                y_scores[m] = Y[m] @ yw[c * T:(c + 1) * T]
+                y_scores[m] = Y[m] @ yw[row0 + c * T:row0 + (c + 1) * T]
             res['y_scores'] = y_scores
             res['y_loadings'] = hostmath.cellwise_xcorr(res['x_scores'], Y, self.cells,
                                                         self.n_cells, bool(inp.get('covariance')))
+            if self.method == 'multiblock':
+                # the two gen_distrib outputs stacked, not row-normalised: cell means of the mean-centred scores first
+                res['y_loadings'] = np.vstack([hostmath.cell_means_centered(
+                    res['x_scores'], self.cells, len(inp.groups), inp.n_cond, inp.get('mean_centering') or 0),
+                    res['y_loadings']])
         else:
             dummy = resampling.dummy_code(inp.groups, inp.n_cond)
             inp['Y'] = dummy
@@ -574,7 +586,7 @@ class _PLSCRun(object):
             if Lc != L:
                 distrib, ci_arr = np.ascontiguousarray(distrib[:, :Lc]), np.ascontiguousarray(ci_arr[:, :Lc])
                 bsr, se = np.ascontiguousarray(bsr[:, :Lc]), np.ascontiguousarray(se[:, :Lc])
-            if self.method == 'behavioral':
+            if self.method in ('behavioral', 'multiblock'):
                 res['bootres'].update(dict(
                     x_weights_normed=bsr, x_weights_stderr=se,
                     y_loadings=res['y_loadings'].copy(), y_loadings_boot=distrib,
@@ -615,17 +627,8 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     return run.run()
 
 
-def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000, n_boot=5000,
-                     n_split=0, rotate=True, ci=95, permsamples=None, bootsamples=None,
-                     seed=None, verbose=True, n_proc=None, contrasts=None, **kwargs):
-    """Mean-centred PLS of X (S, B) sorted into groups x conditions; see
-    pyls.meancentered_pls (argument checks of pyls/types/meancentered.py:16-38).
-
-    ``contrasts`` (T', Lc), T' = groups x conditions (group-major rows): non-rotated PLS, as for
-    :func:`behavioral_pls`; the bootstrap keeps the mean-centred conventions (no add-back of the original)."""
-    if contrasts is not None:
-        kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
-    X = np.asarray(X)
+def _meancentered_design(X, groups, n_cond, mean_centering):
+    """The argument checks of pyls/types/meancentered.py:16-38 -> (groups, mean_centering), with its resets and warnings."""
     if groups is None:
         if len(X) // n_cond != len(X) / n_cond:
             raise ValueError('Provided `X` matrix with {} samples is not evenly divisible into '
@@ -647,8 +650,89 @@ def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000,
         mean_centering = 0
     if mean_centering not in (0, 1, 2):
         raise ValueError('Mean centering type must be in [0, 1, 2].')
+    return groups, mean_centering
+
+
+def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000, n_boot=5000,
+                     n_split=0, rotate=True, ci=95, permsamples=None, bootsamples=None,
+                     seed=None, verbose=True, n_proc=None, contrasts=None, **kwargs):
+    """Mean-centred PLS of X (S, B) sorted into groups x conditions; see
+    pyls.meancentered_pls (argument checks of pyls/types/meancentered.py:16-38).
+
+    ``contrasts`` (T', Lc), T' = groups x conditions (group-major rows): non-rotated PLS, as for
+    :func:`behavioral_pls`; the bootstrap keeps the mean-centred conventions (no add-back of the original)."""
+    if contrasts is not None:
+        kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
+    X = np.asarray(X)
+    groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     run = _PLSCRun('meancentered', X, None, groups=groups, n_cond=n_cond,
                    mean_centering=mean_centering, n_perm=n_perm, n_boot=n_boot, n_split=n_split,
                    rotate=rotate, ci=ci, permsamples=permsamples, bootsamples=bootsamples,
                    seed=seed, verbose=verbose, n_proc=n_proc, **kwargs)
+    return run.run()
+
+
+def _check_multiblock(X, Y, groups, n_cond, kwargs):
+    """What multiblock_pls does not cover, refused on the host before any engine is created or looked up."""
+    if kwargs.get('n_split'):
+        raise ValueError('Split-half resampling (`n_split` > 0) is not available for multiblock PLS')
+    if kwargs.get('test_split'):
+        raise ValueError('Cross-validation (`test_split` > 0) is not available for multiblock PLS')
+    if kwargs.get('contrasts') is not None:
+        raise ValueError('Non-rotated PLS (`contrasts`) is not available for multiblock PLS')
+    if not kwargs.get('permindices', True):
+        raise ValueError('multiblock PLS permutes the task block through index arrays: `permindices=False` '
+                         '(pre-permuted Y matrices) is not available')
+    bscan = kwargs.pop('bscan', None)
+    if bscan is not None and sorted(int(c) for c in np.atleast_1d(bscan)) != list(range(n_cond)):
+        raise ValueError('A behaviour block on a subset of the conditions (`bscan`) is not available: the behaviour '
+                         'block of multiblock PLS covers every condition')
+    for key in ('n_split', 'test_split', 'test_size', 'contrasts'):
+        kwargs.pop(key, None)
+    if X.ndim != 2 or Y.ndim != 2:
+        raise ValueError('Expected 2D arrays for `X` and `Y`')
+    if Y.shape[1] < 1:
+        raise ValueError('multiblock PLS needs at least one behaviour (column of `Y`)')
+    J = len(groups) * n_cond
+    Tp = J + J * Y.shape[1]
+    from .engine import max_tprime
+    if Tp > max_tprime():
+        raise ValueError('multiblock PLS: T\' = J + J T = {} rows (J = {} cells, T = {} behaviours) exceed the limit '
+                         'of {}'.format(Tp, J, Y.shape[1], max_tprime()))
+    if len(X) == len(Y):                                # (a mismatch is reported by the run object, as everywhere)
+        _check_finite(np.asarray(X, dtype=np.float64), 'X')
+        _check_finite(np.asarray(Y, dtype=np.float64), 'Y')
+
+
+def multiblock_pls(X, Y, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000, n_boot=5000,
+                   covariance=False, rotate=True, ci=95, permsamples=None, bootsamples=None, seed=None,
+                   verbose=True, n_proc=None, **kwargs):
+    """Multiblock PLS of X (S, B) sorted into groups x conditions, with behaviours Y (S, T): the condition-means block
+    of :func:`meancentered_pls` and the brain-behaviour block of :func:`behavioral_pls` in ONE decomposition (the Matlab
+    PLS toolbox's method 4 in structure; pyls has no counterpart).  With J = groups x conditions cells,
+
+        R = vstack([rownorm(R_task), rownorm(R_behav)])        # T' = J + J T rows
+
+    where R_task (J, B) is the mean-centred cross-covariance (cell means minus the ``mean_centering`` reference mean),
+    R_behav (J T, B) the per-cell cross-correlation (``covariance=True``: cross-covariance) and rownorm divides every
+    row by its L2 norm over the features (a zero row stays zero), so that neither block's raw scale decides the
+    decomposition.  ``y_weights`` (T', L): the J task rows first (group-major, then condition), then the behaviour rows
+    (group, condition, behaviour).  ``y_scores`` comes from the behaviour rows, cell by cell; ``y_loadings`` (T', L)
+    stacks the cell means of the mean-centred scores and the per-cell correlation of Y with the scores, neither
+    normalised.  Permutations draw ONE index array per resample: the rows of X change cells in the task block and the
+    rows of Y move against X in the behaviour block.  Bootstraps resample X and Y together; the bootstrap ratios follow
+    the behavioural convention (the original is added back, n_boot + 1).  Result keys are those of
+    :func:`behavioral_pls`; a seeded call draws its arrays in the same order.
+
+    Not available (ValueError): ``n_split`` > 0, cross-validation (``test_split``), ``contrasts``,
+    ``permindices=False``, a behaviour block on a subset of the conditions; one group with one condition (the task
+    block is identically zero).  ``mean_centering`` is reset with a warning as in :func:`meancentered_pls`."""
+    X, Y = np.asarray(X), np.asarray(Y)
+    groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
+    groups = [int(g) for g in groups]
+    _check_multiblock(X, Y, groups, n_cond, kwargs)
+    run = _PLSCRun('multiblock', X, Y, groups=groups, n_cond=n_cond, mean_centering=mean_centering,
+                   n_perm=n_perm, n_boot=n_boot, covariance=covariance, rotate=rotate, ci=ci,
+                   permsamples=permsamples, bootsamples=bootsamples, seed=seed, verbose=verbose,
+                   n_proc=n_proc, **kwargs)
     return run.run()
