@@ -294,6 +294,10 @@ void k_cv_rescale(const double* __restrict__ R, long long strideR, int ldr, int 
         dst[b] = v;
         part += mo[b] * v;
     }
+    // the padding columns of the copy are part of the operand: the 64 x 64-block Gram kernel masks the ragged
+    // last 16-column step on its E side only (k_gram_lds; R's own padding is zero), and R2 is not cleared when it
+    // is mapped -- a NaN left there by an earlier owner of the memory reached every Q of the split (S > 64, B % 16 != 0)
+    for (int b = B + threadIdx.x; b < ldr; b += blockDim.x) dst[b] = 0.0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import assert_close
 from oracle import cpu_ref as ref
+import crossval_expect as cx
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +29,12 @@ def _groups(n_groups, n_cond):
 @pytest.mark.parametrize('rotate', [True, False])
 def test_behavioral_matrix(n_groups, n_cond, n_split, rotate):
     import pypyls_amd as pls
+    from pypyls_amd import resampling as rsmp
     groups = _groups(n_groups, n_cond)
+    cvs = rsmp.gen_splits(groups, n_cond, 3, seed=77, test_size=0.25)
     res = pls.behavioral_pls(X, Y, groups=groups, n_cond=n_cond, n_perm=6, n_boot=5,
                              n_split=n_split or 0, test_split=3, test_size=0.25, rotate=rotate,
-                             seed=1234, verbose=False)
+                             seed=1234, verbose=False, _cvsplits=cvs)
     J = n_groups * n_cond
     L = min(J * T, B)
     for attr, shape in [('x_weights', (B, L)), ('y_weights', (J * T, L)), ('singvals', (L,)),
@@ -54,6 +57,17 @@ def test_behavioral_matrix(n_groups, n_cond, n_split, rotate):
                     for i in range(5) for c in ref.dummy_code(groups, n_cond).T.astype(bool))
     if full_rank:
         assert_close(res.bootres.x_weights_normed, want['bootres']['x_weights_normed'], 1e-5, what='bsr')
+    # cross-validation, per entry: the oracle where every training decomposition has full rank, the live-LV
+    # definition otherwise (3 groups x 4 conditions: 10 rows a cell, 7 - 8 of them training, T + 1 = 9 needed)
+    spec = ref.Spec('behavioral', groups, n_cond)
+    exp_r, exp_r2, info = cx.crossval(spec, X, Y, cvs)
+    assert all(i['kappa'] <= cx.KAPPA_MAX for i in info), info
+    if all(i['n_live'] == i['L'] for i in info):
+        exp_r, exp_r2 = ref.crossval(spec, X, Y, cvs)
+    else:
+        assert (n_groups, n_cond) == (3, 4) and all(i['gap'] <= 1e-12 for i in info), info
+    cx.assert_entrywise(res.cvres.pearson_r, res.cvres.r_squared, exp_r, exp_r2,
+                        what='matrix {}g{}c cvres'.format(n_groups, n_cond))
 
 
 @pytest.mark.parametrize('n_groups,n_cond', [(1, 2), (1, 4), (3, 1), (3, 2), (3, 4)])
@@ -244,8 +258,9 @@ def test_behavioral_wide_y(n_groups, n_cond, n_split):
     assert_close(res.permres.pvals, want['permres']['pvals'], 0, what='pvals')
     lead = slice(0, 20)
     assert_close(res.bootres.x_weights_normed[:, lead], want['bootres']['x_weights_normed'][:, lead], 1e-5, what='bsr')
-    assert_close(res.cvres.pearson_r, cv_r, 1e-6, what='cv r')
-    assert_close(res.cvres.r_squared, cv_r2, 1e-6, what='cv r2')
+    info = cx.crossval(spec, Xw, Yw, cvs)[2]
+    assert all(i['n_live'] == i['L'] and i['kappa'] <= cx.KAPPA_MAX for i in info), info
+    cx.assert_entrywise(res.cvres.pearson_r, res.cvres.r_squared, cv_r, cv_r2, what='wide cvres')
     if n_split:
         assert_close(res.splitres.ucorr, want['splitres']['ucorr'], 1e-6, what='ucorr')
         assert_close(res.splitres.vcorr, want['splitres']['vcorr'], 1e-6, what='vcorr')
