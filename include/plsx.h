@@ -660,6 +660,10 @@ int plsx_mfma_f64_peak(plsx_ctx* ctx, double* tflops);
  * [21] 1 when the compact bootstrap blocks of the last launch formed the first
  * moments of the features in their own padding rows (the moment-only blocks then
  * contract X^2 alone), 0 on every other route.
+ * [22] 1 when the last permutation call took the projected route (rotated
+ * permutations of a fixed-X binding with L == T' and every original LV live:
+ * singular values from the row norms of (V0^T A_p) X, no cross-product scratch,
+ * no Gram pass, no small solver; option "no_perm_project"), else 0.
  * Returns the number written. */
 int plsx_last_timing(const plsx_ctx* ctx, double* out, int cap);
 /* Scratch budget of the resampling super-batches (default 48 GB; the R block
@@ -717,7 +721,9 @@ int plsx_set_perm_path(plsx_ctx* ctx, int dual);
  *     "compact_boot_always", "crosscov_sparse" (plsx_crosscov_batch treats its resamples as bootstraps: the compact
  *     blocks wherever plsx_boot_batch would take them, so that tests can read R of a compact launch),
  *     "sepmom_always", "no_moment_rows" (compact bootstrap blocks: first moments from the moment-only blocks even
- *     where the padding rows of a block could deliver them), "no_split_fuse" (split halves: two passes), "split_two_readers"
+ *     where the padding rows of a block could deliver them), "no_perm_project" (rotated permutations on the fixed-X
+ *     route: always R, its Gram matrix and the small solver, also where the row norms of the projected product
+ *     would do), "no_split_fuse" (split halves: two passes), "split_two_readers"
  *     (fused split blocks read by the Gram and the projection kernel instead of the one-pass reader),
  *     "split_reader8" (bit 0: the one-pass reader as the round-5 8-wave block whose matrix waves build the tiles
  *     themselves, instead of the 12-wave block with dedicated construction waves; bit 1: wave kinds in runs of

@@ -306,8 +306,9 @@ bool plsc_single_pass(const plsx_ctx* ctx)
            ctx->Tp <= PLSX_JACOBI_TP && 2 * (size_t)ctx->L * PLSX_ACC_PITCH * 8 <= 72 * 1024 && !ctx->opt[OPT_TWO_PASS_BOOT];
 }
 
-// d (L values on the device, descending): set ctx->graded when a live singular value lies below PLSX_REFINE_TAU d_max.
-int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st)
+// d (L values on the device, descending): set ctx->graded when a live singular value lies below PLSX_REFINE_TAU d_max;
+// *all_live (when asked): d[L - 1] > PLSX_RANK_RTOL d[0], every LV is live.
+int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st, int* all_live)
 {
     std::vector<double> d(ctx->L);
     HIPCHK(hipMemcpyAsync(d.data(), d_sv, (size_t)ctx->L * 8, hipMemcpyDeviceToHost, st));
@@ -316,6 +317,7 @@ int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st)
     for (double v : d) if (v > dmax) dmax = v;
     int graded = 0;
     for (double v : d) if (v > PLSX_RANK_RTOL * dmax && v < PLSX_REFINE_TAU * dmax) graded = 1;
+    if (all_live) *all_live = (ctx->L > 0 && d[ctx->L - 1] > PLSX_RANK_RTOL * d[0]) ? 1 : 0;
     if (graded != ctx->graded) ctx->has_Kd = ctx->has_Kd && !graded;
     ctx->graded = graded && !ctx->opt[OPT_NO_REFINE];
     return 0;
@@ -410,7 +412,7 @@ try {
                    &ctx->Rfull, &ctx->Vp, &ctx->dp, &ctx->Mvd, &ctx->Cm, &ctx->srcx, &ctx->srcy, &ctx->part2,
                    &ctx->Kmat, &ctx->swork, &ctx->spct, &ctx->sc,
                    &ctx->momout, &ctx->R2, &ctx->cvc, &ctx->Qm, &ctx->Vs, &ctx->ds, &ctx->ybar, &ctx->pred,
-                   &ctx->Xn, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
+                   &ctx->Xn, &ctx->ppart, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
                    &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
@@ -800,7 +802,8 @@ try {
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(ctx->V0.p, d_yw, (size_t)ctx->Tp * ctx->L * 8, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->d0.p, d_sv, (size_t)ctx->L * 8, hipMemcpyDeviceToDevice, st));
-    if (int e = note_spectrum(ctx, d_sv, st)) return e;
+    ctx->orig_all_live = 0;
+    if (int e = note_spectrum(ctx, d_sv, st, &ctx->orig_all_live)) return e;
     hipLaunchKernelGGL(k_transpose, dim3(ceil_div(ctx->L, 32), ceil_div(ctx->B, 32)), dim3(32, 8), 0, st,
                        d_xw, ctx->B, ctx->L, ctx->L, ptr<double>(ctx->U0T), ctx->Bpad);
     LAUNCHCHK();
@@ -930,12 +933,28 @@ int perm_dual(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ystack, 
     return PLSX_OK;
 }
 
+// Projected permutations.  The rotated statistic is ssd_l = || column l of V_p d_p Q ||, Q the Procrustes rotation of
+// V0^T V_p = N S P (Q = P^T N^T).  With V0 square and orthogonal (L == T', every original LV live) V0^T V_p is itself
+// orthogonal, so Q = V_p^T V0 exactly and ssd_l^2 = (V0^T V_p d_p^2 V_p^T V0)_ll = (V0^T G_p V0)_ll = || row l of
+// V0^T R_p ||^2, whatever the rank of G_p.  On the fixed-X route the epilogue scales nothing, so V0^T R_p =
+// (V0^T A_p) Xn: the same pass over X with a projected operand, of which only the row norms are kept
+// (run_xprod_fixed_norms) -- no R, no Gram pass, no eigen-solve, no Procrustes SVD.  Every other case keeps
+// run_xprod_fixed -> run_gram -> run_small.
+bool perm_projected(const plsx_ctx* ctx, int rotate)
+{
+    return ctx->fix && rotate && ctx->nc == 0 && ctx->L == ctx->Tp && ctx->has_orig && ctx->orig_all_live &&
+           !ctx->opt[OPT_NO_PERM_PROJECT];
+}
+
 int perm_batch_impl(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ystack, int n, int rotate,
                     double* d_out_sv, void* stream)
 {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->last_perm_projected = 0;
     if (use_dual(ctx)) return perm_dual(ctx, d_perm_idx, d_ystack, n, rotate, d_out_sv, st);
+    const bool projected = perm_projected(ctx, rotate);
+    ctx->last_perm_projected = projected ? 1 : 0;
     const int pg = ctx->fix ? ctx->npgf : ctx->npg;
     const int nb = balanced_batch(n, launch_groups(ctx, n, pg) * pg, pg);
     for (int off = 0; off < n; off += nb) {
@@ -948,6 +967,10 @@ int perm_batch_impl(plsx_ctx* ctx, const int32_t* d_perm_idx, const double* d_ys
         const int* xs = perm_y ? nullptr : idx;
         const int* ys = perm_y ? idx : nullptr;
         const double* yst = d_ystack ? d_ystack + (size_t)off * ctx->S * ctx->T : nullptr;
+        if (projected) {
+            if (int e = run_xprod_fixed_norms(ctx, ys, m, st, yst, d_out_sv + (size_t)off * ctx->L)) return e;
+            continue;
+        }
         if (ctx->fix) {
             if (int e = run_xprod_fixed(ctx, ys, m, st, yst)) return e;
         } else if (int e = run_xprod(ctx, xs, ys, m, st, false, yst)) return e;
@@ -1421,15 +1444,16 @@ try {
     // [12..18]: the path of the last rotation / Gram launch (include/plsx.h); the tail flag rides on the variant
     const auto uvar = [&](int nks) { return (double)(nks > 0 && ctx->urot_tail_l ? nks + 100 : nks); };
     // [21]: the compact blocks of the last launch formed the first moments in their padding rows (compact_moment_rows)
-    double vals[22] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
+    // [22]: the last permutation call took the projected route (perm_projected)
+    double vals[23] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
                        (double)(cmp ? ceil_div(ctx->Tp, 16) : (ctx->sepmom_used ? ctx->MTd : ctx->MT)),
                        (double)ctx->Gcap * ctx->npg, (double)ctx->timed_units, (double)use_dual(ctx), crows,
                        ctx->nt_flops, (double)ctx->quad_series, (double)ctx->quad_MT, (double)ctx->quad_gpl,
                        (double)ctx->urot_waves_l, (double)ctx->urot_splits_l, (double)ctx->urot_rps_l,
                        uvar(ctx->urot_nks_first), (double)ctx->gram_chunks_l, uvar(ctx->urot_nks_last),
                        (double)ctx->gram_kind_l, (double)ctx->split_blocks_l, (double)ctx->split_reader_l,
-                       (double)(cmp && ctx->last_moment_rows ? 1 : 0)};
-    int n = std::min(cap, 22);
+                       (double)(cmp && ctx->last_moment_rows ? 1 : 0), (double)ctx->last_perm_projected};
+    int n = std::min(cap, 23);
     for (int i = 0; i < n; ++i) out[i] = vals[i];
     return n;
 } PLSX_CATCH(const_cast<plsx_ctx*>(cctx))

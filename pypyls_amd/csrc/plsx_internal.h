@@ -41,14 +41,14 @@ enum {
     OPT_SEPMOM_ALWAYS, OPT_NO_GRAM4, OPT_UROT_GENERIC, OPT_UROT_NO_TAIL4, OPT_NO_FIXED_X, OPT_NO_DUAL_PERM,
     OPT_TWO_PASS_BOOT, OPT_SPLIT_INBLOCK, OPT_NO_SPLIT_FUSE, OPT_SPLIT_TWO_READERS, OPT_EXPECT_RESAMPLES,
     OPT_SIMPLS_JACOBI, OPT_PERCENTILE_SORT, OPT_QUAD_SUMS, OPT_SPLIT_READER8, OPT_SIMPLS_GLOBAL,
-    OPT_CROSSCOV_SPARSE, OPT_NO_MOMENT_ROWS, OPT_COUNT
+    OPT_CROSSCOV_SPARSE, OPT_NO_MOMENT_ROWS, OPT_NO_PERM_PROJECT, OPT_COUNT
 };
 static const char* const kOptionNames[OPT_COUNT] = {
     "no_refine", "min_batch", "inblock_moments", "no_compact_boot", "compact_boot_always",
     "sepmom_always", "no_gram4", "urot_generic", "urot_no_tail4", "no_fixed_x", "no_dual_perm",
     "two_pass_boot", "split_inblock", "no_split_fuse", "split_two_readers", "expect_resamples",
     "simpls_jacobi", "percentile_sort", "quad_sums", "split_reader8", "simpls_global",
-    "crosscov_sparse", "no_moment_rows"};
+    "crosscov_sparse", "no_moment_rows", "no_perm_project"};
 
 // k-steps per LDS stage of the 4-tile compact cross-product blocks (T' = 49 .. 64: the headline shape).  A/B lever of
 // tools/ckt_probe.sh (measured: profiles/r06_compact_kt.txt); other tile counts keep 12 / MT.
@@ -125,6 +125,10 @@ struct plsx_ctx {
     int nc = 0;
     Buf Cv, Cfrag, cpart;
     Buf mbpart;                                         // multiblock PLS: chunk partials of the row norms [nres][T'][nchunk]
+    // projected permutations (perm_projected, plsx_core.hip): the row-norm partials of a launch [column block][group][row]
+    Buf ppart;
+    int orig_all_live = 0;                              // every LV of the original is live (plsx_set_original)
+    int last_perm_projected = 0;                        // the last permutation batch took the projected route (plsx_last_timing [22])
     int dual = 0, dual_ok = 0, has_Kd = 0;              // has_Kd: the S x S kernel of the bound data is current
     Buf okx, oky;                                       // regression: usable-row masks (NaN rows)
     Buf psum, psq;                                      // k_urot resample-split partials
@@ -335,7 +339,7 @@ int chip_slots(const void* kernel);
 int pick_parts(long long units, int slots, int lo, int hi);
 SmallArgs small_args(plsx_ctx* ctx, int mode);
 bool plsc_single_pass(const plsx_ctx* ctx);
-int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st);
+int note_spectrum(plsx_ctx* ctx, const double* d_sv, hipStream_t st, int* all_live = nullptr);
 // One accumulator set of the quadratic-form route: C (L x S x S), Vsum (L x S), fed from Vd dense [m][L][S].  nullptr
 // where a QuadSet is optional: the weights' own set (ctx->Cq, ctx->Vsumq, ctx->Vdq; L = LVs / components).
 struct QuadSet { Buf* C; Buf* Vsum; const double* Vd; int L; };
@@ -370,6 +374,8 @@ inline void cperm_close(plsx_ctx* ctx)
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);
 int launch_xprod_acc(plsx_ctx* ctx, const double* Afrag, size_t gstride, int groups, int L, hipStream_t st);
 int run_xprod_fixed(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, const double* ystack);
+// projected permutations: out_sv[r][l] = || row l of (V0^T A_r) Xn || -- no R, no Gram matrix, no small solver
+int run_xprod_fixed_norms(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, const double* ystack, double* out_sv);
 MomLayout moment_layout(const plsx_ctx* ctx, int npairs);
 MomLayout moment2_layout(const plsx_ctx* ctx, int npairs);     // X^2-only blocks (EPI 9)
 int compact_boot_ksteps(int mt);                               // k-steps per LDS stage of the compact bootstrap blocks

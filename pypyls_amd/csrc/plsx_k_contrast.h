@@ -149,6 +149,31 @@ static __global__ void k_contrast_finish(const double* __restrict__ partial, int
     out[idx] = sqrt(s);
 }
 
+// Projected permutations: out[r][l] = sqrt(sum over the column blocks, ascending, of the row-norm partials the fixed-X
+// blocks left (k_xprod EPI 10: part[column block][group][rows], resample r = group * n + rr in rows rr * T' ..)).  The
+// column blocks follow B alone and every partial is the work of one block: the bits of a resample do not depend on the
+// batch, on its place in it or on the scratch budget.
+static __global__ void k_rownorm_finish(const double* __restrict__ part, int ncolblk, int groups, int rows, int n, int Tp,
+                                        int nres, double* __restrict__ out)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)nres * Tp) return;
+    const int r = (int)(idx / Tp), l = (int)(idx - (long long)r * Tp);
+    const double* p = part + (size_t)(r / n) * rows + (r % n) * Tp + l;
+    const size_t step = (size_t)groups * rows;
+    double s = 0.0;
+    int c = 0;
+    for (; c + 8 <= ncolblk; c += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(c + u) * step];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; c < ncolblk; ++c) s += p[(size_t)c * step];
+    out[idx] = sqrt(s);
+}
+
 // Dual-space permutations: s_l^2 = v_l^T G_p v_l (clamped at 0) from the Gram matrix perm_dual forms.  One block per
 // permutation; thread l walks the rows of G (the same address over the block: one broadcast fetch) against column l
 // of the dense V (consecutive over the threads).

@@ -259,6 +259,56 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
     }
 }
 
+// Projected permutations (fixed-X route, L == T', every original LV live): the operand A'_r = V0^T A_r of resample r,
+// cell j, in the fragment order and group layout of the fixed-X blocks (n resamples of T' rows per group).  Column p
+// of A_r holds the z-scored behaviours of the row of Y placed at p, in the T rows of p's cell and nowhere else, so
+//   A'[rr * T' + l][p] = sum_t V0[j T + t][l] * zscore(Y[ysrc[p]][t]) / (n_j - 1),   t ascending: one thread per entry,
+// a fixed summation order, one writer.  mean / std exactly as k_build_A_behav forms them for a permutation (xsrc ==
+// nullptr, correlation mode).  The caller zeroed the operand: rows >= T' of the last tile and the slots of a partly
+// filled last group stay zero.  grid (n_resamples, J), block 256; dynamic LDS: 2 T doubles.
+static __global__ __launch_bounds__(256)
+void k_build_A_proj(const double* __restrict__ Y0, long long y_stride, int T, int S,
+                    const int* __restrict__ cell_start, const int* __restrict__ cell_len,
+                    const int* __restrict__ ysrc, const double* __restrict__ V0, int L,
+                    int n, int Tp, int MT, double* __restrict__ Afrag, size_t group_stride)
+{
+    extern __shared__ double sm_b[];
+    const int r = blockIdx.x, j = blockIdx.y;
+    const int g = r / n, rr = r % n;
+    const double* Y = Y0 + (size_t)r * y_stride;
+    const int start = cell_start[j], len = cell_len[j];
+    const int* ys = ysrc ? ysrc + (size_t)r * S : nullptr;
+    double* mean = sm_b;            // [T]
+    double* rstd = sm_b + T;        // [T]
+    const int tid = threadIdx.x;
+    for (int t = tid; t < T; t += blockDim.x) {
+        double s = 0.0;
+        for (int p = start; p < start + len; ++p) s += Y[(size_t)(ys ? ys[p] : p) * T + t];
+        const double m = s / (double)len;
+        double q = 0.0;
+        for (int p = start; p < start + len; ++p) {
+            const double d = Y[(size_t)(ys ? ys[p] : p) * T + t] - m;
+            q += d * d;
+        }
+        mean[t] = m;
+        rstd[t] = 1.0 / sqrt(q / (double)(len - 1));
+    }
+    __syncthreads();
+    double* A = Afrag + (size_t)g * group_stride;
+    const double inv_nm1 = 1.0 / (double)(len - 1);
+    const double* Vj = V0 + (size_t)j * T * L;              // rows j T .. j T + T - 1 of V0 (T' x L)
+    const int total = len * L;
+    for (int idx = tid; idx < total; idx += blockDim.x) {
+        const int pl = idx / L, l = idx - pl * L;
+        const int p = start + pl;
+        const double* y = Y + (size_t)(ys ? ys[p] : p) * T;
+        double v = 0.0;
+        for (int t = 0; t < T; ++t)
+            v = __builtin_fma((y[t] - mean[t]) * rstd[t] * inv_nm1, Vj[(size_t)t * L + l], v);
+        A[afrag_off(rr * Tp + l, p, MT)] = v;
+    }
+}
+
 // Mean-centred PLS: A = (cell-averaging - reference-averaging) weights, so
 // that A . X = cell means minus the mean_centering reference mean
 // (pyls/compute.py:267-357 with means=True).  grid (n_resamples), block 256.

@@ -62,6 +62,19 @@ __device__ __forceinline__ double load_x_buf(const double* rowbase, int voff)
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0));
 }
 
+// v of another lane of the same 16-lane row, chosen by a DPP control (0x120 + n: rotate the row by n lanes; 0x00 .. 0xff:
+// a permutation of every quad, two bits per lane): two v_mov_b32 with a DPP modifier, no LDS round trip.
+template <int CTRL>
+__device__ __forceinline__ double dpp_row_f64(double v)
+{
+    // (every lane has a source under these controls: the `old` operand is never kept, and passing the source itself
+    // spares the move that would initialise it)
+    const int vl = __double2loint(v), vh = __double2hiint(v);
+    const int lo = __builtin_amdgcn_update_dpp(vl, vl, CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(vh, vh, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
 // NSQ = number of second-moment tiles; they are the LAST NSQ tiles of the block
 // (static split: no per-tile operand select in the MFMA loop -- VALU work between
 // fp64 MFMAs costs matrix-pipe issue slots on gfx950, measured 8 %).
@@ -82,6 +95,9 @@ __device__ __forceinline__ double load_x_buf(const double* rowbase, int voff)
 // 9 = second-moment-only block (NSQ == MT: every tile against X^2) writing the RAW m2 of its 16 MT pairs into the
 //     table that holds 1 / std on the other routes (se.scale): the compact bootstrap blocks whose padding rows deliver
 //     m1 (k_xprod_compact, EPI 3 with se.nmu > 0) form 1 / std from the two themselves.
+// 10 = row norms: nothing of R is stored; the block writes sum_col (A . X)^2 of its 64 columns per row (se.acc_sum:
+//     [column block][group][se.accB rows]) -- rotated permutations with a square orthogonal V0 on the fixed-X route,
+//     whose A operand is V0^T A_p (k_build_A_proj): the statistic is the norm of each row of V0^T R_p.
 template <int MT, int NW, int KT, int NSQ, int EPI = 0>
 __global__ __launch_bounds__(NW * 64, 2)
 void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
@@ -229,6 +245,34 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
     // tile W0+j holds m1 of moment row j*16 + kq + 4*i and the same lane / reg
     // of tile SQ0+j holds m2 of that row.  The A stages are dead: reuse LDS.
     constexpr int W0 = (EPI == 9) ? 0 : MT - 2 * NSQ, SQ0 = MT - NSQ, NMOM = NSQ * 16;
+    if constexpr (EPI == 10) {
+        // row norms (projected permutations): the block's share of sum_col acc^2 per row, in a FIXED order -- the 16
+        // lanes of a row group by a butterfly (lane 0 of the group keeps ((c0 + c8) + (c4 + c12)) + ...), then the four
+        // waves through LDS in wave order.  No atomics; one value per row leaves the block: se.acc_sum[colblk][grp][row]
+        // for the se.accB rows of a group that carry resamples.  Columns >= B of X are zero and add zero.
+        static_assert(NSQ == 0 && NW == 4, "EPI 10 is the fixed-X block");
+        double* sP = smem;                                   // [NW][MT * 16] (the A stages are dead)
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // (DPP moves inside the 16-lane row: rotate by 8, by 4, then the quad's lanes ^ 2 and ^ 1.  __shfl_xor
+                // compiles to ds_bpermute here -- 800 LDS round trips a wave, one after the other next to 200 live
+                // accumulator registers: measured 5.6 ms per launch of 504)
+                double q = acc[m][i] * acc[m][i];
+                q += dpp_row_f64<0x128>(q);
+                q += dpp_row_f64<0x124>(q);
+                q += dpp_row_f64<0x4e>(q);
+                q += dpp_row_f64<0xb1>(q);
+                if ((lane & 15) == 0) sP[wave * (MT * 16) + m * 16 + kq + 4 * i] = q;
+            }
+        __syncthreads();
+        const int rows = se.accB;
+        double* pp = se.acc_sum + ((size_t)colblk * n_groups + grp) * rows;
+        for (int row = tid; row < rows; row += NT)
+            pp[row] = ((sP[row] + sP[MT * 16 + row]) + sP[2 * MT * 16 + row]) + sP[3 * MT * 16 + row];
+        return;
+    }
     if constexpr (EPI == 9) {
         // second-moment-only block: tile j holds the raw m2 of pairs j * 16 .. + 15
         static_assert(MT == NSQ, "EPI 9 runs every tile against X^2");

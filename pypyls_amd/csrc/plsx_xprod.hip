@@ -166,6 +166,64 @@ int run_xprod_fixed(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, co
     }
 }
 
+// Projected permutations (perm_projected, plsx_core.hip): the same blocks over the same Xn with the operand
+// A'_r = V0^T A_r and the row-norm epilogue (k_xprod EPI 10) -- out_sv[r][l] = || row l of V0^T R_r || = the rotated
+// singular value l of permutation r when V0 is square and orthogonal.  Nothing here touches the R scratch, the Gram
+// matrices or the small solver: the operand, 1 / 64 of an R of partials, and one finishing kernel.
+template <int KT>
+int launch_xprod_fixed_norms_t(plsx_ctx* ctx, int groups, SplitEpi se, hipStream_t st)
+{
+    constexpr int MT = 25, NW = 4;
+    const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
+    const size_t lds = std::max(stage, (size_t)NW * MT * 16 * 8);
+    HIPCHK(set_lds(k_xprod<MT, NW, KT, 0, 10>, lds));
+    const int ncolblk = ctx->Bpad / (NW * 16);
+    dim3 grid(ncolblk * round_up(groups, 8)), block(NW * 64);
+    KTimer tm(ctx, KC_XPROD, st);
+    hipLaunchKernelGGL((k_xprod<MT, NW, KT, 0, 10>), grid, block, lds, st,
+                       ptr<double>(ctx->Afrag), ctx->group_stride_f, ptr<double>(ctx->Xn), ctx->Bpad,
+                       ctx->nks, (double*)nullptr, ctx->Bpad, ctx->npgf * ctx->Tpp,
+                       (const int*)nullptr, (const int*)nullptr, (const double*)nullptr, 0,
+                       groups, ncolblk, (double*)nullptr, se, 1);
+    LAUNCHCHK();
+    return 0;
+}
+
+int run_xprod_fixed_norms(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, const double* ystack, double* out_sv)
+{
+    const int groups = ceil_div(nres, ctx->npgf), rows = ctx->npgf * ctx->Tp;
+    const int ncolblk = ctx->Bpad / 64;
+    if (int e = ensure(ctx, ctx->Afrag, (size_t)groups * ctx->group_stride_f * 8 + 4096)) return e;
+    if (int e = ensure(ctx, ctx->ppart, (size_t)ncolblk * groups * rows * 8)) return e;
+    if (ctx->timing) ctx->timed_units += nres;
+    ctx->last_compact_n = 0;
+    HIPCHK(hipMemsetAsync(ctx->Afrag.p, 0, (size_t)groups * ctx->group_stride_f * 8, st));
+    {
+        KTimer tm(ctx, KC_BUILD, st);
+        hipLaunchKernelGGL(k_build_A_proj, dim3(nres, ctx->J), dim3(256), (size_t)2 * ctx->T * 8, st,
+                           ystack ? ystack : ptr<double>(ctx->Y), ystack ? (long long)ctx->S * ctx->T : 0LL, ctx->T, ctx->S,
+                           ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), ysrc, ptr<double>(ctx->V0), ctx->L,
+                           ctx->npgf, ctx->Tp, ctx->MTf, ptr<double>(ctx->Afrag), ctx->group_stride_f);
+        LAUNCHCHK();
+    }
+    SplitEpi se;
+    memset(&se, 0, sizeof(se));
+    se.acc_sum = ptr<double>(ctx->ppart); se.accB = rows;
+    int e;
+    switch (stage_ksteps(ctx->nks)) {
+        case 3: e = launch_xprod_fixed_norms_t<3>(ctx, groups, se, st); break;
+        case 2: e = launch_xprod_fixed_norms_t<2>(ctx, groups, se, st); break;
+        default: e = launch_xprod_fixed_norms_t<1>(ctx, groups, se, st); break;
+    }
+    if (e) return e;
+    KTimer tm(ctx, KC_SMALL, st);
+    const long long count = (long long)nres * ctx->Tp;
+    hipLaunchKernelGGL(k_rownorm_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ptr<double>(ctx->ppart),
+                       ncolblk, groups, rows, ctx->npgf, ctx->Tp, nres, out_sv);
+    LAUNCHCHK();
+    return 0;
+}
+
 // Correlation mode, separate-moments layout: data-only blocks (MTd tiles, npg_d resamples) scaled by
 // 1 / std from a table that moment-only blocks (192 (resample, cell) pairs each) write first.
 template <int MT>

@@ -1055,14 +1055,16 @@ class Engine(object):
         """include/plsx.h, plsx_last_timing.  ``urot_waves`` .. ``gram_kernel`` say how the last rotation (k_urot) and Gram pass
         were launched, ``split_blocks`` / ``split_reader`` how the last split-half pass ran; they are recorded whether or
         not timing is on.  ``moment_rows``: 1 when the compact bootstrap blocks of the last launch formed the first
-        moments of the features in their padding rows (option ``no_moment_rows`` forces 0)."""
-        buf = (ctypes.c_double * 22)()
-        n = self.lib.plsx_last_timing(self.ctx, buf, 22)
+        moments of the features in their padding rows (option ``no_moment_rows`` forces 0).  ``perm_projected``: 1 when
+        the last permutation call took the projected route -- singular values from the row norms of (V0^T A_p) X, no R,
+        no Gram pass, no small solver (option ``no_perm_project`` forces 0)."""
+        buf = (ctypes.c_double * 23)()
+        n = self.lib.plsx_last_timing(self.ctx, buf, 23)
         keys = ['xprod_ms', 'xprod_launches', 'resamples_per_group', 'm_tiles', 'superbatch',
                 'xprod_resamples', 'dual_perm', 'compact_row_fraction', 'nt_flops', 'quad_series', 'quad_m_tiles',
                 'quad_blocks_per_lv', 'urot_waves', 'urot_splits', 'urot_res_per_split', 'urot_variant',
                 'gram_chunks', 'urot_variant_last', 'gram_kernel', 'split_blocks', 'split_reader',
-                'moment_rows']
+                'moment_rows', 'perm_projected']
         return {k: buf[i] for i, k in enumerate(keys[:max(n, 0)])}
 
 
