@@ -577,6 +577,58 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           PLSX_ERR_ARG for c outside 1 .. k, a null pointer or
  *                           capacity < 1; PLSX_ERR_STATE without bound regression
  *                           data or before plsx_simpls_set_original.
+ *   plsx_simpls_set_classes / plsx_simpls_cv_class_begin / plsx_simpls_cv_class_end
+ *                           PLS discriminant analysis: the bound Y is the indicator
+ *                           matrix of G = T classes minus its column means over all
+ *                           S rows (the class frequencies n_g / S), and the
+ *                           cross-validation also classifies its test rows.
+ *                           _set_classes binds one class code 0 .. G - 1 per row of
+ *                           the bound regression data, d_class (S,) int32 on the
+ *                           device; the context keeps its own copy.  PLSX_ERR_STATE
+ *                           without bound regression data, PLSX_ERR_ARG for G != T
+ *                           or a code outside 0 .. G - 1 (checked on the host),
+ *                           PLSX_ERR_UNSUPPORTED (context still usable) for G > 32,
+ *                           the bound of the kernel below.  plsx_set_data clears the
+ *                           binding, and so does a null d_class.
+ *                           _begin (after _set_classes) opens a series that rides
+ *                           along the two cross-validation entries, so that no fit is
+ *                           solved twice: while it is open every
+ *                           plsx_simpls_crossval_batch of m splits appends m blocks
+ *                           [k][G][G] of int32 to d_conf in submission order --
+ *                           block[c - 1][g][h] the usable test rows of true class g
+ *                           that the first c components predict as class h -- and
+ *                           every plsx_simpls_crossval_perm_batch of m permutations
+ *                           appends m blocks, each the SUM over that call's n splits
+ *                           (the true class of position p is that of row perm[p];
+ *                           usability as that entry defines it).  The predicted
+ *                           class is the first maximum over g of
+ *                           yhat_c[p][g] = n_g / S + ybar_tr[g] + sum_{j <= c} t_j[p] q_j[g],
+ *                           the prediction the entries score plus the column mean
+ *                           that the centring took away, i.e. the prediction of the
+ *                           RAW indicators (lowest index on a tie: numpy's argmax).  Kernel k_sd_cv_class runs after
+ *                           k_sd_cv_score on the scores that kernel centred in place:
+ *                           one wavefront per fit, lanes over positions; per
+ *                           component count the y-loadings q_c come from the sums of
+ *                           the scores over the training positions of every class
+ *                           (the bound Y being what it is, Y0 = [class] - frequency:
+ *                           one pass over the scores, Y0 is not read; registers,
+ *                           reduced four at a time in fixed order), the running
+ *                           prediction of a position lives in the fit's idle solver
+ *                           scratch, the G x G counters of the open c in the wave's
+ *                           LDS slice, added to the block with integer atomics.  A
+ *                           bound Y that is NOT the indicator matrix of d_class
+ *                           minus its column means gives counts that mean nothing.  A block is zeroed when it is appended; counts
+ *                           are integers, so the result does not depend on the order
+ *                           in which a permutation's splits arrive, on the batch
+ *                           size, the scratch budget or the route of the solver.
+ *                           d_r, d_r2, d_sse / d_mse of both entries keep their bits
+ *                           with the series open.  A call that would pass `capacity`
+ *                           (blocks) returns PLSX_ERR_ARG before it computes
+ *                           anything.  _end, plsx_set_data, plsx_simpls_set_classes
+ *                           and a second _begin end the series (the buffer stays the
+ *                           caller's).  _begin: PLSX_ERR_STATE without bound
+ *                           regression data or before plsx_simpls_set_classes,
+ *                           PLSX_ERR_ARG for a null buffer or capacity < 1.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -601,6 +653,9 @@ int plsx_simpls_coef_perm_test(plsx_ctx* ctx, const double* d_A, long long n, co
 int plsx_simpls_coef_perm_begin(plsx_ctx* ctx, int c, const double* d_obs, int standardise, int32_t* d_count,
                                 double* d_max, long long capacity);
 int plsx_simpls_coef_perm_end(plsx_ctx* ctx);
+int plsx_simpls_set_classes(plsx_ctx* ctx, const int32_t* d_class, int G, void* stream);
+int plsx_simpls_cv_class_begin(plsx_ctx* ctx, int32_t* d_conf, long long capacity);
+int plsx_simpls_cv_class_end(plsx_ctx* ctx);
 int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity);
 int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
                        double* d_sd, double* d_lo, double* d_hi, void* stream);
@@ -691,7 +746,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * k_col_sd of plsx_simpls_coef_perm_test count here too, k_sd_vip under 10 with
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci),
  * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill),
- * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale).
+ * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale),
+ * 15 k_sd_cv_class (the confusion counts of an open plsx_simpls_cv_class_begin series).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

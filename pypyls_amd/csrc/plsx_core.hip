@@ -8,7 +8,8 @@ namespace plsxi {
 
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
-                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm"};
+                                                 "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm",
+                                                 "k_sd_cv_class"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -416,7 +417,7 @@ try {
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
                    &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
-                   &ctx->Cv, &ctx->Cfrag, &ctx->cpart, &ctx->mbpart})
+                   &ctx->Cv, &ctx->Cfrag, &ctx->cpart, &ctx->mbpart, &ctx->cls, &ctx->clsfreq})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     delete ctx;
@@ -549,6 +550,8 @@ try {
     coef_close(ctx);                                   // (an open coefficient series ends with the binding it belonged to)
     vip_close(ctx);                                    // (... and so does a kept VIP stack)
     cperm_close(ctx);                                  // (... and an open permutation series of the coefficients)
+    cls_close(ctx);                                    // (... and the class codes of its rows with their open series)
+    ctx->has_cls = 0;
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;
     HIPCHK(hipMemsetAsync(ctx->status.p, 0, 4 * sizeof(int), st));

@@ -161,6 +161,13 @@ struct plsx_ctx {
     double* cperm_max = nullptr;
     long long cperm_cap = 0, cperm_n = 0;
     Buf cpA, cppart, colsd;
+    // plsx_simpls_set_classes: one class code per row of the bound regression data (the context's own copy), G = T
+    // classes; plsx_simpls_cv_class_begin: a series of confusion counts rides along plsx_simpls_crossval_batch /
+    // plsx_simpls_crossval_perm_batch -- blocks [k][G][G] int32 appended to the caller's buffer (k_sd_cv_class)
+    Buf cls, clsfreq;                                   // the codes [S] and the class frequencies n_g / S [G]
+    int has_cls = 0, cls_active = 0;
+    int* cls_conf = nullptr;
+    long long cls_cap = 0, cls_n = 0;
     bool has_okx = false, has_oky = false;
     int n_okx = 0;                                      // usable rows of X under the row masks (has_okx)
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
@@ -267,7 +274,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -369,6 +376,12 @@ inline void cperm_close(plsx_ctx* ctx)
     ctx->cperm_active = 0; ctx->cperm_c = 0; ctx->cperm_std = 0;
     ctx->cperm_obs = nullptr; ctx->cperm_count = nullptr; ctx->cperm_max = nullptr;
     ctx->cperm_cap = 0; ctx->cperm_n = 0;
+}
+// an open series of confusion counts ends (plsx_set_data, plsx_simpls_set_classes, a second
+// plsx_simpls_cv_class_begin, plsx_simpls_cv_class_end); the buffer stays the caller's
+inline void cls_close(plsx_ctx* ctx)
+{
+    ctx->cls_active = 0; ctx->cls_conf = nullptr; ctx->cls_cap = 0; ctx->cls_n = 0;
 }
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);

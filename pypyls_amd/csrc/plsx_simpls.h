@@ -126,6 +126,12 @@ struct SdArgs {
     // VIP stack (plsx_simpls_vip_keep): k_sd_vip runs on every resample of the batch
     double* vpG;                // [nres][vp_c][S] row a = sqrt(ssq_a / (|w_a|^2 sum_j ssq_j)) . wd_a scattered to subject space (every entry written), or nullptr
     int vp_c;
+    // confusion counts (plsx_simpls_cv_class_begin): k_sd_cv_class runs after k_sd_cv_score on every fit of the batch
+    const int* cls;             // [S] class code 0 .. T - 1 of every row of the bound data
+    const double* cfreq;        // [T] class frequencies n_g / S: the column means the bound, globally centred indicators lost
+    int* conf;                  // blocks [k][T][T] int32, [c][true][predicted]; fit r adds to block (cls_f0 + r) / cls_n - cls_f0 / cls_n
+    long long cls_f0;           // the batch's first fit in the call's pair list (identity route: 0)
+    int cls_n;                  // fits per block: the splits of a permutation (identity route: 1)
 };
 
 // doubles of LDS one wave of k_sd_step needs (on-chip route: the last S of them are the scatter buffer)
@@ -1423,6 +1429,99 @@ void k_sd_cv_score(SdArgs a)
                     out_sse[(size_t)(c0 + u + 1) * T + t] = se[u];
                 }
         }
+    }
+}
+
+// Classification of the test rows of one fit (plsx_simpls_cv_class_begin), after k_sd_cv_score centred Z in place.  The
+// bound Y is the indicator matrix of G = T classes minus its column means over all S rows (a.cfreq = n_g / S), a.cls
+// the class code of every row; so the fit's Y0[g][p] = [class of p is g] - f_g on its training positions, with
+// f_g = ymean[g] + cfreq[g] the class frequency among them, and zero elsewhere.  Per component count c = 1 .. k:
+//     q_c[g]     = sum_p Y0[g][p] z_c[p] = s_g - f_g sum_h s_h,   s_g = sum of z_c over the training positions of class g
+//                  (Y0 is not read: one pass over z_c and the class codes instead of G passes over S doubles each -- the
+//                  batch's Y0, 8 G S bytes per fit, does not stay in cache between the component counts)
+//     yhat_c[p]  = yhat_{c-1}[p] + z_c[p] q_c                  (yhat_0 = f: the prediction k_sd_cv_score scores, plus the
+//                                                               column means that the global centring of the bound
+//                                                               indicators took away -- the classes are read off the
+//                                                               RAW indicators' prediction)
+//     conf[c][class of p][first maximum of yhat_c[p]] += 1     for every usable test position p
+// The first maximum is numpy's argmax: the lowest index on a tie.  One wavefront per fit, lanes over positions.  Where
+// things live: s_g / q_c in GB registers per lane (GB the compile-time bound of G: 4, 16 or 32; reduced four at a time
+// in fixed order), the running prediction of position p in the fit's Z0 rows -- [G][S], idle once the solver is through
+// -- the role of every position (training / usable test, with its class) as one int in the fit's `va`, both touched by
+// the lane that owns p only, and the G x G counters of the open c in the wave's LDS slice (integer atomics: exact in any
+// order).  After each c the non-zero counters are added to the fit's block with integer atomics: under PERM the n
+// splits of a permutation share one block, which was zeroed when it was appended.  PERM as for k_sd_cv_score: rows of
+// Y and their classes go through the fit's `ys`.
+template <int GB, bool PERM>
+static __global__ __launch_bounds__(256)
+void k_sd_cv_class(SdArgs a)
+{
+    __shared__ int sm_cnt[4][GB * GB];
+    const int S = a.S, G = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= a.nres) return;
+    const int* xs = a.xs + (size_t)r * S;
+    const uint8_t* pm = a.pmask + (size_t)r * S;
+    const double* ym = a.ymean + (size_t)r * G;
+    const int* ysp = a.ys + (size_t)r * S;
+    auto yrow = [&](int p) { if constexpr (PERM) return ysp[p]; else return p; };
+    const double* Z = a.cvZ + (size_t)r * k * S;
+    double* yh = a.Z0 + (size_t)r * S * G;
+    int* role = reinterpret_cast<int*>(a.va + (size_t)r * S);                  // (S ints in the fit's S doubles)
+    const long long blk = (a.cls_f0 + r) / a.cls_n - a.cls_f0 / a.cls_n;       // (64-bit, as the pair list itself)
+    int* out = a.conf + (size_t)blk * k * G * G;
+    int* cnt = sm_cnt[wave];
+    // role of position p: its class on a training position, 64 + its class on a usable test position (outside the
+    // training mask and not a masked row), -1 otherwise
+    for (int p = lane; p < S; p += 64) {
+        const bool te = !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[yrow(p)]);
+        role[p] = (xs[p] >= 0 || te) ? (a.cls[yrow(p)] | (te ? 64 : 0)) : -1;
+    }
+    double f[GB];
+#pragma unroll
+    for (int g = 0; g < GB; ++g) f[g] = g < G ? ym[g] + a.cfreq[g] : 0.0;
+    for (int c = 0; c < k; ++c) {
+        const double* zc = Z + (size_t)c * S;
+        double q[GB];
+#pragma unroll
+        for (int g = 0; g < GB; ++g) q[g] = 0.0;
+        for (int p = lane; p < S; p += 64) {
+            const int rl = role[p];
+            const double z = zc[p];
+#pragma unroll
+            for (int g = 0; g < GB; ++g) q[g] += rl == g ? z : 0.0;
+        }
+#pragma unroll
+        for (int g = 0; g < GB; g += 4)
+            if (g < G) wave_sum4(q[g], q[g + 1], q[g + 2], q[g + 3]);
+        double sall = 0.0;
+#pragma unroll
+        for (int g = 0; g < GB; ++g) sall += q[g];
+#pragma unroll
+        for (int g = 0; g < GB; ++g) q[g] -= f[g] * sall;
+        for (int i = lane; i < G * G; i += 64) cnt[i] = 0;
+        wave_sync();
+        for (int p = lane; p < S; p += 64) {
+            const int rl = role[p];
+            if (rl < 64) continue;
+            const double z = zc[p];
+            double best = 0.0;
+            int arg = 0;
+#pragma unroll
+            for (int g = 0; g < GB; ++g)
+                if (g < G) {
+                    const double v = (c == 0 ? f[g] : yh[(size_t)g * S + p]) + z * q[g];
+                    if (c + 1 < k) yh[(size_t)g * S + p] = v;
+                    if (g == 0 || v > best) { best = v; arg = g; }
+                }
+            atomicAdd(&cnt[(rl - 64) * G + arg], 1);
+        }
+        wave_sync();
+        for (int i = lane; i < G * G; i += 64) {
+            const int v = cnt[i];
+            if (v) atomicAdd(&out[(size_t)c * G * G + i], v);
+        }
+        wave_sync();
     }
 }
 

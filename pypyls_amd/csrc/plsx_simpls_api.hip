@@ -417,6 +417,38 @@ static int coef_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 
 }  // namespace plsxi
 
+// The open series of confusion counts (plsx_simpls_cv_class_begin): room for m more blocks, or PLSX_ERR_ARG before
+// anything is computed; the blocks are zeroed here, in stream order before the kernels that count into them.
+static int cls_reserve(plsx_ctx* ctx, const char* who, int m, hipStream_t st)
+{
+    if (ctx->cls_n + m > ctx->cls_cap) {
+        char msg[240];
+        snprintf(msg, sizeof msg, "%s: the open series of confusion counts holds %lld of %lld blocks, %d more do not fit "
+                 "(plsx_simpls_cv_class_begin)", who, ctx->cls_n, ctx->cls_cap, m);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    const size_t blk = (size_t)ctx->ncomp * ctx->T * ctx->T;
+    HIPCHK(hipMemsetAsync(ctx->cls_conf + (size_t)ctx->cls_n * blk, 0, (size_t)m * blk * sizeof(int), st));
+    return 0;
+}
+
+// k_sd_cv_class on the ms fits k_sd_cv_score has just scored: fit r counts into block (f0 + r) / n - f0 / n behind
+// `first`, the block of the batch's first fit.
+template <bool PERM>
+static int cls_launch(plsx_ctx* ctx, SdArgs a, int ms, long long first, long long f0, int n, hipStream_t st)
+{
+    a.cls = ptr<int>(ctx->cls);
+    a.cfreq = ptr<double>(ctx->clsfreq);
+    a.conf = ctx->cls_conf + (size_t)first * a.k * a.T * a.T;
+    a.cls_f0 = f0; a.cls_n = n;
+    KTimer tm(ctx, KC_CVCLASS, st);
+    void (*class_kernel)(SdArgs) = a.T <= 4 ? k_sd_cv_class<4, PERM> : (a.T <= 16 ? k_sd_cv_class<16, PERM>
+                                                                                  : k_sd_cv_class<32, PERM>);
+    hipLaunchKernelGGL(class_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+    LAUNCHCHK();
+    return 0;
+}
+
 extern "C" {
 
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec, double* d_yload,
@@ -506,6 +538,10 @@ try {
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
     const bool gl = simpls_global(ctx);
+    // (an open series of confusion counts that cannot take the call: refused before anything is computed)
+    const bool series = ctx->cls_active != 0;
+    if (series)
+        if (int e = cls_reserve(ctx, "plsx_simpls_crossval_batch", m, st)) return e;
     // solver batches as for the permutations; a split also holds its dense dual weights Vd and Z = Vd . K
     const int nb = std::min(m, sd_batch(ctx, 8192, 1, 2.0 * k * S * 8.0));
     if (int e = ensure(ctx, ctx->spct, (size_t)nb * (T + 1) * k * 8)) return e;     // pctvar [nb][k], y-loadings [nb][T][k]
@@ -533,12 +569,17 @@ try {
         a.cvr = d_r + (size_t)off * k * T;
         a.cvr2 = d_r2 + (size_t)off * k * T;
         a.cvsse = d_sse + (size_t)off * (k + 1) * T;
-        KTimer tm(ctx, KC_CVSCORE, st);
-        // (more waves than two per SIMD of the chip: the three-waves-per-SIMD variant, as in the solver)
-        void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8> : k_sd_cv_score<16>;
-        hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
-        LAUNCHCHK();
+        {
+            KTimer tm(ctx, KC_CVSCORE, st);
+            // (more waves than two per SIMD of the chip: the three-waves-per-SIMD variant, as in the solver)
+            void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8> : k_sd_cv_score<16>;
+            hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+            LAUNCHCHK();
+        }
+        if (series)                                    // one block per split, in submission order
+            if (int e = cls_launch<false>(ctx, a, ms, ctx->cls_n + off, 0, 1, st)) return e;
     }
+    if (series) ctx->cls_n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -557,6 +598,9 @@ try {
     // the pair list: fit f = permutation f / n under split f % n, m n of them (64-bit), cut into solver batches sized
     // as plsx_simpls_crossval_batch sizes its own; a fit also holds its expanded sources and mask (5 S bytes) and
     // its scores until the reduction over the splits
+    const bool series = ctx->cls_active != 0;
+    if (series)
+        if (int e = cls_reserve(ctx, "plsx_simpls_crossval_perm_batch", m, st)) return e;
     const long long fits = (long long)m * n;
     const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T + 1;       // doubles of scores per fit
     const double extra = 2.0 * k * S * 8.0 + 5.0 * S + 8.0 * per_fit;
@@ -609,15 +653,20 @@ try {
             return e;
         a.cvZ = Z;
         a.cvr = fr; a.cvr2 = fr2; a.cvsse = fsse; a.cvnte = fnte;
-        KTimer tm(ctx, KC_CVSCORE, st);
-        void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8, true> : k_sd_cv_score<16, true>;
-        hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
-        LAUNCHCHK();
-        const int touched = (int)((f0 + ms - 1) / n - f0 / n) + 1;
-        hipLaunchKernelGGL(k_sd_cvp_reduce, dim3(ceil_div((int)(2 * kT) + k + 1, 256), touched), dim3(256), 0, st,
-                           fr, fr2, fsse, fnte, k, T, n, f0, ms, d_r, d_r2, d_mse);
-        LAUNCHCHK();
+        {
+            KTimer tm(ctx, KC_CVSCORE, st);
+            void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8, true> : k_sd_cv_score<16, true>;
+            hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+            LAUNCHCHK();
+            const int touched = (int)((f0 + ms - 1) / n - f0 / n) + 1;
+            hipLaunchKernelGGL(k_sd_cvp_reduce, dim3(ceil_div((int)(2 * kT) + k + 1, 256), touched), dim3(256), 0, st,
+                               fr, fr2, fsse, fnte, k, T, n, f0, ms, d_r, d_r2, d_mse);
+            LAUNCHCHK();
+        }
+        if (series)                                    // one block per permutation: its splits add up in it, in any order
+            if (int e = cls_launch<true>(ctx, a, ms, ctx->cls_n + f0 / n, f0, n, st)) return e;
     }
+    if (series) ctx->cls_n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -936,6 +985,70 @@ try {
                                    d_hi + (size_t)f0, st))
             return e;
     }
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_set_classes(plsx_ctx* ctx, const int32_t* d_class, int G, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_set_classes: data not bound for regression");
+    cls_close(ctx);
+    ctx->has_cls = 0;
+    if (!d_class) return PLSX_OK;                      // (a null pointer clears the binding)
+    char msg[200];
+    if (G != ctx->T) {
+        snprintf(msg, sizeof msg, "plsx_simpls_set_classes: G = %d classes, but the bound Y has T = %d indicator columns",
+                 G, ctx->T);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (G > 32) {
+        snprintf(msg, sizeof msg, "plsx_simpls_set_classes: G = %d classes; k_sd_cv_class keeps one y-loading per class "
+                 "in registers and G x G counters per wave in LDS, at most 32 classes", G);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<int32_t> h(ctx->S);
+    HIPCHK(hipMemcpyAsync(h.data(), d_class, (size_t)ctx->S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < ctx->S; ++i)
+        if (h[i] < 0 || h[i] >= G) {
+            snprintf(msg, sizeof msg, "plsx_simpls_set_classes: row %d has class code %d outside 0 .. %d", i, h[i], G - 1);
+            return fail(ctx, PLSX_ERR_ARG, msg);
+        }
+    // the bound Y is the indicator matrix minus its column means over all S rows: the class frequencies n_g / S
+    std::vector<double> freq(G, 0.0);
+    for (int i = 0; i < ctx->S; ++i) freq[h[i]] += 1.0;
+    for (double& f : freq) f /= ctx->S;
+    if (int e = ensure(ctx, ctx->cls, (size_t)ctx->S * 4)) return e;
+    if (int e = ensure(ctx, ctx->clsfreq, (size_t)G * 8)) return e;
+    HIPCHK(hipMemcpyAsync(ctx->cls.p, d_class, (size_t)ctx->S * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->clsfreq.p, freq.data(), (size_t)G * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ctx->has_cls = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cv_class_begin(plsx_ctx* ctx, int32_t* d_conf, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_class_begin: data not bound for regression");
+    if (!ctx->has_cls)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_class_begin: plsx_simpls_set_classes has not been called");
+    cls_close(ctx);
+    if (!d_conf || capacity < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_cv_class_begin: null buffer or capacity < 1");
+    ctx->cls_conf = d_conf; ctx->cls_cap = capacity; ctx->cls_n = 0;
+    ctx->cls_active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cv_class_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    cls_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 

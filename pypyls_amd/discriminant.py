@@ -1,0 +1,205 @@
+"""
+``pls_da``: PLS discriminant analysis -- SIMPLS on the indicator matrix of the class labels, the class of a row read
+off the largest predicted indicator -- with cross-validated accuracy, balanced accuracy and confusion matrices and
+their permutation test.
+
+The model IS ``pls_regression(X, one_hot(y))``: ``pls_da`` validates the labels, codes them and passes everything on to
+that code path, so everything ``pls_regression`` returns (weights, scores, VIP, coefficients with their bootstrap
+ratios, intervals and p-values, the regression scores of the cross-validation) is returned unchanged.  What is added:
+
+  * the train / test splits are stratified by class (``resampling.gen_stratified_splits``);
+  * the (split) and (permutation, split) fits of the cross-validation are classified where they live, on the device
+    (plsx_simpls_set_classes / plsx_simpls_cv_class_begin; csrc/plsx_simpls.h, k_sd_cv_class): only integer confusion
+    counts come back, per split for the observed labels and summed over the splits per permutation;
+  * :func:`predict_class` for new rows.
+
+There is no split-half reliability (``n_split``) here: the correlation between two halves of indicator loadings answers
+no question anyone asks of a classifier.  Nor ``rotate`` / ``aggfunc`` / 3-D Y, which have no meaning for labels.
+"""
+import numpy as np
+
+from .regression import _usable_rows, pls_regression, predict
+
+MAX_CLASSES = 32            # the bound of k_sd_cv_class (plsx_simpls_set_classes: PLSX_ERR_UNSUPPORTED beyond it)
+
+
+def scores_from_confusion(conf):
+    """conf (G, G, ...) counts, [true class, predicted class, ...] -> (accuracy, balanced_accuracy), each of shape ``...``.
+
+    ``accuracy = trace / total``; ``balanced_accuracy`` is the mean, over the classes that have at least one counted
+    row, of ``conf[g, g] / conf[g, :].sum()`` (the recall of class g) -- a class without a counted row is left out of
+    the mean, it does not count as a recall of zero.  No counted row at all gives NaN."""
+    conf = np.asarray(conf)
+    if conf.ndim < 2 or conf.shape[0] != conf.shape[1]:
+        raise ValueError('Expected confusion counts of shape (G, G, ...), got {}'.format(conf.shape))
+    conf = conf.astype(np.float64)
+    hits = np.einsum('gg...->g...', conf)                            # (G, ...)
+    per_class = conf.sum(axis=1)                                     # (G, ...) counted rows of every true class
+    with np.errstate(divide='ignore', invalid='ignore'):
+        accuracy = hits.sum(axis=0) / per_class.sum(axis=0)
+        present = per_class > 0
+        recall = np.where(present, hits / np.where(present, per_class, 1.0), 0.0)
+        balanced = recall.sum(axis=0) / present.sum(axis=0)
+    return accuracy, balanced
+
+
+def pvals_from_null(observed, null):
+    """``(#{null >= observed} + 1) / (P + 1)`` along the last axis of ``null`` (..., P).  ``>=``, not the strict ``>`` of
+    ``cvres.pearson_r_pvals``: accuracy is a ratio of small integers, an exact tie between a permutation and the observed
+    labels has positive probability, and counting it as "not at least as good" would be anti-conservative."""
+    observed, null = np.asarray(observed, dtype=np.float64), np.asarray(null, dtype=np.float64)
+    return (np.sum(null >= observed[..., None], axis=-1) + 1) / (null.shape[-1] + 1)
+
+
+def confusion_results(blocks, perm_blocks=None):
+    """The keys ``pls_da`` adds to ``cvres`` from what the device counted: blocks (n, k, G, G) per split and, with
+    ``cv_perm``, perm_blocks (P, k, G, G) summed over the splits of every permutation (float64 holding integers)."""
+    conf = np.ascontiguousarray(np.rint(np.asarray(blocks)).astype(np.int64).transpose(2, 3, 1, 0))    # (G, G, k, n)
+    acc, bal = scores_from_confusion(conf)
+    out = dict(confusion=conf, accuracy=acc, balanced_accuracy=bal)
+    if perm_blocks is not None:
+        pconf = np.ascontiguousarray(np.rint(np.asarray(perm_blocks)).astype(np.int64).transpose(2, 3, 1, 0))
+        pacc, pbal = scores_from_confusion(pconf)
+        # the pooled statistic: the same functional of the observed data, the confusion summed over the splits
+        oacc, obal = scores_from_confusion(conf.sum(axis=-1))
+        out.update(perm_confusion=pconf, perm_accuracy=pacc, perm_balanced_accuracy=pbal,
+                   accuracy_pvals=pvals_from_null(oacc, pacc), balanced_accuracy_pvals=pvals_from_null(obal, pbal))
+    return out
+
+
+def encode_labels(y, S=None):
+    """y (S,) labels -> (classes (G,) sorted distinct labels, codes (S,) int64 positions in it).  ValueError for a y that
+    is not 1-D (or not of length S), a NaN or None label, fewer than 2 or more than 32 classes."""
+    y = np.asarray(y)
+    if y.ndim != 1 or (S is not None and len(y) != S):
+        raise ValueError('Provided `y` must be a 1-D array of one label per row of `X`{}; got shape {}'
+                         .format('' if S is None else ' ({} rows)'.format(S), y.shape))
+    if y.dtype == object:
+        if any(v is None or (isinstance(v, (float, np.floating)) and np.isnan(v)) for v in y):
+            raise ValueError('Provided `y` holds a None or NaN label; drop or label such rows before the call')
+    elif y.dtype.kind in 'fc' and np.isnan(y).any():
+        raise ValueError('Provided `y` holds a NaN label; drop or label such rows before the call')
+    try:
+        classes, codes = np.unique(y, return_inverse=True)
+    except TypeError as exc:
+        raise ValueError('Provided `y` holds labels that cannot be sorted: {}'.format(exc)) from exc
+    G = len(classes)
+    if G < 2:
+        raise ValueError('Provided `y` holds {} distinct label(s); a discriminant analysis needs at least 2 classes'
+                         .format(G))
+    if G > MAX_CLASSES:
+        raise ValueError('Provided `y` holds {} distinct labels; at most {} classes are supported, the bound of the '
+                         'device\'s classification kernel (k_sd_cv_class)'.format(G, MAX_CLASSES))
+    return classes, codes.reshape(-1).astype(np.int64)
+
+
+def _label(classes, g):
+    """Label g as a plain Python value, for messages."""
+    return classes[g].item() if hasattr(classes[g], 'item') else classes[g]
+
+
+def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamples=None, bootsamples=None, seed=None,
+           verbose=True, n_proc=None, test_split=0, test_size=0.25, cvsamples=None, cv_perm=0, cvpermsamples=None,
+           coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, **kwargs):
+    """PLS discriminant analysis of the labels ``y`` (S,) on ``X`` (S, B).
+
+    ``classes = np.unique(y)`` (integers, strings, booleans: anything numpy sorts), ``codes`` the position of every
+    label in it, G = len(classes), 2 <= G <= 32.  The model is ``pls_regression(X, Y)`` with ``Y = one_hot(codes)``,
+    (S, G) float64: every keyword above means what it means there and goes to the same code path, and every key that
+    call returns is returned unchanged -- for the same ``cvsamples`` / ``cvpermsamples`` bit for bit.  ``vip_components``
+    gives the usual feature-importance score of PLS-DA, ``coef_components`` the model :func:`predict_class` applies.
+    Added to the result: ``classes``.
+
+    Cross-validation (``test_split`` > 0): the splits are STRATIFIED -- drawn with ``gen_splits(counts, 1, test_split,
+    test_size=test_size)`` on the rows in class-sorted order (a stable argsort of the codes, ``counts`` the class sizes)
+    and scattered back, at the place in the call's random stream where ``pls_regression`` draws its own, so every class
+    keeps ceil or floor of ``n_g (1 - test_size)`` training rows -- or given as ``cvsamples``.  For a split and a
+    component count c the predicted class of a usable test row is the first maximum (``np.argmax``: the lowest index on a
+    tie) of its predicted indicators ``yhat_c`` -- training mean plus the first c scores times their y-loadings, the
+    prediction ``cvres.pearson_r_ncomp`` scores.  ``cvres`` gains
+
+        confusion          (G, G, k, test_split) int   [true class, predicted class, c - 1, split]
+        accuracy           (k, test_split)             trace / total
+        balanced_accuracy  (k, test_split)             mean recall over the classes with a counted test row
+
+    (:func:`scores_from_confusion`).  Rows of X that are NaN throughout belong to neither side and are counted nowhere.
+
+    ``cv_perm=P``: the true class of position p under a permutation is ``codes[perm[p]]``.  The device returns, per
+    permutation, the confusion SUMMED over the splits, and ``cvres`` gains ``perm_confusion`` (G, G, k, P),
+    ``perm_accuracy`` / ``perm_balanced_accuracy`` (k, P) = ``scores_from_confusion(perm_confusion)`` -- the pooled
+    statistic -- and ``accuracy_pvals`` / ``balanced_accuracy_pvals`` (k,), which compare them with the same functional
+    of the observed data, ``scores_from_confusion(confusion.sum(-1))``, as ``(#{null >= observed} + 1) / (P + 1)``.  The
+    comparison is ``>=``, not the strict ``>`` of ``pearson_r_pvals``: accuracy is discrete, exact ties have positive
+    probability, and ``>`` would be anti-conservative.  Every statistic is a function of integer counts: the result does
+    not depend on batch sizes, the scratch budget or the number of GPUs.
+
+    Not offered: ``n_split`` (split-half reliability of indicator loadings answers no question), ``rotate``, ``aggfunc``
+    and 3-D Y.  Bootstraps resample rows as ``pls_regression`` does (not stratified).
+
+    ValueError, before any engine is created or looked up: a ``y`` that is not 1-D of length S; a NaN or None label;
+    fewer than 2 or more than 32 classes (the bound of the device kernel k_sd_cv_class); a class with fewer than 2
+    usable rows; a ``test_size`` that can leave a class without a usable training row; ``cvsamples`` whose training
+    side lacks a usable row of some class; ``n_split``, ``aggfunc`` or ``rotate`` given; and everything
+    ``pls_regression`` refuses."""
+    for name in ('n_split', 'aggfunc', 'rotate'):
+        if name in kwargs:
+            raise ValueError('`pls_da` takes no `{}`: split-half reliability, aggregation of a 3-D Y and rotation are '
+                             'not part of a discriminant analysis'.format(name))
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError('Expected 2D array for `X`, got {}D array instead'.format(X.ndim))
+    S = len(X)
+    classes, codes = encode_labels(y, S)
+    G = len(classes)
+    onehot = np.zeros((S, G), dtype=np.float64)
+    onehot[np.arange(S), codes] = 1.0
+    usable = _usable_rows(X, onehot)
+    n_g = np.bincount(codes, minlength=G)
+    ok_g = np.bincount(codes[usable], minlength=G)
+    if ok_g.min() < 2:
+        g = int(ok_g.argmin())
+        raise ValueError('Every class needs at least 2 usable rows; class {!r} has {} ({} of its {} rows are NaN '
+                         'throughout)'.format(_label(classes, g), int(ok_g[g]), int(n_g[g] - ok_g[g]), int(n_g[g])))
+    n_cv = int(test_split or 0) if (test_size or 0) > 0 else 0
+    if n_cv > 0 and 0 < test_size < 1:
+        if cvsamples is not None:
+            masks = np.asarray(cvsamples)
+            if masks.ndim == 2 and masks.shape == (S, n_cv):           # (any other shape: pls_regression's own message)
+                tr = masks.astype(bool) & usable[:, None]
+                per = np.stack([tr[codes == g].sum(axis=0) for g in range(G)])      # (G, n) usable training rows
+                if per.min() < 1:
+                    g, s = np.unravel_index(int(per.argmin()), per.shape)
+                    raise ValueError('Every cross-validation split needs a usable training row of every class; split {} '
+                                     'of `cvsamples` has none of class {!r}'.format(int(s), _label(classes, g)))
+        else:
+            # the stratified draw keeps ceil or floor of n_g (1 - test_size) training rows of class g; whichever side
+            # the masked rows of the class fall on, one usable training row must remain: the worst case is checked
+            lo = np.floor(n_g * (1 - test_size)).astype(int) - (n_g - ok_g)
+            if lo.min() < 1:
+                g = int(lo.argmin())
+                raise ValueError('Every cross-validation split needs a usable training row of every class; test_size = '
+                                 '{} can leave class {!r} ({} rows, {} of them NaN throughout) without one'
+                                 .format(test_size, _label(classes, g), int(n_g[g]), int(n_g[g] - ok_g[g])))
+    res = pls_regression(X, onehot, n_components=n_components, n_perm=n_perm, n_boot=n_boot, ci=ci,
+                         permsamples=permsamples, bootsamples=bootsamples, seed=seed, verbose=verbose, n_proc=n_proc,
+                         test_split=test_split, test_size=test_size, cvsamples=cvsamples, cv_perm=cv_perm,
+                         cvpermsamples=cvpermsamples, coef_components=coef_components, coef_ci=coef_ci,
+                         coef_perm=coef_perm, vip_components=vip_components, _classes=codes, **kwargs)
+    res['classes'] = classes
+    return res
+
+
+def predict_class(results, X_new, n_components=None):
+    """The predicted class (S_new,) of new rows ``X_new`` (S_new, B) under a ``pls_da`` result:
+    ``results.classes[np.argmax(predict(results, X_new, n_components), axis=1)]`` -- the first maximum of the predicted
+    indicators.  Works on any ``pls_da`` result :func:`predict` works on, also one read back by ``load_results``;
+    ``n_components`` as there.  ValueError for a result without ``classes``."""
+    classes = results.get('classes') if hasattr(results, 'get') else None
+    if classes is None:
+        raise ValueError('`results` is not a pls_da result: it holds no `classes`')
+    classes = np.asarray(classes)
+    yhat = predict(results, X_new, n_components)
+    if yhat.shape[1] != len(classes):
+        raise ValueError('`results.classes` holds {} labels but the model predicts {} indicators'
+                         .format(len(classes), yhat.shape[1]))
+    return classes[np.argmax(yhat, axis=1)]

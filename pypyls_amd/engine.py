@@ -100,6 +100,9 @@ def _load():
         'plsx_simpls_coef_perm_test': ([vp, vp, ctypes.c_longlong, vp, i32, vp, vp, vp], i32),
         'plsx_simpls_coef_perm_begin': ([vp, i32, vp, i32, vp, vp, ctypes.c_longlong], i32),
         'plsx_simpls_coef_perm_end': ([vp], i32),
+        'plsx_simpls_set_classes': ([vp, vp, i32, vp], i32),
+        'plsx_simpls_cv_class_begin': ([vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_cv_class_end': ([vp], i32),
         'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
         'plsx_simpls_vip_ci': ([vp, vp, ctypes.c_longlong, i32, i32, c_d, i32, c_d, vp, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
@@ -138,6 +141,7 @@ def exported_symbols():
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
              'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
+             'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
@@ -927,6 +931,37 @@ class Engine(object):
     def simpls_coef_perm_end(self):
         """Close the permutation series of the coefficients (plsx_simpls_coef_perm_end)."""
         self._check(self.lib.plsx_simpls_coef_perm_end(self.ctx))
+
+    def simpls_set_classes(self, codes):
+        """Bind one class code 0 .. T - 1 per row of the bound regression data, whose Y is the centred indicator matrix
+        of those T classes (plsx_simpls_set_classes); ``None`` clears the binding.  PlsxError: status -1 for a code
+        outside the range, -2 (context still usable) for more than 32 classes."""
+        if codes is None:
+            self._check(self.lib.plsx_simpls_set_classes(self.ctx, None, 0, self._stream()))
+            return
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if codes.shape != (self.S,):
+            raise ValueError('class codes must have shape ({},); got {}'.format(self.S, codes.shape))
+        dev = _torch().from_numpy(codes).to(self.device)
+        self._check(self.lib.plsx_simpls_set_classes(self.ctx, dev.data_ptr(), self.T, self._stream()))
+
+    def simpls_cv_class_begin(self, conf_dev):
+        """Open a series of confusion counts: until :meth:`simpls_cv_class_end` every :meth:`simpls_crossval_into` of m
+        splits appends m blocks (k, T, T) -- [c - 1, true class, predicted class] over the usable test rows -- to
+        ``conf_dev`` (capacity, k, T, T) int32 in submission order, and every :meth:`simpls_crossval_perm_into` of m
+        permutations m blocks, each summed over that call's splits (plsx_simpls_cv_class_begin).  The tensor must stay
+        alive until the series ends.  PlsxError: status -4 before :meth:`simpls_set_classes`, -1 from the call that
+        would pass the capacity."""
+        torch = _torch()
+        if conf_dev.dim() != 4 or tuple(conf_dev.shape[1:]) != (self.k, self.T, self.T) or conf_dev.dtype != torch.int32 \
+                or not conf_dev.is_contiguous():
+            raise ValueError('the confusion counts must be a contiguous (capacity, {}, {}, {}) int32 tensor'
+                             .format(self.k, self.T, self.T))
+        self._check(self.lib.plsx_simpls_cv_class_begin(self.ctx, conf_dev.data_ptr(), int(conf_dev.shape[0])))
+
+    def simpls_cv_class_end(self):
+        """Close the series of confusion counts (plsx_simpls_cv_class_end)."""
+        self._check(self.lib.plsx_simpls_cv_class_end(self.ctx))
 
     def simpls_vip_keep(self, stack):
         """Keep the VIP stack of every bootstrap the :meth:`simpls_boot_into` calls that follow solve: ``stack``

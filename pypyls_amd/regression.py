@@ -49,6 +49,9 @@ Differences from the reference at this commit, on purpose:
     x_weights and y_loadings of SIMPLS in place of the singular vectors, for the observed data and for every
     permutation, in dual space -- no pass over the features (plsx_simpls_split_half_batch; csrc/plsx_simpls.h,
     k_sd_sh_prep / k_sd_sh_expand / k_sd_sh_score).
+  * ``_classes`` (build-only, set by :func:`pypyls_amd.discriminant.pls_da`): Y is the indicator matrix of these class
+    codes; the splits are drawn stratified and the cross-validation also returns confusion counts
+    (plsx_simpls_set_classes / plsx_simpls_cv_class_begin; csrc/plsx_simpls.h, k_sd_cv_class).
 """
 import warnings
 
@@ -351,6 +354,11 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             n_bad = int((~_usable_rows(X, Y_agg)).sum())
             lo_tr = int(np.floor(S * (1 - test_size))) - n_bad
             lo_te = S - int(np.ceil(S * (1 - test_size))) - n_bad
+            if kwargs.get('_classes') is not None:
+                # (pls_da: the draw is stratified, every class keeps ceil or floor of ITS n_g (1 - test_size) rows)
+                n_g = np.bincount(np.asarray(kwargs['_classes']))
+                lo_tr = int(np.floor(n_g * (1 - test_size)).sum()) - n_bad
+                lo_te = S - int(np.ceil(n_g * (1 - test_size)).sum()) - n_bad
             if lo_te < 2:
                 raise ValueError('Every cross-validation split needs at least 2 usable test rows; test_size = {} can '
                                  'leave {} of {} ({} rows are NaN throughout)'.format(test_size, max(lo_te, 0), S, n_bad))
@@ -452,11 +460,14 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             bstream = resampling.IndexStream.of_array(check_index_array(bs, S))
     cv = None
     if n_cv > 0:
-        cv = dict(n=n_cv, masks=cvmasks)
+        cv = dict(n=n_cv, masks=cvmasks, classes=kwargs.get('_classes'))
         if cvmasks is None:
             # one more job at the END of the list: what a seeded call drew before, it draws still
             def cv_draw(r):
-                cv['masks'] = resampling.gen_splits([S], 1, n_cv, seed=r, test_size=test_size)
+                if cv['classes'] is not None:              # (pls_da: stratified by the class codes, at the same place)
+                    cv['masks'] = resampling.gen_stratified_splits(cv['classes'], n_cv, seed=r, test_size=test_size)
+                else:
+                    cv['masks'] = resampling.gen_splits([S], 1, n_cv, seed=r, test_size=test_size)
             jobs.append(cv_draw)
         if cv_perm > 0:
             # ... and the permutations of the cross-validation one more, behind the split masks
@@ -556,6 +567,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         eng.set_data_regression(np.nan_to_num(Xc), np.nan_to_num(Yc), k)
         if masked:
             eng.simpls_set_row_masks(okx, oky)
+    classes = cv.get('classes') if cv is not None else None
+    if classes is not None:
+        # pls_da: Y is the indicator matrix of these class codes; the cross-validation below also classifies its test
+        # rows (plsx_simpls_set_classes / plsx_simpls_cv_class_begin: the confusion counts ride along the batch calls)
+        eng.simpls_set_classes(classes)
     res = PLSResults(inputs=inputs)
     tick('h2d_and_bind')
 
@@ -666,11 +682,16 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             st.warn()
     # cross-validation: this rank's contiguous shard of the splits (the masks exist once the draws are through), in
     # calls of at most one solver batch
-    d_cv = None
+    d_cv = d_conf = d_confp = None
     if cv is not None:
         cvmasks = cv['masks']
         lo, hi = parallel.shard_bounds(cv['n'], rank, world)
         d_cv = [eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k + 1, T))]
+        if classes is not None:
+            # the observed series: one block of confusion counts per split of this rank's shard
+            d_conf = torch.zeros((hi - lo, k, T, T), dtype=torch.int32, device=eng.device)
+            if hi > lo:
+                eng.simpls_cv_class_begin(d_conf)
         bars.append(Bar('Running cross-validation', hi - lo, show, eng.device))
         for a in range(lo, hi, 8192):
             b = min(hi, a + 8192)
@@ -679,6 +700,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             for done in bars:
                 done.poll()
             bars[-1].queued(b - a)
+        if d_conf is not None:
+            eng.simpls_cv_class_end()
         tick('crossval')
     # ... and its permutation test: this rank's contiguous shard of the permutations under ALL the splits.  The
     # (permutation, split) fits are formed, scored and reduced over the splits on the device; a rank keeps three rows
@@ -690,6 +713,12 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         d_cvp = [eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k + 1))]
         bars.append(Bar('Running cross-validation permutations', hi - lo, show, eng.device))
         dm_all = torch.from_numpy(np.ascontiguousarray(cv['masks'].T, dtype=np.uint8)).to(eng.device)
+        if classes is not None:
+            # the permutation series, opened after the observed one has ended: one block per permutation of this rank's
+            # shard, summed over the splits on the device
+            d_confp = torch.zeros((hi - lo, k, T, T), dtype=torch.int32, device=eng.device)
+            if hi > lo:
+                eng.simpls_cv_class_begin(d_confp)
         step = max(1, 65536 // cv['n'])
         for a in range(lo, hi, step):
             b = min(hi, a + step)
@@ -698,6 +727,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             for done in bars:
                 done.poll()
             bars[-1].queued(b - a)
+        if d_confp is not None:
+            eng.simpls_cv_class_end()
         if lead and cv.get('perm_given') is None:
             cvp.warn()
         tick('crossval_perm')
@@ -752,6 +783,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         slices, totals = slices + d_cvp, totals + [cvp.n] * 3
     if d_sh is not None:                                # ... and the two rows per permutation of the split-half means
         slices, totals = slices + d_sh, totals + [n_perm_tot] * 2
+    if d_conf is not None:                              # ... and the confusion counts of pls_da, as float64: they are exact
+        slices, totals = slices + [d_conf.to(torch.float64)], totals + [cv['n']]
+    if d_confp is not None:
+        slices, totals = slices + [d_confp.to(torch.float64)], totals + [cvp.n]
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
@@ -815,6 +850,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 r_squared_pvals=hostmath.perm_sig(obs_r2.ravel(), null_r2.reshape(T * k, P)).reshape(T, k),
                 mse_pvals=hostmath.perm_sig(-obs_mse, -null_mse),          # (smaller is better: #{null < observed})
                 cvpermsamples=np.asarray(cv['perm_given']) if cv.get('perm_given') is not None else cvp.samples))
+        if d_conf is not None:
+            from .discriminant import confusion_results
+            j = i + 3 + (3 if d_cvp is not None else 0) + (2 if d_sh is not None else 0)
+            res['cvres'].update(confusion_results(full[j], full[j + 1] if d_confp is not None else None))
     if d_sh0 is not None:
         orig_uc, orig_vc = (t.cpu().numpy()[0] for t in d_sh0)
         res['splitres'].update(dict(ucorr=orig_uc, vcorr=orig_vc))

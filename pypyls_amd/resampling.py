@@ -258,6 +258,20 @@ def gen_splits(groups, n_cond, n_split, seed=None, test_size=0.5):
     return _py_gen_splits(groups, n_cond, n_split, rs, test_size)
 
 
+def gen_stratified_splits(codes, n_split, seed=None, test_size=0.25):
+    """(S, n_split) boolean train / test masks (True = training row) stratified by the class codes 0 .. G - 1 of the
+    rows: ``gen_splits(counts, 1, n_split, seed, test_size)`` on the rows in class-sorted order (a stable argsort of
+    ``codes``; ``counts`` the class sizes), scattered back to the caller's row order.  Every class keeps ceil or floor of
+    ``n_g (1 - test_size)`` training rows (``pls_da``)."""
+    codes = np.asarray(codes)
+    order = np.argsort(codes, kind='stable')
+    counts = np.bincount(codes)
+    sorted_masks = gen_splits([int(c) for c in counts if c > 0], 1, n_split, seed=seed, test_size=test_size)
+    out = np.empty_like(sorted_masks)
+    out[order] = sorted_masks
+    return out
+
+
 def gen_splits_seeded(groups, n_cond, n_split, seeds, test_size=0.5, rows=False, warn=True):
     """Split masks of many independent streams: element i equals
     ``gen_splits(groups, n_cond, n_split, seed=seeds[i], test_size)`` -- what

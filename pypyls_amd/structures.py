@@ -99,6 +99,7 @@ class PLSInputs(KeyedRecord):
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
+        '_classes',                         # pls_da: class code of every row (Y is their indicator matrix)
     )
 
     def __init__(self, **kwargs):
@@ -154,7 +155,12 @@ class PLSCrossValidationResults(KeyedRecord):
     # (T, k, P), perm_mse (k + 1, P) -- its p-values (T, k), (T, k), (k + 1,) and the permutations (S, P)
     allowed = ('pearson_r', 'r_squared', 'pearson_r_ncomp', 'r_squared_ncomp', 'mse', 'cvsamples',
                'perm_pearson_r', 'perm_r_squared', 'perm_mse', 'pearson_r_pvals', 'r_squared_pvals', 'mse_pvals',
-               'cvpermsamples')
+               'cvpermsamples',
+               # pls_da: confusion (G, G, k, n) int [true, predicted, c - 1, split], accuracy / balanced_accuracy (k, n);
+               # with cv_perm=P: perm_confusion (G, G, k, P) summed over the splits of a permutation, perm_accuracy /
+               # perm_balanced_accuracy (k, P) of that sum, accuracy_pvals / balanced_accuracy_pvals (k,)
+               'confusion', 'accuracy', 'balanced_accuracy', 'perm_confusion', 'perm_accuracy',
+               'perm_balanced_accuracy', 'accuracy_pvals', 'balanced_accuracy_pvals')
 
 
 class PLSResults(KeyedRecord):
@@ -165,7 +171,9 @@ class PLSResults(KeyedRecord):
                # pls_regression(coef_components=c): Y ~ intercept (T,) + X @ coefs (B, T)
                'coefs', 'intercept',
                # pls_regression(vip_components=c): (B,) variable importance in projection of the c-component model
-               'vip')
+               'vip',
+               # pls_da: (G,) the sorted distinct labels; column g of Y is the indicator of classes[g]
+               'classes')
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
