@@ -262,10 +262,28 @@ static __global__ void k_build_A_behav(const double* __restrict__ Y0, long long 
 // Projected permutations (fixed-X route, L == T', every original LV live): the operand A'_r = V0^T A_r of resample r,
 // cell j, in the fragment order and group layout of the fixed-X blocks (n resamples of T' rows per group).  Column p
 // of A_r holds the z-scored behaviours of the row of Y placed at p, in the T rows of p's cell and nowhere else, so
-//   A'[rr * T' + l][p] = sum_t V0[j T + t][l] * zscore(Y[ysrc[p]][t]) / (n_j - 1),   t ascending: one thread per entry,
-// a fixed summation order, one writer.  mean / std exactly as k_build_A_behav forms them for a permutation (xsrc ==
-// nullptr, correlation mode).  The caller zeroed the operand: rows >= T' of the last tile and the slots of a partly
-// filled last group stay zero.  grid (n_resamples, J), block 256; dynamic LDS: 2 T doubles.
+//   A'[rr * T' + l][p] = sum_t V0[j T + t][l] * zscore(Y[ysrc[p]][t]) / (n_j - 1),   t ascending: a fixed summation
+// order, one writer per entry.  mean / std exactly as k_build_A_behav forms them for a permutation (xsrc == nullptr,
+// correlation mode).  The scaled z-score of a (row, behaviour) does not depend on l: the cell's rows go through LDS
+// in chunks of `ch` rows (a multiple of 4) -- the chunk's ch x T scaled z-scores are written once, then a thread
+// forms entry l of four rows at a time (one read of V0 per four fma), against the cell's T x L block of V0 in LDS
+// (VLDS) or, where that block is too large, in global memory.  Nothing outlives the launch.  The caller zeroed the
+// operand: rows >= T' of the last tile and the slots of a partly filled last group stay zero.
+// grid (n_resamples, J), block 256; dynamic LDS: build_A_proj_lds(T, L) bytes, ch = build_A_proj_chunk(T, L) (64 up
+// to T = 52 at L = T; 52 at T = L = 55; from T L > 3072 on the block of V0 stays in global memory).
+#define PLSX_PROJ_LDS_DOUBLES 6144     // 48 KB a block: three blocks per CU
+__host__ __device__ constexpr bool build_A_proj_vlds(int T, int L) { return T * L <= PLSX_PROJ_LDS_DOUBLES / 2; }
+__host__ __device__ constexpr int build_A_proj_chunk(int T, int L)
+{
+    const int room = (PLSX_PROJ_LDS_DOUBLES - 2 * T - (build_A_proj_vlds(T, L) ? T * L : 0)) / T;
+    return room >= 64 ? 64 : room < 4 ? 4 : room & ~3;
+}
+__host__ __device__ constexpr size_t build_A_proj_lds(int T, int L)
+{
+    return ((size_t)2 * T + (size_t)build_A_proj_chunk(T, L) * T + (build_A_proj_vlds(T, L) ? (size_t)T * L : 0)) * 8;
+}
+
+template <bool VLDS>
 static __global__ __launch_bounds__(256)
 void k_build_A_proj(const double* __restrict__ Y0, long long y_stride, int T, int S,
                     const int* __restrict__ cell_start, const int* __restrict__ cell_len,
@@ -278,9 +296,15 @@ void k_build_A_proj(const double* __restrict__ Y0, long long y_stride, int T, in
     const double* Y = Y0 + (size_t)r * y_stride;
     const int start = cell_start[j], len = cell_len[j];
     const int* ys = ysrc ? ysrc + (size_t)r * S : nullptr;
+    const int ch = build_A_proj_chunk(T, L);
     double* mean = sm_b;            // [T]
     double* rstd = sm_b + T;        // [T]
+    double* sZ = sm_b + 2 * T;      // [ch][T]: (y - mean) * rstd / (n_j - 1) of the chunk's rows
+    double* sV = sZ + ch * T;       // [T][L]: rows j T .. j T + T - 1 of V0 (T' x L)
+    const double* Vj = V0 + (size_t)j * T * L;
     const int tid = threadIdx.x;
+    if (VLDS)
+        for (int i = tid; i < T * L; i += blockDim.x) sV[i] = Vj[i];
     for (int t = tid; t < T; t += blockDim.x) {
         double s = 0.0;
         for (int p = start; p < start + len; ++p) s += Y[(size_t)(ys ? ys[p] : p) * T + t];
@@ -296,16 +320,33 @@ void k_build_A_proj(const double* __restrict__ Y0, long long y_stride, int T, in
     __syncthreads();
     double* A = Afrag + (size_t)g * group_stride;
     const double inv_nm1 = 1.0 / (double)(len - 1);
-    const double* Vj = V0 + (size_t)j * T * L;              // rows j T .. j T + T - 1 of V0 (T' x L)
-    const int total = len * L;
-    for (int idx = tid; idx < total; idx += blockDim.x) {
-        const int pl = idx / L, l = idx - pl * L;
-        const int p = start + pl;
-        const double* y = Y + (size_t)(ys ? ys[p] : p) * T;
-        double v = 0.0;
-        for (int t = 0; t < T; ++t)
-            v = __builtin_fma((y[t] - mean[t]) * rstd[t] * inv_nm1, Vj[(size_t)t * L + l], v);
-        A[afrag_off(rr * Tp + l, p, MT)] = v;
+    const double* Vs = VLDS ? sV : Vj;
+    for (int c0 = 0; c0 < len; c0 += ch) {
+        const int nr = min(ch, len - c0);
+        for (int idx = tid; idx < nr * T; idx += blockDim.x) {
+            const int pl = idx / T, t = idx - pl * T;
+            const int p = start + c0 + pl;
+            sZ[idx] = (Y[(size_t)(ys ? ys[p] : p) * T + t] - mean[t]) * rstd[t] * inv_nm1;
+        }
+        __syncthreads();
+        // rows 4 q .. 4 q + 3 of the chunk, entry l; the rows of the last four beyond nr read what an earlier chunk
+        // left (or nothing yet) inside sZ and are not stored
+        const int nq = (nr + 3) >> 2;
+        for (int idx = tid; idx < nq * L; idx += blockDim.x) {
+            const int q = idx / L, l = idx - q * L;
+            const double* z = sZ + (size_t)q * 4 * T;
+            double v[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int t = 0; t < T; ++t) {
+                const double w = Vs[(size_t)t * L + l];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = __builtin_fma(z[i * T + t], w, v[i]);
+            }
+            const int p0 = start + c0 + q * 4;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (q * 4 + i < nr) A[afrag_off(rr * Tp + l, p0 + i, MT)] = v[i];
+        }
+        __syncthreads();
     }
 }
 

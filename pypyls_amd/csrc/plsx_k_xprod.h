@@ -62,19 +62,6 @@ __device__ __forceinline__ double load_x_buf(const double* rowbase, int voff)
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0));
 }
 
-// v of another lane of the same 16-lane row, chosen by a DPP control (0x120 + n: rotate the row by n lanes; 0x00 .. 0xff:
-// a permutation of every quad, two bits per lane): two v_mov_b32 with a DPP modifier, no LDS round trip.
-template <int CTRL>
-__device__ __forceinline__ double dpp_row_f64(double v)
-{
-    // (every lane has a source under these controls: the `old` operand is never kept, and passing the source itself
-    // spares the move that would initialise it)
-    const int vl = __double2loint(v), vh = __double2hiint(v);
-    const int lo = __builtin_amdgcn_update_dpp(vl, vl, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(vh, vh, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
 // NSQ = number of second-moment tiles; they are the LAST NSQ tiles of the block
 // (static split: no per-tile operand select in the MFMA loop -- VALU work between
 // fp64 MFMAs costs matrix-pipe issue slots on gfx950, measured 8 %).
@@ -98,6 +85,18 @@ __device__ __forceinline__ double dpp_row_f64(double v)
 // 10 = row norms: nothing of R is stored; the block writes sum_col (A . X)^2 of its 64 columns per row (se.acc_sum:
 //     [column block][group][se.accB rows]) -- rotated permutations with a square orthogonal V0 on the fixed-X route,
 //     whose A operand is V0^T A_p (k_build_A_proj): the statistic is the norm of each row of V0^T R_p.
+//     The tiles are held TRANSPOSED.  For v_mfma_f64_16x16x4 the two operand layouts coincide (A wants A[i][k] at lane
+//     16 k + i, B wants B[k][n] at lane 16 k + n), so the same two registers in the other order -- mfma(x, a, acc) for
+//     mfma(a, x, acc) -- give D^T: lane & 15 = row inside the tile, (lane >> 4, register r) = column 4 r + (lane >> 4)
+//     of the wave's 16.  Every accumulator element receives the same products in the same k order (the same bits), the
+//     loop issues the same instructions, and a lane's four registers of a tile are four columns of ONE row: the sum
+//     of squares over the columns starts lane-local (4 fp64 operations a tile) and ends with 16 partials per row in LDS.
+//     With the rows on lane >> 4 and the registers (every other epilogue) each of a lane's 100 values is another row
+//     and has to be added over 16 lanes: 400 additions and 800 DPP moves a lane, 4.2 ms per launch of 504 at the
+//     headline shape (74.17 against 69.92 for the same loop, operands NOT exchanged, with this epilogue -- a timing
+//     build, its values are wrong).  The exchange itself is not free as the instruction count suggests: the loop with
+//     x as the A operand measures 1 - 3 ms per launch slower, by how many LDS reads run ahead (see the main loop).
+//     profiles/perm_rownorm_lanes_compare.txt has the figures.
 template <int MT, int NW, int KT, int NSQ, int EPI = 0>
 __global__ __launch_bounds__(NW * 64, 2)
 void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
@@ -219,8 +218,24 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
             const double b = xb[s];
             const double bsq = (NSQ > 0) ? b * b : 0.0;
 #pragma unroll
-            for (int m = 0; m < NA; ++m)
-                acc[m] = mfma_f64(sA[(s * MT + m) * 64], (m < MT - NSQ) ? b : bsq, acc[m]);
+            for (int m = 0; m < NA; ++m) {
+                // EPI 10: the same two registers in the other order -- the transposed tile (see the epilogue list above)
+                if constexpr (EPI == 10) acc[m] = mfma_f64(b, sA[(s * MT + m) * 64], acc[m]);
+                else acc[m] = mfma_f64(sA[(s * MT + m) * 64], (m < MT - NSQ) ? b : bsq, acc[m]);
+            }
+        }
+        if constexpr (EPI == 10) {
+            // With the operands exchanged hipcc keeps only three LDS reads of A (two fragments each) ahead of the MFMAs
+            // -- the other instantiations get five -- and the loop ran slower for it.  The order is pinned instead:
+            // seven reads up front, then one read per two MFMAs.  Per launch of 504 at the headline shape: 73.4 ms as
+            // hipcc orders it, 72.1 with five reads ahead, 71.3 with seven (248 registers), 72.9 with eight, 71.2
+            // with nine (256 registers: nothing left); profiles/perm_rownorm_lanes_compare.txt.
+            __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);
+#pragma unroll
+            for (int i = 0; i < (KT * MT) / 2; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
         }
 #pragma unroll
         for (int s = 0; s < KT; ++s) xb[s] = xn[s];
@@ -246,31 +261,40 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
     // of tile SQ0+j holds m2 of that row.  The A stages are dead: reuse LDS.
     constexpr int W0 = (EPI == 9) ? 0 : MT - 2 * NSQ, SQ0 = MT - NSQ, NMOM = NSQ * 16;
     if constexpr (EPI == 10) {
-        // row norms (projected permutations): the block's share of sum_col acc^2 per row, in a FIXED order -- the 16
-        // lanes of a row group by a butterfly (lane 0 of the group keeps ((c0 + c8) + (c4 + c12)) + ...), then the four
-        // waves through LDS in wave order.  No atomics; one value per row leaves the block: se.acc_sum[colblk][grp][row]
-        // for the se.accB rows of a group that carry resamples.  Columns >= B of X are zero and add zero.
+        // row norms (projected permutations): the block's share of sum_col acc^2 per row, in a FIXED order.  The tiles are
+        // transposed (operands exchanged in the main loop): lane (kq, i) holds row m * 16 + i of tile m at the wave's
+        // columns kq, 4 + kq, 8 + kq, 12 + kq in registers 0 .. 3, so its share of the row's norm is lane-local:
+        //   q = ((a0^2 + a1^2) + a2^2) + a3^2     (fma chain, register order)
+        // -- no cross-lane move.  A row then has 16 partials, one per (wave, kq), i.e. per column class
+        // c % 4 = kq of the wave's 16 columns: they meet in LDS (the A stages are dead), partial p = wave * 4 + kq in
+        // sP[p][MT * 16], and one thread per row adds them as ((p0 + p1) + (p2 + p3)) per wave, then
+        // ((w0 + w1) + (w2 + w3)) over the waves.  No atomics; one value per row leaves the block:
+        // se.acc_sum[colblk][grp][row] for the se.accB rows of a group that carry resamples.  Columns >= B of X are
+        // zero and add zero.
         static_assert(NSQ == 0 && NW == 4, "EPI 10 is the fixed-X block");
-        double* sP = smem;                                   // [NW][MT * 16] (the A stages are dead)
+        constexpr int PP = MT * 16;                          // pitch of a partial: the rows of a block
+        double* sP = smem;                                   // [NW * 4][PP]
+        double* sq = sP + (wave * 4 + kq) * PP + (lane & 15);
 #pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                // (DPP moves inside the 16-lane row: rotate by 8, by 4, then the quad's lanes ^ 2 and ^ 1.  __shfl_xor
-                // compiles to ds_bpermute here -- 800 LDS round trips a wave, one after the other next to 200 live
-                // accumulator registers: measured 5.6 ms per launch of 504)
-                double q = acc[m][i] * acc[m][i];
-                q += dpp_row_f64<0x128>(q);
-                q += dpp_row_f64<0x124>(q);
-                q += dpp_row_f64<0x4e>(q);
-                q += dpp_row_f64<0xb1>(q);
-                if ((lane & 15) == 0) sP[wave * (MT * 16) + m * 16 + kq + 4 * i] = q;
-            }
+        for (int m = 0; m < MT; ++m) {
+            double q = acc[m][0] * acc[m][0];
+            q = __builtin_fma(acc[m][1], acc[m][1], q);
+            q = __builtin_fma(acc[m][2], acc[m][2], q);
+            q = __builtin_fma(acc[m][3], acc[m][3], q);
+            sq[m * 16] = q;
+        }
         __syncthreads();
         const int rows = se.accB;
         double* pp = se.acc_sum + ((size_t)colblk * n_groups + grp) * rows;
-        for (int row = tid; row < rows; row += NT)
-            pp[row] = ((sP[row] + sP[MT * 16 + row]) + sP[2 * MT * 16 + row]) + sP[3 * MT * 16 + row];
+        for (int row = tid; row < rows; row += NT) {
+            double w[NW];
+#pragma unroll
+            for (int v = 0; v < NW; ++v) {
+                const double* p = sP + v * 4 * PP + row;
+                w[v] = (p[0] + p[PP]) + (p[2 * PP] + p[3 * PP]);
+            }
+            pp[row] = (w[0] + w[1]) + (w[2] + w[3]);
+        }
         return;
     }
     if constexpr (EPI == 9) {

@@ -175,7 +175,9 @@ int launch_xprod_fixed_norms_t(plsx_ctx* ctx, int groups, SplitEpi se, hipStream
 {
     constexpr int MT = 25, NW = 4;
     const size_t stage = (size_t)2 * (((size_t)KT * MT * 64 + 127) / 128) * 128 * 8;
-    const size_t lds = std::max(stage, (size_t)NW * MT * 16 * 8);
+    // epilogue: 16 partials (wave, kq) of the block's MT * 16 rows -- 51 200 B, the stage pair of KT = 2 and twice
+    // that of KT = 1; two blocks per CU fit at every KT (the KT = 3 pair, 76 800 B, is the largest)
+    const size_t lds = std::max(stage, (size_t)NW * 4 * MT * 16 * 8);
     HIPCHK(set_lds(k_xprod<MT, NW, KT, 0, 10>, lds));
     const int ncolblk = ctx->Bpad / (NW * 16);
     dim3 grid(ncolblk * round_up(groups, 8)), block(NW * 64);
@@ -200,7 +202,9 @@ int run_xprod_fixed_norms(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t 
     HIPCHK(hipMemsetAsync(ctx->Afrag.p, 0, (size_t)groups * ctx->group_stride_f * 8, st));
     {
         KTimer tm(ctx, KC_BUILD, st);
-        hipLaunchKernelGGL(k_build_A_proj, dim3(nres, ctx->J), dim3(256), (size_t)2 * ctx->T * 8, st,
+        // (48 KB of LDS at the most: no attribute to raise)
+        auto kern = build_A_proj_vlds(ctx->T, ctx->L) ? k_build_A_proj<true> : k_build_A_proj<false>;
+        hipLaunchKernelGGL(kern, dim3(nres, ctx->J), dim3(256), build_A_proj_lds(ctx->T, ctx->L), st,
                            ystack ? ystack : ptr<double>(ctx->Y), ystack ? (long long)ctx->S * ctx->T : 0LL, ctx->T, ctx->S,
                            ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), ysrc, ptr<double>(ctx->V0), ctx->L,
                            ctx->npgf, ctx->Tp, ctx->MTf, ptr<double>(ctx->Afrag), ctx->group_stride_f);
