@@ -719,6 +719,9 @@ int plsx_mfma_f64_peak(plsx_ctx* ctx, double* tflops);
  * permutations of a fixed-X binding with L == T' and every original LV live:
  * singular values from the row norms of (V0^T A_p) X, no cross-product scratch,
  * no Gram pass, no small solver; option "no_perm_project"), else 0.
+ * [23] column tiles per wave of the compact bootstrap blocks of the last
+ * launch: 4 (blocks of 256 feature columns) or 2 (128), 0 when the last
+ * launch had no such blocks; options "no_compact_wide", "compact_wide_always".
  * Returns the number written. */
 int plsx_last_timing(const plsx_ctx* ctx, double* out, int cap);
 /* Scratch budget of the resampling super-batches (default 48 GB; the R block
@@ -777,7 +780,10 @@ int plsx_set_perm_path(plsx_ctx* ctx, int dual);
  *     "compact_boot_always", "crosscov_sparse" (plsx_crosscov_batch treats its resamples as bootstraps: the compact
  *     blocks wherever plsx_boot_batch would take them, so that tests can read R of a compact launch),
  *     "sepmom_always", "no_moment_rows" (compact bootstrap blocks: first moments from the moment-only blocks even
- *     where the padding rows of a block could deliver them), "no_perm_project" (rotated permutations on the fixed-X
+ *     where the padding rows of a block could deliver them), "no_compact_wide" (compact bootstrap blocks: two
+ *     column tiles per wave, blocks of 128 columns, also where blocks of 256 are the default),
+ *     "compact_wide_always" (tests: four column tiles per wave wherever they are compiled, T' <= 64),
+ *     "no_perm_project" (rotated permutations on the fixed-X
  *     route: always R, its Gram matrix and the small solver, also where the row norms of the projected product
  *     would do), "no_split_fuse" (split halves: two passes), "split_two_readers"
  *     (fused split blocks read by the Gram and the projection kernel instead of the one-pass reader),

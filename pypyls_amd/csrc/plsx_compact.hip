@@ -11,16 +11,19 @@ namespace plsxi {
 // Here every bootstrap has a block of its own that contracts over the rows it draws (k_xprod IDX: row table,
 // multiplicities folded into A), scaled by the 1 / std table of the moment-only blocks as in the
 // separate-moments layout.  ceil(T'/16) tiles x ~0.632 S/4 k-steps instead of 24 tiles x S/4 k-steps per 7.
-template <int MT, int KT, bool TAIL = false>
+// NC: column tiles per wave, 2 (128-column blocks) or 4 (256-column blocks, up to four tiles of rows; compact_boot_wide,
+// plsx_xprod.hip, says which a launch takes).  The block-id -> (group, column block) map is the same with either count
+// of column blocks: the 8 groups of a sweep on one XCD per column block.
+template <int MT, int KT, bool TAIL = false, int NC = 2>
 int launch_xprod_cboot(plsx_ctx* ctx, int nres, int nks_c, SplitEpi se, hipStream_t st)
 {
     // (moment rows only with the scales in registers: the LDS scale table of compact_lds_bytes is never theirs)
     se.nmu = compact_moment_rows(ctx) ? ctx->Tp : 0;
-    const size_t lds = compact_lds_bytes(MT, KT, 3, nks_c, se.npairs);
-    HIPCHK(set_lds(k_xprod_compact<MT, KT, 3, TAIL>, lds));
-    const int ncolblk = ceil_div(ctx->Bpad, 128);
+    const size_t lds = compact_lds_bytes(MT, KT, 3, nks_c, se.npairs, NC);
+    HIPCHK(set_lds(k_xprod_compact<MT, KT, 3, TAIL, NC>, lds));
+    const int ncolblk = ceil_div(ctx->Bpad, 64 * NC);
     KTimer tm(ctx, KC_XPROD, st);
-    hipLaunchKernelGGL((k_xprod_compact<MT, KT, 3, TAIL>), dim3(round_up(ncolblk, 8) * round_up(nres, 8)), dim3(256),
+    hipLaunchKernelGGL((k_xprod_compact<MT, KT, 3, TAIL, NC>), dim3(round_up(ncolblk, 8) * round_up(nres, 8)), dim3(256),
                        lds, st, ptr<double>(ctx->Afrag_c), (size_t)nks_c * MT * 64, ptr<double>(ctx->Xc), ctx->Bpad, nks_c,
                        ptr<double>(ctx->R), ctx->Bpad, ctx->Tpp, ptr<int>(ctx->out_row_c), ptr<int>(ctx->mom_idx_c),
                        ptr<double>(ctx->momn_m), nres, ncolblk, se);
@@ -32,6 +35,19 @@ int launch_cboot(plsx_ctx* ctx, int nres, int nks_c, SplitEpi se, hipStream_t st
 {
     const int MTc = ceil_div(ctx->Tp, 16);
     const bool tail = ctx->Tp - (MTc - 1) * 16 <= 4 && MTc >= 2;
+    if (compact_boot_wide(ctx)) {
+        // (the k-steps per stage of compact_boot_ksteps(mt, true))
+        switch (MTc) {
+            case 1: return launch_xprod_cboot<1, 6, false, 4>(ctx, nres, nks_c, se, st);
+            case 2: return tail ? launch_xprod_cboot<2, 4, true, 4>(ctx, nres, nks_c, se, st)
+                                : launch_xprod_cboot<2, 4, false, 4>(ctx, nres, nks_c, se, st);
+            case 3: return tail ? launch_xprod_cboot<3, 3, true, 4>(ctx, nres, nks_c, se, st)
+                                : launch_xprod_cboot<3, 3, false, 4>(ctx, nres, nks_c, se, st);
+            case 4: return tail ? launch_xprod_cboot<4, PLSX_CKTW, true, 4>(ctx, nres, nks_c, se, st)
+                                : launch_xprod_cboot<4, PLSX_CKTW, false, 4>(ctx, nres, nks_c, se, st);
+            default: return fail(ctx, PLSX_ERR_STATE, "compact bootstrap blocks of 256 columns: T' > 64");
+        }
+    }
     switch (MTc) {
         case 1: return launch_xprod_cboot<1, 12>(ctx, nres, nks_c, se, st);
         case 2: return tail ? launch_xprod_cboot<2, 6, true>(ctx, nres, nks_c, se, st)

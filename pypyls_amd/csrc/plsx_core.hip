@@ -1448,15 +1448,18 @@ try {
     const auto uvar = [&](int nks) { return (double)(nks > 0 && ctx->urot_tail_l ? nks + 100 : nks); };
     // [21]: the compact blocks of the last launch formed the first moments in their padding rows (compact_moment_rows)
     // [22]: the last permutation call took the projected route (perm_projected)
-    double vals[23] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
+    // [23]: column tiles per wave of the compact bootstrap blocks of the last launch: 2 (128-column blocks) or 4 (256), 0: no
+    //       compact bootstrap launch
+    double vals[24] = {ms, (double)launches, (double)(cmp ? 1 : (ctx->sepmom_used ? ctx->npg_d : ctx->npg)),
                        (double)(cmp ? ceil_div(ctx->Tp, 16) : (ctx->sepmom_used ? ctx->MTd : ctx->MT)),
                        (double)ctx->Gcap * ctx->npg, (double)ctx->timed_units, (double)use_dual(ctx), crows,
                        ctx->nt_flops, (double)ctx->quad_series, (double)ctx->quad_MT, (double)ctx->quad_gpl,
                        (double)ctx->urot_waves_l, (double)ctx->urot_splits_l, (double)ctx->urot_rps_l,
                        uvar(ctx->urot_nks_first), (double)ctx->gram_chunks_l, uvar(ctx->urot_nks_last),
                        (double)ctx->gram_kind_l, (double)ctx->split_blocks_l, (double)ctx->split_reader_l,
-                       (double)(cmp && ctx->last_moment_rows ? 1 : 0), (double)ctx->last_perm_projected};
-    int n = std::min(cap, 23);
+                       (double)(cmp && ctx->last_moment_rows ? 1 : 0), (double)ctx->last_perm_projected,
+                       (double)(cmp ? (ctx->last_compact_wide ? 4 : 2) : 0)};
+    int n = std::min(cap, 24);
     for (int i = 0; i < n; ++i) out[i] = vals[i];
     return n;
 } PLSX_CATCH(const_cast<plsx_ctx*>(cctx))

@@ -41,19 +41,24 @@ enum {
     OPT_SEPMOM_ALWAYS, OPT_NO_GRAM4, OPT_UROT_GENERIC, OPT_UROT_NO_TAIL4, OPT_NO_FIXED_X, OPT_NO_DUAL_PERM,
     OPT_TWO_PASS_BOOT, OPT_SPLIT_INBLOCK, OPT_NO_SPLIT_FUSE, OPT_SPLIT_TWO_READERS, OPT_EXPECT_RESAMPLES,
     OPT_SIMPLS_JACOBI, OPT_PERCENTILE_SORT, OPT_QUAD_SUMS, OPT_SPLIT_READER8, OPT_SIMPLS_GLOBAL,
-    OPT_CROSSCOV_SPARSE, OPT_NO_MOMENT_ROWS, OPT_NO_PERM_PROJECT, OPT_COUNT
+    OPT_CROSSCOV_SPARSE, OPT_NO_MOMENT_ROWS, OPT_NO_PERM_PROJECT, OPT_NO_COMPACT_WIDE, OPT_COMPACT_WIDE_ALWAYS, OPT_COUNT
 };
 static const char* const kOptionNames[OPT_COUNT] = {
     "no_refine", "min_batch", "inblock_moments", "no_compact_boot", "compact_boot_always",
     "sepmom_always", "no_gram4", "urot_generic", "urot_no_tail4", "no_fixed_x", "no_dual_perm",
     "two_pass_boot", "split_inblock", "no_split_fuse", "split_two_readers", "expect_resamples",
     "simpls_jacobi", "percentile_sort", "quad_sums", "split_reader8", "simpls_global",
-    "crosscov_sparse", "no_moment_rows", "no_perm_project"};
+    "crosscov_sparse", "no_moment_rows", "no_perm_project", "no_compact_wide", "compact_wide_always"};
 
 // k-steps per LDS stage of the 4-tile compact cross-product blocks (T' = 49 .. 64: the headline shape).  A/B lever of
 // tools/ckt_probe.sh (measured: profiles/r06_compact_kt.txt); other tile counts keep 12 / MT.
 #ifndef PLSX_CKT
 #define PLSX_CKT 3
+#endif
+// ... and of the same blocks with four column tiles per wave (compact_boot_wide; measured:
+// profiles/compact_wide_compare.txt)
+#ifndef PLSX_CKTW
+#define PLSX_CKTW 2
 #endif
 
 struct plsx_ctx {
@@ -181,6 +186,7 @@ struct plsx_ctx {
     int quad_MT = 0, quad_gpl = 0, quad_series = 0;     // block height / blocks per LV of the last closing pass; series closed on that route while timing
     int last_compact_n = 0, last_compact_ktot = 0;   // compact launch behind the last run_xprod (0: none)
     int last_moment_rows = 0;                        // ... and whether its blocks formed the first moments themselves
+    int last_compact_wide = 0;                       // ... and whether they held four column tiles per wave (256-column blocks)
     // how the last run_urot / Gram pass was launched (plsx_last_timing [12..18]; recorded whether or not timing is on)
     int urot_waves_l = 0, urot_splits_l = 0, urot_rps_l = 0;   // waves per block, resample splits, resamples per split
     int urot_nks_first = 0, urot_nks_last = 0, urot_tail_l = 0; // NKS template argument of the first / last L chunk's launch, TAIL
@@ -391,7 +397,8 @@ int run_xprod_fixed(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, co
 int run_xprod_fixed_norms(plsx_ctx* ctx, const int* ysrc, int nres, hipStream_t st, const double* ystack, double* out_sv);
 MomLayout moment_layout(const plsx_ctx* ctx, int npairs);
 MomLayout moment2_layout(const plsx_ctx* ctx, int npairs);     // X^2-only blocks (EPI 9)
-int compact_boot_ksteps(int mt);                               // k-steps per LDS stage of the compact bootstrap blocks
+bool compact_boot_wide(const plsx_ctx* ctx);                   // the compact bootstrap blocks hold four column tiles per wave
+int compact_boot_ksteps(int mt, bool wide);                    // k-steps per LDS stage of the compact bootstrap blocks
 bool compact_moment_rows(const plsx_ctx* ctx);                 // the compact bootstrap blocks form m1 in their padding rows
 int launch_moment_blocks_raw(plsx_ctx* ctx, const MomLayout& ml, SplitEpi se, hipStream_t st);   // EPI 6: raw m1, m2
 int ensure_compact_maps(plsx_ctx* ctx);

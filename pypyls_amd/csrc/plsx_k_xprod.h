@@ -621,11 +621,13 @@ __host__ __device__ constexpr int compact_stage_lds(int MT, int KT) { return ((K
 // cells whose 1 / std (16 bytes per lane and cell) a lane of epilogue 3 holds in registers: they arrive in the
 // registers that hold the next stage's X fragments in every pass but the last, so as many as a stage has k-steps;
 // four at the most (the store loop selects among them with compares)
-__host__ __device__ constexpr int compact_scale_regs(int KT) { return KT < 4 ? KT : 4; }
-__host__ __device__ constexpr size_t compact_lds_bytes(int MT, int KT, int EPI, int nks, int J)
+// (NC column tiles per wave: 16 NC bytes per lane and cell, in the 16 NC bytes per k-step of the X fragments -- the
+// same count at either width)
+__host__ __device__ constexpr int compact_scale_regs(int KT, int NC = 2) { return KT < 4 ? KT : 4; }
+__host__ __device__ constexpr size_t compact_lds_bytes(int MT, int KT, int EPI, int nks, int J, int NC = 2)
 {
     const size_t loop = (size_t)MT * 16 * 8 + (size_t)2 * compact_stage_lds(MT, KT) * 8 + (size_t)nks * 4 * 4;
-    if (EPI == 3) return loop + (J > compact_scale_regs(KT) ? (size_t)J * 128 * 8 : 0);
+    if (EPI == 3) return loop + (J > compact_scale_regs(KT, NC) ? (size_t)J * (64 * NC) * 8 : 0);
     // epilogue 5: u1, v1, u2, v2, sF : [5][J][128] and the row constants [MT * 16][5] over the stages and the table
     const size_t epi5 = (size_t)MT * 16 * 8 + (size_t)5 * J * 128 * 8 + (size_t)MT * 16 * 5 * 8;
     return EPI == 5 && epi5 > loop ? epi5 : loop;
@@ -634,15 +636,285 @@ __host__ __device__ constexpr size_t compact_lds_bytes(int MT, int KT, int EPI, 
 // waves per SIMD the register allocation is held to: what each variant runs at (epilogue 3: 7 / 6 at two tiles with /
 // without the tail, 5 at four tiles with the tail -- the headline --, 4 otherwise up to six tiles, 3 up to nine and at
 // ten with the tail, 2 beyond)
-__host__ __device__ constexpr int compact_waves(int MT, int EPI, bool TAIL)
+__host__ __device__ constexpr int compact_waves(int MT, int EPI, bool TAIL, int NC = 2)
 {
+    // four column tiles per wave (epilogue 3, up to four tiles of rows): twice the accumulators and X fragments -- 4 waves
+    // at one tile, 3 beyond (the headline, four tiles with the tail: 160 registers), 2 at four tiles without the tail
+    if (NC == 4) return MT == 1 ? 4 : (MT == 4 && !TAIL) ? 2 : 3;
     if (EPI == 3 && MT == 2) return TAIL ? 7 : 6;            // (72 / 80 registers: where they stood before they had moment rows to read)
     if (EPI == 3) return MT > 10 ? 2 : MT == 10 ? (TAIL ? 3 : 2) : MT > 6 ? 3 : MT > 4 ? 4 : (MT == 4 && TAIL) ? 5 : 4;
     return (EPI == 5 && MT == 4 && !TAIL) ? 3 : 4;
 }
 
-template <int MT, int KT, int EPI, bool TAIL>
-__global__ __launch_bounds__(256, compact_waves(MT, EPI, TAIL))
+// NC = 4: FOUR interleaved column tiles per wave (epilogue 3, up to four tiles of rows).  Lane c holds columns 4c .. 4c+3
+// of the wave's 64, a block is 4 waves x 64 = 256 columns: one LDS read of an A tile feeds four MFMAs, a lane loads 32
+// contiguous bytes of an X row (512 per row and wave) and stores 32 per row, and a launch has half the blocks -- half
+// the A re-staging, table fills, prologue round trips, barriers and dispatches per column.  The A stages, the row
+// table, the row maps, the single prologue barrier and the two-passes-per-trip loop are those of the two-tile body
+// below; every element of R receives the same products in the same k order, and 1 / std the same operations: the
+// same bits.  The comments of the two-tile body are not repeated here.
+template <int MT, int KT, bool TAIL>
+__device__ __forceinline__ void compact_wide_block(double* smem, const double* __restrict__ Afrag, size_t group_stride,
+                                                   const double* __restrict__ X, int ldx, int nks,
+                                                   double* __restrict__ R, int ldr, int rows_per_group,
+                                                   const int* __restrict__ out_row, const int* __restrict__ mom_idx,
+                                                   const double* __restrict__ mom_n, int n_groups, int ncolblk,
+                                                   const SplitEpi& se)
+{
+    constexpr int NC = 4, NW = 4, NT = NW * 64, BC = NW * 16 * NC;
+    constexpr int STAGE = KT * MT * 64;
+    constexpr int STAGE_LDS = compact_stage_lds(MT, KT);
+    constexpr int PASSES = (STAGE + NT * 2 - 1) / (NT * 2);
+    constexpr bool EVEN = (STAGE % (NT * 2)) == 0;
+    constexpr int MF = TAIL ? MT - 1 : MT;
+    constexpr int NSCR = compact_scale_regs(KT, NC);
+    static_assert(MT * 16 <= NT, "the row maps are staged by one thread per row");
+    const int ncb = (ncolblk + 7) & ~7;
+    const int sweep = blockIdx.x / (8 * ncb);
+    const int within = blockIdx.x - sweep * (8 * ncb);
+    const int slot = within >> 3;
+    const int grp = sweep * 8 + (slot & 7);
+    const int colblk = (slot >> 3) * 8 + (within & 7);
+    if (grp >= n_groups || colblk >= ncolblk) return;
+    const double* Ag = Afrag + (size_t)grp * group_stride;
+    const int swave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+
+    d4 acc[NC][MF > 0 ? MF : 1];
+    double tl[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        tl[c] = 0.0;
+#pragma unroll
+        for (int m = 0; m < MF; ++m) acc[c][m] = (d4){0.0, 0.0, 0.0, 0.0};
+    }
+
+    int* s_out = reinterpret_cast<int*>(smem);
+    double* sStage = smem + MT * 16;
+    int* s_tab = reinterpret_cast<int*>(sStage + 2 * STAGE_LDS);
+    const int J3 = se.npairs;
+    double* sW = reinterpret_cast<double*>(s_tab + nks * 4) + swave * (J3 * 64);   // [J3][64]: 1 / std, this wave's columns
+    d2 scr[NSCR][2];                                          // ... or per cell in registers (columns 0, 1 | 2, 3 of the lane)
+    const int mrow0 = se.nmu;
+    int cnt_lo[NSCR], cnt_hi[NSCR];
+    {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kq = lane >> 4;
+    const int cw = wave * 64 + 4 * (lane & 15);              // this lane's first column inside the block
+    const int col = colblk * BC + cw;
+    const bool live = col < ldr;                             // (ldr is a multiple of 64: whole waves)
+    const int lcol8 = (live ? col : 0) * 8;
+    const int toff = (lane & 48) + (lane & 3) - lane;
+
+    const int* tabg = se.row_tab + (size_t)grp * nks * 4;
+    const int ldx8 = ldx * 8;
+    int row0[KT];
+#pragma unroll
+    for (int s = 0; s < KT; ++s) row0[s] = tabg[s * 4 + kq];
+    stage_copy_buf<NT, PASSES, EVEN, STAGE>(Ag, sStage, tid, swave);
+    int orw = -1, mix = -1;
+    if (tid < MT * 16) {
+        orw = out_row[tid];
+        mix = mom_idx[tid];
+    }
+    const int ksteps = max(1, (se.row_cnt[grp] + 3) >> 2);
+    const int nkt = (ksteps + KT - 1) / KT;
+    const int ntab = nkt * KT * 4;
+    auto tab_load = [&](int i0, int (&v)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = tabg[min(i0 + u * NT + tid, ntab - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(v[u]));
+    };
+    auto tab_store = [&](int i0, const int (&v)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u * NT + tid < ntab) s_tab[i0 + u * NT + tid] = v[u] * ldx8;
+    };
+    int tv[4];
+    tab_load(0, tv);
+    d2 xa[KT][2], xb[KT][2];
+#pragma unroll
+    for (int s = 0; s < KT; ++s) {
+        xa[s][0] = load_x2_buf(X, row0[s] * ldx8 + lcol8);
+        xa[s][1] = load_x2_buf(X, row0[s] * ldx8 + lcol8 + 16);
+    }
+    tab_store(0, tv);
+    for (int i0 = 4 * NT; i0 < ntab; i0 += 4 * NT) { tab_load(i0, tv); tab_store(i0, tv); }
+    if (tid < MT * 16) {
+        const int rows_valid = min(rows_per_group, se.accB - grp * rows_per_group);
+        s_out[tid] = (orw < 0 || orw >= rows_valid) ? -1 : (orw | ((mix + 1) << 16));
+    }
+#pragma unroll
+    for (int s = 0; s < KT; ++s) { asm volatile("" : "+v"(xa[s][0])); asm volatile("" : "+v"(xa[s][1])); }
+    __syncthreads();
+
+    const double* sA0 = sStage + lane;
+    const double* sT0 = sA0 + toff;
+    auto contract = [&](auto curc, const d2 (&xc)[KT][2], auto full, int nlive) {
+        const int cur = curc;
+        const double* sA = sA0 + cur * STAGE_LDS;
+        const double* sT = sT0 + cur * STAGE_LDS;
+#pragma unroll
+        for (int s = 0; s < KT; ++s) {
+            if (!decltype(full)::value && s >= nlive) continue;
+            const double b[NC] = {xc[s][0].x, xc[s][0].y, xc[s][1].x, xc[s][1].y};
+#pragma unroll
+            for (int m = 0; m < MF; ++m) {
+                const double a = sA[(s * MT + m) * 64];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc[c][m] = mfma_f64(a, b[c], acc[c][m]);
+            }
+            if constexpr (TAIL) {
+                const double a = sT[(s * MT + MT - 1) * 64];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) tl[c] = mfma_f64_4x4(a, b[c], tl[c]);
+            }
+        }
+    };
+    const int* tp = s_tab + KT * 4 + kq;
+    const double* An = Ag + STAGE;
+    auto pass = [&](auto curc, const d2 (&xc)[KT][2], d2 (&xn)[KT][2]) {
+        constexpr int CUR = decltype(curc)::value;
+        stage_copy_buf<NT, PASSES, EVEN, STAGE>(An, sStage + (CUR ^ 1) * STAGE_LDS, tid, swave);
+#pragma unroll
+        for (int s = 0; s < KT; ++s) {
+            xn[s][0] = load_x2_buf(X, tp[s * 4] + lcol8);
+            xn[s][1] = load_x2_buf(X, tp[s * 4] + lcol8 + 16);
+        }
+        An += STAGE;
+        tp += KT * 4;
+        contract(curc, xc, std::true_type(), KT);
+        __syncthreads();
+    };
+    // the last pass: the block's 1 / std (or raw m2) per cell, 32 bytes per lane and cell into registers, or each wave's
+    // own 64 columns of the table by LDS-DMA (two pieces of 4 bytes per lane and cell) into its part of the LDS area
+    auto last = [&](int cur, const d2 (&xc)[KT][2]) {
+#pragma unroll
+        for (int j = 0; j < NSCR; ++j) { scr[j][0] = scr[j][1] = (d2){1.0, 1.0}; cnt_lo[j] = 0; cnt_hi[j] = 0; }
+        if (J3 <= NSCR) {
+            if (mrow0 > 0) {
+#pragma unroll
+                for (int j = 0; j < NSCR; ++j)
+                    if (j < J3) {
+                        const double v = mom_n[(size_t)grp * J3 + j];
+                        cnt_lo[j] = __builtin_amdgcn_readfirstlane(__double2loint(v));
+                        cnt_hi[j] = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < NSCR; ++j)
+                if (j < J3) {
+                    const char* p = reinterpret_cast<const char*>(se.scale + ((size_t)grp * J3 + j) * ldr) + lcol8;
+                    scr[j][0] = *reinterpret_cast<const d2*>(p);
+                    scr[j][1] = *reinterpret_cast<const d2*>(p + 16);
+                }
+        } else if (live) {
+            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(se.scale + (size_t)grp * J3 * ldr + colblk * BC + swave * 64), (short)0, 0x7fffffff, PLSX_RSRC_FLAGS);
+            const int ln4 = __lane_id() * 4;
+            for (int j = 0; j < J3; ++j) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                    rs, (__attribute__((address_space(3))) void*)(sW + j * 64), 4, ln4, j * ldr * 8, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                    rs, (__attribute__((address_space(3))) void*)(sW + j * 64 + 32), 4, ln4, j * ldr * 8 + 256, 0, 0);
+            }
+        }
+        contract(cur, xc, std::false_type(), ksteps - (nkt - 1) * KT);
+    };
+    {
+        std::integral_constant<int, 0> c0;
+        std::integral_constant<int, 1> c1;
+        int kt = 0, cur = 0;
+        for (; kt + 2 < nkt; kt += 2) { pass(c0, xa, xb); pass(c1, xb, xa); }
+        if (kt + 1 < nkt) {
+            pass(c0, xa, xb);
+#pragma unroll
+            for (int s = 0; s < KT; ++s) { xa[s][0] = xb[s][0]; xa[s][1] = xb[s][1]; }
+            cur = 1;
+        }
+        last(cur, xa);
+    }
+    }
+
+    // ---- moment rows: 1 / std from the block's own first moments --------------------------------------------------
+    // scr[j] holds m2 of the lane's four columns, m1 sits in row r = T' + j of the last tile (lane 16 (r % 4) + column,
+    // register (r % 16) / 4).  The four lanes that share the four columns would all form the same four values: the
+    // 16-lane row q = lane >> 4 forms column q's, ONE chain of two divisions and a square root per lane and cell as in
+    // the two-tile body, and the rows exchange.
+    if (mrow0 > 0 && J3 <= NSCR) {
+        const int ln = __lane_id();
+        const int q = ln >> 4;
+#pragma unroll
+        for (int j = 0; j < NSCR; ++j) {
+            if (j >= J3) continue;
+            const int r = mrow0 + j;
+            const int src = ((r & 3) << 4) | (ln & 15);
+            double m1 = 0.0;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                double a;
+                if constexpr (TAIL) a = tl[c];
+                else {
+                    const int ri = (r & 15) >> 2;
+                    a = acc[c][MT - 1][0];
+#pragma unroll
+                    for (int i = 1; i < 4; ++i)
+                        if (ri == i) a = acc[c][MT - 1][i];
+                }
+                const double v = __shfl(a, src);
+                if (q == c) m1 = v;
+            }
+            const double nn = __hiloint2double(cnt_hi[j], cnt_lo[j]);
+            const double m2 = q == 0 ? scr[j][0].x : q == 1 ? scr[j][0].y : q == 2 ? scr[j][1].x : scr[j][1].y;
+            const double var = (m2 - m1 * m1 / nn) / (nn - 1.0);
+            double sc = (var > 0.0) ? sd_rsqrt(var) : 0.0;
+            asm volatile("" : "+v"(sc));
+            const int c15 = ln & 15;
+            scr[j][0] = (d2){__shfl(sc, c15), __shfl(sc, c15 | 16)};
+            scr[j][1] = (d2){__shfl(sc, c15 | 32), __shfl(sc, c15 | 48)};
+        }
+    }
+
+    // ---- epilogue: stores (the lane's constants derived again, opaque to the compiler) ------------------------------
+    int tid16 = threadIdx.x * 16;
+    asm volatile("" : "+v"(tid16));
+    const int tid = tid16 >> 4, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
+    const int cw = wave * 64 + 4 * (lane & 15), col = colblk * BC + cw;
+    if (col >= ldr) return;
+    if (J3 > NSCR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wave's own copy of its scales)
+    double* Rg = R + (size_t)grp * rows_per_group * ldr + col;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (TAIL && m == MT - 1 && i > 0) break;
+            const int packed = s_out[m * 16 + kq + 4 * i];
+            if (packed < 0) continue;
+            const int orow = packed & 0xffff, mi = (packed >> 16) - 1;
+            d2 s0 = (d2){1.0, 1.0}, s1 = (d2){1.0, 1.0};
+            if (J3 > NSCR) {
+                if (mi >= 0) {
+                    s0 = *reinterpret_cast<const d2*>(&sW[mi * 64 + 4 * (lane & 15)]);
+                    s1 = *reinterpret_cast<const d2*>(&sW[mi * 64 + 4 * (lane & 15) + 2]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NSCR; ++j)
+                    if (mi == j) { s0 = scr[j][0]; s1 = scr[j][1]; }
+            }
+            double v[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) v[c] = (TAIL && m == MT - 1) ? tl[c] : acc[c][m < MF ? m : 0][i];
+            d2* dst = reinterpret_cast<d2*>(&Rg[(size_t)orow * ldr]);
+            // (ordinary stores: nontemporal ones, as epilogue 8 has, measured within the launch-to-launch spread at either
+            // width, profiles/compact_wide_compare.txt)
+            dst[0] = (d2){v[0] * s0.x, v[1] * s0.y};
+            dst[1] = (d2){v[2] * s1.x, v[3] * s1.y};
+        }
+}
+
+template <int MT, int KT, int EPI, bool TAIL, int NC = 2>
+__global__ __launch_bounds__(256, compact_waves(MT, EPI, TAIL, NC))
 void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
                      const double* __restrict__ X, int ldx, int nks,
                      double* __restrict__ R, int ldr, int rows_per_group,
@@ -650,7 +922,13 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
                      const double* __restrict__ mom_n, int n_groups, int ncolblk, SplitEpi se)
 {
     static_assert(EPI == 3 || EPI == 5 || EPI == 8, "compact blocks: bootstrap (3), fused split-half (5) or raw first-half sums (8)");
+    static_assert(NC == 2 || (NC == 4 && EPI == 3 && MT <= 4), "four column tiles per wave: bootstraps of up to four tiles");
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    if constexpr (NC == 4) {
+        compact_wide_block<MT, KT, TAIL>(smem, Afrag, group_stride, X, ldx, nks, R, ldr, rows_per_group, out_row, mom_idx,
+                                         mom_n, n_groups, ncolblk, se);
+        return;
+    }
     constexpr int NW = 4, NT = NW * 64, BC = NW * 32;       // threads, columns of a block
     constexpr int STAGE = KT * MT * 64;
     constexpr int STAGE_LDS = compact_stage_lds(MT, KT);

@@ -375,9 +375,25 @@ bool compact_boot_ok(const plsx_ctx* ctx)
     return cost_c * 1.1 < (double)mt_dense / npg_dense && npg_dense <= 16;
 }
 
-// k-steps per LDS stage of the compact bootstrap blocks of mt tiles (two column tiles per wave; launch_cboot compiles
-// the same values in)
-int compact_boot_ksteps(int mt) { return mt == 4 ? PLSX_CKT : std::max(1, 12 / mt); }
+// Block width of the compact bootstrap blocks: four column tiles per wave (256-column blocks, k_xprod_compact NC = 4)
+// where that was measured to win -- four tiles of rows with the tail, T' = 49 .. 52: the headline shape,
+// profiles/compact_wide_compare.txt -- and two (128-column blocks) everywhere else.  no_compact_wide forces two,
+// compact_wide_always four wherever they are compiled (up to four tiles of rows): A/B runs and the tests.
+bool compact_boot_wide(const plsx_ctx* ctx)
+{
+    const int mt = ceil_div(ctx->Tp, 16);
+    if (mt > 4 || ctx->opt[OPT_NO_COMPACT_WIDE]) return false;
+    if (ctx->opt[OPT_COMPACT_WIDE_ALWAYS]) return true;
+    return mt == 4 && ctx->Tp - (mt - 1) * 16 <= 4;
+}
+
+// k-steps per LDS stage of the compact bootstrap blocks of mt tiles at either width (launch_cboot compiles the same
+// values in)
+int compact_boot_ksteps(int mt, bool wide)
+{
+    if (wide) return mt == 4 ? PLSX_CKTW : mt == 3 ? 3 : mt == 2 ? 4 : 6;
+    return mt == 4 ? PLSX_CKT : std::max(1, 12 / mt);
+}
 
 // Moment rows: a compact bootstrap block issues whole tiles -- 16 mt rows, or 16 (mt - 1) + 4 when its last tile runs
 // on the 4x4x4 shape -- and the rows beyond T' are zero rows of its A operand.  With the multiplicities of cell j's
@@ -391,13 +407,15 @@ bool compact_moment_rows(const plsx_ctx* ctx)
     const int mt = ceil_div(ctx->Tp, 16);
     const bool tail = mt >= 2 && ctx->Tp - (mt - 1) * 16 <= 4;
     const int rows = tail ? (mt - 1) * 16 + 4 : mt * 16;
-    return ctx->J <= compact_scale_regs(compact_boot_ksteps(mt)) && rows - ctx->Tp >= ctx->J;
+    const bool wide = compact_boot_wide(ctx);
+    return ctx->J <= compact_scale_regs(compact_boot_ksteps(mt, wide), wide ? 4 : 2) && rows - ctx->Tp >= ctx->J;
 }
 
 int run_xprod_cboot(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, hipStream_t st,
                     const double* ystack, long long ystride)
 {
-    const int S = ctx->S, J = ctx->J, MTc = ceil_div(ctx->Tp, 16), KT = compact_boot_ksteps(MTc);
+    const bool wide = compact_boot_wide(ctx);
+    const int S = ctx->S, J = ctx->J, MTc = ceil_div(ctx->Tp, 16), KT = compact_boot_ksteps(MTc, wide);
     const int nks_c = round_up(ceil_div(S, 4), KT);
     const int npairs = nres * J;
     const bool mrows = compact_moment_rows(ctx);
@@ -417,6 +435,7 @@ int run_xprod_cboot(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, h
     HIPCHK(hipMemsetAsync(ctx->mask_c.p, 0, (size_t)nres * S, st));
     int* row_cnt = ptr<int>(ctx->rowtab_c) + (size_t)nres * nks_c * 4;
     ctx->last_compact_n = nres; ctx->last_compact_ktot = nks_c * 4; ctx->last_moment_rows = mrows ? 1 : 0;
+    ctx->last_compact_wide = wide ? 1 : 0;
     {
         KTimer tm(ctx, KC_BUILD, st);
         hipLaunchKernelGGL(k_drawn_mask, dim3(ceil_div(S, 256), nres), dim3(256), 0, st, xsrc, S, ptr<uint8_t>(ctx->mask_c));

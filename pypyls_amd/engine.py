@@ -1092,14 +1092,16 @@ class Engine(object):
         not timing is on.  ``moment_rows``: 1 when the compact bootstrap blocks of the last launch formed the first
         moments of the features in their padding rows (option ``no_moment_rows`` forces 0).  ``perm_projected``: 1 when
         the last permutation call took the projected route -- singular values from the row norms of (V0^T A_p) X, no R,
-        no Gram pass, no small solver (option ``no_perm_project`` forces 0)."""
-        buf = (ctypes.c_double * 23)()
-        n = self.lib.plsx_last_timing(self.ctx, buf, 23)
+        no Gram pass, no small solver (option ``no_perm_project`` forces 0).  ``compact_col_tiles``: column tiles per wave
+        of the compact bootstrap blocks of the last launch -- 4 (blocks of 256 columns) or 2 (128; option
+        ``no_compact_wide`` forces it, ``compact_wide_always`` forces 4 up to T' = 64), 0 without such a launch."""
+        buf = (ctypes.c_double * 24)()
+        n = self.lib.plsx_last_timing(self.ctx, buf, 24)
         keys = ['xprod_ms', 'xprod_launches', 'resamples_per_group', 'm_tiles', 'superbatch',
                 'xprod_resamples', 'dual_perm', 'compact_row_fraction', 'nt_flops', 'quad_series', 'quad_m_tiles',
                 'quad_blocks_per_lv', 'urot_waves', 'urot_splits', 'urot_res_per_split', 'urot_variant',
                 'gram_chunks', 'urot_variant_last', 'gram_kernel', 'split_blocks', 'split_reader',
-                'moment_rows', 'perm_projected']
+                'moment_rows', 'perm_projected', 'compact_col_tiles']
         return {k: buf[i] for i, k in enumerate(keys[:max(n, 0)])}
 
 
