@@ -629,6 +629,51 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
  *                           caller's).  _begin: PLSX_ERR_STATE without bound
  *                           regression data or before plsx_simpls_set_classes,
  *                           PLSX_ERR_ARG for a null buffer or capacity < 1.
+ *   plsx_simpls_cv_auc_begin / plsx_simpls_cv_auc_end
+ *                           The area under the ROC curve of every class against the
+ *                           rest, from the same predictions: a second series with
+ *                           the rules of plsx_simpls_cv_class_begin, independent of
+ *                           it (none, either or both may be open).  While it is open
+ *                           every plsx_simpls_crossval_batch of m splits appends m
+ *                           blocks [k][G][2] of int64 to d_auc in submission order,
+ *                           and every plsx_simpls_crossval_perm_batch of m
+ *                           permutations appends m blocks, each the SUM over that
+ *                           call's n splits.  With pos the usable test positions of
+ *                           a fit whose true class is g (under a permutation that of
+ *                           row perm[p]), neg its other usable test positions and
+ *                           v[p] = yhat_c[p][g], the prediction of the raw indicator
+ *                           that k_sd_cv_class takes the argmax of,
+ *                             block[c - 1][g][0] = u2    = sum over i in pos, j in neg of
+ *                                                          2 if v[i] > v[j], 1 if v[i] == v[j], else 0
+ *                             block[c - 1][g][1] = pairs = |pos| |neg|
+ *                           so that AUC = u2 / (2 pairs): Mann-Whitney, ties one
+ *                           half.  A comparison with a NaN prediction is false both
+ *                           ways: such a pair stays in `pairs` and adds nothing to
+ *                           u2.  The counts are 64-bit: a permutation's sum over 100
+ *                           splits at S = 20 000 passes 2^31.  Kernel k_sd_cv_auc
+ *                           runs after k_sd_cv_score (and after k_sd_cv_class where
+ *                           that series is open too): one wavefront per fit; it
+ *                           lists the usable test positions class by class once,
+ *                           forms q_c and the running prediction of the listed
+ *                           positions as k_sd_cv_class does (the fit's idle solver
+ *                           scratch), and per class lets the lanes own the positives
+ *                           and walk the negatives, staged 64 at a time in the
+ *                           wave's LDS slice; per-lane integer counts, a 64-bit wave
+ *                           reduction and one 64-bit integer atomic per count.  A
+ *                           block is zeroed when it is appended; the counts are
+ *                           integers, so the result does not depend on the order in
+ *                           which a permutation's splits arrive, on the batch size,
+ *                           the scratch budget or the route of the solver.  d_r,
+ *                           d_r2, d_sse / d_mse of both entries and the blocks of an
+ *                           open confusion series keep their bits with the series
+ *                           open.  A call that would pass `capacity` (blocks) of
+ *                           either open series returns PLSX_ERR_ARG before it
+ *                           computes anything or zeroes a block.  _end,
+ *                           plsx_set_data, plsx_simpls_set_classes and a second
+ *                           _begin end the series (the buffer stays the caller's).
+ *                           _begin: PLSX_ERR_STATE without bound regression data or
+ *                           before plsx_simpls_set_classes, PLSX_ERR_ARG for a null
+ *                           buffer or capacity < 1.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -656,6 +701,8 @@ int plsx_simpls_coef_perm_end(plsx_ctx* ctx);
 int plsx_simpls_set_classes(plsx_ctx* ctx, const int32_t* d_class, int G, void* stream);
 int plsx_simpls_cv_class_begin(plsx_ctx* ctx, int32_t* d_conf, long long capacity);
 int plsx_simpls_cv_class_end(plsx_ctx* ctx);
+int plsx_simpls_cv_auc_begin(plsx_ctx* ctx, int64_t* d_auc, long long capacity);
+int plsx_simpls_cv_auc_end(plsx_ctx* ctx);
 int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity);
 int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
                        double* d_sd, double* d_lo, double* d_hi, void* stream);
@@ -750,7 +797,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci),
  * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill),
  * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale),
- * 15 k_sd_cv_class (the confusion counts of an open plsx_simpls_cv_class_begin series).
+ * 15 k_sd_cv_class (the confusion counts of an open plsx_simpls_cv_class_begin series),
+ * 16 k_sd_cv_auc (the AUC counts of an open plsx_simpls_cv_auc_begin series).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

@@ -9,7 +9,7 @@ namespace plsxi {
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
                                                  "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm",
-                                                 "k_sd_cv_class"};
+                                                 "k_sd_cv_class", "k_sd_cv_auc"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -551,6 +551,7 @@ try {
     vip_close(ctx);                                    // (... and so does a kept VIP stack)
     cperm_close(ctx);                                  // (... and an open permutation series of the coefficients)
     cls_close(ctx);                                    // (... and the class codes of its rows with their open series)
+    auc_close(ctx);
     ctx->has_cls = 0;
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;

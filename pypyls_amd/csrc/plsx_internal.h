@@ -173,6 +173,12 @@ struct plsx_ctx {
     int has_cls = 0, cls_active = 0;
     int* cls_conf = nullptr;
     long long cls_cap = 0, cls_n = 0;
+    // plsx_simpls_cv_auc_begin: a second series on the same two calls, open or not whatever the first is -- blocks
+    // [k][G][2] int64 appended to the caller's buffer (k_sd_cv_auc): twice the Mann-Whitney U of every class against the
+    // rest, and the pairs it was counted over
+    int auc_active = 0;
+    long long* auc_out = nullptr;
+    long long auc_cap = 0, auc_n = 0;
     bool has_okx = false, has_oky = false;
     int n_okx = 0;                                      // usable rows of X under the row masks (has_okx)
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
@@ -280,7 +286,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -388,6 +394,12 @@ inline void cperm_close(plsx_ctx* ctx)
 inline void cls_close(plsx_ctx* ctx)
 {
     ctx->cls_active = 0; ctx->cls_conf = nullptr; ctx->cls_cap = 0; ctx->cls_n = 0;
+}
+// an open series of AUC counts ends (plsx_set_data, plsx_simpls_set_classes, a second plsx_simpls_cv_auc_begin,
+// plsx_simpls_cv_auc_end); the buffer stays the caller's
+inline void auc_close(plsx_ctx* ctx)
+{
+    ctx->auc_active = 0; ctx->auc_out = nullptr; ctx->auc_cap = 0; ctx->auc_n = 0;
 }
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);

@@ -132,6 +132,9 @@ struct SdArgs {
     int* conf;                  // blocks [k][T][T] int32, [c][true][predicted]; fit r adds to block (cls_f0 + r) / cls_n - cls_f0 / cls_n
     long long cls_f0;           // the batch's first fit in the call's pair list (identity route: 0)
     int cls_n;                  // fits per block: the splits of a permutation (identity route: 1)
+    // AUC counts (plsx_simpls_cv_auc_begin): k_sd_cv_auc runs after k_sd_cv_score (and k_sd_cv_class) on every fit of the
+    // batch; cls / cfreq / cls_f0 / cls_n as above
+    long long* auc;             // blocks [k][T][2] int64, [c][class][u2, pairs]; the block of fit r as for conf
 };
 
 // doubles of LDS one wave of k_sd_step needs (on-chip route: the last S of them are the scatter buffer)
@@ -1522,6 +1525,153 @@ void k_sd_cv_class(SdArgs a)
             if (v) atomicAdd(&out[(size_t)c * G * G + i], v);
         }
         wave_sync();
+    }
+}
+
+// What lanes of this wave stored to global memory is visible to its other lanes, and no more than that: a fence of
+// workgroup scope (the wave's stores have reached the compute unit's write-through L1, which its loads go through)
+// instead of wave_global_sync()'s device-wide one, whose write-back of L2 is paid by every wave that calls it
+// ("PLS-DA: AUC").
+__device__ __forceinline__ void wave_cu_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// 64-bit integer sum over the wave (exact in any order)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// One-vs-rest AUC counts of the test rows of one fit (plsx_simpls_cv_auc_begin), after k_sd_cv_score centred Z in place
+// and, where that series is open too, after k_sd_cv_class.  Per component count c and class g, with pos the usable test
+// positions of true class g, neg the other usable test positions and v[p] = yhat_c[p][g] (the prediction k_sd_cv_class
+// takes the argmax of, formed here by the same arithmetic: f, one pass over z_c and the roles for q_c, wave_sum4 in the
+// same fixed order),
+//     u2    = sum over i in pos, j in neg of (2 if v[i] > v[j], 1 if v[i] == v[j], else 0)       twice Mann-Whitney's U
+//     pairs = |pos| |neg|
+// A comparison with a NaN is false both ways: the pair counts in `pairs` and adds nothing to u2.  One wavefront per
+// fit.  Where things live (all of it idle once k_sd_cv_score and k_sd_cv_class are through, and stream order puts this
+// kernel behind them): the role of every position as one int in the first half of the fit's `va` (S ints, as
+// k_sd_cv_class writes them), the usable test positions listed CLASS BY CLASS in its second half (S more ints: `va` is S
+// doubles), where the list of class g starts in the wave's LDS slice, the running prediction of listed position i in
+// the fit's Z0 rows, [G][S] indexed by the place in the list -- so the positives of a class are contiguous and a lane
+// that owns one is never idle because its neighbour's position belongs to another class.  Per class the lanes own the
+// positives, 64 at a time, and walk the negatives, which the wave stages 64 at a time in its LDS slice (a read of one
+// address by every lane); a lane without a positive, and a staged place without a negative, hold a NaN and count
+// nothing.  Per-lane counts are 32-bit (at most ceil(S / 64) S comparisons per lane and class), their sum over the wave
+// 64-bit, and one lane adds u2 and pairs to the fit's block with 64-bit integer atomics: under PERM the n splits of a
+// permutation share one block, which was zeroed when it was appended.  The list and the predictions are written by one
+// lane and read by another through global memory: wave_cu_sync() between.  PERM as for k_sd_cv_class.
+template <int GB, bool PERM>
+static __global__ __launch_bounds__(256)
+void k_sd_cv_auc(SdArgs a)
+{
+    __shared__ double sm_stage[4][64];
+    __shared__ int sm_start[4][GB + 1];
+    const int S = a.S, G = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= a.nres) return;
+    const int* xs = a.xs + (size_t)r * S;
+    const uint8_t* pm = a.pmask + (size_t)r * S;
+    const double* ym = a.ymean + (size_t)r * G;
+    const int* ysp = a.ys + (size_t)r * S;
+    auto yrow = [&](int p) { if constexpr (PERM) return ysp[p]; else return p; };
+    const double* Z = a.cvZ + (size_t)r * k * S;
+    double* yh = a.Z0 + (size_t)r * S * G;
+    int* role = reinterpret_cast<int*>(a.va + (size_t)r * S);                  // (S ints in the first half of the fit's S doubles)
+    int* list = role + S;                                                      // (... and S ints in the second)
+    const long long blk = (a.cls_f0 + r) / a.cls_n - a.cls_f0 / a.cls_n;       // (64-bit, as the pair list itself)
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(a.auc) + (size_t)blk * k * G * 2;
+    double* stage = sm_stage[wave];
+    int* start = sm_start[wave];
+    const double nan = __builtin_nan("");
+    // role of position p, as k_sd_cv_class defines it: its class on a training position, 64 + its class on a usable test
+    // position, -1 otherwise (written and read by the lane that owns p)
+    for (int p = lane; p < S; p += 64) {
+        const bool te = !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[yrow(p)]);
+        role[p] = (xs[p] >= 0 || te) ? (a.cls[yrow(p)] | (te ? 64 : 0)) : -1;
+    }
+    // the usable test positions, class by class and ascending within a class: list[start[g] .. start[g + 1])
+    int nl = 0;
+    for (int g = 0; g < G; ++g) {
+        if (lane == 0) start[g] = nl;
+        for (int p0 = 0; p0 < S; p0 += 64) {
+            const int p = p0 + lane;
+            const bool hit = p < S && role[p] == (64 | g);
+            const unsigned long long m = __ballot(hit);
+            if (hit) list[nl + __popcll(m & ((1ull << lane) - 1ull))] = p;     // (nl + rank < the S usable positions at most)
+            nl += __popcll(m);
+        }
+    }
+    if (lane == 0) start[G] = nl;
+    wave_cu_sync();
+    double f[GB];
+#pragma unroll
+    for (int g = 0; g < GB; ++g) f[g] = g < G ? ym[g] + a.cfreq[g] : 0.0;
+    for (int c = 0; c < k; ++c) {
+        const double* zc = Z + (size_t)c * S;
+        double q[GB];
+#pragma unroll
+        for (int g = 0; g < GB; ++g) q[g] = 0.0;
+        for (int p = lane; p < S; p += 64) {
+            const int rl = role[p];
+            const double z = zc[p];
+#pragma unroll
+            for (int g = 0; g < GB; ++g) q[g] += rl == g ? z : 0.0;
+        }
+#pragma unroll
+        for (int g = 0; g < GB; g += 4)
+            if (g < G) wave_sum4(q[g], q[g + 1], q[g + 2], q[g + 3]);
+        double sall = 0.0;
+#pragma unroll
+        for (int g = 0; g < GB; ++g) sall += q[g];
+#pragma unroll
+        for (int g = 0; g < GB; ++g) q[g] -= f[g] * sall;
+        // the running prediction of the listed positions
+        for (int i = lane; i < nl; i += 64) {
+            const double z = zc[list[i]];
+#pragma unroll
+            for (int g = 0; g < GB; ++g)
+                if (g < G) {
+                    const double v = (c == 0 ? f[g] : yh[(size_t)g * S + i]) + z * q[g];
+                    yh[(size_t)g * S + i] = v;
+                }
+        }
+        wave_cu_sync();
+        for (int g = 0; g < G; ++g) {
+            const int s0 = start[g], npos = start[g + 1] - s0, nneg = nl - npos;
+            if (npos == 0 || nneg == 0) continue;                              // (wave-uniform)
+            const double* vg = yh + (size_t)g * S;
+            unsigned long long u2 = 0;
+            for (int i0 = 0; i0 < npos; i0 += 64) {
+                const double vi = i0 + lane < npos ? vg[s0 + i0 + lane] : nan;
+                unsigned gt = 0, eq = 0;
+                for (int t0 = 0; t0 < nneg; t0 += 64) {
+                    const int t = t0 + lane;                                   // the t-th negative: the list without [s0, s0 + npos)
+                    const double vj = t < nneg ? vg[t < s0 ? t : t + npos] : nan;
+                    wave_sync();                                               // (the reads of the last 64 are through)
+                    stage[lane] = vj;
+                    wave_sync();
+#pragma unroll
+                    for (int u = 0; u < 64; ++u) {
+                        const double w = stage[u];
+                        gt += vi > w ? 1u : 0u;
+                        eq += vi == w ? 1u : 0u;
+                    }
+                }
+                u2 += 2ull * gt + eq;
+            }
+            u2 = wave_sum_u64(u2);
+            if (lane == 0) {
+                atomicAdd(&out[((size_t)c * G + g) * 2], u2);
+                atomicAdd(&out[((size_t)c * G + g) * 2 + 1], (unsigned long long)npos * (unsigned long long)nneg);
+            }
+        }
+        wave_cu_sync();                                                    // (this c's reads before the next c's writes)
     }
 }
 

@@ -417,18 +417,31 @@ static int coef_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 
 }  // namespace plsxi
 
-// The open series of confusion counts (plsx_simpls_cv_class_begin): room for m more blocks, or PLSX_ERR_ARG before
-// anything is computed; the blocks are zeroed here, in stream order before the kernels that count into them.
+// The open series of confusion counts (plsx_simpls_cv_class_begin) and of AUC counts (plsx_simpls_cv_auc_begin): room for
+// m more blocks in each that is open, or PLSX_ERR_ARG before anything is computed or zeroed; the blocks are zeroed
+// here, in stream order before the kernels that count into them.
 static int cls_reserve(plsx_ctx* ctx, const char* who, int m, hipStream_t st)
 {
-    if (ctx->cls_n + m > ctx->cls_cap) {
+    if (ctx->cls_active && ctx->cls_n + m > ctx->cls_cap) {
         char msg[240];
         snprintf(msg, sizeof msg, "%s: the open series of confusion counts holds %lld of %lld blocks, %d more do not fit "
                  "(plsx_simpls_cv_class_begin)", who, ctx->cls_n, ctx->cls_cap, m);
         return fail(ctx, PLSX_ERR_ARG, msg);
     }
-    const size_t blk = (size_t)ctx->ncomp * ctx->T * ctx->T;
-    HIPCHK(hipMemsetAsync(ctx->cls_conf + (size_t)ctx->cls_n * blk, 0, (size_t)m * blk * sizeof(int), st));
+    if (ctx->auc_active && ctx->auc_n + m > ctx->auc_cap) {
+        char msg[240];
+        snprintf(msg, sizeof msg, "%s: the open series of AUC counts holds %lld of %lld blocks, %d more do not fit "
+                 "(plsx_simpls_cv_auc_begin)", who, ctx->auc_n, ctx->auc_cap, m);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (ctx->cls_active) {
+        const size_t blk = (size_t)ctx->ncomp * ctx->T * ctx->T;
+        HIPCHK(hipMemsetAsync(ctx->cls_conf + (size_t)ctx->cls_n * blk, 0, (size_t)m * blk * sizeof(int), st));
+    }
+    if (ctx->auc_active) {
+        const size_t blk = (size_t)ctx->ncomp * ctx->T * 2;
+        HIPCHK(hipMemsetAsync(ctx->auc_out + (size_t)ctx->auc_n * blk, 0, (size_t)m * blk * sizeof(long long), st));
+    }
     return 0;
 }
 
@@ -445,6 +458,22 @@ static int cls_launch(plsx_ctx* ctx, SdArgs a, int ms, long long first, long lon
     void (*class_kernel)(SdArgs) = a.T <= 4 ? k_sd_cv_class<4, PERM> : (a.T <= 16 ? k_sd_cv_class<16, PERM>
                                                                                   : k_sd_cv_class<32, PERM>);
     hipLaunchKernelGGL(class_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+    LAUNCHCHK();
+    return 0;
+}
+
+// k_sd_cv_auc on the same fits, behind k_sd_cv_score and, where that series is open too, k_sd_cv_class: blocks as there.
+template <bool PERM>
+static int auc_launch(plsx_ctx* ctx, SdArgs a, int ms, long long first, long long f0, int n, hipStream_t st)
+{
+    a.cls = ptr<int>(ctx->cls);
+    a.cfreq = ptr<double>(ctx->clsfreq);
+    a.auc = ctx->auc_out + (size_t)first * a.k * a.T * 2;
+    a.cls_f0 = f0; a.cls_n = n;
+    KTimer tm(ctx, KC_CVAUC, st);
+    void (*auc_kernel)(SdArgs) = a.T <= 4 ? k_sd_cv_auc<4, PERM> : (a.T <= 16 ? k_sd_cv_auc<16, PERM>
+                                                                              : k_sd_cv_auc<32, PERM>);
+    hipLaunchKernelGGL(auc_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
     LAUNCHCHK();
     return 0;
 }
@@ -539,8 +568,8 @@ try {
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
     const bool gl = simpls_global(ctx);
     // (an open series of confusion counts that cannot take the call: refused before anything is computed)
-    const bool series = ctx->cls_active != 0;
-    if (series)
+    const bool series = ctx->cls_active != 0, aucs = ctx->auc_active != 0;
+    if (series || aucs)
         if (int e = cls_reserve(ctx, "plsx_simpls_crossval_batch", m, st)) return e;
     // solver batches as for the permutations; a split also holds its dense dual weights Vd and Z = Vd . K
     const int nb = std::min(m, sd_batch(ctx, 8192, 1, 2.0 * k * S * 8.0));
@@ -578,8 +607,11 @@ try {
         }
         if (series)                                    // one block per split, in submission order
             if (int e = cls_launch<false>(ctx, a, ms, ctx->cls_n + off, 0, 1, st)) return e;
+        if (aucs)
+            if (int e = auc_launch<false>(ctx, a, ms, ctx->auc_n + off, 0, 1, st)) return e;
     }
     if (series) ctx->cls_n += m;
+    if (aucs) ctx->auc_n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -598,8 +630,8 @@ try {
     // the pair list: fit f = permutation f / n under split f % n, m n of them (64-bit), cut into solver batches sized
     // as plsx_simpls_crossval_batch sizes its own; a fit also holds its expanded sources and mask (5 S bytes) and
     // its scores until the reduction over the splits
-    const bool series = ctx->cls_active != 0;
-    if (series)
+    const bool series = ctx->cls_active != 0, aucs = ctx->auc_active != 0;
+    if (series || aucs)
         if (int e = cls_reserve(ctx, "plsx_simpls_crossval_perm_batch", m, st)) return e;
     const long long fits = (long long)m * n;
     const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T + 1;       // doubles of scores per fit
@@ -665,8 +697,11 @@ try {
         }
         if (series)                                    // one block per permutation: its splits add up in it, in any order
             if (int e = cls_launch<true>(ctx, a, ms, ctx->cls_n + f0 / n, f0, n, st)) return e;
+        if (aucs)
+            if (int e = auc_launch<true>(ctx, a, ms, ctx->auc_n + f0 / n, f0, n, st)) return e;
     }
     if (series) ctx->cls_n += m;
+    if (aucs) ctx->auc_n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -994,6 +1029,7 @@ try {
     if (ctx->method != PLSX_REGRESSION)
         return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_set_classes: data not bound for regression");
     cls_close(ctx);
+    auc_close(ctx);
     ctx->has_cls = 0;
     if (!d_class) return PLSX_OK;                      // (a null pointer clears the binding)
     char msg[200];
@@ -1049,6 +1085,28 @@ int plsx_simpls_cv_class_end(plsx_ctx* ctx)
 try {
     if (!ctx) return PLSX_ERR_ARG;
     cls_close(ctx);
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cv_auc_begin(plsx_ctx* ctx, int64_t* d_auc, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_auc_begin: data not bound for regression");
+    if (!ctx->has_cls)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_auc_begin: plsx_simpls_set_classes has not been called");
+    auc_close(ctx);
+    if (!d_auc || capacity < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_cv_auc_begin: null buffer or capacity < 1");
+    ctx->auc_out = reinterpret_cast<long long*>(d_auc); ctx->auc_cap = capacity; ctx->auc_n = 0;
+    ctx->auc_active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cv_auc_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    auc_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 

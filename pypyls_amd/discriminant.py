@@ -1,7 +1,7 @@
 """
 ``pls_da``: PLS discriminant analysis -- SIMPLS on the indicator matrix of the class labels, the class of a row read
 off the largest predicted indicator -- with cross-validated accuracy, balanced accuracy and confusion matrices and
-their permutation test.
+their permutation test, and on request the cross-validated one-vs-rest AUC of every class with its own.
 
 The model IS ``pls_regression(X, one_hot(y))``: ``pls_da`` validates the labels, codes them and passes everything on to
 that code path, so everything ``pls_regression`` returns (weights, scores, VIP, coefficients with their bootstrap
@@ -11,6 +11,8 @@ ratios, intervals and p-values, the regression scores of the cross-validation) i
   * the (split) and (permutation, split) fits of the cross-validation are classified where they live, on the device
     (plsx_simpls_set_classes / plsx_simpls_cv_class_begin; csrc/plsx_simpls.h, k_sd_cv_class): only integer confusion
     counts come back, per split for the observed labels and summed over the splits per permutation;
+  * ``auc=True``: the same fits also rank their test rows (plsx_simpls_cv_auc_begin; k_sd_cv_auc) -- per class the
+    ordered pairs (row of the class, other row) that its predicted indicator puts in the right order, again integers;
   * :func:`predict_class` for new rows.
 
 There is no split-half reliability (``n_split``) here: the correlation between two halves of indicator loadings answers
@@ -67,6 +69,50 @@ def confusion_results(blocks, perm_blocks=None):
     return out
 
 
+def auc_from_counts(counts):
+    """counts (G, 2, ...) -- ``[g, 0] = u2``: over the pairs (counted row of class g, counted row of another class), 2
+    where the predicted indicator of class g is larger on the first, 1 where the two are equal; ``[g, 1] = pairs``: the
+    number of such pairs -- -> ``(auc, auc_macro)`` of shapes (G, ...) and ``...``.
+
+    ``auc[g] = u2 / (2 pairs)``: the one-vs-rest area under the ROC curve of class g (Mann-Whitney, ties one half), NaN
+    where there is no pair -- no counted row of the class, or none of any other.  ``auc_macro`` is the mean of ``auc[g]``
+    over the classes that have a pair, NaN if none has."""
+    counts = np.asarray(counts)
+    if counts.ndim < 2 or counts.shape[1] != 2:
+        raise ValueError('Expected AUC counts of shape (G, 2, ...), got {}'.format(counts.shape))
+    counts = counts.astype(np.float64)
+    u2, pairs = counts[:, 0], counts[:, 1]
+    present = pairs > 0
+    auc = np.where(present, u2 / np.where(present, 2.0 * pairs, 1.0), np.nan)
+    n = present.sum(axis=0)
+    macro = np.where(n > 0, np.where(present, auc, 0.0).sum(axis=0) / np.where(n > 0, n, 1), np.nan)
+    return auc, macro
+
+
+def _pvals_nan(observed, null):
+    """:func:`pvals_from_null`, NaN where the observed value is NaN (a NaN in the null is not ``>=`` anything)."""
+    observed = np.asarray(observed, dtype=np.float64)
+    with np.errstate(invalid='ignore'):
+        p = pvals_from_null(observed, null)
+    return np.where(np.isnan(observed), np.nan, p)
+
+
+def auc_results(blocks, perm_blocks=None):
+    """The keys ``pls_da(auc=True)`` adds to ``cvres`` from what the device counted: blocks (n, k, G, 2) per split and,
+    with ``cv_perm``, perm_blocks (P, k, G, 2) summed over the splits of every permutation (float64 holding integers)."""
+    cnt = np.ascontiguousarray(np.rint(np.asarray(blocks)).astype(np.int64).transpose(2, 3, 1, 0))     # (G, 2, k, n)
+    auc, macro = auc_from_counts(cnt)
+    out = dict(auc_counts=cnt, auc=auc, auc_macro=macro)
+    if perm_blocks is not None:
+        pcnt = np.ascontiguousarray(np.rint(np.asarray(perm_blocks)).astype(np.int64).transpose(2, 3, 1, 0))
+        pauc, pmacro = auc_from_counts(pcnt)
+        # the pooled statistic: the same functional of the observed data, the counts summed over the splits
+        oauc, omacro = auc_from_counts(cnt.sum(axis=-1))
+        out.update(perm_auc_counts=pcnt, perm_auc=pauc, perm_auc_macro=pmacro,
+                   auc_pvals=_pvals_nan(oauc, pauc), auc_macro_pvals=_pvals_nan(omacro, pmacro))
+    return out
+
+
 def encode_labels(y, S=None):
     """y (S,) labels -> (classes (G,) sorted distinct labels, codes (S,) int64 positions in it).  ValueError for a y that
     is not 1-D (or not of length S), a NaN or None label, fewer than 2 or more than 32 classes."""
@@ -100,7 +146,7 @@ def _label(classes, g):
 
 def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamples=None, bootsamples=None, seed=None,
            verbose=True, n_proc=None, test_split=0, test_size=0.25, cvsamples=None, cv_perm=0, cvpermsamples=None,
-           coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, **kwargs):
+           coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, auc=False, **kwargs):
     """PLS discriminant analysis of the labels ``y`` (S,) on ``X`` (S, B).
 
     ``classes = np.unique(y)`` (integers, strings, booleans: anything numpy sorts), ``codes`` the position of every
@@ -124,6 +170,23 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
 
     (:func:`scores_from_confusion`).  Rows of X that are NaN throughout belong to neither side and are counted nowhere.
 
+    ``auc=True`` (needs ``test_split`` > 0): the same fits also give the one-vs-rest area under the ROC curve of every
+    class, which does not depend on where a threshold is placed and so does not move with class imbalance the way
+    accuracy does.  For a split, a component count c and a class g, over the pairs (usable test row i of class g, usable
+    test row j of another class) and with ``v = yhat_c[:, g]``, ``u2`` counts 2 where ``v[i] > v[j]`` and 1 where
+    ``v[i] == v[j]`` (Mann-Whitney, ties one half), ``pairs`` the pairs.  ``cvres`` gains
+
+        auc_counts         (G, 2, k, test_split) int   [class, (u2, pairs), c - 1, split]
+        auc                (G, k, test_split)          u2 / (2 pairs); NaN where a split's test side lacks class g or
+                                                       holds nothing else
+        auc_macro          (k, test_split)             mean over the classes with a pair
+
+    (:func:`auc_from_counts`) and, with ``cv_perm=P``, ``perm_auc_counts`` (G, 2, k, P) summed over the splits of a
+    permutation, ``perm_auc`` (G, k, P) / ``perm_auc_macro`` (k, P) = ``auc_from_counts(perm_auc_counts)`` -- the pooled
+    statistic -- and ``auc_pvals`` (G, k) / ``auc_macro_pvals`` (k,) against ``auc_from_counts(auc_counts.sum(-1))``, by
+    the same ``>=`` rule as below; a NaN observed value gives a NaN p-value.  Without ``auc=True`` nothing is added and
+    nothing else changes.
+
     ``cv_perm=P``: the true class of position p under a permutation is ``codes[perm[p]]``.  The device returns, per
     permutation, the confusion SUMMED over the splits, and ``cvres`` gains ``perm_confusion`` (G, G, k, P),
     ``perm_accuracy`` / ``perm_balanced_accuracy`` (k, P) = ``scores_from_confusion(perm_confusion)`` -- the pooled
@@ -138,13 +201,18 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
 
     ValueError, before any engine is created or looked up: a ``y`` that is not 1-D of length S; a NaN or None label;
     fewer than 2 or more than 32 classes (the bound of the device kernel k_sd_cv_class); a class with fewer than 2
-    usable rows; a ``test_size`` that can leave a class without a usable training row; ``cvsamples`` whose training
+    usable rows; ``auc=True`` without ``test_split``; a ``test_size`` that can leave a class without a usable training row; ``cvsamples`` whose training
     side lacks a usable row of some class; ``n_split``, ``aggfunc`` or ``rotate`` given; and everything
     ``pls_regression`` refuses."""
     for name in ('n_split', 'aggfunc', 'rotate'):
         if name in kwargs:
             raise ValueError('`pls_da` takes no `{}`: split-half reliability, aggregation of a 3-D Y and rotation are '
                              'not part of a discriminant analysis'.format(name))
+    if auc and not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+        raise ValueError('`auc=True` needs a cross-validation: the AUC is counted over the test rows of `test_split` > 0 '
+                         'splits (with `test_size` > 0)')
+    if auc:
+        kwargs = dict(kwargs, _auc=True)
     X = np.asarray(X)
     if X.ndim != 2:
         raise ValueError('Expected 2D array for `X`, got {}D array instead'.format(X.ndim))

@@ -103,6 +103,8 @@ def _load():
         'plsx_simpls_set_classes': ([vp, vp, i32, vp], i32),
         'plsx_simpls_cv_class_begin': ([vp, vp, ctypes.c_longlong], i32),
         'plsx_simpls_cv_class_end': ([vp], i32),
+        'plsx_simpls_cv_auc_begin': ([vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_cv_auc_end': ([vp], i32),
         'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
         'plsx_simpls_vip_ci': ([vp, vp, ctypes.c_longlong, i32, i32, c_d, i32, c_d, vp, vp, vp, vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
@@ -142,6 +144,7 @@ def exported_symbols():
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
              'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
+             'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
@@ -962,6 +965,25 @@ class Engine(object):
     def simpls_cv_class_end(self):
         """Close the series of confusion counts (plsx_simpls_cv_class_end)."""
         self._check(self.lib.plsx_simpls_cv_class_end(self.ctx))
+
+    def simpls_cv_auc_begin(self, auc_dev):
+        """Open a series of AUC counts, independent of the confusion series: until :meth:`simpls_cv_auc_end` every
+        :meth:`simpls_crossval_into` of m splits appends m blocks (k, T, 2) -- [c - 1, class, (u2, pairs)]: twice the
+        Mann-Whitney U of the predicted indicator of the class between the usable test rows of the class and the other
+        usable test rows, ties counted once, and the number of such pairs -- to ``auc_dev`` (capacity, k, T, 2) int64 in
+        submission order, and every :meth:`simpls_crossval_perm_into` of m permutations m blocks, each summed over that
+        call's splits (plsx_simpls_cv_auc_begin).  The tensor must stay alive until the series ends.  PlsxError: status
+        -4 before :meth:`simpls_set_classes`, -1 from the call that would pass the capacity."""
+        torch = _torch()
+        if auc_dev.dim() != 4 or tuple(auc_dev.shape[1:]) != (self.k, self.T, 2) or auc_dev.dtype != torch.int64 \
+                or not auc_dev.is_contiguous():
+            raise ValueError('the AUC counts must be a contiguous (capacity, {}, {}, 2) int64 tensor'
+                             .format(self.k, self.T))
+        self._check(self.lib.plsx_simpls_cv_auc_begin(self.ctx, auc_dev.data_ptr(), int(auc_dev.shape[0])))
+
+    def simpls_cv_auc_end(self):
+        """Close the series of AUC counts (plsx_simpls_cv_auc_end)."""
+        self._check(self.lib.plsx_simpls_cv_auc_end(self.ctx))
 
     def simpls_vip_keep(self, stack):
         """Keep the VIP stack of every bootstrap the :meth:`simpls_boot_into` calls that follow solve: ``stack``

@@ -52,6 +52,8 @@ Differences from the reference at this commit, on purpose:
   * ``_classes`` (build-only, set by :func:`pypyls_amd.discriminant.pls_da`): Y is the indicator matrix of these class
     codes; the splits are drawn stratified and the cross-validation also returns confusion counts
     (plsx_simpls_set_classes / plsx_simpls_cv_class_begin; csrc/plsx_simpls.h, k_sd_cv_class).
+  * ``_auc`` (build-only, set by ``pls_da(auc=True)``; needs ``_classes``): the cross-validation also returns the
+    one-vs-rest AUC counts of every class (plsx_simpls_cv_auc_begin; k_sd_cv_auc).
 """
 import warnings
 
@@ -461,6 +463,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     cv = None
     if n_cv > 0:
         cv = dict(n=n_cv, masks=cvmasks, classes=kwargs.get('_classes'))
+        cv['auc'] = bool(kwargs.get('_auc')) and cv['classes'] is not None
         if cvmasks is None:
             # one more job at the END of the list: what a seeded call drew before, it draws still
             def cv_draw(r):
@@ -682,7 +685,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             st.warn()
     # cross-validation: this rank's contiguous shard of the splits (the masks exist once the draws are through), in
     # calls of at most one solver batch
-    d_cv = d_conf = d_confp = None
+    d_cv = d_conf = d_confp = d_auc = d_aucp = None
     if cv is not None:
         cvmasks = cv['masks']
         lo, hi = parallel.shard_bounds(cv['n'], rank, world)
@@ -692,6 +695,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             d_conf = torch.zeros((hi - lo, k, T, T), dtype=torch.int32, device=eng.device)
             if hi > lo:
                 eng.simpls_cv_class_begin(d_conf)
+            if cv['auc']:
+                # ... and, beside it, one block of AUC counts (plsx_simpls_cv_auc_begin: an independent series)
+                d_auc = torch.zeros((hi - lo, k, T, 2), dtype=torch.int64, device=eng.device)
+                if hi > lo:
+                    eng.simpls_cv_auc_begin(d_auc)
         bars.append(Bar('Running cross-validation', hi - lo, show, eng.device))
         for a in range(lo, hi, 8192):
             b = min(hi, a + 8192)
@@ -702,6 +710,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             bars[-1].queued(b - a)
         if d_conf is not None:
             eng.simpls_cv_class_end()
+        if d_auc is not None:
+            eng.simpls_cv_auc_end()
         tick('crossval')
     # ... and its permutation test: this rank's contiguous shard of the permutations under ALL the splits.  The
     # (permutation, split) fits are formed, scored and reduced over the splits on the device; a rank keeps three rows
@@ -719,6 +729,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             d_confp = torch.zeros((hi - lo, k, T, T), dtype=torch.int32, device=eng.device)
             if hi > lo:
                 eng.simpls_cv_class_begin(d_confp)
+            if cv['auc']:
+                d_aucp = torch.zeros((hi - lo, k, T, 2), dtype=torch.int64, device=eng.device)
+                if hi > lo:
+                    eng.simpls_cv_auc_begin(d_aucp)
         step = max(1, 65536 // cv['n'])
         for a in range(lo, hi, step):
             b = min(hi, a + step)
@@ -729,6 +743,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             bars[-1].queued(b - a)
         if d_confp is not None:
             eng.simpls_cv_class_end()
+        if d_aucp is not None:
+            eng.simpls_cv_auc_end()
         if lead and cv.get('perm_given') is None:
             cvp.warn()
         tick('crossval_perm')
@@ -787,6 +803,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         slices, totals = slices + [d_conf.to(torch.float64)], totals + [cv['n']]
     if d_confp is not None:
         slices, totals = slices + [d_confp.to(torch.float64)], totals + [cvp.n]
+    for t, n in ((d_auc, cv['n'] if cv is not None else 0), (d_aucp, cvp.n if cvp is not None else 0)):
+        if t is not None:                               # ... and the AUC counts, the same way: exact below 2^53
+            assert t.numel() == 0 or int(t.max().item()) < 2 ** 53, 'AUC counts beyond 2^53 do not ride as float64'
+            slices, totals = slices + [t.to(torch.float64)], totals + [n]
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
@@ -854,6 +874,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             from .discriminant import confusion_results
             j = i + 3 + (3 if d_cvp is not None else 0) + (2 if d_sh is not None else 0)
             res['cvres'].update(confusion_results(full[j], full[j + 1] if d_confp is not None else None))
+            if d_auc is not None:
+                from .discriminant import auc_results
+                j += 2 if d_confp is not None else 1
+                res['cvres'].update(auc_results(full[j], full[j + 1] if d_aucp is not None else None))
     if d_sh0 is not None:
         orig_uc, orig_vc = (t.cpu().numpy()[0] for t in d_sh0)
         res['splitres'].update(dict(ucorr=orig_uc, vcorr=orig_vc))

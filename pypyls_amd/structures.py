@@ -100,6 +100,7 @@ class PLSInputs(KeyedRecord):
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
         '_classes',                         # pls_da: class code of every row (Y is their indicator matrix)
+        '_auc',                             # pls_da(auc=True): the cross-validation also returns AUC counts (only when asked for)
     )
 
     def __init__(self, **kwargs):
@@ -160,7 +161,13 @@ class PLSCrossValidationResults(KeyedRecord):
                # with cv_perm=P: perm_confusion (G, G, k, P) summed over the splits of a permutation, perm_accuracy /
                # perm_balanced_accuracy (k, P) of that sum, accuracy_pvals / balanced_accuracy_pvals (k,)
                'confusion', 'accuracy', 'balanced_accuracy', 'perm_confusion', 'perm_accuracy',
-               'perm_balanced_accuracy', 'accuracy_pvals', 'balanced_accuracy_pvals')
+               'perm_balanced_accuracy', 'accuracy_pvals', 'balanced_accuracy_pvals',
+               # pls_da(auc=True): auc_counts (G, 2, k, n) int [class, (u2, pairs), c - 1, split], auc (G, k, n) one-vs-rest
+               # AUC = u2 / (2 pairs), auc_macro (k, n) its mean over the classes with a pair; with cv_perm=P:
+               # perm_auc_counts (G, 2, k, P) summed over the splits of a permutation, perm_auc (G, k, P) / perm_auc_macro
+               # (k, P) of that sum, auc_pvals (G, k) / auc_macro_pvals (k,)
+               'auc_counts', 'auc', 'auc_macro', 'perm_auc_counts', 'perm_auc', 'perm_auc_macro', 'auc_pvals',
+               'auc_macro_pvals')
 
 
 class PLSResults(KeyedRecord):
