@@ -550,8 +550,8 @@ try {
     coef_close(ctx);                                   // (an open coefficient series ends with the binding it belonged to)
     vip_close(ctx);                                    // (... and so does a kept VIP stack)
     cperm_close(ctx);                                  // (... and an open permutation series of the coefficients)
-    cls_close(ctx);                                    // (... and the class codes of its rows with their open series)
-    auc_close(ctx);
+    count_close(ctx->cls_series);                      // (... and the class codes of its rows with their open series)
+    count_close(ctx->auc_series);
     ctx->has_cls = 0;
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;

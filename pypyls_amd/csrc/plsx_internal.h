@@ -9,7 +9,7 @@
 //   plsx_small.hip       k_small, k_refine_gram, k_rotate_rows; plsx_smallql{1,2}.hip: k_small_ql (plsx_smallql.h)
 //   plsx_urot.hip        k_urot, k_ucorr_partial
 //   plsx_split.hip       split-half and cross-validation
-//   plsx_simpls_api.hip  SIMPLS regression
+//   plsx_simpls_api.hip  SIMPLS regression: the solver batch (run_simpls_dual on an SdRequest), products with K (sd_times_K), one cross-validation body (cv_fit_score), the count series of PLS-DA (CountSeries)
 //   plsx_comm.hip        the exported collective (RCCL through dlopen)
 #pragma once
 #include "plsx_kernels.h"
@@ -60,6 +60,23 @@ static const char* const kOptionNames[OPT_COUNT] = {
 #ifndef PLSX_CKTW
 #define PLSX_CKTW 2
 #endif
+
+// A series of count blocks that rides along plsx_simpls_crossval_batch / plsx_simpls_crossval_perm_batch, appended to the
+// caller's buffer: one block per split or permutation (plsx_simpls_api.hip: count_begin, count_reserve, count_launch).
+struct CountSeries {
+    const char* what;                                   // what a block counts, in the refusal of a call that does not fit
+    const char* entry;                                  // the entry that opens the series, in that refusal and its own
+    int active = 0;
+    char* base = nullptr;                               // the caller's buffer
+    long long cap = 0, n = 0;                           // blocks it holds / blocks appended
+    size_t blk_bytes = 0;                               // bytes of one block (fixed when the series opens)
+};
+// an open series of counts ends (plsx_set_data, plsx_simpls_set_classes, a second _begin, its _end); the buffer stays
+// the caller's
+inline void count_close(CountSeries& s)
+{
+    s.active = 0; s.base = nullptr; s.cap = 0; s.n = 0;
+}
 
 struct plsx_ctx {
     int device = 0;
@@ -170,15 +187,12 @@ struct plsx_ctx {
     // classes; plsx_simpls_cv_class_begin: a series of confusion counts rides along plsx_simpls_crossval_batch /
     // plsx_simpls_crossval_perm_batch -- blocks [k][G][G] int32 appended to the caller's buffer (k_sd_cv_class)
     Buf cls, clsfreq;                                   // the codes [S] and the class frequencies n_g / S [G]
-    int has_cls = 0, cls_active = 0;
-    int* cls_conf = nullptr;
-    long long cls_cap = 0, cls_n = 0;
+    int has_cls = 0;
+    CountSeries cls_series{"confusion counts", "plsx_simpls_cv_class_begin"};
     // plsx_simpls_cv_auc_begin: a second series on the same two calls, open or not whatever the first is -- blocks
     // [k][G][2] int64 appended to the caller's buffer (k_sd_cv_auc): twice the Mann-Whitney U of every class against the
     // rest, and the pairs it was counted over
-    int auc_active = 0;
-    long long* auc_out = nullptr;
-    long long auc_cap = 0, auc_n = 0;
+    CountSeries auc_series{"AUC counts", "plsx_simpls_cv_auc_begin"};
     bool has_okx = false, has_oky = false;
     int n_okx = 0;                                      // usable rows of X under the row masks (has_okx)
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
@@ -388,18 +402,6 @@ inline void cperm_close(plsx_ctx* ctx)
     ctx->cperm_active = 0; ctx->cperm_c = 0; ctx->cperm_std = 0;
     ctx->cperm_obs = nullptr; ctx->cperm_count = nullptr; ctx->cperm_max = nullptr;
     ctx->cperm_cap = 0; ctx->cperm_n = 0;
-}
-// an open series of confusion counts ends (plsx_set_data, plsx_simpls_set_classes, a second
-// plsx_simpls_cv_class_begin, plsx_simpls_cv_class_end); the buffer stays the caller's
-inline void cls_close(plsx_ctx* ctx)
-{
-    ctx->cls_active = 0; ctx->cls_conf = nullptr; ctx->cls_cap = 0; ctx->cls_n = 0;
-}
-// an open series of AUC counts ends (plsx_set_data, plsx_simpls_set_classes, a second plsx_simpls_cv_auc_begin,
-// plsx_simpls_cv_auc_end); the buffer stays the caller's
-inline void auc_close(plsx_ctx* ctx)
-{
-    ctx->auc_active = 0; ctx->auc_out = nullptr; ctx->auc_cap = 0; ctx->auc_n = 0;
 }
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);

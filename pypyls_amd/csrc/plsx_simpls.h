@@ -1278,6 +1278,15 @@ void k_sd_final(SdArgs a)
     }
 }
 
+// Usable test position p of a cross-validated fit: outside its training mask `pm` and not a masked (all-NaN) row of X
+// or of the Y row the fit observes there -- p itself, under PERM row ysp[p] (`ysp`: the fit's `ys`): get_mask(X,
+// Y[perm]).  The one definition k_sd_cv_score, k_sd_cv_class and k_sd_cv_auc share.
+template <bool PERM>
+__device__ __forceinline__ bool sd_cv_is_test(const SdArgs& a, const uint8_t* pm, const int* ysp, int p)
+{
+    return !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[PERM ? ysp[p] : p]);
+}
+
 // Cross-validation of one train / test split (plsx_simpls_crossval_batch), after the solver ran on the training rows
 // (a.pmask: test positions excluded like masked rows) and Z = Vd . K was formed.  With wd_j the dual weights (centred
 // over the training rows, zero elsewhere) and K of the bound, globally centred data,
@@ -1317,8 +1326,7 @@ void k_sd_cv_score(SdArgs a)
     double* out_r2 = a.cvr2 + (size_t)r * k * T;
     double* out_sse = a.cvsse + (size_t)r * (k + 1) * T;
     const double ninc = a.scal[(size_t)r * 4];
-    // usable test position: outside the training mask and not a masked (all-NaN) row
-    auto is_test = [&](int p) { return !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[yrow(p)]); };
+    auto is_test = [&](int p) { return sd_cv_is_test<PERM>(a, pm, ysp, p); };
     // ---- scores of every position, centred by their training mean (in place)
     for (int j0 = 0; j0 < k; j0 += 4) {
         double* z0 = Z + (size_t)min(j0, k - 1) * S;
@@ -1435,8 +1443,9 @@ void k_sd_cv_score(SdArgs a)
     }
 }
 
-// Classification of the test rows of one fit (plsx_simpls_cv_class_begin), after k_sd_cv_score centred Z in place.  The
-// bound Y is the indicator matrix of G = T classes minus its column means over all S rows (a.cfreq = n_g / S), a.cls
+// The class prediction of a cross-validated fit (PLS-DA), after k_sd_cv_score centred Z in place: what k_sd_cv_class
+// takes the argmax of and k_sd_cv_auc ranks, defined HERE ONCE for both so that their counts speak of the same numbers.
+// The bound Y is the indicator matrix of G = T classes minus its column means over all S rows (a.cfreq = n_g / S), a.cls
 // the class code of every row; so the fit's Y0[g][p] = [class of p is g] - f_g on its training positions, with
 // f_g = ymean[g] + cfreq[g] the class frequency among them, and zero elsewhere.  Per component count c = 1 .. k:
 //     q_c[g]     = sum_p Y0[g][p] z_c[p] = s_g - f_g sum_h s_h,   s_g = sum of z_c over the training positions of class g
@@ -1446,15 +1455,68 @@ void k_sd_cv_score(SdArgs a)
 //                                                               column means that the global centring of the bound
 //                                                               indicators took away -- the classes are read off the
 //                                                               RAW indicators' prediction)
+// One wavefront per fit r, lanes over positions.  f, s_g / q_c: GB registers per lane (GB the compile-time bound of G:
+// 4, 16 or 32).  The role of every position is one int in the first half of the fit's `va` (S ints in S doubles, idle
+// once k_sd_cv_score is through), written and read by the lane that owns p only.  PERM as for k_sd_cv_score: rows of Y
+// and their classes go through the fit's `ys`.  Each kernel keeps the running prediction yhat its own way.
+
+// role of position p: its class on a training position, 64 + its class on a usable test position, -1 otherwise
+template <bool PERM>
+__device__ __forceinline__ void sd_cv_roles(const SdArgs& a, int r, int lane, int* role)
+{
+    const int S = a.S;
+    const int* xs = a.xs + (size_t)r * S;
+    const uint8_t* pm = a.pmask + (size_t)r * S;
+    const int* ysp = a.ys + (size_t)r * S;
+    for (int p = lane; p < S; p += 64) {
+        const bool te = sd_cv_is_test<PERM>(a, pm, ysp, p);
+        role[p] = (xs[p] >= 0 || te) ? (a.cls[PERM ? ysp[p] : p] | (te ? 64 : 0)) : -1;
+    }
+}
+
+// f_g, the class frequencies among the fit's training positions: yhat_0
+template <int GB>
+__device__ __forceinline__ void sd_cv_class_f(const SdArgs& a, int r, double (&f)[GB])
+{
+    const int G = a.T;
+    const double* ym = a.ymean + (size_t)r * G;
+#pragma unroll
+    for (int g = 0; g < GB; ++g) f[g] = g < G ? ym[g] + a.cfreq[g] : 0.0;
+}
+
+// q_c[g] of component c from its centred scores zc: one pass for s_g, reduced four classes at a time in fixed order.
+// (s is an array of the helper's own, copied out at the end: accumulated through the out-parameter, the compiler
+// keeps it in another form than the kernels' own arrays and k_sd_cv_class<16> takes 141 VGPRs instead of 123.)
+template <int GB>
+__device__ __forceinline__ void sd_cv_class_q(const int* role, const double* zc, int S, int G, int lane,
+                                              const double (&f)[GB], double (&q)[GB])
+{
+    double s[GB];
+#pragma unroll
+    for (int g = 0; g < GB; ++g) s[g] = 0.0;
+    for (int p = lane; p < S; p += 64) {
+        const int rl = role[p];
+        const double z = zc[p];
+#pragma unroll
+        for (int g = 0; g < GB; ++g) s[g] += rl == g ? z : 0.0;
+    }
+#pragma unroll
+    for (int g = 0; g < GB; g += 4)
+        if (g < G) wave_sum4(s[g], s[g + 1], s[g + 2], s[g + 3]);
+    double sall = 0.0;
+#pragma unroll
+    for (int g = 0; g < GB; ++g) sall += s[g];
+#pragma unroll
+    for (int g = 0; g < GB; ++g) q[g] = s[g] - f[g] * sall;
+}
+
+// Classification of the test rows of one fit (plsx_simpls_cv_class_begin), on the prediction above:
 //     conf[c][class of p][first maximum of yhat_c[p]] += 1     for every usable test position p
-// The first maximum is numpy's argmax: the lowest index on a tie.  One wavefront per fit, lanes over positions.  Where
-// things live: s_g / q_c in GB registers per lane (GB the compile-time bound of G: 4, 16 or 32; reduced four at a time
-// in fixed order), the running prediction of position p in the fit's Z0 rows -- [G][S], idle once the solver is through
-// -- the role of every position (training / usable test, with its class) as one int in the fit's `va`, both touched by
-// the lane that owns p only, and the G x G counters of the open c in the wave's LDS slice (integer atomics: exact in any
-// order).  After each c the non-zero counters are added to the fit's block with integer atomics: under PERM the n
-// splits of a permutation share one block, which was zeroed when it was appended.  PERM as for k_sd_cv_score: rows of
-// Y and their classes go through the fit's `ys`.
+// The first maximum is numpy's argmax: the lowest index on a tie.  The running prediction of position p lives in the
+// fit's Z0 rows -- [G][S], idle once the solver is through -- touched by the lane that owns p only, and the G x G
+// counters of the open c in the wave's LDS slice (integer atomics: exact in any order).  After each c the non-zero
+// counters are added to the fit's block with integer atomics: under PERM the n splits of a permutation share one
+// block, which was zeroed when it was appended.
 template <int GB, bool PERM>
 static __global__ __launch_bounds__(256)
 void k_sd_cv_class(SdArgs a)
@@ -1463,45 +1525,19 @@ void k_sd_cv_class(SdArgs a)
     const int S = a.S, G = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
     const int r = blockIdx.x * 4 + wave;
     if (r >= a.nres) return;
-    const int* xs = a.xs + (size_t)r * S;
-    const uint8_t* pm = a.pmask + (size_t)r * S;
-    const double* ym = a.ymean + (size_t)r * G;
-    const int* ysp = a.ys + (size_t)r * S;
-    auto yrow = [&](int p) { if constexpr (PERM) return ysp[p]; else return p; };
     const double* Z = a.cvZ + (size_t)r * k * S;
     double* yh = a.Z0 + (size_t)r * S * G;
-    int* role = reinterpret_cast<int*>(a.va + (size_t)r * S);                  // (S ints in the fit's S doubles)
+    int* role = reinterpret_cast<int*>(a.va + (size_t)r * S);
     const long long blk = (a.cls_f0 + r) / a.cls_n - a.cls_f0 / a.cls_n;       // (64-bit, as the pair list itself)
     int* out = a.conf + (size_t)blk * k * G * G;
     int* cnt = sm_cnt[wave];
-    // role of position p: its class on a training position, 64 + its class on a usable test position (outside the
-    // training mask and not a masked row), -1 otherwise
-    for (int p = lane; p < S; p += 64) {
-        const bool te = !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[yrow(p)]);
-        role[p] = (xs[p] >= 0 || te) ? (a.cls[yrow(p)] | (te ? 64 : 0)) : -1;
-    }
+    sd_cv_roles<PERM>(a, r, lane, role);
     double f[GB];
-#pragma unroll
-    for (int g = 0; g < GB; ++g) f[g] = g < G ? ym[g] + a.cfreq[g] : 0.0;
+    sd_cv_class_f(a, r, f);
     for (int c = 0; c < k; ++c) {
         const double* zc = Z + (size_t)c * S;
         double q[GB];
-#pragma unroll
-        for (int g = 0; g < GB; ++g) q[g] = 0.0;
-        for (int p = lane; p < S; p += 64) {
-            const int rl = role[p];
-            const double z = zc[p];
-#pragma unroll
-            for (int g = 0; g < GB; ++g) q[g] += rl == g ? z : 0.0;
-        }
-#pragma unroll
-        for (int g = 0; g < GB; g += 4)
-            if (g < G) wave_sum4(q[g], q[g + 1], q[g + 2], q[g + 3]);
-        double sall = 0.0;
-#pragma unroll
-        for (int g = 0; g < GB; ++g) sall += q[g];
-#pragma unroll
-        for (int g = 0; g < GB; ++g) q[g] -= f[g] * sall;
+        sd_cv_class_q(role, zc, S, G, lane, f, q);
         for (int i = lane; i < G * G; i += 64) cnt[i] = 0;
         wave_sync();
         for (int p = lane; p < S; p += 64) {
@@ -1546,26 +1582,24 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-// One-vs-rest AUC counts of the test rows of one fit (plsx_simpls_cv_auc_begin), after k_sd_cv_score centred Z in place
-// and, where that series is open too, after k_sd_cv_class.  Per component count c and class g, with pos the usable test
-// positions of true class g, neg the other usable test positions and v[p] = yhat_c[p][g] (the prediction k_sd_cv_class
-// takes the argmax of, formed here by the same arithmetic: f, one pass over z_c and the roles for q_c, wave_sum4 in the
-// same fixed order),
+// One-vs-rest AUC counts of the test rows of one fit (plsx_simpls_cv_auc_begin), behind k_sd_cv_score and, where that
+// series is open too, k_sd_cv_class in stream order.  Per component count c and class g, with pos the usable test
+// positions of true class g, neg the other usable test positions and v[p] = yhat_c[p][g], the class prediction defined
+// above k_sd_cv_class (sd_cv_roles, sd_cv_class_f, sd_cv_class_q: the same helpers, hence the same numbers),
 //     u2    = sum over i in pos, j in neg of (2 if v[i] > v[j], 1 if v[i] == v[j], else 0)       twice Mann-Whitney's U
 //     pairs = |pos| |neg|
-// A comparison with a NaN is false both ways: the pair counts in `pairs` and adds nothing to u2.  One wavefront per
-// fit.  Where things live (all of it idle once k_sd_cv_score and k_sd_cv_class are through, and stream order puts this
-// kernel behind them): the role of every position as one int in the first half of the fit's `va` (S ints, as
-// k_sd_cv_class writes them), the usable test positions listed CLASS BY CLASS in its second half (S more ints: `va` is S
-// doubles), where the list of class g starts in the wave's LDS slice, the running prediction of listed position i in
-// the fit's Z0 rows, [G][S] indexed by the place in the list -- so the positives of a class are contiguous and a lane
-// that owns one is never idle because its neighbour's position belongs to another class.  Per class the lanes own the
+// A comparison with a NaN is false both ways: the pair counts in `pairs` and adds nothing to u2.  Where things live
+// beyond the roles (all of it idle once k_sd_cv_score and k_sd_cv_class are through): the usable test positions listed
+// CLASS BY CLASS in the second half of the fit's `va` (S more ints), where the list of class g starts in the wave's LDS
+// slice, the running prediction of listed position i in the fit's Z0 rows, [G][S] indexed by the place in the list --
+// so the positives of a class are contiguous and a lane that owns one is never idle because its neighbour's position
+// belongs to another class.  Per class the lanes own the
 // positives, 64 at a time, and walk the negatives, which the wave stages 64 at a time in its LDS slice (a read of one
 // address by every lane); a lane without a positive, and a staged place without a negative, hold a NaN and count
 // nothing.  Per-lane counts are 32-bit (at most ceil(S / 64) S comparisons per lane and class), their sum over the wave
 // 64-bit, and one lane adds u2 and pairs to the fit's block with 64-bit integer atomics: under PERM the n splits of a
 // permutation share one block, which was zeroed when it was appended.  The list and the predictions are written by one
-// lane and read by another through global memory: wave_cu_sync() between.  PERM as for k_sd_cv_class.
+// lane and read by another through global memory: wave_cu_sync() between.
 template <int GB, bool PERM>
 static __global__ __launch_bounds__(256)
 void k_sd_cv_auc(SdArgs a)
@@ -1575,11 +1609,6 @@ void k_sd_cv_auc(SdArgs a)
     const int S = a.S, G = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
     const int r = blockIdx.x * 4 + wave;
     if (r >= a.nres) return;
-    const int* xs = a.xs + (size_t)r * S;
-    const uint8_t* pm = a.pmask + (size_t)r * S;
-    const double* ym = a.ymean + (size_t)r * G;
-    const int* ysp = a.ys + (size_t)r * S;
-    auto yrow = [&](int p) { if constexpr (PERM) return ysp[p]; else return p; };
     const double* Z = a.cvZ + (size_t)r * k * S;
     double* yh = a.Z0 + (size_t)r * S * G;
     int* role = reinterpret_cast<int*>(a.va + (size_t)r * S);                  // (S ints in the first half of the fit's S doubles)
@@ -1589,12 +1618,7 @@ void k_sd_cv_auc(SdArgs a)
     double* stage = sm_stage[wave];
     int* start = sm_start[wave];
     const double nan = __builtin_nan("");
-    // role of position p, as k_sd_cv_class defines it: its class on a training position, 64 + its class on a usable test
-    // position, -1 otherwise (written and read by the lane that owns p)
-    for (int p = lane; p < S; p += 64) {
-        const bool te = !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[yrow(p)]);
-        role[p] = (xs[p] >= 0 || te) ? (a.cls[yrow(p)] | (te ? 64 : 0)) : -1;
-    }
+    sd_cv_roles<PERM>(a, r, lane, role);
     // the usable test positions, class by class and ascending within a class: list[start[g] .. start[g + 1])
     int nl = 0;
     for (int g = 0; g < G; ++g) {
@@ -1610,27 +1634,11 @@ void k_sd_cv_auc(SdArgs a)
     if (lane == 0) start[G] = nl;
     wave_cu_sync();
     double f[GB];
-#pragma unroll
-    for (int g = 0; g < GB; ++g) f[g] = g < G ? ym[g] + a.cfreq[g] : 0.0;
+    sd_cv_class_f(a, r, f);
     for (int c = 0; c < k; ++c) {
         const double* zc = Z + (size_t)c * S;
         double q[GB];
-#pragma unroll
-        for (int g = 0; g < GB; ++g) q[g] = 0.0;
-        for (int p = lane; p < S; p += 64) {
-            const int rl = role[p];
-            const double z = zc[p];
-#pragma unroll
-            for (int g = 0; g < GB; ++g) q[g] += rl == g ? z : 0.0;
-        }
-#pragma unroll
-        for (int g = 0; g < GB; g += 4)
-            if (g < G) wave_sum4(q[g], q[g + 1], q[g + 2], q[g + 3]);
-        double sall = 0.0;
-#pragma unroll
-        for (int g = 0; g < GB; ++g) sall += q[g];
-#pragma unroll
-        for (int g = 0; g < GB; ++g) q[g] -= f[g] * sall;
+        sd_cv_class_q(role, zc, S, G, lane, f, q);
         // the running prediction of the listed positions
         for (int i = lane; i < nl; i += 64) {
             const double z = zc[list[i]];

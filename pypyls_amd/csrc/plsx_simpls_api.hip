@@ -55,30 +55,54 @@ int simpls_form_K(plsx_ctx* ctx, hipStream_t st)
     return nt_strips(ctx, ptr<double>(ctx->Xc), ctx->Bpad, S, ptr<double>(ctx->Xc), ctx->Bpad, S, ctx->B, K, S, st);
 }
 
-int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, bool scatter,
-                    double* pctvar, double* yload, double* cvec, hipStream_t st,
-                    const double* ystack = nullptr, bool align_signs = false, double* Vd = nullptr,
-                    const uint8_t* pmask = nullptr, SdArgs* args_out = nullptr, bool weights_only = false)
+// A [rows][S] against the bound K (S x S, symmetric) into Z [rows][S], on the route of the component step
+static int sd_times_K(plsx_ctx* ctx, const double* A, int rows, double* Z, hipStream_t st)
 {
-    // weights_only (without scatter): k_sd_step keeps the dual weights WD in the batch's state (a.weights), nothing
-    // leaves the solver but pctvar -- k_sd_final does not run (the permutation test of the coefficients reads the state)
-    // Vd (with scatter): the dual weights go out dense, [nres][k][S] (k_sd_final writes every entry), not into the A operand
-    // pmask: [nres][S] positions a resample keeps (cross-validation: its training rows); args_out: the carved-out
-    // state of the batch, for a kernel that runs after the chain (valid until the next call)
+    const int S = ctx->S;
+    const double* K = ptr<double>(ctx->Kmat);
+    if (simpls_global(ctx)) return nt_strips(ctx, A, S, rows, K, S, S, S, Z, S, st);
+    return run_nt(ctx, A, 0, S, rows, K, 0, S, S, nullptr, 0, 0, 0, S, 1, Z, 0, S, nullptr, 0, 0, st);
+}
+
+// What a caller asks of one solver batch (run_simpls_dual): a call site sets the fields it uses.
+struct SdRequest {
+    const int* xsrc = nullptr;          // [nres][S] X source of every position, or nullptr: identity
+    const int* ysrc = nullptr;          // [nres][S] Y source, or nullptr
+    int nres = 0;                       // resamples of the batch
+    bool scatter = false;               // the dual weights leave the solver (k_sd_final runs); without it pctvar is all that does
+    double* pctvar = nullptr;           // [nres][k]
+    double* yload = nullptr;            // [nres][T][k]
+    double* cvec = nullptr;             // [nres][T][k]
+    const double* ystack = nullptr;     // [nres][S][T] a Y of its own per resample, or nullptr: the bound Y
+    bool align_signs = false;           // (with scatter) signs aligned in dual space against ctx->Qs
+    double* Vd = nullptr;               // (with scatter) the dual weights go out dense, [nres][k][S] (k_sd_final writes every
+                                        // entry), not into the A operand
+    const uint8_t* pmask = nullptr;     // [nres][S] positions a resample keeps (cross-validation: its training rows)
+    SdArgs* args_out = nullptr;         // the carved-out state of the batch, for a kernel that runs after the chain (valid
+                                        // until the next call)
+    bool weights_only = false;          // (without scatter) k_sd_step keeps the dual weights WD in the batch's state
+                                        // (a.weights), nothing leaves the solver but pctvar -- k_sd_final does not run (the
+                                        // permutation test of the coefficients reads the state)
+};
+
+int run_simpls_dual(plsx_ctx* ctx, const SdRequest& q, hipStream_t st)
+{
+    const int nres = q.nres;
+    const bool scatter = q.scatter;
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
     const int groups = ceil_div(nres, ctx->npg);
     if (int e = ensure_scratch(ctx, std::min(groups, ctx->Gcap))) return e;
     SdArgs a;
     memset(&a, 0, sizeof(a));
     a.jacobi_eig = ctx->opt[OPT_SIMPLS_JACOBI] ? 1 : 0;
-    a.weights = (scatter || weights_only) ? 1 : 0;
+    a.weights = (scatter || q.weights_only) ? 1 : 0;
     a.S = S; a.T = T; a.k = k; a.nres = nres;
-    a.Yc = ystack ? ystack : ptr<double>(ctx->Y);
-    a.y_stride = ystack ? (long long)S * T : 0;
+    a.Yc = q.ystack ? q.ystack : ptr<double>(ctx->Y);
+    a.y_stride = q.ystack ? (long long)S * T : 0;
     a.okx = ctx->has_okx ? ptr<uint8_t>(ctx->okx) : nullptr;
     a.oky = ctx->has_oky ? ptr<uint8_t>(ctx->oky) : nullptr;
-    a.xsrc = xsrc; a.ysrc = ysrc;
-    a.pmask = pmask;
+    a.xsrc = q.xsrc; a.ysrc = q.ysrc;
+    a.pmask = q.pmask;
     // per-resample state, carved out of one scratch buffer (doubles)
     const bool gl = simpls_global(ctx);
     const size_t n = (size_t)nres;
@@ -107,9 +131,9 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
     a.scal = w; w += n * 4;
     a.Wt = w; w += gemm_rows * S;
     a.Zt = w;
-    a.pctvar = pctvar; a.yload = yload; a.cvec = cvec;
-    if (scatter && Vd) {
-        a.Vd = Vd;                                     // (k_sd_final writes every entry)
+    a.pctvar = q.pctvar; a.yload = q.yload; a.cvec = q.cvec;
+    if (scatter && q.Vd) {
+        a.Vd = q.Vd;                                   // (k_sd_final writes every entry)
     } else if (scatter) {
         // the solver batch may span several cross-product batches: its own span of A operands
         if (int e = ensure(ctx, ctx->Afrag, (size_t)groups * ctx->group_stride * 8 + 4096)) return e;
@@ -118,7 +142,6 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
         a.lay.n = ctx->npg; a.lay.Tp = ctx->Tp; a.lay.J = 1; a.lay.T = T; a.lay.MT = ctx->MT;
         a.lay.w0 = ctx->w0; a.lay.sq0 = ctx->sq0; a.lay.Tpp = ctx->Tpp;
     }
-    const double* K = ptr<double>(ctx->Kmat);
     // one wavefront per resample; as many waves per block as keep >= 2 blocks of k_sd_step on a CU
     const size_t step_wave = gl ? simpls_global_lds_bytes(T, k) : sd_step_lds(S, T, k) * 8;
     const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (72 * 1024) / step_wave));
@@ -138,11 +161,7 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
         LAUNCHCHK();
     }
     // GEMM 0: (T + 1) subject-space vectors per resample against K (symmetric)
-    if (gl) {
-        if (int e = nt_strips(ctx, a.Wt, S, (int)gemm_rows, K, S, S, S, a.Zt, S, st)) return e;
-    } else if (int e = run_nt(ctx, a.Wt, 0, S, (int)gemm_rows, K, 0, S, S, nullptr, 0, 0, 0, S, 1, a.Zt, 0, S,
-                              nullptr, 0, 0, st))
-        return e;
+    if (int e = sd_times_K(ctx, a.Wt, (int)gemm_rows, a.Zt, st)) return e;
     {
         KTimer tm(ctx, KC_SIMPLS, st);
         void (*post0_kernel)(SdArgs) =
@@ -172,15 +191,11 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
             LAUNCHCHK();
         }
         // GEMM c: K beta for every resample of the batch (the last component needs none)
-        if (c + 1 < k && gl) {
-            if (int e = nt_strips(ctx, a.Wt, S, nres, K, S, S, S, a.Zt, S, st)) return e;
-        } else if (c + 1 < k)
-            if (int e = run_nt(ctx, a.Wt, 0, S, nres, K, 0, S, S, nullptr, 0, 0, 0, S, 1, a.Zt, 0, S,
-                               nullptr, 0, 0, st))
-                return e;
+        if (c + 1 < k)
+            if (int e = sd_times_K(ctx, a.Wt, nres, a.Zt, st)) return e;
     }
     if (scatter) {          // (permutations: pctvar is all that leaves the solver -- no y-loadings, no weights)
-        a.Qs = align_signs ? ptr<double>(ctx->Qs) : nullptr;
+        a.Qs = q.align_signs ? ptr<double>(ctx->Qs) : nullptr;
         KTimer tm(ctx, KC_SIMPLS, st);
         // (per wave: the signs and, on the on-chip route, one subject-space scatter buffer)
         const size_t lds_f = (size_t)wpb * (gl ? k : k + S) * 8;
@@ -192,7 +207,7 @@ int run_simpls_dual(plsx_ctx* ctx, const int* xsrc, const int* ysrc, int nres, b
         hipLaunchKernelGGL(final_kernel, grid, block, lds_f, st, a);
         LAUNCHCHK();
     }
-    if (args_out) *args_out = a;
+    if (q.args_out) *q.args_out = a;
 #ifdef PLSX_SD_PROBE
     {
         unsigned long long h[16][32];
@@ -417,64 +432,117 @@ static int coef_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 
 }  // namespace plsxi
 
-// The open series of confusion counts (plsx_simpls_cv_class_begin) and of AUC counts (plsx_simpls_cv_auc_begin): room for
-// m more blocks in each that is open, or PLSX_ERR_ARG before anything is computed or zeroed; the blocks are zeroed
-// here, in stream order before the kernels that count into them.
-static int cls_reserve(plsx_ctx* ctx, const char* who, int m, hipStream_t st)
+// The two series of counts that ride along the cross-validation entries (CountSeries): confusion counts, blocks
+// [k][G][G] int32 (plsx_simpls_cv_class_begin), and AUC counts, blocks [k][G][2] int64 (plsx_simpls_cv_auc_begin).  The
+// bodies of their _begin / _end entries:
+static int count_begin(plsx_ctx* ctx, bool auc, void* d_buf, long long capacity)
 {
-    if (ctx->cls_active && ctx->cls_n + m > ctx->cls_cap) {
-        char msg[240];
-        snprintf(msg, sizeof msg, "%s: the open series of confusion counts holds %lld of %lld blocks, %d more do not fit "
-                 "(plsx_simpls_cv_class_begin)", who, ctx->cls_n, ctx->cls_cap, m);
-        return fail(ctx, PLSX_ERR_ARG, msg);
-    }
-    if (ctx->auc_active && ctx->auc_n + m > ctx->auc_cap) {
-        char msg[240];
-        snprintf(msg, sizeof msg, "%s: the open series of AUC counts holds %lld of %lld blocks, %d more do not fit "
-                 "(plsx_simpls_cv_auc_begin)", who, ctx->auc_n, ctx->auc_cap, m);
-        return fail(ctx, PLSX_ERR_ARG, msg);
-    }
-    if (ctx->cls_active) {
-        const size_t blk = (size_t)ctx->ncomp * ctx->T * ctx->T;
-        HIPCHK(hipMemsetAsync(ctx->cls_conf + (size_t)ctx->cls_n * blk, 0, (size_t)m * blk * sizeof(int), st));
-    }
-    if (ctx->auc_active) {
-        const size_t blk = (size_t)ctx->ncomp * ctx->T * 2;
-        HIPCHK(hipMemsetAsync(ctx->auc_out + (size_t)ctx->auc_n * blk, 0, (size_t)m * blk * sizeof(long long), st));
-    }
+    NEED_DATA();
+    CountSeries& s = auc ? ctx->auc_series : ctx->cls_series;
+    const std::string who = s.entry;
+    if (ctx->method != PLSX_REGRESSION) return fail(ctx, PLSX_ERR_STATE, who + ": data not bound for regression");
+    if (!ctx->has_cls) return fail(ctx, PLSX_ERR_STATE, who + ": plsx_simpls_set_classes has not been called");
+    count_close(s);
+    if (!d_buf || capacity < 1) return fail(ctx, PLSX_ERR_ARG, who + ": null buffer or capacity < 1");
+    s.base = static_cast<char*>(d_buf); s.cap = capacity; s.n = 0;
+    s.blk_bytes = (size_t)ctx->ncomp * ctx->T * (auc ? 2 * sizeof(long long) : ctx->T * sizeof(int));
+    s.active = 1;
+    return PLSX_OK;
+}
+
+static int count_end(plsx_ctx* ctx, bool auc)
+{
+    if (!ctx) return PLSX_ERR_ARG;
+    count_close(auc ? ctx->auc_series : ctx->cls_series);
+    return PLSX_OK;
+}
+
+// Room for m more blocks in each series that is open, or PLSX_ERR_ARG before anything is computed or zeroed; the blocks
+// are zeroed here, in stream order before the kernels that count into them.
+static int count_reserve(plsx_ctx* ctx, const char* who, int m, hipStream_t st)
+{
+    CountSeries* const both[2] = {&ctx->cls_series, &ctx->auc_series};
+    for (const CountSeries* s : both)
+        if (s->active && s->n + m > s->cap) {
+            char msg[240];
+            snprintf(msg, sizeof msg, "%s: the open series of %s holds %lld of %lld blocks, %d more do not fit (%s)", who,
+                     s->what, s->n, s->cap, m, s->entry);
+            return fail(ctx, PLSX_ERR_ARG, msg);
+        }
+    for (const CountSeries* s : both)
+        if (s->active) HIPCHK(hipMemsetAsync(s->base + (size_t)s->n * s->blk_bytes, 0, (size_t)m * s->blk_bytes, st));
     return 0;
 }
 
-// k_sd_cv_class on the ms fits k_sd_cv_score has just scored: fit r counts into block (f0 + r) / n - f0 / n behind
-// `first`, the block of the batch's first fit.
+// The counting kernel of an open series (k_sd_cv_class, or k_sd_cv_auc behind it) on the ms fits k_sd_cv_score has just
+// scored: fit r counts into block (f0 + r) / n - f0 / n behind block `blk0` of this call, the block of the batch's
+// first fit.
 template <bool PERM>
-static int cls_launch(plsx_ctx* ctx, SdArgs a, int ms, long long first, long long f0, int n, hipStream_t st)
+static int count_launch(plsx_ctx* ctx, const CountSeries& s, SdArgs a, int ms, long long blk0, long long f0, int n,
+                        hipStream_t st)
 {
+    const bool auc = &s == &ctx->auc_series;
+    char* out = s.base + (size_t)(s.n + blk0) * s.blk_bytes;
     a.cls = ptr<int>(ctx->cls);
     a.cfreq = ptr<double>(ctx->clsfreq);
-    a.conf = ctx->cls_conf + (size_t)first * a.k * a.T * a.T;
+    if (auc) a.auc = reinterpret_cast<long long*>(out); else a.conf = reinterpret_cast<int*>(out);
     a.cls_f0 = f0; a.cls_n = n;
-    KTimer tm(ctx, KC_CVCLASS, st);
-    void (*class_kernel)(SdArgs) = a.T <= 4 ? k_sd_cv_class<4, PERM> : (a.T <= 16 ? k_sd_cv_class<16, PERM>
-                                                                                  : k_sd_cv_class<32, PERM>);
-    hipLaunchKernelGGL(class_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+    KTimer tm(ctx, auc ? KC_CVAUC : KC_CVCLASS, st);
+    void (*kernel)(SdArgs) =
+        auc ? (a.T <= 4 ? k_sd_cv_auc<4, PERM> : (a.T <= 16 ? k_sd_cv_auc<16, PERM> : k_sd_cv_auc<32, PERM>))
+            : (a.T <= 4 ? k_sd_cv_class<4, PERM> : (a.T <= 16 ? k_sd_cv_class<16, PERM> : k_sd_cv_class<32, PERM>));
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
     LAUNCHCHK();
     return 0;
 }
 
-// k_sd_cv_auc on the same fits, behind k_sd_cv_score and, where that series is open too, k_sd_cv_class: blocks as there.
-template <bool PERM>
-static int auc_launch(plsx_ctx* ctx, SdArgs a, int ms, long long first, long long f0, int n, hipStream_t st)
+// Scratch of a cross-validation batch of nb fits: pctvar [nb][k] with the y-loadings [nb][T][k] behind it, the right
+// singular vectors, the dense dual weights Vd and Z = Vd . K
+static int cv_scratch(plsx_ctx* ctx, int nb)
 {
-    a.cls = ptr<int>(ctx->cls);
-    a.cfreq = ptr<double>(ctx->clsfreq);
-    a.auc = ctx->auc_out + (size_t)first * a.k * a.T * 2;
-    a.cls_f0 = f0; a.cls_n = n;
-    KTimer tm(ctx, KC_CVAUC, st);
-    void (*auc_kernel)(SdArgs) = a.T <= 4 ? k_sd_cv_auc<4, PERM> : (a.T <= 16 ? k_sd_cv_auc<16, PERM>
-                                                                              : k_sd_cv_auc<32, PERM>);
-    hipLaunchKernelGGL(auc_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
-    LAUNCHCHK();
+    const size_t S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    if (int e = ensure(ctx, ctx->spct, nb * (T + 1) * k * 8)) return e;
+    if (int e = ensure(ctx, ctx->sc, nb * T * k * 8)) return e;
+    if (int e = ensure(ctx, ctx->Vdq, nb * k * S * 8)) return e;
+    return ensure(ctx, ctx->Zcv, nb * k * S * 8);
+}
+
+// Where k_sd_cv_score leaves the scores of a batch's fits: [ms][k][T], [ms][k][T], [ms][k + 1][T] and, PERM only, [ms]
+struct CvScores { double* r; double* r2; double* sse; double* nte; };
+
+// One solver batch of cross-validated fits, end to end (plsx_simpls_crossval_batch, PERM: plsx_simpls_crossval_perm_batch):
+// the ms fits on their training positions (`pmask` [ms][S]; X keeps its rows, Y takes rows `ysrc` or its own), ONE
+// product with K, the scores, `after_score` in the scores' timed bracket (the reduction of the permuted entry), and the
+// counts of the series that are open, whose blocks are addressed as count_launch says.  nb: the fits cv_scratch was
+// sized for.
+template <bool PERM, class F>
+static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const uint8_t* pmask, const CvScores& out,
+                        long long blk0, long long f0, int n, hipStream_t st, F after_score)
+{
+    const int k = ctx->ncomp;
+    SdArgs a;
+    // identity X sources, the test positions excluded, weights wanted; the signs stay as the solver produced them
+    // (t_j q_j^T does not depend on them)
+    SdRequest q;
+    q.ysrc = ysrc; q.nres = ms; q.scatter = true;
+    q.pctvar = ptr<double>(ctx->spct); q.yload = q.pctvar + (size_t)nb * k; q.cvec = ptr<double>(ctx->sc);
+    q.Vd = ptr<double>(ctx->Vdq); q.pmask = pmask; q.args_out = &a;
+    if (int e = run_simpls_dual(ctx, q, st)) return e;
+    // ONE product with K: the scores of all k nested models at every row, training and test
+    a.cvZ = ptr<double>(ctx->Zcv);
+    if (int e = sd_times_K(ctx, q.Vd, ms * k, a.cvZ, st)) return e;
+    a.cvr = out.r; a.cvr2 = out.r2; a.cvsse = out.sse; a.cvnte = out.nte;
+    {
+        KTimer tm(ctx, KC_CVSCORE, st);
+        // (more waves than two per SIMD of the chip: the three-waves-per-SIMD variant, as in the solver)
+        void (*score_kernel)(SdArgs) = (ms > 2048 && !simpls_global(ctx)) ? k_sd_cv_score<8, PERM> : k_sd_cv_score<16, PERM>;
+        hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
+        LAUNCHCHK();
+        if (int e = after_score()) return e;
+    }
+    for (const CountSeries* s : {&ctx->cls_series, &ctx->auc_series})
+        if (s->active)
+            if (int e = count_launch<PERM>(ctx, *s, a, ms, blk0, f0, n, st)) return e;
     return 0;
 }
 
@@ -488,7 +556,10 @@ try {
     if (!d_xwT || !d_pctvar || !d_cvec || !d_yload) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_decompose: null output");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
-    if (int e = run_simpls_dual(ctx, nullptr, nullptr, 1, true, d_pctvar, d_yload, d_cvec, st)) return e;
+    SdRequest q;
+    q.nres = 1; q.scatter = true;
+    q.pctvar = d_pctvar; q.yload = d_yload; q.cvec = d_cvec;
+    if (int e = run_simpls_dual(ctx, q, st)) return e;
     if (int e = run_xprod(ctx, nullptr, nullptr, 1, st, true)) return e;
     hipLaunchKernelGGL(k_gather_cols, dim3(ceil_div(ctx->Tp * ctx->B, 256), 1), dim3(256), 0, st,
                        ptr<double>(ctx->R), ctx->strideR, ctx->Bpad, 0, ctx->Tp, ctx->B, d_xwT);
@@ -544,11 +615,11 @@ try {
         const int m = std::min(nb, n - off);
         SdArgs sda;
         // Y is permuted, X is not (BasePLS.make_permutation, base.py:599)
-        if (int e = run_simpls_dual(ctx, nullptr, d_perm_idx + (size_t)off * ctx->S, m, false,
-                                    d_out + (size_t)off * ctx->ncomp, ptr<double>(ctx->spct),
-                                    ptr<double>(ctx->sc), st, nullptr, false, nullptr, nullptr, series ? &sda : nullptr,
-                                    series))
-            return e;
+        SdRequest q;
+        q.ysrc = d_perm_idx + (size_t)off * ctx->S; q.nres = m;
+        q.pctvar = d_out + (size_t)off * ctx->ncomp; q.yload = ptr<double>(ctx->spct); q.cvec = ptr<double>(ctx->sc);
+        q.args_out = series ? &sda : nullptr; q.weights_only = series;
+        if (int e = run_simpls_dual(ctx, q, st)) return e;
         if (series)
             if (int e = coef_perm_append(ctx, sda, m, st)) return e;
     }
@@ -566,52 +637,22 @@ try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
-    const bool gl = simpls_global(ctx);
-    // (an open series of confusion counts that cannot take the call: refused before anything is computed)
-    const bool series = ctx->cls_active != 0, aucs = ctx->auc_active != 0;
-    if (series || aucs)
-        if (int e = cls_reserve(ctx, "plsx_simpls_crossval_batch", m, st)) return e;
+    // (an open series of counts that cannot take the call: refused before anything is computed)
+    if (int e = count_reserve(ctx, "plsx_simpls_crossval_batch", m, st)) return e;
     // solver batches as for the permutations; a split also holds its dense dual weights Vd and Z = Vd . K
     const int nb = std::min(m, sd_batch(ctx, 8192, 1, 2.0 * k * S * 8.0));
-    if (int e = ensure(ctx, ctx->spct, (size_t)nb * (T + 1) * k * 8)) return e;     // pctvar [nb][k], y-loadings [nb][T][k]
-    if (int e = ensure(ctx, ctx->sc, (size_t)nb * T * k * 8)) return e;
-    if (int e = ensure(ctx, ctx->Vdq, (size_t)nb * k * S * 8)) return e;
-    if (int e = ensure(ctx, ctx->Zcv, (size_t)nb * k * S * 8)) return e;
-    const double* K = ptr<double>(ctx->Kmat);
-    double* Vd = ptr<double>(ctx->Vdq);
-    double* Z = ptr<double>(ctx->Zcv);
+    if (int e = cv_scratch(ctx, nb)) return e;
     for (int off = 0; off < m; off += nb) {
         const int ms = std::min(nb, m - off);
-        SdArgs a;
-        // the fit on the training rows: identity sources, the test positions excluded, weights wanted; the signs stay
-        // as the solver produced them (t_j q_j^T does not depend on them)
-        if (int e = run_simpls_dual(ctx, nullptr, nullptr, ms, true, ptr<double>(ctx->spct),
-                                    ptr<double>(ctx->spct) + (size_t)nb * k, ptr<double>(ctx->sc), st, nullptr, false, Vd,
-                                    d_masks + (size_t)off * S, &a))
+        // the fits on the training rows of the splits themselves; one block of counts per split, in submission order
+        const CvScores out = {d_r + (size_t)off * k * T, d_r2 + (size_t)off * k * T, d_sse + (size_t)off * (k + 1) * T,
+                              nullptr};
+        if (int e = cv_fit_score<false>(ctx, nb, ms, nullptr, d_masks + (size_t)off * S, out, off, 0, 1, st,
+                                        [] { return 0; }))
             return e;
-        // ONE product with K: the scores of all k nested models at every row, training and test
-        if (gl) {
-            if (int e = nt_strips(ctx, Vd, S, ms * k, K, S, S, S, Z, S, st)) return e;
-        } else if (int e = run_nt(ctx, Vd, 0, S, ms * k, K, 0, S, S, nullptr, 0, 0, 0, S, 1, Z, 0, S, nullptr, 0, 0, st))
-            return e;
-        a.cvZ = Z;
-        a.cvr = d_r + (size_t)off * k * T;
-        a.cvr2 = d_r2 + (size_t)off * k * T;
-        a.cvsse = d_sse + (size_t)off * (k + 1) * T;
-        {
-            KTimer tm(ctx, KC_CVSCORE, st);
-            // (more waves than two per SIMD of the chip: the three-waves-per-SIMD variant, as in the solver)
-            void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8> : k_sd_cv_score<16>;
-            hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
-            LAUNCHCHK();
-        }
-        if (series)                                    // one block per split, in submission order
-            if (int e = cls_launch<false>(ctx, a, ms, ctx->cls_n + off, 0, 1, st)) return e;
-        if (aucs)
-            if (int e = auc_launch<false>(ctx, a, ms, ctx->auc_n + off, 0, 1, st)) return e;
     }
-    if (series) ctx->cls_n += m;
-    if (aucs) ctx->auc_n += m;
+    if (ctx->cls_series.active) ctx->cls_series.n += m;
+    if (ctx->auc_series.active) ctx->auc_series.n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -626,13 +667,10 @@ try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
-    const bool gl = simpls_global(ctx);
     // the pair list: fit f = permutation f / n under split f % n, m n of them (64-bit), cut into solver batches sized
     // as plsx_simpls_crossval_batch sizes its own; a fit also holds its expanded sources and mask (5 S bytes) and
     // its scores until the reduction over the splits
-    const bool series = ctx->cls_active != 0, aucs = ctx->auc_active != 0;
-    if (series || aucs)
-        if (int e = cls_reserve(ctx, "plsx_simpls_crossval_perm_batch", m, st)) return e;
+    if (int e = count_reserve(ctx, "plsx_simpls_crossval_perm_batch", m, st)) return e;
     const long long fits = (long long)m * n;
     const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T + 1;       // doubles of scores per fit
     const double extra = 2.0 * k * S * 8.0 + 5.0 * S + 8.0 * per_fit;
@@ -644,21 +682,14 @@ try {
         const long long full = fits / nb, bs = (fits + full - 1) / full;
         if (sd_batch(ctx, (int)bs, 1, extra) == (int)bs) nb = (int)bs;
     }
-    if (int e = ensure(ctx, ctx->spct, (size_t)nb * (T + 1) * k * 8)) return e;     // pctvar [nb][k], y-loadings [nb][T][k]
-    if (int e = ensure(ctx, ctx->sc, (size_t)nb * T * k * 8)) return e;
-    if (int e = ensure(ctx, ctx->Vdq, (size_t)nb * k * S * 8)) return e;
-    if (int e = ensure(ctx, ctx->Zcv, (size_t)nb * k * S * 8)) return e;
+    if (int e = cv_scratch(ctx, nb)) return e;
     if (int e = ensure(ctx, ctx->cvpsrc, (size_t)nb * S * 5)) return e;
     if (int e = ensure(ctx, ctx->cvpfit, (size_t)nb * per_fit * 8)) return e;
-    const double* K = ptr<double>(ctx->Kmat);
-    double* Vd = ptr<double>(ctx->Vdq);
-    double* Z = ptr<double>(ctx->Zcv);
     int* ysrc = ptr<int>(ctx->cvpsrc);
     uint8_t* pmask = reinterpret_cast<uint8_t*>(ysrc + (size_t)nb * S);
     double* fr = ptr<double>(ctx->cvpfit);
-    double* fr2 = fr + (size_t)nb * kT;
-    double* fsse = fr2 + (size_t)nb * kT;
-    double* fnte = fsse + (size_t)nb * (k + 1) * T;
+    double* fsse = fr + 2 * (size_t)nb * kT;
+    const CvScores fs = {fr, fr + (size_t)nb * kT, fsse, fsse + (size_t)nb * (k + 1) * T};
     // the running sums over the splits live in the outputs (k_sd_cvp_reduce)
     HIPCHK(hipMemsetAsync(d_r, 0, (size_t)m * kT * 8, st));
     HIPCHK(hipMemsetAsync(d_r2, 0, (size_t)m * kT * 8, st));
@@ -671,37 +702,20 @@ try {
                                ysrc, pmask);
             LAUNCHCHK();
         }
-        SdArgs a;
-        // the fit on the training positions of (X, Y[perm]): X keeps its rows, Y takes the permutation's (as
-        // plsx_simpls_perm_batch), the test positions are excluded (as plsx_simpls_crossval_batch), weights wanted
-        if (int e = run_simpls_dual(ctx, nullptr, ysrc, ms, true, ptr<double>(ctx->spct),
-                                    ptr<double>(ctx->spct) + (size_t)nb * k, ptr<double>(ctx->sc), st, nullptr, false, Vd,
-                                    pmask, &a))
-            return e;
-        // ONE product with K: the scores of all k nested models at every row, training and test
-        if (gl) {
-            if (int e = nt_strips(ctx, Vd, S, ms * k, K, S, S, S, Z, S, st)) return e;
-        } else if (int e = run_nt(ctx, Vd, 0, S, ms * k, K, 0, S, S, nullptr, 0, 0, 0, S, 1, Z, 0, S, nullptr, 0, 0, st))
-            return e;
-        a.cvZ = Z;
-        a.cvr = fr; a.cvr2 = fr2; a.cvsse = fsse; a.cvnte = fnte;
-        {
-            KTimer tm(ctx, KC_CVSCORE, st);
-            void (*score_kernel)(SdArgs) = (ms > 2048 && !gl) ? k_sd_cv_score<8, true> : k_sd_cv_score<16, true>;
-            hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
-            LAUNCHCHK();
+        // the fits on the training positions of (X, Y[perm]): X keeps its rows, Y takes the permutation's (as
+        // plsx_simpls_perm_batch), the test positions are excluded (as plsx_simpls_crossval_batch); one block of counts
+        // per permutation: its splits add up in it, in any order
+        auto reduce = [&] {
             const int touched = (int)((f0 + ms - 1) / n - f0 / n) + 1;
             hipLaunchKernelGGL(k_sd_cvp_reduce, dim3(ceil_div((int)(2 * kT) + k + 1, 256), touched), dim3(256), 0, st,
-                               fr, fr2, fsse, fnte, k, T, n, f0, ms, d_r, d_r2, d_mse);
+                               fs.r, fs.r2, fs.sse, fs.nte, k, T, n, f0, ms, d_r, d_r2, d_mse);
             LAUNCHCHK();
-        }
-        if (series)                                    // one block per permutation: its splits add up in it, in any order
-            if (int e = cls_launch<true>(ctx, a, ms, ctx->cls_n + f0 / n, f0, n, st)) return e;
-        if (aucs)
-            if (int e = auc_launch<true>(ctx, a, ms, ctx->auc_n + f0 / n, f0, n, st)) return e;
+            return 0;
+        };
+        if (int e = cv_fit_score<true>(ctx, nb, ms, ysrc, pmask, fs, f0 / n, f0, n, st, reduce)) return e;
     }
-    if (series) ctx->cls_n += m;
-    if (aucs) ctx->auc_n += m;
+    if (ctx->cls_series.active) ctx->cls_series.n += m;
+    if (ctx->auc_series.active) ctx->auc_series.n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -764,10 +778,11 @@ try {
         SdArgs a;
         // the fit on all usable rows of (X, Y[perm]): X keeps its rows, Y takes the permutation's (as
         // plsx_simpls_perm_batch; nullptr: the observed arrangement); the scores stay in the batch's state
-        if (int e = run_simpls_dual(ctx, nullptr, d_perm_idx ? d_perm_idx + (size_t)off * S : nullptr, ms, false,
-                                    ptr<double>(ctx->spct), ptr<double>(ctx->spct) + (size_t)nb * k, ptr<double>(ctx->sc),
-                                    st, nullptr, false, nullptr, nullptr, &a))
-            return e;
+        SdRequest q;
+        q.ysrc = d_perm_idx ? d_perm_idx + (size_t)off * S : nullptr; q.nres = ms;
+        q.pctvar = ptr<double>(ctx->spct); q.yload = q.pctvar + (size_t)nb * k; q.cvec = ptr<double>(ctx->sc);
+        q.args_out = &a;
+        if (int e = run_simpls_dual(ctx, q, st)) return e;
         h.nres = ms; h.a0 = off;
         h.xs = a.xs; h.Y0 = a.Y0; h.XW = a.XW;
         {
@@ -815,9 +830,9 @@ try {
     // must fit in free device memory (what an earlier series left allocated counts as free) and in the scratch budget
     const double cbytes = 8.0 * T * (double)S * S;
     const double pbytes = 16.0 * T * (double)round_up(S, 64) * round_up(S, 64);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const double have = (double)free_b + (double)ctx->Cc.bytes + (double)ctx->part.bytes;
+    double have;
+    if (int e = free_bytes(ctx, ctx->Cc, &have)) return e;
+    have += (double)ctx->part.bytes;
     const double budget = ctx->scratch_gb * 1073741824.0;
     if (cbytes + pbytes > have || cbytes + pbytes > budget || !nt_sym_fits(S)) {
         char msg[320];
@@ -1028,8 +1043,8 @@ try {
     NEED_DATA();
     if (ctx->method != PLSX_REGRESSION)
         return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_set_classes: data not bound for regression");
-    cls_close(ctx);
-    auc_close(ctx);
+    count_close(ctx->cls_series);
+    count_close(ctx->auc_series);
     ctx->has_cls = 0;
     if (!d_class) return PLSX_OK;                      // (a null pointer clears the binding)
     char msg[200];
@@ -1068,46 +1083,22 @@ try {
 
 int plsx_simpls_cv_class_begin(plsx_ctx* ctx, int32_t* d_conf, long long capacity)
 try {
-    NEED_DATA();
-    if (ctx->method != PLSX_REGRESSION)
-        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_class_begin: data not bound for regression");
-    if (!ctx->has_cls)
-        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_class_begin: plsx_simpls_set_classes has not been called");
-    cls_close(ctx);
-    if (!d_conf || capacity < 1)
-        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_cv_class_begin: null buffer or capacity < 1");
-    ctx->cls_conf = d_conf; ctx->cls_cap = capacity; ctx->cls_n = 0;
-    ctx->cls_active = 1;
-    return PLSX_OK;
+    return count_begin(ctx, false, d_conf, capacity);
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_cv_class_end(plsx_ctx* ctx)
 try {
-    if (!ctx) return PLSX_ERR_ARG;
-    cls_close(ctx);
-    return PLSX_OK;
+    return count_end(ctx, false);
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_cv_auc_begin(plsx_ctx* ctx, int64_t* d_auc, long long capacity)
 try {
-    NEED_DATA();
-    if (ctx->method != PLSX_REGRESSION)
-        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_auc_begin: data not bound for regression");
-    if (!ctx->has_cls)
-        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_auc_begin: plsx_simpls_set_classes has not been called");
-    auc_close(ctx);
-    if (!d_auc || capacity < 1)
-        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_cv_auc_begin: null buffer or capacity < 1");
-    ctx->auc_out = reinterpret_cast<long long*>(d_auc); ctx->auc_cap = capacity; ctx->auc_n = 0;
-    ctx->auc_active = 1;
-    return PLSX_OK;
+    return count_begin(ctx, true, d_auc, capacity);
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_cv_auc_end(plsx_ctx* ctx)
 try {
-    if (!ctx) return PLSX_ERR_ARG;
-    auc_close(ctx);
-    return PLSX_OK;
+    return count_end(ctx, true);
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream)
@@ -1184,12 +1175,15 @@ try {
         const bool single = simpls_single_pass(ctx);
         SdArgs sda;                      // the batch's solver state, for an open coefficient series or a kept VIP stack
         const bool want_state = ctx->coef_active || ctx->vipG;
+        SdRequest q;
+        q.xsrc = q.ysrc = idx; q.nres = ms; q.scatter = true;
+        q.pctvar = ptr<double>(ctx->spct); q.yload = yl; q.cvec = ptr<double>(ctx->sc);
+        q.ystack = yst; q.args_out = want_state ? &sda : nullptr;
         if (ctx->quad_active) {
             // quadratic-form route: the aligned dual weights stay in dual space (plsx_boot_finish passes the features)
             if (int e = ensure(ctx, ctx->Vdq, (size_t)ms * k * ctx->S * 8)) return e;
-            if (int e = run_simpls_dual(ctx, idx, idx, ms, true, ptr<double>(ctx->spct), yl, ptr<double>(ctx->sc), st, yst,
-                                        true, ptr<double>(ctx->Vdq), nullptr, want_state ? &sda : nullptr))
-                return e;
+            q.align_signs = true; q.Vd = ptr<double>(ctx->Vdq);
+            if (int e = run_simpls_dual(ctx, q, st)) return e;
             if (ctx->timing) ctx->timed_units += ms;
             if (int e = quad_accumulate(ctx, ms, st)) return e;
             if (ctx->coef_active)
@@ -1198,9 +1192,8 @@ try {
                 if (int e = vip_append(ctx, sda, ms, st)) return e;
             continue;
         }
-        if (int e = run_simpls_dual(ctx, idx, idx, ms, true, ptr<double>(ctx->spct), yl, ptr<double>(ctx->sc), st, yst,
-                                    single, nullptr, nullptr, want_state ? &sda : nullptr))
-            return e;
+        q.align_signs = single;
+        if (int e = run_simpls_dual(ctx, q, st)) return e;
         // (the solver state of the batch outlives the feature passes below: they work in buffers of their own)
         if (ctx->coef_active)
             if (int e = coef_accumulate(ctx, sda, ms, st)) return e;
