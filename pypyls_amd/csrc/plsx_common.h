@@ -58,3 +58,14 @@ __device__ __forceinline__ double sd_rsqrt(double x)
     y = y * __builtin_fma(-0.5 * x * y, y, 1.5);
     return y;
 }
+
+// Is a sum of squared deviations formed from raw moments, d = m2 - m1 * m1 / n, more than its own rounding error?
+// For n values that are all the same number both terms equal n c^2 up to (3 n + 1) u m2, u = 2^-53 (DESIGN section 3,
+// "Cell-constant features": one rounding of c^2, up to n - 1 additions behind m2, twice that behind m1 * m1, two more
+// roundings), so whatever does not exceed 4 (n + 1) u m2 has no correct digit and counts as zero: the feature is
+// constant on the cell and its scale is 0.  A difference taken from the cell's full-sample sums (the second half of
+// a split) carries the error of those sums: the caller passes their n and m2 (doubled, see there).
+__device__ __forceinline__ bool raw_ss_live(double d, double n, double m2)
+{
+    return d > (n + 1.0) * 0x1p-51 * m2;
+}

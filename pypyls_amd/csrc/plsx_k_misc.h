@@ -293,7 +293,9 @@ static __global__ void k_boot_rel(const double* __restrict__ orig, const double*
     const double q = usq[i] + (add_orig ? o * o : 0.0);
     const double e = sqrt(fabs(q - s * s / n) / (n - 1.0));
     se[i] = e;
-    bsr[i] = o / e;
+    // a weight that is exactly 0 in the original and in every bootstrap (a feature that is constant in every cell,
+    // DESIGN section 3) has ratio 0, not 0 / 0
+    bsr[i] = (o == 0.0 && e == 0.0) ? 0.0 : o / e;
 }
 
 static __global__ void k_iota_rows(int* __restrict__ dst, int n, int S)

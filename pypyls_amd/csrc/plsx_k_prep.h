@@ -32,7 +32,9 @@ static __global__ void k_center_pad(const double* __restrict__ X, const double* 
 // Xn[i][b] = Xc[i][b] / std_{cell(i)}(Xc[:, b])  (ddof = 1): the features as the
 // un-resampled X enters every per-cell z-score.  Permutations leave X fixed
 // (pyls/base.py:599), so their cross-products can use Xn and skip the moment
-// tiles.  One thread per column, rows visited in order.
+// tiles.  One thread per column, rows visited in order.  A feature whose rows in the cell all hold the bits of the
+// first has no z-score: scale 0 -- the two-pass variance alone does not say so, the rounded mean
+// of n equal numbers usually misses them by an ulp and var comes out near 1e-34 c^2, not 0.
 static __global__ void k_cell_scale(const double* __restrict__ Xc, int ldx, int B, int J,
                              const int* __restrict__ cell_start, const int* __restrict__ cell_len,
                              double* __restrict__ Xn)
@@ -42,12 +44,18 @@ static __global__ void k_cell_scale(const double* __restrict__ Xc, int ldx, int 
     for (int j = 0; j < J; ++j) {
         const int r0 = cell_start[j], n = cell_len[j];
         double s = 0.0;
-        for (int i = r0; i < r0 + n; ++i) s += Xc[(size_t)i * ldx + b];
+        const long long first = __double_as_longlong(Xc[(size_t)r0 * ldx + b]);
+        bool same = true;
+        for (int i = r0; i < r0 + n; ++i) {
+            const double x = Xc[(size_t)i * ldx + b];
+            s += x;
+            same = same && __double_as_longlong(x) == first;
+        }
         const double mean = s / (double)n;
         double q = 0.0;
         for (int i = r0; i < r0 + n; ++i) { const double d = Xc[(size_t)i * ldx + b] - mean; q += d * d; }
         const double var = q / (double)(n - 1);
-        const double sc = (var > 0.0) ? 1.0 / sqrt(var) : 0.0;
+        const double sc = (!same && var > 0.0) ? 1.0 / sqrt(var) : 0.0;
         for (int i = r0; i < r0 + n; ++i) Xn[(size_t)i * ldx + b] = Xc[(size_t)i * ldx + b] * sc;
     }
 }

@@ -337,8 +337,9 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
                 if (pair >= se.npairs || col >= ldr) continue;
                 const double m1 = acc[j][i], m2 = acc[NSQ + j][i];
                 const double nn = mom_n[pair];
-                const double var = (m2 - m1 * m1 / nn) / (nn - 1.0);
-                se.scale[(size_t)pair * ldr + col] = (var > 0.0) ? sd_rsqrt(var) : 0.0;
+                const double ss = m2 - m1 * m1 / nn;
+                const double var = ss / (nn - 1.0);
+                se.scale[(size_t)pair * ldr + col] = raw_ss_live(ss, nn, m2) ? sd_rsqrt(var) : 0.0;
             }
         return;
     }
@@ -491,15 +492,20 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
                 const double SF = se.cellS1[(size_t)jc * ldr + col], SFF = se.cellS2[(size_t)jc * ldr + col];
                 const double n2 = nF - n1;
                 const bool ok = n1 > 1.5 && n2 > 1.5;
-                const double var1 = ok ? (m2 - m1 * m1 / n1) / (n1 - 1.0) : 0.0;
+                // (the second half's moments are differences of the full sample's: their rounding bound is the full
+                // sample's, twice -- one share for each of the two sums subtracted)
+                const double ss1 = m2 - m1 * m1 / n1;
+                const double var1 = ok ? ss1 / (n1 - 1.0) : 0.0;
                 const double s2x = SF - m1, s2xx = SFF - m2;
-                const double var2 = ok ? (s2xx - s2x * s2x / n2) / (n2 - 1.0) : 0.0;
-                const double varF = (SFF - SF * SF / nF) / (nF - 1.0);
+                const double ss2 = s2xx - s2x * s2x / n2;
+                const double var2 = ok ? ss2 / (n2 - 1.0) : 0.0;
+                const double ssF = SFF - SF * SF / nF;
+                const double varF = ssF / (nF - 1.0);
                 w5[0 * nmu * 16 + o] = ok ? m1 / n1 : 0.0;
-                w5[1 * nmu * 16 + o] = (var1 > 0.0) ? 1.0 / sqrt(var1) : 0.0;
+                w5[1 * nmu * 16 + o] = (ok && raw_ss_live(ss1, n1, m2)) ? 1.0 / sqrt(var1) : 0.0;
                 w5[2 * nmu * 16 + o] = ok ? s2x / n2 : 0.0;
-                w5[3 * nmu * 16 + o] = (var2 > 0.0) ? 1.0 / sqrt(var2) : 0.0;
-                w5[4 * nmu * 16 + o] = (varF > 0.0) ? sqrt(varF) : 0.0;
+                w5[3 * nmu * 16 + o] = (ok && raw_ss_live(ss2, 2.0 * nF + 1.0, SFF)) ? 1.0 / sqrt(var2) : 0.0;
+                w5[4 * nmu * 16 + o] = raw_ss_live(ssF, nF, SFF) ? sqrt(varF) : 0.0;
             }
         __syncthreads();
         double* Rg = R + (size_t)grp * rows_per_group * ldr + col;
@@ -546,8 +552,9 @@ void k_xprod(const double* __restrict__ Afrag, size_t group_stride,
             const int o = mr * 16 + (lane & 15);
             const double m1 = sS[o], m2 = sQ[o];
             const double nn = mom_n[(size_t)grp * nmom_pad + mr];
-            const double var = (m2 - m1 * m1 / nn) / (nn - 1.0);
-            const double sc = (var > 0.0) ? 1.0 / sqrt(var) : 0.0;
+            const double ss = m2 - m1 * m1 / nn;
+            const double var = ss / (nn - 1.0);
+            const double sc = raw_ss_live(ss, nn, m2) ? 1.0 / sqrt(var) : 0.0;
             sS[o] = sc;
             if (mom_out) {       // training mean / inverse std of the features (cross-validation)
                 double* mo = mom_out + ((size_t)grp * nmom_pad + mr) * 2 * ldr + col;
@@ -866,8 +873,9 @@ __device__ __forceinline__ void compact_wide_block(double* smem, const double* _
             }
             const double nn = __hiloint2double(cnt_hi[j], cnt_lo[j]);
             const double m2 = q == 0 ? scr[j][0].x : q == 1 ? scr[j][0].y : q == 2 ? scr[j][1].x : scr[j][1].y;
-            const double var = (m2 - m1 * m1 / nn) / (nn - 1.0);
-            double sc = (var > 0.0) ? sd_rsqrt(var) : 0.0;
+            const double ss = m2 - m1 * m1 / nn;
+            const double var = ss / (nn - 1.0);
+            double sc = raw_ss_live(ss, nn, m2) ? sd_rsqrt(var) : 0.0;
             asm volatile("" : "+v"(sc));
             const int c15 = ln & 15;
             scr[j][0] = (d2){__shfl(sc, c15), __shfl(sc, c15 | 16)};
@@ -1158,8 +1166,9 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
                 const double nn = __hiloint2double(cnt_hi[j], cnt_lo[j]);
                 const double m1x = __shfl(a0, src), m1y = __shfl(a1, src);
                 const double m1 = second ? m1y : m1x, m2 = second ? scr[j].y : scr[j].x;
-                const double var = (m2 - m1 * m1 / nn) / (nn - 1.0);
-                double sc = (var > 0.0) ? sd_rsqrt(var) : 0.0;
+                const double ss = m2 - m1 * m1 / nn;
+                const double var = ss / (nn - 1.0);
+                double sc = raw_ss_live(ss, nn, m2) ? sd_rsqrt(var) : 0.0;
                 asm volatile("" : "+v"(sc));
                 const double other = __shfl_xor(sc, 16);
                 scr[j] = second ? (d2){other, sc} : (d2){sc, other};
@@ -1235,15 +1244,18 @@ void k_xprod_compact(const double* __restrict__ Afrag, size_t group_stride,
                 const double SF = se.cellS1[(size_t)jc * ldr + cb0 + c], SFF = se.cellS2[(size_t)jc * ldr + cb0 + c];
                 const double n2 = nF - n1;
                 const bool ok = n1 > 1.5 && n2 > 1.5;
-                const double var1 = ok ? (m2 - m1 * m1 / n1) / (n1 - 1.0) : 0.0;
+                const double ss1 = m2 - m1 * m1 / n1;                // (bounds as in the split epilogue of k_xprod)
+                const double var1 = ok ? ss1 / (n1 - 1.0) : 0.0;
                 const double s2x = SF - m1, s2xx = SFF - m2;
-                const double var2 = ok ? (s2xx - s2x * s2x / n2) / (n2 - 1.0) : 0.0;
-                const double varF = (SFF - SF * SF / nF) / (nF - 1.0);
+                const double ss2 = s2xx - s2x * s2x / n2;
+                const double var2 = ok ? ss2 / (n2 - 1.0) : 0.0;
+                const double ssF = SFF - SF * SF / nF;
+                const double varF = ssF / (nF - 1.0);
                 u1 = ok ? m1 / n1 : 0.0;
-                v1 = (var1 > 0.0) ? 1.0 / sqrt(var1) : 0.0;
+                v1 = (ok && raw_ss_live(ss1, n1, m2)) ? 1.0 / sqrt(var1) : 0.0;
                 u2 = ok ? s2x / n2 : 0.0;
-                v2 = (var2 > 0.0) ? 1.0 / sqrt(var2) : 0.0;
-                sF = (varF > 0.0) ? sqrt(varF) : 0.0;
+                v2 = (ok && raw_ss_live(ss2, 2.0 * nF + 1.0, SFF)) ? 1.0 / sqrt(var2) : 0.0;
+                sF = raw_ss_live(ssF, nF, SFF) ? sqrt(varF) : 0.0;
             }
             const int o = jc * BC + c;
             w5[0 * J * BC + o] = u1; w5[1 * J * BC + o] = v1; w5[2 * J * BC + o] = u2;

@@ -52,14 +52,16 @@ static __global__ void k_split_colconst(const double* __restrict__ m1t, const do
     const double m1 = m1t[(size_t)pair * ldr + c], m2 = m2t[(size_t)pair * ldr + c];
     const double SF = cellS1[(size_t)jc * ldr + c], SFF = cellS2[(size_t)jc * ldr + c];
     const bool ok = n1 > 1.5 && n2 > 1.5;
-    const double var1 = ok ? (m2 - m1 * m1 / n1) / (n1 - 1.0) : 0.0;
+    const double ss1 = m2 - m1 * m1 / n1;                            // (bounds as in the split epilogue of k_xprod)
+    const double var1 = ok ? ss1 / (n1 - 1.0) : 0.0;
     const double s2x = SF - m1, s2xx = SFF - m2;
-    const double var2 = ok ? (s2xx - s2x * s2x / n2) / (n2 - 1.0) : 0.0;
+    const double ss2 = s2xx - s2x * s2x / n2;
+    const double var2 = ok ? ss2 / (n2 - 1.0) : 0.0;
     double* o = cc + (size_t)pair * 4 * ldr + c;
     o[0] = ok ? m1 / n1 : 0.0;
-    o[ldr] = (var1 > 0.0) ? 1.0 / sqrt(var1) : 0.0;
+    o[ldr] = (ok && raw_ss_live(ss1, n1, m2)) ? 1.0 / sqrt(var1) : 0.0;
     o[2 * (size_t)ldr] = ok ? s2x / n2 : 0.0;
-    o[3 * (size_t)ldr] = (var2 > 0.0) ? 1.0 / sqrt(var2) : 0.0;
+    o[3 * (size_t)ldr] = (ok && raw_ss_live(ss2, 2.0 * nF + 1.0, SFF)) ? 1.0 / sqrt(var2) : 0.0;
 }
 
 // sF[j][b] = full-sample std (ddof 1) of feature b inside cell j.  grid (ceil(ldr / 256), J).
@@ -70,8 +72,9 @@ static __global__ void k_cell_sd(const double* __restrict__ cellS1, const double
     if (c >= ldr) return;
     const double nF = (double)cell_len[j];
     const double SF = cellS1[(size_t)j * ldr + c], SFF = cellS2[(size_t)j * ldr + c];
-    const double varF = (nF > 1.5) ? (SFF - SF * SF / nF) / (nF - 1.0) : 0.0;
-    sF[(size_t)j * ldr + c] = (varF > 0.0) ? sqrt(varF) : 0.0;
+    const double ssF = SFF - SF * SF / nF;
+    const double varF = (nF > 1.5) ? ssF / (nF - 1.0) : 0.0;
+    sF[(size_t)j * ldr + c] = (nF > 1.5 && raw_ss_live(ssF, nF, SFF)) ? sqrt(varF) : 0.0;
 }
 
 struct SplitFusedArgs {
