@@ -245,6 +245,52 @@ int plsx_boot_finish(plsx_ctx* ctx, double* d_usum, double* d_usq, void* stream)
 int plsx_boot_route(const plsx_ctx* ctx);
 
 /*
+ * Percentile intervals of the rotated bootstrap weights of PLS-C (behavioral and mean-centred PLS; no reference
+ * counterpart: the (B, L, n_boot) series is 400 GB at B = 200 000, L = 50, n_boot = 5000).  With A_b (T' x S) the
+ * cross-product operand of bootstrap b in subject space (count-weighted, zero outside a row's own cell) and M_b
+ * (T' x L) the rotation operand of the small solver, W_b = M_b^T A_b (L x S) and what plsx_boot_batch adds into
+ * d_usum for bootstrap b is
+ *   U_b[f][l] = sum_g sigma_{b,g}(f) . sum_{s in cell g} W_b[l][s] . Xc[s][f]
+ * sigma = 1 in the unscaled modes (mean-centred PLS, PLSX_FLAG_COVARIANCE); in correlation mode sigma_{b,g}(f) is
+ * 1 / std (ddof 1) of feature f over the rows bootstrap b draws into cell g, from the raw moments as the cross-product
+ * epilogues form it, and 0 for a cell-constant feature.  The units are those of x_weights @ diag(singvals).
+ *
+ *   plsx_boot_keep          d_M (capacity, m, T') fp64, dense: every bootstrap that later plsx_boot_batch calls solve
+ *                           leaves the first m columns of M_b, transposed, appended in submission order -- on every
+ *                           bootstrap route (general feature pass, compact blocks, single-pass / quadratic-form,
+ *                           T' > 64, graded resamples after their refinement).  Bootstrap-major, so that the stacks
+ *                           of several contexts concatenate.  d_usum, d_usq, d_distrib keep their bits.  A batch that
+ *                           no longer fits returns PLSX_ERR_ARG before it computes anything.  plsx_set_data,
+ *                           plsx_set_original and plsx_boot_keep(ctx, NULL, 0, 0) end the keeping; the buffer stays
+ *                           the caller's.  PLSX_ERR_STATE without bound PLS-C data and a set original,
+ *                           PLSX_ERR_UNSUPPORTED with contrasts or a multiblock binding, PLSX_ERR_ARG for m outside
+ *                           1 .. L, a null buffer or capacity < 1.
+ *   plsx_boot_weights_ci    d_boot_idx (n, S) int32 index rows, d_M (n, m, T') -- a kept stack, the gathered stacks
+ *                           of several ranks, or ANY stack and index rows (the entry keeps no state of the series) --
+ *                           -> d_lo / d_hi (B, m): the interpolated order statistics
+ *                           (1 - g) x[i] + g x[i + 1] of {U_b[f][l] : b < n} at (i_lo, g_lo) and (i_hi, g_hi), as
+ *                           plsx_percentile_ci takes them.  The pass rebuilds A_b from the index rows with the
+ *                           builders of the bootstrap routes, forms W (n, m, S), and walks the features in chunks of
+ *                           whole 128-feature blocks: per chunk the scale table sigma [cell][feature][bootstrap]
+ *                           (correlation mode only, k_weights_scale), the series [feature][l][n] (k_weights_prod:
+ *                           k_coef_prod's tile with the contraction run cell segment by cell segment, each segment's
+ *                           partial tile multiplied by sigma before it joins the total), then the selection kernels
+ *                           (option "percentile_sort" applies).  The (B, m, n) array never exists whole: a chunk's
+ *                           series is 2 GB at most, and series, scale table, stack and W stay inside the scratch
+ *                           budget and free device memory.  Every entry is one block's contraction in a fixed order
+ *                           (cells ascending, subjects ascending): the same bits run to run and whatever the
+ *                           chunking; no floating-point atomics.
+ *                           Limits: PLSX_ERR_UNSUPPORTED (context still usable, sizes in plsx_last_error) for
+ *                           n > 16384, when not even the smallest chunk fits, for m T' > 20448 (the LDS of the
+ *                           dual-weight kernel) and for a multiblock binding; PLSX_ERR_ARG for n < 1, m outside
+ *                           1 .. L, an index outside 0 .. n - 1, a null pointer; PLSX_ERR_STATE without bound PLS-C
+ *                           data.
+ */
+int plsx_boot_keep(plsx_ctx* ctx, double* d_M, long long capacity, int m);
+int plsx_boot_weights_ci(plsx_ctx* ctx, const int32_t* d_boot_idx, const double* d_M, int n, int m, int i_lo,
+                         double g_lo, int i_hi, double g_hi, double* d_lo, double* d_hi, void* stream);
+
+/*
  * Split-half reliability -- BasePLS.split_half (pyls/base.py:714-770) for np
  * data arrangements (the original data and/or permuted data, base.py:705-708)
  * with ns split masks each.  For every arrangement the library decomposes
@@ -798,7 +844,9 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill),
  * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale),
  * 15 k_sd_cv_class (the confusion counts of an open plsx_simpls_cv_class_begin series),
- * 16 k_sd_cv_auc (the AUC counts of an open plsx_simpls_cv_auc_begin series).
+ * 16 k_sd_cv_auc (the AUC counts of an open plsx_simpls_cv_auc_begin series),
+ * 17 k_weights_prod (the feature pass of plsx_boot_weights_ci: one launch per chunk of features; its scale table
+ * counts under 8, its operand builders under 7, its selection under 12).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

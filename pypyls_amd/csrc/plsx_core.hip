@@ -9,7 +9,7 @@ namespace plsxi {
 const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small", "k_urot", "k_nt_gemm",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
                                                  "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm",
-                                                 "k_sd_cv_class", "k_sd_cv_auc"};
+                                                 "k_sd_cv_class", "k_sd_cv_auc", "k_weights_prod"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -409,7 +409,7 @@ try {
     (void)plsx_comm_destroy(ctx);
     for (Buf* b : {&ctx->Xc, &ctx->xmean, &ctx->Y, &ctx->cell_of_row, &ctx->cell_start, &ctx->cell_len,
                    &ctx->out_row, &ctx->mom_idx, &ctx->mom_n, &ctx->Afrag, &ctx->R, &ctx->Gm, &ctx->Pm,
-                   &ctx->part, &ctx->Mfrag, &ctx->U0T, &ctx->V0, &ctx->d0, &ctx->tmpW,
+                   &ctx->wciW, &ctx->wciCnt, &ctx->wciScale, &ctx->part, &ctx->Mfrag, &ctx->U0T, &ctx->V0, &ctx->d0, &ctx->tmpW,
                    &ctx->Rfull, &ctx->Vp, &ctx->dp, &ctx->Mvd, &ctx->Cm, &ctx->srcx, &ctx->srcy, &ctx->part2,
                    &ctx->Kmat, &ctx->swork, &ctx->spct, &ctx->sc,
                    &ctx->momout, &ctx->R2, &ctx->cvc, &ctx->Qm, &ctx->Vs, &ctx->ds, &ctx->ybar, &ctx->pred,
@@ -550,6 +550,7 @@ try {
     coef_close(ctx);                                   // (an open coefficient series ends with the binding it belonged to)
     vip_close(ctx);                                    // (... and so does a kept VIP stack)
     cperm_close(ctx);                                  // (... and an open permutation series of the coefficients)
+    wkeep_close(ctx);                                  // (... and a kept stack of rotation operands)
     count_close(ctx->cls_series);                      // (... and the class codes of its rows with their open series)
     count_close(ctx->auc_series);
     ctx->has_cls = 0;
@@ -769,6 +770,7 @@ try {
     if (Lc < 0 || Lc > ctx->L) return fail(ctx, PLSX_ERR_ARG, "plsx_set_contrasts: Lc must lie in 0 .. min(T', B)");
     // the original of the other mode is not this mode's: plsx_decompose / plsx_set_original follow
     ctx->has_orig = false; ctx->quad_active = 0; ctx->graded = 0;
+    wkeep_close(ctx);                                  // (a kept stack of rotation operands ends with the original it belonged to)
     ctx->nc = 0;
     if (Lc == 0 || !d_C) return PLSX_OK;
     const int tot = ctx->nks_t * ctx->LT * 64;
@@ -830,6 +832,7 @@ try {
         LAUNCHCHK();
     }
     ctx->has_orig = true; ctx->quad_active = 0;
+    wkeep_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -1117,6 +1120,7 @@ int boot_single_pass(plsx_ctx* ctx, const int32_t* d_boot_idx, int n, double* d_
             SmallArgs a = small_args(ctx, SMALL_BOOT);
             if (int e = run_small(ctx, a, m, st)) return e;
         }
+        if (int e = wkeep_append(ctx, m, st)) return e;
         // gen_distrib of a resample is its cross-product with the score columns: P_r itself
         HIPCHK(hipMemcpyAsync(d_distrib + (size_t)off * Tp * L, ctx->Pm.p, (size_t)m * Tp * L * 8,
                               hipMemcpyDeviceToDevice, st));
@@ -1191,6 +1195,14 @@ try {
     NEED_ORIG();
     if (!d_boot_idx || !d_usum || !d_usq || !d_distrib || n < 1)
         return fail(ctx, PLSX_ERR_ARG, "plsx_boot_batch: bad arguments");
+    if (ctx->wkeep && ctx->wkeep_n + n > ctx->wkeep_cap) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "plsx_boot_batch: %d bootstraps do not fit the stack of plsx_boot_keep (%lld of %lld "
+                 "kept)", n, ctx->wkeep_n, ctx->wkeep_cap);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (ctx->wkeep && ctx->nc > 0)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_boot_batch: plsx_boot_keep is not available with contrasts");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     // unscaled modes: one pass over the features per bootstrap (see boot_single_pass)
@@ -1210,6 +1222,7 @@ try {
             SmallArgs a = small_args(ctx, SMALL_BOOT);
             if (int e = run_small(ctx, a, m, st, R)) return e;
         }
+        if (int e = wkeep_append(ctx, m, st)) return e;
         if (int e = run_urot(ctx, m, d_usum, d_usq, nullptr, st)) return e;
         dim3 g(ceil_div(ctx->Tp * ctx->L, 256), m);
         hipLaunchKernelGGL(k_gather_cols, g, dim3(256), 0, st, R, ctx->strideR, ctx->Bpad, ctx->B, ctx->Tp,

@@ -10,6 +10,7 @@
 //   plsx_urot.hip        k_urot, k_ucorr_partial
 //   plsx_split.hip       split-half and cross-validation
 //   plsx_simpls_api.hip  SIMPLS regression: the solver batch (run_simpls_dual on an SdRequest), products with K (sd_times_K), one cross-validation body (cv_fit_score), the count series of PLS-DA (CountSeries)
+//   plsx_weightsci.hip   percentile intervals of the PLS-C x_weights: plsx_boot_keep, plsx_boot_weights_ci
 //   plsx_comm.hip        the exported collective (RCCL through dlopen)
 #pragma once
 #include "plsx_kernels.h"
@@ -174,6 +175,13 @@ struct plsx_ctx {
     double* vipG = nullptr;
     long long vip_cap = 0, vip_n = 0;
     int vip_c = 0;
+    // plsx_boot_keep: every bootstrap a plsx_boot_batch call solves also leaves the first wkeep_m columns of its rotation
+    // operand M_b, appended [wkeep_n][wkeep_m][T'] to the caller's buffer (k_keep_M); plsx_boot_weights_ci: the dual weights
+    // W [n][m][S], the draw counts [n][S] and the scale table of a chunk of features [J][fc][n]
+    double* wkeep = nullptr;
+    long long wkeep_cap = 0, wkeep_n = 0;
+    int wkeep_m = 0;
+    Buf wciW, wciCnt, wciScale;
     // plsx_simpls_coef_perm_begin: a permutation series of the coefficients rides along plsx_simpls_perm_batch -- the
     // caller's observed coefficients (B, T), counts (B, T) and maxima [cperm_n][T] (appended), the batch's A_p dense
     // [m][T][S] (cpA), the partial maxima of a chunk of feature blocks (cppart), the feature scale s_f (colsd)
@@ -300,7 +308,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -395,6 +403,11 @@ inline void vip_close(plsx_ctx* ctx)
 {
     ctx->vipG = nullptr; ctx->vip_cap = 0; ctx->vip_n = 0; ctx->vip_c = 0;
 }
+// a kept stack of rotation operands ends (plsx_set_data, plsx_set_original, plsx_boot_keep(ctx, NULL, 0, 0))
+inline void wkeep_close(plsx_ctx* ctx)
+{
+    ctx->wkeep = nullptr; ctx->wkeep_cap = 0; ctx->wkeep_n = 0; ctx->wkeep_m = 0;
+}
 // an open permutation series of the coefficients ends (plsx_set_data, plsx_simpls_set_original, a second
 // plsx_simpls_coef_perm_begin, plsx_simpls_coef_perm_end); the buffers stay the caller's
 inline void cperm_close(plsx_ctx* ctx)
@@ -455,6 +468,9 @@ int run_urot(plsx_ctx* ctx, int nres, double* usum, double* usq, double* out, hi
 int launch_ucorr(plsx_ctx* ctx, dim3 grid, dim3 block, hipStream_t st, const double* M, int tpc,
                  double* part, int npairs);
 int ucorr_slots();
+// ---- plsx_weightsci.hip ----
+// plsx_boot_keep's share of a solver batch: M_r of the `m` resamples whose operands the small solver just left in ctx->Mfrag
+int wkeep_append(plsx_ctx* ctx, int m, hipStream_t st);
 // ---- plsx_simpls_api.hip ----
 bool simpls_single_pass(const plsx_ctx* ctx);
 size_t simpls_global_lds_bytes(int T, int k);

@@ -43,6 +43,7 @@
 //   plsx_k_contrast.h  non-rotated PLS (plsx_set_contrasts): k_contrast_norms (|| R_r^T v_l || in one pass over R_r), k_contrast_quad (the same from G_p), k_contrast_fill (V as every resample's rotation operand)
 //   plsx_k_multiblock.h  multiblock PLS (PLSX_MULTIBLOCK): the row normalisation of the stacked cross-covariance matrix (k_mb_rownorm, k_mb_rowscale)
 //   plsx_k_vip.h       VIP scores of the SIMPLS bootstraps: the feature pass k_vip_prod, the moments of its series (k_vip_moments)
+//   plsx_k_weightsci.h percentile intervals of the PLS-C x_weights: the kept rotation operands (k_keep_M), the dual weights rebuilt from them (k_weights_W), the scale table of the correlation mode (k_weights_scale), the feature pass k_weights_prod
 #pragma once
 #include "plsx_common.h"
 #include "plsx_k_prep.h"
@@ -57,3 +58,4 @@
 #include "plsx_k_vip.h"
 #include "plsx_k_contrast.h"
 #include "plsx_k_multiblock.h"
+#include "plsx_k_weightsci.h"

@@ -65,6 +65,8 @@ def _load():
         'plsx_boot_begin': ([vp, ctypes.c_longlong, vp], i32),
         'plsx_boot_finish': ([vp, vp, vp, vp], i32),
         'plsx_boot_route': ([vp], i32),
+        'plsx_boot_keep': ([vp, vp, ctypes.c_longlong, i32], i32),
+        'plsx_boot_weights_ci': ([vp, vp, vp, i32, i32, i32, c_d, i32, c_d, vp, vp, vp], i32),
         'plsx_split_route': ([vp], i32),
         'plsx_split_half_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
         'plsx_split_half_batch_y': ([vp, vp, vp, i32, vp, i32, vp, vp, vp], i32),
@@ -138,7 +140,7 @@ def exported_symbols():
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
              'plsx_crosscov_batch', 'plsx_scratch_read', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
-             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
+             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
@@ -790,6 +792,39 @@ class Engine(object):
         self._check(self.lib.plsx_boot_batch(self.ctx, idx_dev.data_ptr(), idx_dev.shape[0],
                                              usum.data_ptr(), usq.data_ptr(), dist_dev.data_ptr(),
                                              self._stream()))
+
+    def boot_keep(self, stack=None):
+        """Have every :meth:`boot_into` that follows also keep the bootstrap's rotation operand: ``stack`` (capacity, m,
+        T'), a contiguous float64 tensor on this device, receives the first m columns of M_b, transposed, in submission
+        order (plsx_boot_keep).  ``None`` ends the keeping.  PlsxError: status -4 without bound PLS-C data and a set
+        original, -2 with contrasts or multiblock data, -1 from the batch that would overflow the stack."""
+        if stack is None:
+            self._check(self.lib.plsx_boot_keep(self.ctx, None, 0, 0))
+            return
+        torch = _torch()
+        if stack.dim() != 3 or stack.shape[2] != self.Tp or stack.dtype != torch.float64 or not stack.is_contiguous():
+            raise ValueError('the kept stack must be a contiguous (capacity, m, {}) float64 tensor'.format(self.Tp))
+        self._check(self.lib.plsx_boot_keep(self.ctx, stack.data_ptr(), int(stack.shape[0]), int(stack.shape[1])))
+
+    def boot_weights_ci(self, idx_dev, stack, ci=95):
+        """Percentile interval of the rotated bootstrap weights: ``idx_dev`` (n, S) int32 index rows and ``stack`` (n, m,
+        T') -- a kept stack, the gathered stacks of several ranks, or any contiguous float64 device tensor of that shape
+        -> (lo, hi) device tensors (B, m), ``np.percentile(U_boot[:, :m], [(100 - ci) / 2, 100 - (100 - ci) / 2],
+        axis=-1)`` of the (B, L, n) series of ``single_boot(...)[1]``, in the units of ``x_weights @ diag(singvals)``,
+        without that array ever existing (plsx_boot_weights_ci).  No sync.  PlsxError status -2 (context still usable)
+        for n > 16384 or a stack that does not fit the scratch budget."""
+        torch = _torch()
+        if stack.dim() != 3 or stack.shape[2] != self.Tp or stack.dtype != torch.float64 or not stack.is_contiguous():
+            raise ValueError('the stack must be a contiguous (n, m, {}) float64 tensor'.format(self.Tp))
+        n, m = int(stack.shape[0]), int(stack.shape[1])
+        if tuple(idx_dev.shape) != (n, self.S) or idx_dev.dtype != torch.int32 or not idx_dev.is_contiguous():
+            raise ValueError('the index rows must be a contiguous ({}, {}) int32 tensor'.format(n, self.S))
+        idx = _virtual_indices(max(n, 1), ci)
+        lo, hi = self._empty((self.B, max(m, 1))), self._empty((self.B, max(m, 1)))
+        self._check(self.lib.plsx_boot_weights_ci(self.ctx, idx_dev.data_ptr(), stack.data_ptr(), n, m, idx[0][0],
+                                                  idx[0][1], idx[1][0], idx[1][1], lo.data_ptr(), hi.data_ptr(),
+                                                  self._stream()))
+        return lo, hi
 
     def simpls_perm_into(self, idx_dev, out_dev):
         """idx_dev (n, S) int32, out_dev (n, k): pctvar of the permuted Y."""

@@ -106,6 +106,31 @@ def _check_contrasts(contrasts, Tp, B, n_split):
     return V
 
 
+def _check_weights_ci(weights_ci, method, L, n_boot, bootsamples, contrasts):
+    """What ``weights_ci`` does not cover, refused on the host before any engine is created or looked up -> the number
+    of latent variables m (True: all L)."""
+    if method == 'multiblock':
+        raise ValueError('Percentile intervals of the x_weights (`weights_ci`) are not available for multiblock PLS')
+    if contrasts:
+        raise ValueError('Percentile intervals of the x_weights (`weights_ci`) are not available for non-rotated PLS '
+                         '(`contrasts`)')
+    n_boot = n_boot or 0
+    if n_boot > 0 and bootsamples is not None and np.ndim(bootsamples) == 2:
+        n_boot = np.shape(bootsamples)[1]
+    if n_boot < 1:
+        raise ValueError('`weights_ci` needs bootstraps (`n_boot` > 0)')
+    if n_boot > 16384:
+        raise ValueError('`weights_ci` takes at most 16384 bootstraps (the bound of the selection kernels); got '
+                         '`n_boot` = {}'.format(n_boot))
+    if weights_ci is True:
+        return L
+    if isinstance(weights_ci, (bool, np.bool_)) or not isinstance(weights_ci, (int, np.integer)) \
+            or not 1 <= int(weights_ci) <= L:
+        raise ValueError('`weights_ci` must be True or a number of latent variables in 1 .. {}; got {!r}'
+                         .format(L, weights_ci))
+    return int(weights_ci)
+
+
 class _PLSCRun(object):
     """One analysis; the counterpart of BasePLS + subclass (pyls/base.py:232)."""
 
@@ -139,6 +164,17 @@ class _PLSCRun(object):
             kwargs['contrasts'] = np.asarray(kwargs['contrasts'], dtype=np.float64)
         else:
             kwargs.pop('contrasts', None)
+        # weights_ci: LVs whose rotated bootstrap weights get percentile intervals (None: not asked for)
+        self.weights_m = None
+        if kwargs.get('weights_ci', False) is not False and kwargs.get('weights_ci') is not None:
+            Xa = np.asarray(X)
+            T = 1 if Y is None else (np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 0)
+            if Xa.ndim != 2 or T < 1:
+                raise ValueError('Expected 2D arrays for `X` and `Y`')
+            self.weights_m = _check_weights_ci(kwargs['weights_ci'], method, min(len(groups) * n_cond * T, Xa.shape[1]),
+                                               kwargs.get('n_boot'), kwargs.get('bootsamples'), self.V is not None)
+        else:
+            kwargs.pop('weights_ci', None)
         # measurement hooks of bench.py --mode analysis (not inputs of the analysis): a dict that receives
         # per-phase wall times; (rank, world) of a world emulated on one GPU
         self.phases = kwargs.pop('_phases', None)
@@ -350,7 +386,7 @@ class _PLSCRun(object):
         pstream, bstream, ystack = self.perm_stream, self.boot_stream, self.ystack
         n_perm_tot = pstream.n if pstream is not None else (ystack.shape[0] if ystack is not None else 0)
         n_boot_tot = bstream.n if bstream is not None else 0
-        d_perm = d_dist = usum = usq = None
+        d_perm = d_dist = d_keep = usum = usq = None
         plo, phi = parallel.shard_bounds(n_perm_tot, rank, world)
         # Chunked shipping (IndexStream.chunks: 256 rows, then 4 x longer ranges) lets the device start while the
         # generator thread still draws.  It pays at both ends of the size range: c4's shard is device-seconds long
@@ -396,6 +432,11 @@ class _PLSCRun(object):
             # the series of this rank's bootstraps: where the weights are linear in the (unscaled) features the
             # library accumulates S x S moments per batch and passes the features once, in boot_finish
             eng.boot_begin(sum(hi - lo for lo, hi in bchunks))
+            if self.weights_m is not None:
+                # weights_ci: every bootstrap also leaves its rotation operand (m, T'); the stack rides in the collective
+                d_keep = eng._zeros((d_dist.shape[0], self.weights_m, eng.Tp))
+                if d_keep.shape[0] > 0:
+                    eng.boot_keep(d_keep)
             bar = Bar('Running bootstraps', sum(hi - lo for lo, hi in bchunks), show, eng.device)
             bars.append(bar)
             for blo, bhi in bchunks:
@@ -407,6 +448,8 @@ class _PLSCRun(object):
                     bar.queued(b - a)
                 off += bhi - blo
             eng.boot_finish(usum, usq)
+            if d_keep is not None:
+                eng.boot_keep(None)
         # host work that needs no device result runs while the device is busy: page-locked landing zones of
         # the results (56 us per MB to map), the index arrays in the reference's layout and dtype ((S, n)
         # C-contiguous int64), the host-sized scores of the original data
@@ -471,6 +514,10 @@ class _PLSCRun(object):
             cyclic.append(len(slices))
             slices.append(d_dist)
             totals.append(n_boot_tot)
+            if d_keep is not None:
+                cyclic.append(len(slices))
+                slices.append(d_keep)
+                totals.append(n_boot_tot)
         cv_splits = self.cv_splits
         if cv_splits is not None:
             # cross-validation (behavioral.py:219-221, 82-170): its shard rides in the same buffer
@@ -506,6 +553,13 @@ class _PLSCRun(object):
             d_full = full[k]                                                           # (n_boot, T', L)
             k += 1
             d_series = eng.transpose_dev(d_full.reshape(n_boot_tot, eng.Tp * L))       # (T' L, n_boot) series
+            if d_keep is not None:
+                # weights_ci: the closing pass over the gathered stack (n_boot, m, T') and ALL index rows, on this rank
+                tick('finish_and_d2h')
+                d_wlo, d_whi = eng.boot_weights_ci(eng.rows_tensor(bstream.rows[:n_boot_tot]), full[k].contiguous(),
+                                                   ci=inp.get('ci', 95))
+                k += 1
+                tick('weights_ci')
             lo_hi = eng.percentile_ci_dev(d_series, ci=inp.get('ci', 95))
             h_dist = eng.to_host_async(d_series, pin['dist'])
             d_bs = eng.scale_columns(d_xw, d_sv)                                       # x_weights @ singvals
@@ -595,6 +649,8 @@ class _PLSCRun(object):
                 res['bootres'].update(dict(
                     x_weights_normed=bsr, x_weights_stderr=se, bootsamples=bootsamp,
                     contrast=contrast, contrast_boot=distrib, contrast_ci=ci_arr))
+            if d_keep is not None:
+                res['bootres']['x_weights_ci'] = np.stack([d_wlo.cpu().numpy(), d_whi.cpu().numpy()], -1)   # (B, m, 2)
 
         res['varexp'] = hostmath.varexp(sv)
         res['singvals'] = sv
@@ -606,7 +662,7 @@ class _PLSCRun(object):
 def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_split=0,
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
-                   contrasts=None, **kwargs):
+                   contrasts=None, weights_ci=False, **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
     shard the resamples over (module docstring); ``device_ids=[...]`` names them.
 
@@ -616,9 +672,19 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     ||R.T @ V[:, l]||``, ``x_weights`` the normalised ``R.T @ V``; permutations test each contrast (``rotate`` has no
     meaning), bootstraps give the reliability of each contrast's weights, and every result has Lc columns.  The
     cross-validation is not run (``cvres`` stays empty) and ``n_split`` > 0 raises.  A seeded call draws the same
-    resampling arrays as the call without contrasts."""
+    resampling arrays as the call without contrasts.
+
+    ``weights_ci`` (True: all L latent variables; an int m: the first m, 1 <= m <= L): ``bootres.x_weights_ci`` (B, m, 2),
+    the lower / upper ``ci`` percentile bound (numpy's linear interpolation) of the Procrustes-rotated, singular-value-
+    scaled bootstrap weights U_b over the ``n_boot`` bootstraps.  The units are those of ``x_weights @ diag(singvals)``,
+    the numerator of ``bootres.x_weights_normed``; the original fit is not part of the series (as for
+    ``y_loadings_ci``).  The (B, m, n_boot) series is formed on the device one chunk of features at a time and never
+    exists whole.  Needs 1 <= ``n_boot`` <= 16384; not available with ``contrasts`` (ValueError).  Every other array of
+    the result keeps its bits and a seeded call draws the same resampling arrays."""
     if contrasts is not None:
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
+    if weights_ci is not False:
+        kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
     run = _PLSCRun('behavioral', np.asarray(X), np.asarray(Y), groups=groups, n_cond=n_cond,
                    n_perm=n_perm, n_boot=n_boot, n_split=n_split, test_size=test_size,
                    test_split=test_split, covariance=covariance, rotate=rotate, ci=ci,
@@ -655,14 +721,19 @@ def _meancentered_design(X, groups, n_cond, mean_centering):
 
 def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000, n_boot=5000,
                      n_split=0, rotate=True, ci=95, permsamples=None, bootsamples=None,
-                     seed=None, verbose=True, n_proc=None, contrasts=None, **kwargs):
+                     seed=None, verbose=True, n_proc=None, contrasts=None, weights_ci=False, **kwargs):
     """Mean-centred PLS of X (S, B) sorted into groups x conditions; see
     pyls.meancentered_pls (argument checks of pyls/types/meancentered.py:16-38).
 
     ``contrasts`` (T', Lc), T' = groups x conditions (group-major rows): non-rotated PLS, as for
-    :func:`behavioral_pls`; the bootstrap keeps the mean-centred conventions (no add-back of the original)."""
+    :func:`behavioral_pls`; the bootstrap keeps the mean-centred conventions (no add-back of the original).
+
+    ``weights_ci`` (True or an int m): ``bootres.x_weights_ci`` (B, m, 2), percentile intervals of the rotated bootstrap
+    weights in the units of ``x_weights @ diag(singvals)``, as for :func:`behavioral_pls`."""
     if contrasts is not None:
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
+    if weights_ci is not False:
+        kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
     X = np.asarray(X)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     run = _PLSCRun('meancentered', X, None, groups=groups, n_cond=n_cond,

@@ -97,6 +97,7 @@ class PLSInputs(KeyedRecord):
         'coef_perm',                        # pls_regression: permutation p-values of its coefficients (only when asked for)
         'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
+        'weights_ci',                       # behavioral_pls / meancentered_pls: percentile intervals of the x_weights (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
         '_classes',                         # pls_da: class code of every row (Y is their indicator matrix)
@@ -134,7 +135,11 @@ class PLSBootResults(KeyedRecord):
                'coefs_ci',
                # pls_regression(vip_components=c): (B,) standard deviation (ddof = 1) and (B, 2) lower / upper percentile
                # bound of the VIP scores over the n_boot bootstraps (the original is not added to the series)
-               'vip_stderr', 'vip_ci')
+               'vip_stderr', 'vip_ci',
+               # behavioral_pls / meancentered_pls(weights_ci=m): (B, m, 2) lower / upper percentile bound of the rotated
+               # bootstrap weights U_b over the n_boot bootstraps, in the units of x_weights @ diag(singvals) -- the
+               # numerator of x_weights_normed (the original is not added to the series, as for y_loadings_ci)
+               'x_weights_ci')
 
 
 class PLSPermResults(KeyedRecord):
