@@ -339,6 +339,29 @@ int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_
                         void* stream);
 
 /*
+ * Permutation null of the cross-validation (no reference counterpart; the rule of plsx_simpls_crossval_perm_batch):
+ * the whole cross-validation above, under the same n splits, for each of m permutations of the rows of Y, averaged
+ * over the splits in split order.  A permutation leaves the feature side of a fit untouched, so the call forms ONE
+ * S x S matrix per split -- the Gram product of the rows of X centred and scaled by that split's per-cell training
+ * mean / std inside the contraction (k_cvp_moments, k_cvp_gram; with covariance one matrix whose test rows alone are
+ * scaled) -- and every (permutation, split) fit is S x S work: A, W' = A M^T, G = W' A^T, the small solver, the
+ * scores.  A feature whose training rows of a cell all hold the same bits has scale 0 (k_cell_scale's rule).
+ *   d_masks    (n, S) uint8, 1 = training row
+ *   d_perm_idx (m, S) int32: row p of permutation i is row d_perm_idx[i][p] of Y; every row a permutation of 0 .. S-1
+ *   d_r, d_r2  (m, T) out: the means over the n splits of Pearson r and r^2; a NaN score of one (permutation, split)
+ *              makes that permutation's mean NaN
+ * The caller passes ALL of its permutations in one call: a split's matrix is formed once per call and is not kept
+ * between calls.  Splits and permutations run in groups sized by free device memory and the scratch budget; the
+ * chunking of the contraction follows (S, B) alone, so the bits of a result depend neither on the groups nor on how
+ * the permutations are cut into calls.  The context is left as found (the call maps and frees its own matrices).
+ * PLSX_ERR_ARG: not a behavioural binding, null pointers, n < 1 or m < 1.  PLSX_ERR_UNSUPPORTED (context still
+ * usable): multiblock PLS, contrasts set, or one split's matrices with one permutation's operands and the scores do
+ * not fit free device memory and the scratch budget (the message has the sizes).
+ */
+int plsx_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                             double* d_r, double* d_r2, void* stream);
+
+/*
  * SIMPLS regression (pyls/types/regression.py:56-186, 248-373), solved per
  * resample in the S-dimensional dual space (K = X0 X0^T); k = n_components.
  *   plsx_simpls_decompose   original data: d_xwT (k, B) x_weights transposed,
@@ -846,7 +869,11 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * 15 k_sd_cv_class (the confusion counts of an open plsx_simpls_cv_class_begin series),
  * 16 k_sd_cv_auc (the AUC counts of an open plsx_simpls_cv_auc_begin series),
  * 17 k_weights_prod (the feature pass of plsx_boot_weights_ci: one launch per chunk of features; its scale table
- * counts under 8, its operand builders under 7, its selection under 12).
+ * counts under 8, its operand builders under 7, its selection under 12),
+ * 18 k_cvp_moments (the per-split training mean / scale tables of plsx_crossval_perm_batch),
+ * 19 k_cvp_gram (its scaled Gram product with the sum of the partial tiles; its operand builder counts under 7, its
+ * small solver under 2, its scores under 9), 20 k_cvp_w and 21 k_cvp_g (its products W' = A M^T and G = W' A^T:
+ * k_nt_gemm launches, which class 4 counts as well), 22 k_cvp_mean (its mean over the splits).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

@@ -1,0 +1,190 @@
+// plsx_cvperm.hip -- permutation null of the behavioural cross-validation in dual space (plsx_crossval_perm_batch)
+// Part of libplsx.so (plsx_internal.h has the map of translation units).  gfx950 only.
+//
+// One S x S matrix per SPLIT (plsx_k_cvperm.h has the algebra) serves every permutation: the feature pass runs once
+// per split of a call, never per (permutation, split), and each fit is S x S work -- A (k_cvp_build_A), W' = A M^T
+// and G = W' A^T (run_nt), the small solver returning V and d, the scores (k_cvp_final).  The caller hands ALL of
+// its permutations to one call: a split's matrix lives for the group of splits it was formed with and is not kept
+// between calls.
+#include "plsx_internal.h"
+#include "plsx_k_cvperm.h"
+
+using namespace plsxi;
+
+namespace {
+
+// what the call maps for itself and gives back when it returns: the context's own buffers keep their owners
+struct CvpScratch {
+    Buf M, mu, inv, part, r, r2, z;
+    ~CvpScratch() { for (Buf* b : {&M, &mu, &inv, &part, &r, &r2, &z}) release(*b); }
+};
+
+// Blocks along the contraction of k_cvp_gram: about 1024 blocks per split, at least 512 columns each -- a function
+// of (S, B) alone, so a split's bits follow neither the batch, the scratch budget nor the way the call is cut.
+void cvp_chunks(int S, int B, int* kchunk, int* nchunk)
+{
+    const int mt = ceil_div(S, 64);
+    int nc = std::max(1, ceil_div(1024, ceil_div(mt, 2) * mt));
+    nc = std::min(nc, std::max(1, B / 512));
+    *kchunk = round_up(ceil_div(B, nc), NT_KB);
+    *nchunk = ceil_div(B, *kchunk);
+}
+
+int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m, double* d_r,
+                double* d_r2, hipStream_t st)
+{
+    const int S = ctx->S, B = ctx->B, T = ctx->T, J = ctx->J, Tp = ctx->Tp, L = ctx->L;
+    const int Sd = round_up(S, 8), ldt = ctx->Bpad, mt = ceil_div(S, 64);
+    int kchunk = 0, nchunk = 0;
+    cvp_chunks(S, B, &kchunk, &nchunk);
+    const double tiles = (double)mt * mt;
+    // bytes of one split (matrix, tables, partial tiles), of one permutation (A, W', G, V, d, z, predictions) and of
+    // the scores of the whole call
+    const double per_split = (double)S * Sd * 8 + 2.0 * J * ldt * 8 + (double)nchunk * tiles * 4096 * 8;
+    const size_t mfrag = (size_t)ctx->nks_t * ctx->LT * 64 * 8;     // (the solver also leaves its rotation operand)
+    const double per_perm = 2.0 * Tp * Sd * 8 + (double)Tp * Tp * 8 + (double)Tp * L * 8 + (double)L * 8 +
+                            (double)S * T * 8 + (double)S * L * 8 + (double)J * T * 8 + (double)mfrag;
+    const double fixed = 2.0 * m * (double)n * T * 8;
+    size_t fre = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fre, &tot));
+    const double limit = std::min(ctx->scratch_gb * 1073741824.0, 0.9 * (double)fre);
+    if (fixed + per_split + per_perm > limit || (long long)ceil_div(mt, 2) * mt > 65535 ||
+        (double)J * ldt >= 2147483648.0) {
+        char msg[384];
+        snprintf(msg, sizeof msg,
+                 "plsx_crossval_perm_batch: one split (S = %d, B = %d: %.1f MB of matrix, tables and partial tiles), one "
+                 "permutation's operands (T' = %d: %.1f MB) and the scores of %d x %d fits (%.1f MB) do not fit %.1f MB "
+                 "of free device memory and scratch budget",
+                 S, B, per_split / 1048576.0, Tp, per_perm / 1048576.0, m, n, fixed / 1048576.0, limit / 1048576.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    // splits per group: half of what is left, 4 GB at most; permutations per pass: the rest, within the operand and
+    // grid bounds of the tiled products (as perm_dual)
+    const double room = limit - fixed;
+    int gs = (int)std::max(1.0, std::min((double)n, std::floor(std::min(0.5 * room, 4294967296.0) / per_split)));
+    gs = std::min(gs, 65535);
+    long long mb = (long long)std::max(1.0, std::floor((room - gs * per_split) / per_perm));
+    mb = std::min<long long>(mb, std::min<long long>(32768, (2LL << 30) / ((long long)Tp * Sd * 8)));
+    mb = std::min<long long>(mb, 60000LL * 64 / ((long long)Tp * mt));
+    mb = std::max<long long>(1, std::min<long long>(mb, m));
+
+    CvpScratch sc;
+    if (int e = ensure(ctx, sc.M, (size_t)gs * S * Sd * 8)) return e;
+    if (int e = ensure(ctx, sc.mu, (size_t)gs * J * ldt * 8)) return e;
+    if (int e = ensure(ctx, sc.inv, (size_t)gs * J * ldt * 8)) return e;
+    if (int e = ensure(ctx, sc.part, (size_t)gs * nchunk * mt * mt * 4096 * 8)) return e;
+    if (int e = ensure(ctx, sc.r, (size_t)m * n * T * 8)) return e;
+    if (int e = ensure(ctx, sc.r2, (size_t)m * n * T * 8)) return e;
+    if (int e = ensure(ctx, sc.z, (size_t)mb * S * L * 8)) return e;
+    const size_t abytes = (size_t)mb * Tp * Sd * 8;
+    if (int e = ensure(ctx, ctx->Ad, abytes)) return e;
+    if (int e = ensure(ctx, ctx->Wd, abytes)) return e;
+    if (int e = ensure(ctx, ctx->Gm, (size_t)mb * Tp * Tp * 8)) return e;
+    if (int e = ensure(ctx, ctx->Vs, (size_t)mb * Tp * L * 8)) return e;
+    if (int e = ensure(ctx, ctx->ds, (size_t)mb * L * 8)) return e;
+    if (int e = ensure(ctx, ctx->Mfrag, (size_t)mb * mfrag + 1024)) return e;
+    if (int e = ensure(ctx, ctx->ybar, (size_t)mb * J * T * 8)) return e;
+    if (int e = ensure(ctx, ctx->pred, (size_t)mb * S * T * 8)) return e;
+
+    for (int s0 = 0; s0 < n; s0 += gs) {
+        const int g = std::min(gs, n - s0);
+        const uint8_t* mk = d_masks + (size_t)s0 * S;
+        {
+            KTimer tm(ctx, KC_CVPMOM, st);
+            hipLaunchKernelGGL(k_cvp_moments, dim3(ceil_div(B, 256), ceil_div(g, CVP_SB)), dim3(256), 0, st,
+                               ptr<double>(ctx->Xc), ctx->Bpad, B, J, ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len),
+                               mk, S, g, ptr<double>(sc.mu), ptr<double>(sc.inv), ldt);
+            LAUNCHCHK();
+        }
+        {
+            CvpGramArgs a;
+            a.X = ptr<double>(ctx->Xc); a.ldx = ctx->Bpad; a.S = S; a.K = B;
+            a.mu = ptr<double>(sc.mu); a.inv = ptr<double>(sc.inv); a.ldt = ldt; a.J = J;
+            a.cell_of_row = ptr<int>(ctx->cell_of_row); a.masks = mk; a.cov = ctx->cov;
+            a.kchunk = kchunk; a.nchunk = nchunk; a.mtiles = mt; a.part = ptr<double>(sc.part);
+            KTimer tm(ctx, KC_CVPGRAM, st);
+            hipLaunchKernelGGL(k_cvp_gram, dim3(nchunk, ceil_div(mt, 2) * mt, g), dim3(256), 0, st, a);
+            LAUNCHCHK();
+            hipLaunchKernelGGL(k_cvp_reduce, dim3((unsigned)(((long long)S * S + 255) / 256), g), dim3(256), 0, st,
+                               ptr<double>(sc.part), nchunk, mt, S, ptr<double>(sc.M), Sd);
+            LAUNCHCHK();
+        }
+        for (int s = 0; s < g; ++s) {
+            const uint8_t* mks = mk + (size_t)s * S;
+            const double* Ms = ptr<double>(sc.M) + (size_t)s * S * Sd;
+            for (int p0 = 0; p0 < m; p0 += (int)mb) {
+                const int mm = std::min<int>((int)mb, m - p0);
+                const int* idx = d_perm_idx + (size_t)p0 * S;
+                HIPCHK(hipMemsetAsync(ctx->Ad.p, 0, (size_t)mm * Tp * Sd * 8, st));
+                {
+                    KTimer tm(ctx, KC_BUILD, st);
+                    hipLaunchKernelGGL(k_cvp_build_A, dim3(mm, J), dim3(256), (size_t)2 * T * 8, st, ptr<double>(ctx->Y), T,
+                                       S, ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), mks, idx, Tp, ctx->cov,
+                                       ptr<double>(ctx->Ad), Sd);
+                    LAUNCHCHK();
+                }
+                // W' = A M^T, all permutations stacked ((mm T') x S); every entry is one block's whole contraction
+                {
+                    KTimer tm(ctx, KC_CVPW, st);
+                    if (int e = run_nt(ctx, ptr<double>(ctx->Ad), 0, Sd, mm * Tp, Ms, 0, Sd, S, nullptr, 0, 0, 0, S, 1,
+                                       ptr<double>(ctx->Wd), 0, Sd, nullptr, 0, 0, st, false, false, true))
+                        return e;
+                }
+                // G_p = W'_p A_p^T
+                {
+                    KTimer tm(ctx, KC_CVPG, st);
+                    if (int e = run_nt(ctx, ptr<double>(ctx->Wd), (long long)Tp * Sd, Sd, Tp, ptr<double>(ctx->Ad),
+                                       (long long)Tp * Sd, Sd, Tp, nullptr, 0, 0, 0, S, mm, ptr<double>(ctx->Gm),
+                                       (long long)Tp * Tp, Tp, nullptr, 0, 0, st, false, false, true))
+                        return e;
+                }
+                SmallArgs a = small_args(ctx, SMALL_DECOMP);
+                a.out_V = ptr<double>(ctx->Vs); a.out_d = ptr<double>(ctx->ds);
+                if (int e = run_small(ctx, a, mm, st)) return e;
+                {
+                    KTimer tm(ctx, KC_CVSCORE, st);
+                    const size_t o = ((size_t)p0 * n + s0 + s) * T;
+                    hipLaunchKernelGGL(k_cvp_final, dim3(mm), dim3(256), 0, st, ptr<double>(ctx->Wd), Sd,
+                                       ptr<double>(ctx->Vs), ptr<double>(ctx->ds), ptr<double>(ctx->Y), mks, idx,
+                                       ptr<int>(ctx->cell_of_row), S, T, J, Tp, L, ptr<double>(ctx->ybar),
+                                       ptr<double>(sc.z), ptr<double>(ctx->pred), ptr<double>(sc.r) + o, ptr<double>(sc.r2) + o,
+                                       (long long)n * T);
+                    LAUNCHCHK();
+                }
+            }
+        }
+    }
+    // the mean over the splits, in split order (a NaN score makes its permutation's mean NaN)
+    {
+        KTimer tm(ctx, KC_CVPMEAN, st);
+        hipLaunchKernelGGL(k_mean_axis1, dim3(ceil_div(m * T, 256)), dim3(256), 0, st, ptr<double>(sc.r), m, n, T, d_r);
+        LAUNCHCHK();
+        hipLaunchKernelGGL(k_mean_axis1, dim3(ceil_div(m * T, 256)), dim3(256), 0, st, ptr<double>(sc.r2), m, n, T, d_r2);
+        LAUNCHCHK();
+    }
+    HIPCHK(hipStreamSynchronize(st));                  // the call's own scratch goes when it returns
+    return PLSX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plsx_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                             double* d_r, double* d_r2, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method == PLSX_MULTIBLOCK)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_perm_batch: cross-validation is not built for multiblock PLS");
+    if (ctx->method != PLSX_BEHAVIORAL)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_perm_batch: cross-validation is defined for behavioral PLS");
+    if (!d_masks || !d_perm_idx || !d_r || !d_r2 || n < 1 || m < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_perm_batch: bad arguments");
+    if (ctx->nc > 0)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_perm_batch: cross-validation predicts from a fitted "
+                                               "decomposition, which non-rotated PLS (contrasts are set) does not have");
+    HIPCHK(hipSetDevice(ctx->device));
+    return cvperm_impl(ctx, d_masks, n, d_perm_idx, m, d_r, d_r2, static_cast<hipStream_t>(stream));
+} PLSX_CATCH(ctx)
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 //   plsx_urot.hip        k_urot, k_ucorr_partial
 //   plsx_split.hip       split-half and cross-validation
 //   plsx_simpls_api.hip  SIMPLS regression: the solver batch (run_simpls_dual on an SdRequest), products with K (sd_times_K), one cross-validation body (cv_fit_score), the count series of PLS-DA (CountSeries)
+//   plsx_cvperm.hip      permutation null of the behavioural cross-validation in dual space: plsx_crossval_perm_batch (plsx_k_cvperm.h)
 //   plsx_weightsci.hip   percentile intervals of the PLS-C x_weights: plsx_boot_keep, plsx_boot_weights_ci
 //   plsx_comm.hip        the exported collective (RCCL through dlopen)
 #pragma once
@@ -308,7 +309,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.

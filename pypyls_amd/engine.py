@@ -61,6 +61,7 @@ def _load():
         'plsx_perm_batch': ([vp, vp, i32, i32, vp, vp], i32),
         'plsx_perm_batch_y': ([vp, vp, i32, i32, vp, vp], i32),
         'plsx_crossval_batch': ([vp, vp, i32, vp, vp, vp], i32),
+        'plsx_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
         'plsx_boot_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_boot_begin': ([vp, ctypes.c_longlong, vp], i32),
         'plsx_boot_finish': ([vp, vp, vp, vp], i32),
@@ -140,7 +141,7 @@ def exported_symbols():
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
              'plsx_crosscov_batch', 'plsx_scratch_read', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
-             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
+             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
@@ -676,6 +677,31 @@ class Engine(object):
         r, r2 = self._empty((m, self.T)), self._empty((m, self.T))
         self._check(self.lib.plsx_crossval_batch(self.ctx, dm.data_ptr(), m, r.data_ptr(), r2.data_ptr(),
                                                  self._stream()))
+        self.sync()
+        return r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy()
+
+    def crossval_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev):
+        """Device form of :meth:`crossval_perm`: masks (n, S) uint8, index rows (m, S) int32 -> r, r2 (m, T), the means
+        over the n splits (plsx_crossval_perm_batch).  Pass all of the caller's permutations at once: every split's
+        S x S matrix is formed once per call."""
+        n, m = masks_dev.shape[0], idx_dev.shape[0]
+        self._check(self.lib.plsx_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
+                                                      r_dev.data_ptr(), r2_dev.data_ptr(), self._stream()))
+
+    def crossval_perm(self, splits, perms):
+        """Permutation null of the cross-validation: splits (S, n) bool, True = training row; perms (S, m), one
+        permutation of 0 .. S-1 per column -> perm_pearson_r, perm_r_squared (T, m): for every permutation of the rows
+        of Y the scores of :meth:`crossval` under the same splits, averaged over the splits."""
+        torch = _torch()
+        splits = np.asarray(splits)
+        if splits.ndim != 2 or splits.shape[0] != self.S:
+            raise ValueError('split masks must have shape (S, n) with S = {}'.format(self.S))
+        idx = check_index_array(np.asarray(perms), self.S)
+        dm = torch.from_numpy(np.ascontiguousarray(splits.T, dtype=np.uint8)).to(self.device)
+        di = torch.from_numpy(np.ascontiguousarray(idx.T, dtype=np.int32)).to(self.device)
+        m = di.shape[0]
+        r, r2 = self._empty((m, self.T)), self._empty((m, self.T))
+        self.crossval_perm_into(dm, di, r, r2)
         self.sync()
         return r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy()
 

@@ -177,6 +177,7 @@ class _PLSCRun(object):
             kwargs.pop('weights_ci', None)
         # measurement hooks of bench.py --mode analysis (not inputs of the analysis): a dict that receives
         # per-phase wall times; (rank, world) of a world emulated on one GPU
+        self.cvperm_given = kwargs.pop('_cvpermsamples', None)     # behavioral_pls(cv_perm=): validated (S, P) or None
         self.phases = kwargs.pop('_phases', None)
         self.emulate = kwargs.pop('_emulate', None)
         self.device_ids = kwargs.pop('device_ids', None)
@@ -260,6 +261,15 @@ class _PLSCRun(object):
             if self.cv_splits is None:
                 jobs.append(lambda rs: setattr(self, 'cv_splits', resampling.gen_splits(
                     inp.groups, inp.n_cond, inp.test_split, seed=rs, test_size=inp.test_size)))
+        # cv_perm: the permutations of the cross-validation come after everything else a seeded call draws, the masks
+        # included -- every other array of the call keeps its bits
+        self.cvperm_stream = None
+        if (inp.get('cv_perm') or 0) > 0:
+            if self.cvperm_given is not None:
+                self.cvperm_stream = resampling.IndexStream.of_array(self.cvperm_given)
+            else:
+                self.cvperm_stream = resampling.IndexStream('perm', inp.groups, inp.n_cond, int(inp.get('cv_perm')))
+                jobs.append(self.cvperm_stream.draw)
         return resampling.DrawThread(self.rs, jobs)
 
     def run(self):
@@ -465,7 +475,7 @@ class _PLSCRun(object):
             if bstream is not None:
                 bootsamp = self.boot_given if self.boot_given is not None else bstream.samples
         draws.join()
-        for st in (pstream, bstream):
+        for st in (pstream, bstream, self.cvperm_stream):
             if st is not None and lead:
                 st.warn()
         for bar in bars:
@@ -530,6 +540,23 @@ class _PLSCRun(object):
             slices.append(torch.from_numpy(np.ascontiguousarray(local_cv)).to(eng.device))
             totals.append(cv_splits.shape[1])
             tick('crossval')
+        cvp = self.cvperm_stream if cv_splits is not None else None
+        if cvp is not None:
+            # cv_perm: the ranks shard the PERMUTATIONS, every rank under all the splits -- one S x S matrix per split
+            # serves all of a rank's permutations, handed over in one call (plsx_crossval_perm_batch); the null rides
+            # in the same collective
+            qlo, qhi = parallel.shard_bounds(cvp.n, rank, world)
+            d_null = eng._zeros((qhi - qlo, 2 * Y.shape[1]))
+            if qhi > qlo:
+                cvp.wait(qhi)
+                dmk = torch.from_numpy(np.ascontiguousarray(cv_splits.T, dtype=np.uint8)).to(eng.device)
+                nr, nr2 = eng._empty((qhi - qlo, Y.shape[1])), eng._empty((qhi - qlo, Y.shape[1]))
+                eng.crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2)
+                d_null = torch.cat([nr, nr2], dim=1)
+                eng.sync()
+            slices.append(d_null)
+            totals.append(cvp.n)
+            tick('crossval_perm')
         sums = [usum, usq] if usum is not None else []
         full, summed = parallel.collect_device(slices, totals, sums, cyclic=cyclic, emulate=emulate, team=team)
         if not lead:
@@ -578,6 +605,18 @@ class _PLSCRun(object):
             cv = full[k].cpu().numpy().T
             res['cvres'].update(dict(pearson_r=np.ascontiguousarray(cv[:Tn]),
                                      r_squared=np.ascontiguousarray(cv[Tn:])))
+            if cvp is not None:
+                k += 1
+                null = full[k].cpu().numpy().T                                        # (2 T, P)
+                null_r, null_r2 = np.ascontiguousarray(null[:Tn]), np.ascontiguousarray(null[Tn:])
+                with np.errstate(invalid='ignore'):                                   # (a NaN null value compares false)
+                    res['cvres'].update(dict(
+                        perm_pearson_r=null_r, perm_r_squared=null_r2,
+                        pearson_r_pvals=hostmath.perm_sig(res['cvres']['pearson_r'].mean(axis=-1), null_r),
+                        r_squared_pvals=hostmath.perm_sig(res['cvres']['r_squared'].mean(axis=-1), null_r2),
+                        cvpermsamples=(np.asarray(self.cvperm_given) if self.cvperm_given is not None
+                                       else cvp.samples),
+                        cvsamples=np.ascontiguousarray(cv_splits, dtype=bool)))
         eng.sync()
         tick('finish_and_d2h')
         xw = _host_array(h_xw)
@@ -659,10 +698,48 @@ class _PLSCRun(object):
         return res
 
 
+def _check_cv_perm(cv_perm, cvpermsamples, X, test_split, test_size, contrasts):
+    """The checks of ``behavioral_pls(cv_perm=, cvpermsamples=)``, on the host before any engine (wording and order of
+    ``pls_regression``) -> False when not asked for, else the validated (S, P) array or None (to be drawn)."""
+    if isinstance(cv_perm, (bool, np.bool_)) or not isinstance(cv_perm, (int, np.integer)) or cv_perm < 0:
+        raise ValueError('Provided `cv_perm` must be a non-negative integer; got {!r}'.format(cv_perm))
+    if int(cv_perm) == 0:
+        return False
+    if not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+        raise ValueError('`cv_perm` needs cross-validation: it permutes Y under the splits of `test_split` > 0 with '
+                         '`test_size` > 0; got test_split = {!r}, test_size = {!r}'.format(test_split, test_size))
+    if contrasts is not None:
+        raise ValueError('`cv_perm` is not available with `contrasts`: non-rotated PLS has no fitted decomposition to '
+                         'predict from, its cross-validation is not run')
+    if cvpermsamples is None:
+        return None
+    from .engine import check_index_array
+    S = len(X)
+    cvperm = np.asarray(cvpermsamples)
+    if cvperm.ndim != 2 or cvperm.shape != (S, int(cv_perm)):
+        raise ValueError('Provided `cvpermsamples` must have shape (S, cv_perm) = ({}, {}); got {}'
+                         .format(S, int(cv_perm), cvperm.shape))
+    cvperm = check_index_array(cvperm, S)
+    if not np.array_equal(np.sort(cvperm, axis=0), np.broadcast_to(np.arange(S)[:, None], cvperm.shape)):
+        bad = int(np.flatnonzero((np.sort(cvperm, axis=0) != np.arange(S)[:, None]).any(axis=0))[0])
+        raise ValueError('Provided `cvpermsamples` must hold one permutation of 0 .. {} per column; column {} '
+                         'is not one'.format(S - 1, bad))
+    return cvperm
+
+
+def _refuse_cv_perm(kwargs, what):
+    """``cv_perm`` / ``cvpermsamples`` belong to behavioral_pls: refused on the host, before any engine."""
+    if kwargs.get('cv_perm') or kwargs.get('cvpermsamples') is not None:
+        raise ValueError('`cv_perm` (the permutation test of the cross-validation) is not available for {}: only '
+                         'behavioral PLS is cross-validated'.format(what))
+    kwargs.pop('cv_perm', None)
+    kwargs.pop('cvpermsamples', None)
+
+
 def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_split=0,
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
-                   contrasts=None, weights_ci=False, **kwargs):
+                   contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
     shard the resamples over (module docstring); ``device_ids=[...]`` names them.
 
@@ -680,11 +757,26 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     the numerator of ``bootres.x_weights_normed``; the original fit is not part of the series (as for
     ``y_loadings_ci``).  The (B, m, n_boot) series is formed on the device one chunk of features at a time and never
     exists whole.  Needs 1 <= ``n_boot`` <= 16384; not available with ``contrasts`` (ValueError).  Every other array of
-    the result keeps its bits and a seeded call draws the same resampling arrays."""
+    the result keeps its bits and a seeded call draws the same resampling arrays.
+
+    Permutation test of the cross-validation: ``cv_perm=P`` (needs ``test_split`` > 0 and ``test_size`` > 0; 0, the
+    default: nothing is added, nothing changes) runs the whole cross-validation, under the same splits, for P
+    permutations of the rows of Y -- drawn after everything else a seeded call draws, the split masks included, or
+    given as ``cvpermsamples`` (S, P), one permutation of 0 .. S-1 per column.  ``cvres`` gains ``perm_pearson_r`` /
+    ``perm_r_squared`` (T, P), the mean over the splits of every permutation's scores; ``pearson_r_pvals`` /
+    ``r_squared_pvals`` (T,) = (#{null > mean over the splits of the observed score} + 1) / (P + 1), a NaN null value
+    counting as not larger; ``cvpermsamples`` (S, P) and ``cvsamples`` (S, test_split), the training masks the null rests
+    on.  The feature side of a fit does not see the permutation, so the device forms one S x S matrix per split and
+    every (permutation, split) fit is S x S work.  GPUs shard the permutations.  Not available with ``contrasts``
+    (ValueError); a cohort whose per-split matrix does not fit the device is refused."""
     if contrasts is not None:
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
+    cvperm = _check_cv_perm(cv_perm, cvpermsamples, np.asarray(X), test_split, test_size, contrasts)
+    if cvperm is not False:
+        kwargs['cv_perm'] = int(cv_perm)           # (recorded in `inputs` only when asked for)
+        kwargs['_cvpermsamples'] = cvperm
     run = _PLSCRun('behavioral', np.asarray(X), np.asarray(Y), groups=groups, n_cond=n_cond,
                    n_perm=n_perm, n_boot=n_boot, n_split=n_split, test_size=test_size,
                    test_split=test_split, covariance=covariance, rotate=rotate, ci=ci,
@@ -734,6 +826,7 @@ def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000,
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
+    _refuse_cv_perm(kwargs, 'mean-centred PLS')
     X = np.asarray(X)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     run = _PLSCRun('meancentered', X, None, groups=groups, n_cond=n_cond,
@@ -798,6 +891,7 @@ def multiblock_pls(X, Y, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000
     Not available (ValueError): ``n_split`` > 0, cross-validation (``test_split``), ``contrasts``,
     ``permindices=False``, a behaviour block on a subset of the conditions; one group with one condition (the task
     block is identically zero).  ``mean_centering`` is reset with a warning as in :func:`meancentered_pls`."""
+    _refuse_cv_perm(kwargs, 'multiblock PLS')
     X, Y = np.asarray(X), np.asarray(Y)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     groups = [int(g) for g in groups]
