@@ -362,6 +362,40 @@ int plsx_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const
                              double* d_r, double* d_r2, void* stream);
 
 /*
+ * Out-of-sample score correlation of the latent variables (no reference counterpart; the train / test statistic of
+ * the PLS / CCA stability literature): plsx_crossval_batch plus, from the same pass -- the cross-product, the
+ * decompositions and Q run once -- for every split and LV l the Pearson correlation, over ALL test rows of the split
+ * in row order, of
+ *   x_score[p][l] = the z_l the prediction uses (zmap of the test row by the training mean / std of its cell, projected
+ *                   through U_live = R^T V_live / d_live; a cell-constant feature has scale 0), and
+ *   y_score[p][l] = (y_p - training mean of its cell j) / training std (ddof = 1; covariance: not divided)
+ *                   . V[jT .. (j+1)T, l]   -- the normalisation R was built with
+ * (k_cv_lv, after k_cv_final).  Both scores flip with the sign of the training SVD: no alignment.  LV l is the l-th
+ * largest singular value of the split's fit; a per-LV value is only as stable as the gap around that singular value.
+ *   d_r, d_r2  (m, T) out: bit for bit those of plsx_crossval_batch on the same masks
+ *   d_lv       (m, L) out: clamped to [-1, 1]; NaN for an LV that is not live (d_l <= PLSX_RANK_RTOL d_1) and where
+ *              either score has no variance over the test rows (0 / 0)
+ * The sums run in one fixed order (lane partials over ascending rows, an xor tree; no atomics).  Arguments, refusals
+ * and error codes as plsx_crossval_batch, d_lv required.
+ */
+int plsx_crossval_lv_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, double* d_lv,
+                           void* stream);
+
+/*
+ * plsx_crossval_perm_batch plus the score correlations above of every (permutation, split) fit (k_cvp_lv, on the z
+ * that the scoring kernel of the fit left; no further S x S or feature-sized work).
+ *   d_r, d_r2   (m, T) out: bit for bit those of plsx_crossval_perm_batch on the same masks and permutations
+ *   d_lv        (m, L) out: the means over the n splits, in split order; one NaN makes a permutation's mean NaN
+ *   d_lv_pairs  (m, n, L) out or NULL: the value of every (permutation, split); with NULL they live in scratch of the call
+ * The fixed summation order makes the bits independent of the groups of splits and permutations, of the scratch budget
+ * and of how the permutations are cut into calls.  The size model counts (S, L) more per permutation of a pass and
+ * (m, n, L) for the call.  Refusals and error codes as plsx_crossval_perm_batch (d_lv required); the context is left
+ * as found.
+ */
+int plsx_crossval_perm_lv_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                                double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, void* stream);
+
+/*
  * SIMPLS regression (pyls/types/regression.py:56-186, 248-373), solved per
  * resample in the S-dimensional dual space (K = X0 X0^T); k = n_components.
  *   plsx_simpls_decompose   original data: d_xwT (k, B) x_weights transposed,
@@ -873,7 +907,9 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * 18 k_cvp_moments (the per-split training mean / scale tables of plsx_crossval_perm_batch),
  * 19 k_cvp_gram (its scaled Gram product with the sum of the partial tiles; its operand builder counts under 7, its
  * small solver under 2, its scores under 9), 20 k_cvp_w and 21 k_cvp_g (its products W' = A M^T and G = W' A^T:
- * k_nt_gemm launches, which class 4 counts as well), 22 k_cvp_mean (its mean over the splits).
+ * k_nt_gemm launches, which class 4 counts as well), 22 k_cvp_mean (its mean over the splits),
+ * 23 k_cv_final (the predictions and scores of plsx_crossval_batch / plsx_crossval_lv_batch), 24 k_cv_lv and
+ * 25 k_cvp_lv (the score correlations of the latent variables of plsx_crossval_lv_batch / plsx_crossval_perm_lv_batch).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

@@ -10,7 +10,7 @@ const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
                                                  "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm",
                                                  "k_sd_cv_class", "k_sd_cv_auc", "k_weights_prod", "k_cvp_moments", "k_cvp_gram", "k_cvp_w", "k_cvp_g",
-                                                 "k_cvp_mean"};
+                                                 "k_cvp_mean", "k_cv_final", "k_cv_lv", "k_cvp_lv"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -413,7 +413,7 @@ try {
                    &ctx->wciW, &ctx->wciCnt, &ctx->wciScale, &ctx->part, &ctx->Mfrag, &ctx->U0T, &ctx->V0, &ctx->d0, &ctx->tmpW,
                    &ctx->Rfull, &ctx->Vp, &ctx->dp, &ctx->Mvd, &ctx->Cm, &ctx->srcx, &ctx->srcy, &ctx->part2,
                    &ctx->Kmat, &ctx->swork, &ctx->spct, &ctx->sc,
-                   &ctx->momout, &ctx->R2, &ctx->cvc, &ctx->Qm, &ctx->Vs, &ctx->ds, &ctx->ybar, &ctx->pred,
+                   &ctx->momout, &ctx->R2, &ctx->cvc, &ctx->Qm, &ctx->Vs, &ctx->ds, &ctx->ybar, &ctx->pred, &ctx->lvsc,
                    &ctx->Xn, &ctx->ppart, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,

@@ -3,9 +3,10 @@
 //
 // One S x S matrix per SPLIT (plsx_k_cvperm.h has the algebra) serves every permutation: the feature pass runs once
 // per split of a call, never per (permutation, split), and each fit is S x S work -- A (k_cvp_build_A), W' = A M^T
-// and G = W' A^T (run_nt), the small solver returning V and d, the scores (k_cvp_final).  The caller hands ALL of
-// its permutations to one call: a split's matrix lives for the group of splits it was formed with and is not kept
-// between calls.
+// and G = W' A^T (run_nt), the small solver returning V and d, the scores (k_cvp_final) and, for
+// plsx_crossval_perm_lv_batch, the score correlations of the latent variables (k_cvp_lv, on the z k_cvp_final left).
+// The caller hands ALL of its permutations to one call: a split's matrix lives for the group of splits it was formed
+// with and is not kept between calls.
 #include "plsx_internal.h"
 #include "plsx_k_cvperm.h"
 
@@ -15,8 +16,8 @@ namespace {
 
 // what the call maps for itself and gives back when it returns: the context's own buffers keep their owners
 struct CvpScratch {
-    Buf M, mu, inv, part, r, r2, z;
-    ~CvpScratch() { for (Buf* b : {&M, &mu, &inv, &part, &r, &r2, &z}) release(*b); }
+    Buf M, mu, inv, part, r, r2, z, ysc, lv;
+    ~CvpScratch() { for (Buf* b : {&M, &mu, &inv, &part, &r, &r2, &z, &ysc, &lv}) release(*b); }
 };
 
 // Blocks along the contraction of k_cvp_gram: about 1024 blocks per split, at least 512 columns each -- a function
@@ -30,8 +31,10 @@ void cvp_chunks(int S, int B, int* kchunk, int* nchunk)
     *nchunk = ceil_div(B, *kchunk);
 }
 
-int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m, double* d_r,
-                double* d_r2, hipStream_t st)
+// d_lv (m, L) != nullptr: also the score correlations of the latent variables, their split means to d_lv and the
+// (permutation, split) values to d_lv_pairs (m, n, L) when given (else to scratch of the call)
+int cvperm_impl(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, hipStream_t st)
 {
     const int S = ctx->S, B = ctx->B, T = ctx->T, J = ctx->J, Tp = ctx->Tp, L = ctx->L;
     const int Sd = round_up(S, 8), ldt = ctx->Bpad, mt = ceil_div(S, 64);
@@ -39,12 +42,14 @@ int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_p
     cvp_chunks(S, B, &kchunk, &nchunk);
     const double tiles = (double)mt * mt;
     // bytes of one split (matrix, tables, partial tiles), of one permutation (A, W', G, V, d, z, predictions) and of
-    // the scores of the whole call
+    // the scores of the whole call; with the LV correlations one more (S, L) per permutation (the y-scores) and their
+    // (m, n, L) values
     const double per_split = (double)S * Sd * 8 + 2.0 * J * ldt * 8 + (double)nchunk * tiles * 4096 * 8;
     const size_t mfrag = (size_t)ctx->nks_t * ctx->LT * 64 * 8;     // (the solver also leaves its rotation operand)
     const double per_perm = 2.0 * Tp * Sd * 8 + (double)Tp * Tp * 8 + (double)Tp * L * 8 + (double)L * 8 +
-                            (double)S * T * 8 + (double)S * L * 8 + (double)J * T * 8 + (double)mfrag;
-    const double fixed = 2.0 * m * (double)n * T * 8;
+                            (double)S * T * 8 + (double)S * L * 8 + (double)J * T * 8 + (double)mfrag +
+                            (d_lv ? (double)S * L * 8 : 0.0);
+    const double fixed = 2.0 * m * (double)n * T * 8 + (d_lv ? (double)m * n * L * 8 : 0.0);
     size_t fre = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fre, &tot));
     const double limit = std::min(ctx->scratch_gb * 1073741824.0, 0.9 * (double)fre);
@@ -52,10 +57,10 @@ int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_p
         (double)J * ldt >= 2147483648.0) {
         char msg[384];
         snprintf(msg, sizeof msg,
-                 "plsx_crossval_perm_batch: one split (S = %d, B = %d: %.1f MB of matrix, tables and partial tiles), one "
+                 "%s: one split (S = %d, B = %d: %.1f MB of matrix, tables and partial tiles), one "
                  "permutation's operands (T' = %d: %.1f MB) and the scores of %d x %d fits (%.1f MB) do not fit %.1f MB "
                  "of free device memory and scratch budget",
-                 S, B, per_split / 1048576.0, Tp, per_perm / 1048576.0, m, n, fixed / 1048576.0, limit / 1048576.0);
+                 who, S, B, per_split / 1048576.0, Tp, per_perm / 1048576.0, m, n, fixed / 1048576.0, limit / 1048576.0);
         return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
     }
     // splits per group: half of what is left, 4 GB at most; permutations per pass: the rest, within the operand and
@@ -76,6 +81,14 @@ int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_p
     if (int e = ensure(ctx, sc.r, (size_t)m * n * T * 8)) return e;
     if (int e = ensure(ctx, sc.r2, (size_t)m * n * T * 8)) return e;
     if (int e = ensure(ctx, sc.z, (size_t)mb * S * L * 8)) return e;
+    double* lv_pairs = d_lv_pairs;
+    if (d_lv) {
+        if (int e = ensure(ctx, sc.ysc, (size_t)mb * S * L * 8)) return e;
+        if (!lv_pairs) {
+            if (int e = ensure(ctx, sc.lv, (size_t)m * n * L * 8)) return e;
+            lv_pairs = ptr<double>(sc.lv);
+        }
+    }
     const size_t abytes = (size_t)mb * Tp * Sd * 8;
     if (int e = ensure(ctx, ctx->Ad, abytes)) return e;
     if (int e = ensure(ctx, ctx->Wd, abytes)) return e;
@@ -151,6 +164,15 @@ int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_p
                                        (long long)n * T);
                     LAUNCHCHK();
                 }
+                if (d_lv) {
+                    KTimer tm(ctx, KC_CVPLV, st);
+                    hipLaunchKernelGGL(k_cvp_lv, dim3(mm), dim3(256), (size_t)2 * J * T * 8, st, ptr<double>(ctx->Vs),
+                                       ptr<double>(ctx->ds), ptr<double>(ctx->Y), mks, idx, ptr<int>(ctx->cell_of_row),
+                                       ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), S, T, J, Tp, L, ctx->cov,
+                                       ptr<double>(sc.z), ptr<double>(sc.ysc),
+                                       lv_pairs + ((size_t)p0 * n + s0 + s) * L, (long long)n * L);
+                    LAUNCHCHK();
+                }
             }
         }
     }
@@ -161,9 +183,31 @@ int cvperm_impl(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_p
         LAUNCHCHK();
         hipLaunchKernelGGL(k_mean_axis1, dim3(ceil_div(m * T, 256)), dim3(256), 0, st, ptr<double>(sc.r2), m, n, T, d_r2);
         LAUNCHCHK();
+        if (d_lv) {
+            hipLaunchKernelGGL(k_mean_axis1, dim3(ceil_div(m * L, 256)), dim3(256), 0, st, lv_pairs, m, n, L, d_lv);
+            LAUNCHCHK();
+        }
     }
     HIPCHK(hipStreamSynchronize(st));                  // the call's own scratch goes when it returns
     return PLSX_OK;
+}
+
+// the checks both entries share; `who` names the entry in the messages
+int cvperm_entry(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                 double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, bool want_lv, void* stream)
+{
+    const std::string w(who);
+    if (ctx->method == PLSX_MULTIBLOCK)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": cross-validation is not built for multiblock PLS");
+    if (ctx->method != PLSX_BEHAVIORAL)
+        return fail(ctx, PLSX_ERR_ARG, w + ": cross-validation is defined for behavioral PLS");
+    if (!d_masks || !d_perm_idx || !d_r || !d_r2 || (want_lv && !d_lv) || n < 1 || m < 1)
+        return fail(ctx, PLSX_ERR_ARG, w + ": bad arguments");
+    if (ctx->nc > 0)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": cross-validation predicts from a fitted "
+                                                "decomposition, which non-rotated PLS (contrasts are set) does not have");
+    HIPCHK(hipSetDevice(ctx->device));
+    return cvperm_impl(ctx, who, d_masks, n, d_perm_idx, m, d_r, d_r2, d_lv, d_lv_pairs, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -174,17 +218,16 @@ int plsx_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const
                              double* d_r, double* d_r2, void* stream)
 try {
     NEED_DATA();
-    if (ctx->method == PLSX_MULTIBLOCK)
-        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_perm_batch: cross-validation is not built for multiblock PLS");
-    if (ctx->method != PLSX_BEHAVIORAL)
-        return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_perm_batch: cross-validation is defined for behavioral PLS");
-    if (!d_masks || !d_perm_idx || !d_r || !d_r2 || n < 1 || m < 1)
-        return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_perm_batch: bad arguments");
-    if (ctx->nc > 0)
-        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_perm_batch: cross-validation predicts from a fitted "
-                                               "decomposition, which non-rotated PLS (contrasts are set) does not have");
-    HIPCHK(hipSetDevice(ctx->device));
-    return cvperm_impl(ctx, d_masks, n, d_perm_idx, m, d_r, d_r2, static_cast<hipStream_t>(stream));
+    return cvperm_entry(ctx, "plsx_crossval_perm_batch", d_masks, n, d_perm_idx, m, d_r, d_r2, nullptr, nullptr, false,
+                        stream);
+} PLSX_CATCH(ctx)
+
+int plsx_crossval_perm_lv_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                                double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, void* stream)
+try {
+    NEED_DATA();
+    return cvperm_entry(ctx, "plsx_crossval_perm_lv_batch", d_masks, n, d_perm_idx, m, d_r, d_r2, d_lv, d_lv_pairs, true,
+                        stream);
 } PLSX_CATCH(ctx)
 
 }  // extern "C"

@@ -117,6 +117,7 @@ struct plsx_ctx {
     Buf Rfull, Vp, dp, Mvd, Cm, srcx, srcy, part2;     // split-half scratch
     Buf Kmat, swork, spct, sc;                          // SIMPLS: K = Xc Xc^T, dual-solver scratch
     Buf momout, R2, cvc, Qm, Vs, ds, ybar, pred;        // cross-validation scratch
+    Buf lvsc;                                           // plsx_crossval_lv_batch: x- and y-scores of a pass's test rows, 2 x [splits][S][L]
     Buf Xn, out_row_f, mom_idx_f;                       // fixed-X fast path
     Buf Kd, Ad, Wd;                                     // dual permutation path (S x S kernel)
     Buf Zcv;                                            // SIMPLS cross-validation: Z = Vd . K, the scores of a batch of splits [n][k][S]
@@ -309,7 +310,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_CVFINAL, KC_CVLV, KC_CVPLV, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.

@@ -1,6 +1,6 @@
 // plsx_k_cvperm.h -- permutation null of the behavioural cross-validation in dual space (plsx_crossval_perm_batch):
 // the per-split moment tables (k_cvp_moments), the scaled Gram product (k_cvp_gram, k_cvp_reduce), the A operand of a
-// (permutation, split) fit (k_cvp_build_A) and its scores (k_cvp_final).
+// (permutation, split) fit (k_cvp_build_A), its scores (k_cvp_final) and the score correlations of its latent variables (k_cvp_lv).
 // Included by plsx_cvperm.hip after plsx_kernels.h.  gfx950 only.
 //
 // A permutation of Y leaves the feature side of a cross-validated fit untouched: under split s, with c(i) the cell of
@@ -326,4 +326,35 @@ void k_cvp_final(const double* __restrict__ W /* [m][Tp][ld] */, int ld,
         out_r[(size_t)i * out_stride + t] = (r > 1.0) ? 1.0 : ((r < -1.0) ? -1.0 : r);
         out_r2[(size_t)i * out_stride + t] = 1.0 - sres / vy;
     }
+}
+
+// Out-of-sample score correlations of the latent variables of permutation r under one split (block = permutation),
+// after k_cvp_final of the same (pass, split): the x_scores are the z that kernel left in `zbuf` (0 for a dead LV), the
+// y_scores (plsx_k_finish.h has the definition and the three shared stages) are formed here over (row, LV) into `ybuf`.
+// No S x S or feature-sized work.  out_lv: entry (r, l) at r * out_stride + l.
+// grid (permutations of the pass), block 256, dynamic LDS 2 J T doubles.
+static __global__ __launch_bounds__(256)
+void k_cvp_lv(const double* __restrict__ V /* [m][Tp][L] */, const double* __restrict__ d /* [m][L] */,
+              const double* __restrict__ Y, const uint8_t* __restrict__ mk, const int* __restrict__ perm,
+              const int* __restrict__ cell_of_pos, const int* __restrict__ cell_start, const int* __restrict__ cell_len,
+              int S, int T, int J, int Tp, int L, int covariance, const double* zbuf /* [m][S][L] */,
+              double* ybuf /* scratch [m][S][L] */, double* __restrict__ out_lv, long long out_stride)
+{
+    extern __shared__ double sm_cvlv[];
+    double* mean = sm_cvlv;
+    double* rstd = sm_cvlv + J * T;
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int* ys = perm + (size_t)i * S;
+    const double* Vi = V + (size_t)i * Tp * L;
+    const double* di = d + (size_t)i * L;
+    double* yi = ybuf + (size_t)i * S * L;
+    cvlv_y_moments(Y, ys, mk, cell_start, cell_len, T, J, covariance, mean, rstd);
+    __syncthreads();
+    for (long long idx = tid; idx < (long long)S * L; idx += blockDim.x) {
+        const int p = (int)(idx / L), l = (int)(idx % L);
+        if (mk[p]) continue;
+        yi[idx] = cvlv_y_score(Y + (size_t)ys[p] * T, mean, rstd, Vi, cell_of_pos[p], T, L, l);
+    }
+    __syncthreads();
+    cvlv_pearson(zbuf + (size_t)i * S * L, yi, mk, di, S, L, out_lv + (size_t)i * out_stride);
 }

@@ -1,4 +1,4 @@
-// plsx_k_finish.h -- split-half projections and finishing (k_ucorr_partial, k_split_final), cross-validation, percentile intervals.
+// plsx_k_finish.h -- split-half projections and finishing (k_ucorr_partial, k_split_final), cross-validation (k_cv_final, k_cv_lv), percentile intervals.
 // Included through plsx_kernels.h (which documents the operand layouts and lists the kernel headers in order).  gfx950 only.
 #pragma once
 #include "plsx_common.h"
@@ -360,6 +360,132 @@ void k_cv_final(const double* __restrict__ Q /* [m*J][Tp][S] */, const double* _
         out_r[(size_t)i * T + t] = (r > 1.0) ? 1.0 : ((r < -1.0) ? -1.0 : r);
         out_r2[(size_t)i * T + t] = 1.0 - sres / vy;
     }
+}
+
+// ---------------------------------------------------------------------------
+// out-of-sample score correlation of the latent variables (plsx_crossval_lv_batch, plsx_crossval_perm_lv_batch)
+// ---------------------------------------------------------------------------
+// For test row p of cell j under one training decomposition (V, d):
+//   x_score[p][l] = z_l of the prediction (k_cv_final / k_cvp_final)
+//   y_score[p][l] = sum_t (y_pt - mean_jt) rstd_jt V[j T + t][l],   mean / std (ddof = 1; covariance: rstd = 1) of the
+//                   training rows of the cell -- the normalisation R was built with
+//   lv[l]         = Pearson r of the two over ALL test rows of the split, clamped to [-1, 1]; NaN for a dead LV
+// Both scores flip with the sign of column l of V: no alignment.  Every sum below has one order, fixed by (S, T, J, L)
+// and the mask alone: a lane adds its rows in ascending order, the 64 lanes meet in an xor tree (every lane ends with
+// the same bits).  No atomics.
+
+static __device__ __forceinline__ double cvlv_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Stage 1 of both kernels: mean[j T + t], rstd[j T + t] (LDS) over the training rows of cell j, Y read through `ys`
+// (row p of the fit is row ys[p] of Y; nullptr: the identity).  One wave per value, two passes (mean, then squares).
+static __device__ void cvlv_y_moments(const double* __restrict__ Y, const int* __restrict__ ys,
+                                      const uint8_t* __restrict__ mk, const int* __restrict__ cell_start,
+                                      const int* __restrict__ cell_len, int T, int J, int covariance,
+                                      double* mean, double* rstd)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int idx = wave; idx < J * T; idx += nw) {
+        const int j = idx / T, t = idx - j * T;
+        const int r0 = cell_start[j], r1 = r0 + cell_len[j];
+        double s = 0.0, cnt = 0.0;
+        for (int p = r0 + lane; p < r1; p += 64)
+            if (mk[p]) { s += Y[(size_t)(ys ? ys[p] : p) * T + t]; cnt += 1.0; }
+        s = cvlv_wave_sum(s);
+        cnt = cvlv_wave_sum(cnt);
+        const double m = s / cnt;
+        double q = 0.0;
+        for (int p = r0 + lane; p < r1; p += 64)
+            if (mk[p]) { const double dv = Y[(size_t)(ys ? ys[p] : p) * T + t] - m; q += dv * dv; }
+        q = cvlv_wave_sum(q);
+        if (lane == 0) {
+            mean[idx] = m;
+            rstd[idx] = covariance ? 1.0 : 1.0 / sqrt(q / (cnt - 1.0));
+        }
+    }
+}
+
+// y_score of (test row p of cell j, LV l): one T-long dot, t ascending; adjacent l read a row of V coalesced.
+static __device__ __forceinline__ double cvlv_y_score(const double* __restrict__ yrow, const double* mean,
+                                                      const double* rstd, const double* __restrict__ Vi, int j, int T,
+                                                      int L, int l)
+{
+    double y = 0.0;
+    for (int t = 0; t < T; ++t)
+        y += (yrow[t] - mean[j * T + t]) * rstd[j * T + t] * Vi[(size_t)(j * T + t) * L + l];
+    return y;
+}
+
+// Stage 3 of both kernels: wave w takes the LVs l = w, w + waves, ...; the five Pearson sums of xs[p][l], ys[p][l]
+// ([S][L]) over the test rows.  out[l] for every l < L.
+static __device__ void cvlv_pearson(const double* xs, const double* ysc,
+                                    const uint8_t* __restrict__ mk, const double* __restrict__ di, int S, int L,
+                                    double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const double dmax = di[0];
+    for (int l = wave; l < L; l += nw) {
+        double sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0, n = 0;
+        for (int p = lane; p < S; p += 64) {
+            if (mk[p]) continue;
+            const double x = xs[(size_t)p * L + l], y = ysc[(size_t)p * L + l];
+            sx += x; sy += y; sxx += x * x; syy += y * y; sxy += x * y; n += 1.0;
+        }
+        sx = cvlv_wave_sum(sx); sy = cvlv_wave_sum(sy); sxx = cvlv_wave_sum(sxx); syy = cvlv_wave_sum(syy);
+        sxy = cvlv_wave_sum(sxy); n = cvlv_wave_sum(n);
+        if (lane == 0) {
+            const double cov = sxy - sx * sy / n, vx = sxx - sx * sx / n, vy = syy - sy * sy / n;
+            const double r = cov / sqrt(vx * vy);
+            out[l] = !(di[l] > PLSX_RANK_RTOL * dmax) ? __builtin_nan("")
+                                                      : ((r > 1.0) ? 1.0 : ((r < -1.0) ? -1.0 : r));
+        }
+    }
+}
+
+// Score correlations of one train/test split on the feature route (block = split), after k_cv_final of the same pass:
+// z is formed again from Q, c, V, d in k_cv_final's order (u ascending, then / d), but spread over (row, LV) -- a
+// thread holds one dot of length T', not a whole row -- and meets the y_score in `xs` / `ysc`.
+// grid (splits), block 256, dynamic LDS 2 J T doubles.
+static __global__ __launch_bounds__(256)
+void k_cv_lv(const double* __restrict__ Q /* [m*J][Tp][S] */, const double* __restrict__ cvec,
+             const double* __restrict__ V /* [m][Tp][L] */, const double* __restrict__ d /* [m][L] */,
+             const double* __restrict__ Y, const uint8_t* __restrict__ masks, const int* __restrict__ cell_of_pos,
+             const int* __restrict__ cell_start, const int* __restrict__ cell_len, int S, int T, int J, int Tp, int L,
+             int covariance, double* xs /* scratch [m][S][L] */, double* ysc /* [m][S][L] */,
+             double* __restrict__ out_lv /* [m][L] */)
+{
+    extern __shared__ double sm_cvlv[];
+    double* mean = sm_cvlv;
+    double* rstd = sm_cvlv + J * T;
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const uint8_t* mk = masks + (size_t)i * S;
+    const double* Vi = V + (size_t)i * Tp * L;
+    const double* di = d + (size_t)i * L;
+    double* xi = xs + (size_t)i * S * L;
+    double* yi = ysc + (size_t)i * S * L;
+    cvlv_y_moments(Y, nullptr, mk, cell_start, cell_len, T, J, covariance, mean, rstd);
+    __syncthreads();
+    const double dmax = di[0];
+    for (long long idx = tid; idx < (long long)S * L; idx += blockDim.x) {
+        const int p = (int)(idx / L), l = (int)(idx % L);
+        if (mk[p]) continue;
+        const int j = cell_of_pos[p];
+        double z = 0.0;
+        if (di[l] > PLSX_RANK_RTOL * dmax) {
+            const double* Qs = Q + (size_t)(i * J + j) * Tp * S;
+            const double* cs = cvec + (size_t)(i * J + j) * Tp;
+            for (int u = 0; u < Tp; ++u) z += (Qs[(size_t)u * S + p] - cs[u]) * Vi[(size_t)u * L + l];
+            z /= di[l];
+        }
+        xi[idx] = z;
+        yi[idx] = cvlv_y_score(Y + (size_t)p * T, mean, rstd, Vi, j, T, L, l);
+    }
+    __syncthreads();
+    cvlv_pearson(xi, yi, mk, di, S, L, out_lv + (size_t)i * L);
 }
 
 // ---------------------------------------------------------------------------

@@ -44,7 +44,7 @@
 //   plsx_k_multiblock.h  multiblock PLS (PLSX_MULTIBLOCK): the row normalisation of the stacked cross-covariance matrix (k_mb_rownorm, k_mb_rowscale)
 //   plsx_k_vip.h       VIP scores of the SIMPLS bootstraps: the feature pass k_vip_prod, the moments of its series (k_vip_moments)
 //   plsx_k_weightsci.h percentile intervals of the PLS-C x_weights: the kept rotation operands (k_keep_M), the dual weights rebuilt from them (k_weights_W), the scale table of the correlation mode (k_weights_scale), the feature pass k_weights_prod
-//   plsx_k_cvperm.h    (included by plsx_cvperm.hip alone, not from here) permutation null of the behavioural cross-validation in dual space: k_cvp_moments, the scaled Gram product k_cvp_gram + k_cvp_reduce, k_cvp_build_A, k_cvp_final
+//   plsx_k_cvperm.h    (included by plsx_cvperm.hip alone, not from here) permutation null of the behavioural cross-validation in dual space: k_cvp_moments, the scaled Gram product k_cvp_gram + k_cvp_reduce, k_cvp_build_A, k_cvp_final, the score correlations of the latent variables k_cvp_lv (its stages shared with k_cv_lv: plsx_k_finish.h)
 #pragma once
 #include "plsx_common.h"
 #include "plsx_k_prep.h"

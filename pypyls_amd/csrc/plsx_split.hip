@@ -357,7 +357,7 @@ try {
 
 namespace plsxi {
 
-int crossval_impl(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, hipStream_t st);
+int crossval_impl(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, double* d_lv, hipStream_t st);
 
 // Lay the groups out again with / without the per-cell moment rows (covariance mode carries
 // them only while cross-validation needs the training mean / std of every feature).
@@ -371,35 +371,56 @@ int replan_moments(plsx_ctx* ctx, int want)
 
 }  // namespace plsxi
 
+namespace {
+
+// both cross-validation entries: the checks, the moment rows planned in for the call; d_lv (m, L) or nullptr
+int crossval_entry(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int m, double* d_r, double* d_r2,
+                   double* d_lv, bool want_lv, void* stream)
+{
+    const std::string w(who);
+    if (ctx->method == PLSX_MULTIBLOCK)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": cross-validation is not built for multiblock PLS");
+    if (ctx->method != PLSX_BEHAVIORAL)
+        return fail(ctx, PLSX_ERR_ARG, w + ": cross-validation is defined for behavioral PLS");
+    if (!d_masks || !d_r || !d_r2 || (want_lv && !d_lv) || m < 1) return fail(ctx, PLSX_ERR_ARG, w + ": bad arguments");
+    if (ctx->nc > 0)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": cross-validation predicts from a fitted decomposition, "
+                                               "which non-rotated PLS (contrasts are set) does not have");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->momrows) return crossval_impl(ctx, d_masks, m, d_r, d_r2, d_lv, st);
+    HIPCHK(hipStreamSynchronize(st));                  // the row maps of queued launches are about to change
+    if (int e = replan_moments(ctx, 1)) return e;
+    const int rc = crossval_impl(ctx, d_masks, m, d_r, d_r2, d_lv, st);
+    HIPCHK(hipStreamSynchronize(st));
+    if (int e = replan_moments(ctx, 0)) return e;
+    return rc;
+}
+
+}  // namespace
+
 extern "C" {
 
 int plsx_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, void* stream)
 try {
     NEED_DATA();
-    if (ctx->method == PLSX_MULTIBLOCK)
-        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_batch: cross-validation is not built for multiblock PLS");
-    if (ctx->method != PLSX_BEHAVIORAL)
-        return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_batch: cross-validation is defined for behavioral PLS");
-    if (!d_masks || !d_r || !d_r2 || m < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_batch: bad arguments");
-    if (ctx->nc > 0)
-        return fail(ctx, PLSX_ERR_UNSUPPORTED, "plsx_crossval_batch: cross-validation predicts from a fitted decomposition, "
-                                               "which non-rotated PLS (contrasts are set) does not have");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->momrows) return crossval_impl(ctx, d_masks, m, d_r, d_r2, st);
-    HIPCHK(hipStreamSynchronize(st));                  // the row maps of queued launches are about to change
-    if (int e = replan_moments(ctx, 1)) return e;
-    const int rc = crossval_impl(ctx, d_masks, m, d_r, d_r2, st);
-    HIPCHK(hipStreamSynchronize(st));
-    if (int e = replan_moments(ctx, 0)) return e;
-    return rc;
+    return crossval_entry(ctx, "plsx_crossval_batch", d_masks, m, d_r, d_r2, nullptr, false, stream);
+} PLSX_CATCH(ctx)
+
+int plsx_crossval_lv_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, double* d_lv,
+                           void* stream)
+try {
+    NEED_DATA();
+    return crossval_entry(ctx, "plsx_crossval_lv_batch", d_masks, m, d_r, d_r2, d_lv, true, stream);
 } PLSX_CATCH(ctx)
 
 }  // extern "C"
 
 namespace plsxi {
 
-int crossval_impl(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, hipStream_t st)
+// d_lv (m, L) != nullptr: also the out-of-sample score correlations of the latent variables (k_cv_lv), from the Q, c,
+// V and d of the same pass
+int crossval_impl(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, double* d_lv, hipStream_t st)
 {
     const int S = ctx->S, T = ctx->T, J = ctx->J, Tp = ctx->Tp, L = ctx->L;
     // splits per pass: bounded by the super-batch and by the J rescaled copies kept in R2
@@ -441,11 +462,25 @@ int crossval_impl(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, dou
             return e2;
         if (int e2 = ensure(ctx, ctx->ybar, (size_t)mm * J * T * 8)) return e2;
         if (int e2 = ensure(ctx, ctx->pred, (size_t)mm * S * T * 8)) return e2;
-        hipLaunchKernelGGL(k_cv_final, dim3(mm), dim3(256), 0, st, ptr<double>(ctx->Qm), ptr<double>(ctx->cvc),
-                           ptr<double>(ctx->Vs), ptr<double>(ctx->ds), ptr<double>(ctx->Y), mk,
-                           ptr<int>(ctx->cell_of_row), S, T, J, Tp, L, ptr<double>(ctx->ybar),
-                           ptr<double>(ctx->pred), d_r + (size_t)off * T, d_r2 + (size_t)off * T);
-        LAUNCHCHK();
+        {
+            KTimer tm(ctx, KC_CVFINAL, st);
+            hipLaunchKernelGGL(k_cv_final, dim3(mm), dim3(256), 0, st, ptr<double>(ctx->Qm), ptr<double>(ctx->cvc),
+                               ptr<double>(ctx->Vs), ptr<double>(ctx->ds), ptr<double>(ctx->Y), mk,
+                               ptr<int>(ctx->cell_of_row), S, T, J, Tp, L, ptr<double>(ctx->ybar),
+                               ptr<double>(ctx->pred), d_r + (size_t)off * T, d_r2 + (size_t)off * T);
+            LAUNCHCHK();
+        }
+        if (d_lv) {
+            // the x- and y-scores of the pass's test rows, [mm][S][L] each
+            if (int e2 = ensure(ctx, ctx->lvsc, (size_t)2 * mm * S * L * 8)) return e2;
+            KTimer tm(ctx, KC_CVLV, st);
+            hipLaunchKernelGGL(k_cv_lv, dim3(mm), dim3(256), (size_t)2 * J * T * 8, st, ptr<double>(ctx->Qm),
+                               ptr<double>(ctx->cvc), ptr<double>(ctx->Vs), ptr<double>(ctx->ds), ptr<double>(ctx->Y), mk,
+                               ptr<int>(ctx->cell_of_row), ptr<int>(ctx->cell_start), ptr<int>(ctx->cell_len), S, T, J,
+                               Tp, L, ctx->cov, ptr<double>(ctx->lvsc), ptr<double>(ctx->lvsc) + (size_t)mm * S * L,
+                               d_lv + (size_t)off * L);
+            LAUNCHCHK();
+        }
     }
     return PLSX_OK;
 }

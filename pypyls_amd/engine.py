@@ -62,6 +62,8 @@ def _load():
         'plsx_perm_batch_y': ([vp, vp, i32, i32, vp, vp], i32),
         'plsx_crossval_batch': ([vp, vp, i32, vp, vp, vp], i32),
         'plsx_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
+        'plsx_crossval_lv_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_crossval_perm_lv_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp, vp], i32),
         'plsx_boot_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_boot_begin': ([vp, ctypes.c_longlong, vp], i32),
         'plsx_boot_finish': ([vp, vp, vp, vp], i32),
@@ -141,7 +143,7 @@ def exported_symbols():
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
              'plsx_crosscov_batch', 'plsx_scratch_read', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
-             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
+             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_crossval_lv_batch', 'plsx_crossval_perm_lv_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
@@ -666,8 +668,9 @@ class Engine(object):
         """1 when the last split-half pass took the one-pass reader over raw first-half sums (plsx_split_route)."""
         return int(self.lib.plsx_split_route(self.ctx))
 
-    def crossval(self, splits):
-        """splits (S, m) bool, True = training row -> pearson_r, r_squared (T, m)."""
+    def crossval(self, splits, lv=False):
+        """splits (S, m) bool, True = training row -> pearson_r, r_squared (T, m); with ``lv`` also lv_corr (L, m), the
+        out-of-sample score correlation of every latent variable from the same pass (plsx_crossval_lv_batch)."""
         torch = _torch()
         splits = np.asarray(splits)
         if splits.ndim != 2 or splits.shape[0] != self.S:
@@ -675,18 +678,49 @@ class Engine(object):
         dm = torch.from_numpy(np.ascontiguousarray(splits.T, dtype=np.uint8)).to(self.device)
         m = dm.shape[0]
         r, r2 = self._empty((m, self.T)), self._empty((m, self.T))
+        if lv:
+            c = self._empty((m, self.L))
+            self._check(self.lib.plsx_crossval_lv_batch(self.ctx, dm.data_ptr(), m, r.data_ptr(), r2.data_ptr(),
+                                                        c.data_ptr(), self._stream()))
+            self.sync()
+            return r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy(), c.cpu().numpy().T.copy()
         self._check(self.lib.plsx_crossval_batch(self.ctx, dm.data_ptr(), m, r.data_ptr(), r2.data_ptr(),
                                                  self._stream()))
         self.sync()
         return r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy()
 
-    def crossval_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev):
+    def crossval_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev, lv_dev=None, lv_pairs_dev=None):
         """Device form of :meth:`crossval_perm`: masks (n, S) uint8, index rows (m, S) int32 -> r, r2 (m, T), the means
         over the n splits (plsx_crossval_perm_batch).  Pass all of the caller's permutations at once: every split's
-        S x S matrix is formed once per call."""
+        S x S matrix is formed once per call.  ``lv_dev`` (m, L): also the split means of the score correlations of
+        the latent variables, ``lv_pairs_dev`` (m, n, L) their (permutation, split) values
+        (plsx_crossval_perm_lv_batch)."""
         n, m = masks_dev.shape[0], idx_dev.shape[0]
-        self._check(self.lib.plsx_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
-                                                      r_dev.data_ptr(), r2_dev.data_ptr(), self._stream()))
+        if lv_dev is None:
+            self._check(self.lib.plsx_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
+                                                          r_dev.data_ptr(), r2_dev.data_ptr(), self._stream()))
+            return
+        self._check(self.lib.plsx_crossval_perm_lv_batch(
+            self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m, r_dev.data_ptr(), r2_dev.data_ptr(),
+            lv_dev.data_ptr(), None if lv_pairs_dev is None else lv_pairs_dev.data_ptr(), self._stream()))
+
+    def crossval_perm_lv(self, splits, perms):
+        """:meth:`crossval_perm` with the score correlations of the latent variables -> perm_pearson_r, perm_r_squared
+        (T, m), perm_lv_corr (L, m) the split means, and the (permutation, split) values (L, m, n)."""
+        torch = _torch()
+        splits = np.asarray(splits)
+        if splits.ndim != 2 or splits.shape[0] != self.S:
+            raise ValueError('split masks must have shape (S, n) with S = {}'.format(self.S))
+        idx = check_index_array(np.asarray(perms), self.S)
+        dm = torch.from_numpy(np.ascontiguousarray(splits.T, dtype=np.uint8)).to(self.device)
+        di = torch.from_numpy(np.ascontiguousarray(idx.T, dtype=np.int32)).to(self.device)
+        m, n = di.shape[0], dm.shape[0]
+        r, r2 = self._empty((m, self.T)), self._empty((m, self.T))
+        c, pairs = self._empty((m, self.L)), self._empty((m, n, self.L))
+        self.crossval_perm_into(dm, di, r, r2, c, pairs)
+        self.sync()
+        return (r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy(), c.cpu().numpy().T.copy(),
+                np.ascontiguousarray(pairs.cpu().numpy().transpose(2, 0, 1)))
 
     def crossval_perm(self, splits, perms):
         """Permutation null of the cross-validation: splits (S, n) bool, True = training row; perms (S, m), one

@@ -178,6 +178,7 @@ class _PLSCRun(object):
         # measurement hooks of bench.py --mode analysis (not inputs of the analysis): a dict that receives
         # per-phase wall times; (rank, world) of a world emulated on one GPU
         self.cvperm_given = kwargs.pop('_cvpermsamples', None)     # behavioral_pls(cv_perm=): validated (S, P) or None
+        self.cv_lv_m = kwargs.pop('_cv_lv_m', None)                # behavioral_pls(cv_lv=): validated LV count or None
         self.phases = kwargs.pop('_phases', None)
         self.emulate = kwargs.pop('_emulate', None)
         self.device_ids = kwargs.pop('device_ids', None)
@@ -532,11 +533,17 @@ class _PLSCRun(object):
         if cv_splits is not None:
             # cross-validation (behavioral.py:219-221, 82-170): its shard rides in the same buffer
             clo, chi = parallel.shard_bounds(cv_splits.shape[1], rank, world)
-            if chi > clo:
+            # cv_lv: the score correlations of the first lvm latent variables come out of the same pass
+            # (plsx_crossval_lv_batch) and ride in the same slice, 2 T + lvm columns wide
+            lvm = self.cv_lv_m or 0
+            if chi > clo and lvm:
+                r, r2, lvc = eng.crossval(cv_splits[:, clo:chi], lv=True)
+                local_cv = np.vstack([r, r2, lvc[:lvm]]).T                            # (m_loc, 2 T + lvm)
+            elif chi > clo:
                 r, r2 = eng.crossval(cv_splits[:, clo:chi])
                 local_cv = np.vstack([r, r2]).T                                       # (m_loc, 2 T)
             else:
-                local_cv = np.zeros((0, 2 * Y.shape[1]))
+                local_cv = np.zeros((0, 2 * Y.shape[1] + lvm))
             slices.append(torch.from_numpy(np.ascontiguousarray(local_cv)).to(eng.device))
             totals.append(cv_splits.shape[1])
             tick('crossval')
@@ -546,13 +553,19 @@ class _PLSCRun(object):
             # serves all of a rank's permutations, handed over in one call (plsx_crossval_perm_batch); the null rides
             # in the same collective
             qlo, qhi = parallel.shard_bounds(cvp.n, rank, world)
-            d_null = eng._zeros((qhi - qlo, 2 * Y.shape[1]))
+            d_null = eng._zeros((qhi - qlo, 2 * Y.shape[1] + lvm))
             if qhi > qlo:
                 cvp.wait(qhi)
                 dmk = torch.from_numpy(np.ascontiguousarray(cv_splits.T, dtype=np.uint8)).to(eng.device)
                 nr, nr2 = eng._empty((qhi - qlo, Y.shape[1])), eng._empty((qhi - qlo, Y.shape[1]))
-                eng.crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2)
-                d_null = torch.cat([nr, nr2], dim=1)
+                if lvm:
+                    # cv_lv: the split means of every permutation's score correlations (plsx_crossval_perm_lv_batch)
+                    nlv = eng._empty((qhi - qlo, eng.L))
+                    eng.crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2, nlv)
+                    d_null = torch.cat([nr, nr2, nlv[:, :lvm]], dim=1)
+                else:
+                    eng.crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2)
+                    d_null = torch.cat([nr, nr2], dim=1)
                 eng.sync()
             slices.append(d_null)
             totals.append(cvp.n)
@@ -604,11 +617,17 @@ class _PLSCRun(object):
             Tn = Y.shape[1]
             cv = full[k].cpu().numpy().T
             res['cvres'].update(dict(pearson_r=np.ascontiguousarray(cv[:Tn]),
-                                     r_squared=np.ascontiguousarray(cv[Tn:])))
+                                     r_squared=np.ascontiguousarray(cv[Tn:2 * Tn])))
+            if lvm:
+                res['cvres']['lv_corr'] = np.ascontiguousarray(cv[2 * Tn:])           # (lvm, test_split)
             if cvp is not None:
                 k += 1
-                null = full[k].cpu().numpy().T                                        # (2 T, P)
-                null_r, null_r2 = np.ascontiguousarray(null[:Tn]), np.ascontiguousarray(null[Tn:])
+                null = full[k].cpu().numpy().T                                        # (2 T [+ lvm], P)
+                null_r, null_r2 = np.ascontiguousarray(null[:Tn]), np.ascontiguousarray(null[Tn:2 * Tn])
+                if lvm:
+                    null_lv = np.ascontiguousarray(null[2 * Tn:])
+                    res['cvres'].update(dict(perm_lv_corr=null_lv,
+                                             lv_corr_pvals=_lv_corr_pvals(res['cvres']['lv_corr'], null_lv)))
                 with np.errstate(invalid='ignore'):                                   # (a NaN null value compares false)
                     res['cvres'].update(dict(
                         perm_pearson_r=null_r, perm_r_squared=null_r2,
@@ -727,6 +746,46 @@ def _check_cv_perm(cv_perm, cvpermsamples, X, test_split, test_size, contrasts):
     return cvperm
 
 
+def _check_cv_lv(cv_lv, X, Y, groups, n_cond, test_split, test_size, contrasts):
+    """The checks of ``behavioral_pls(cv_lv=)``, on the host before any engine -> False when not asked for, else the
+    number of latent variables m (True: all L = min(T', B))."""
+    if cv_lv is False or cv_lv is None:
+        return False
+    if not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+        raise ValueError('`cv_lv` needs cross-validation: it correlates the scores of the test rows under the splits of '
+                         '`test_split` > 0 with `test_size` > 0; got test_split = {!r}, test_size = {!r}'
+                         .format(test_split, test_size))
+    if contrasts is not None:
+        raise ValueError('`cv_lv` is not available with `contrasts`: non-rotated PLS has no fitted decomposition to '
+                         'project through, its cross-validation is not run')
+    if X.ndim != 2 or Y.ndim != 2:
+        raise ValueError('Expected 2D arrays for `X` and `Y`')
+    n_groups = 1 if groups is None else (len(groups) if isinstance(groups, (list, np.ndarray)) else 1)
+    L = min(n_groups * int(n_cond) * Y.shape[1], X.shape[1])
+    if cv_lv is True:
+        return L
+    if isinstance(cv_lv, (bool, np.bool_)) or not isinstance(cv_lv, (int, np.integer)) or not 1 <= int(cv_lv) <= L:
+        raise ValueError('`cv_lv` must be True or a number of latent variables in 1 .. {}; got {!r}'.format(L, cv_lv))
+    return int(cv_lv)
+
+
+def _refuse_cv_lv(kwargs, what):
+    """``cv_lv`` belongs to behavioral_pls: refused on the host, before any engine."""
+    if kwargs.get('cv_lv') not in (None, False):
+        raise ValueError('`cv_lv` (the out-of-sample score correlation of the latent variables) is not available for '
+                         '{}: only behavioral PLS is cross-validated'.format(what))
+    kwargs.pop('cv_lv', None)
+
+
+def _lv_corr_pvals(observed, null):
+    """observed (m, n splits), null (m, P) split means -> (m,): (#{null > observed mean} + 1) / (P + 1); a NaN null value
+    compares false, a NaN observed mean gives NaN."""
+    mean = np.asarray(observed, dtype=np.float64).mean(axis=-1)
+    with np.errstate(invalid='ignore'):
+        p = hostmath.perm_sig(mean, null)
+    return np.where(np.isnan(mean), np.nan, p)
+
+
 def _refuse_cv_perm(kwargs, what):
     """``cv_perm`` / ``cvpermsamples`` belong to behavioral_pls: refused on the host, before any engine."""
     if kwargs.get('cv_perm') or kwargs.get('cvpermsamples') is not None:
@@ -739,7 +798,7 @@ def _refuse_cv_perm(kwargs, what):
 def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_split=0,
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
-                   contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, **kwargs):
+                   contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, cv_lv=False, **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
     shard the resamples over (module docstring); ``device_ids=[...]`` names them.
 
@@ -768,7 +827,20 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     counting as not larger; ``cvpermsamples`` (S, P) and ``cvsamples`` (S, test_split), the training masks the null rests
     on.  The feature side of a fit does not see the permutation, so the device forms one S x S matrix per split and
     every (permutation, split) fit is S x S work.  GPUs shard the permutations.  Not available with ``contrasts``
-    (ValueError); a cohort whose per-split matrix does not fit the device is refused."""
+    (ValueError); a cohort whose per-split matrix does not fit the device is refused.
+
+    Out-of-sample score correlation of the latent variables: ``cv_lv`` (True: all L latent variables; an int m: the
+    first m, 1 <= m <= L; needs ``test_split`` > 0 and ``test_size`` > 0; False, the default: nothing is added, nothing
+    changes).  For every split the held-out rows are projected through the weights fitted on the others: the brain score
+    is the z the prediction uses, the behaviour score is the test row of Y, centred (and, without ``covariance``, scaled)
+    by the training moments of its cell, times the cell's rows of the training V.  ``cvres.lv_corr`` (m, test_split) is
+    their Pearson correlation over all test rows of the split, per latent variable (LV l = the l-th largest singular
+    value of the split's fit); NaN for a latent variable that is not live.  With ``cv_perm=P`` also ``perm_lv_corr``
+    (m, P), the mean over the splits under every permutation, and ``lv_corr_pvals`` (m,) = (#{null > mean over the
+    splits of the observed value} + 1) / (P + 1), NaN where that observed mean is NaN.  Every other array of the
+    result keeps its bits and a seeded call draws the same resampling arrays.  A single latent variable, unlike the
+    prediction, is only as stable as the gap around its singular value.  Not available with ``contrasts``
+    (ValueError)."""
     if contrasts is not None:
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     if weights_ci is not False:
@@ -777,6 +849,10 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     if cvperm is not False:
         kwargs['cv_perm'] = int(cv_perm)           # (recorded in `inputs` only when asked for)
         kwargs['_cvpermsamples'] = cvperm
+    lvm = _check_cv_lv(cv_lv, np.asarray(X), np.asarray(Y), groups, n_cond, test_split, test_size, contrasts)
+    if lvm is not False:
+        kwargs['cv_lv'] = cv_lv                    # (recorded in `inputs` only when asked for)
+        kwargs['_cv_lv_m'] = lvm
     run = _PLSCRun('behavioral', np.asarray(X), np.asarray(Y), groups=groups, n_cond=n_cond,
                    n_perm=n_perm, n_boot=n_boot, n_split=n_split, test_size=test_size,
                    test_split=test_split, covariance=covariance, rotate=rotate, ci=ci,
@@ -827,6 +903,7 @@ def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000,
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
     _refuse_cv_perm(kwargs, 'mean-centred PLS')
+    _refuse_cv_lv(kwargs, 'mean-centred PLS')
     X = np.asarray(X)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     run = _PLSCRun('meancentered', X, None, groups=groups, n_cond=n_cond,
@@ -892,6 +969,7 @@ def multiblock_pls(X, Y, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000
     ``permindices=False``, a behaviour block on a subset of the conditions; one group with one condition (the task
     block is identically zero).  ``mean_centering`` is reset with a warning as in :func:`meancentered_pls`."""
     _refuse_cv_perm(kwargs, 'multiblock PLS')
+    _refuse_cv_lv(kwargs, 'multiblock PLS')
     X, Y = np.asarray(X), np.asarray(Y)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     groups = [int(g) for g in groups]

@@ -98,6 +98,7 @@ class PLSInputs(KeyedRecord):
         'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         'weights_ci',                       # behavioral_pls / meancentered_pls: percentile intervals of the x_weights (only when given)
+        'cv_lv',                            # behavioral_pls: out-of-sample score correlation of the latent variables (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
         '_classes',                         # pls_da: class code of every row (Y is their indicator matrix)
@@ -159,7 +160,10 @@ class PLSCrossValidationResults(KeyedRecord):
     # per component count (no counterpart in the reference, which cross-validates behavioral PLS only)
     # pls_regression(cv_perm=P): the null of the split-means under permuted Y -- perm_pearson_r / perm_r_squared
     # (T, k, P), perm_mse (k + 1, P) -- its p-values (T, k), (T, k), (k + 1,) and the permutations (S, P)
+    # behavioral_pls(cv_lv=m): lv_corr (m, n) the out-of-sample correlation of brain and behaviour scores per latent
+    # variable and split; with cv_perm=P: perm_lv_corr (m, P) the split means under permuted Y, lv_corr_pvals (m,)
     allowed = ('pearson_r', 'r_squared', 'pearson_r_ncomp', 'r_squared_ncomp', 'mse', 'cvsamples',
+               'lv_corr', 'perm_lv_corr', 'lv_corr_pvals',
                'perm_pearson_r', 'perm_r_squared', 'perm_mse', 'pearson_r_pvals', 'r_squared_pvals', 'mse_pvals',
                'cvpermsamples',
                # pls_da: confusion (G, G, k, n) int [true, predicted, c - 1, split], accuracy / balanced_accuracy (k, n);
