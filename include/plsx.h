@@ -471,6 +471,70 @@ int plsx_crossval_perm_lv_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, co
  *                           No bound on m beyond the outputs.  PLSX_ERR_STATE
  *                           without bound regression data; PLSX_ERR_ARG for a null
  *                           pointer, n < 1 or m < 1.
+ *   plsx_simpls_set_confounds  confound regression (no reference counterpart):
+ *                           d_Z (S, q) nuisance variables, 1 <= q <= 15.  Call it
+ *                           after plsx_set_data(PLSX_REGRESSION) and, with masked
+ *                           rows, after plsx_simpls_set_row_masks (a row counts as
+ *                           usable iff okx and oky say so; Z must be finite there).
+ *                           Forms Z~ = [1, Z - zbar] over the usable rows and
+ *                           residualises the bound Xc and Y in place, X_r = M X,
+ *                           Y_r = M Y with M = I - Z~ (Z~^T Z~)^-1 Z~^T (k_cf_resid:
+ *                           lanes over the features, sums over the rows in
+ *                           ascending order, no atomics; masked rows are written as
+ *                           zeros); d_gx (q, B) / d_gy (q, T) out, or NULL: the
+ *                           slopes of X / Y on Z - zbar.  K is then formed again
+ *                           from X_r (not updated: the update cancels where the
+ *                           confounds carry most of the variance) and Z~ is kept
+ *                           for the fold entries below.  Every entry that follows
+ *                           -- decomposition, permutations, bootstraps, split-half,
+ *                           the coefficient and VIP series -- runs on (X_r, Y_r);
+ *                           the confound regression is not refitted per resample.
+ *                           PLSX_ERR_STATE without bound regression data;
+ *                           PLSX_ERR_ARG for a null d_Z, q outside 1 .. 15 or a
+ *                           Cholesky pivot of Z~^T Z~ at or below 1e-10 of its
+ *                           diagonal entry (rank deficiency; the bound data are
+ *                           then untouched).  plsx_set_data clears it.
+ *   plsx_simpls_crossval_confound_batch  plsx_simpls_crossval_batch with the
+ *                           confound regression fitted on the training rows of
+ *                           every split and applied to all its rows
+ *                           (cross-validated confound regression): with D the
+ *                           training indicator of split s, P_s = (Z~^T D Z~)^-1
+ *                           Z~^T D and M_s = I - Z~ P_s, the fit and its scores are
+ *                           those of plsx_simpls_crossval_batch on (M_s X, M_s Y).
+ *                           M_s M = M_s, so the bound residuals serve; nothing
+ *                           B-sized is touched: K_s = M_s K_r M_s^T = K_r - Z~ F_s^T
+ *                           - F_s Z~^T with C_s = K_r P_s^T, E_s = P_s C_s,
+ *                           F_s = C_s - Z~ E_s / 2 (k_cf_fold_prep, one k_nt_gemm,
+ *                           k_cf_fold_F, k_cf_fold_K) and Y_s = M_s Y_r
+ *                           (k_cf_fold_Y) go to the solver as the fit's own K and
+ *                           Y.  Arguments and outputs as plsx_simpls_crossval_batch;
+ *                           the test rows are scored on the fold-residualised Y.
+ *                           Splits go in groups of as many K_s (8 S^2 bytes each,
+ *                           with one fit's state) as fit half the scratch budget.
+ *                           An open series of counts (PLS-DA) is not supported:
+ *                           PLSX_ERR_STATE.
+ *   plsx_simpls_crossval_confound_perm_batch  its null under permuted Y, as
+ *                           plsx_simpls_crossval_perm_batch: Freedman-Lane's
+ *                           arrangement (I - M) Y + Y_r[perm] collapses under M_s to
+ *                           Y_{s,p} = M_s (Y_r[perm_p]) -- the residualised Y is
+ *                           permuted and residualised again per fold.  The fits of
+ *                           one split share K_s; a solver batch is [splits of a
+ *                           group][permutations of a chunk].  Splits are processed
+ *                           in ascending order, each permutation's running sum is
+ *                           carried in the output and divided by n after the last
+ *                           split (k_cf_cvp_acc: no atomics), so a call repeats to
+ *                           the bit.  Row masks must not be bound with it (the
+ *                           caller refuses).  Outputs as
+ *                           plsx_simpls_crossval_perm_batch.
+ *                           Both fold entries: PLSX_ERR_STATE before
+ *                           plsx_simpls_set_confounds; PLSX_ERR_ARG for a null
+ *                           pointer, n < 1, m < 1, or a split on whose training
+ *                           rows Z~ is rank deficient (named in the message);
+ *                           PLSX_ERR_UNSUPPORTED, the context still usable, on the
+ *                           global route of the solver (the simpls_global option or
+ *                           S beyond the on-chip bound: K_s would be gigabytes a
+ *                           split) and when one K_s plus one fit does not fit half
+ *                           the scratch budget.
  *   plsx_simpls_split_half_batch  split-half reliability of the SIMPLS components
  *                           (BasePLS.split_half, pyls/base.py:366-397, with SIMPLS
  *                           in place of the SVD): for each of np arrangements
@@ -791,6 +855,11 @@ int plsx_simpls_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n
                                     double* d_r, double* d_r2, double* d_mse, void* stream);
 int plsx_simpls_split_half_batch(plsx_ctx* ctx, const int32_t* d_perm_idx, int np, const uint8_t* d_masks, int ns,
                                  double* d_ucorr, double* d_vcorr, void* stream);
+int plsx_simpls_set_confounds(plsx_ctx* ctx, const double* d_Z, int q, double* d_gx, double* d_gy, void* stream);
+int plsx_simpls_crossval_confound_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, double* d_r, double* d_r2,
+                                        double* d_sse, void* stream);
+int plsx_simpls_crossval_confound_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx,
+                                             int m, double* d_r, double* d_r2, double* d_mse, void* stream);
 int plsx_simpls_coef_begin(plsx_ctx* ctx, int c, void* stream);
 int plsx_simpls_coef_finish(plsx_ctx* ctx, double* d_bsum, double* d_bsq, void* stream);
 int plsx_simpls_coef_keep(plsx_ctx* ctx, double* d_A, long long capacity);
@@ -910,6 +979,11 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * k_nt_gemm launches, which class 4 counts as well), 22 k_cvp_mean (its mean over the splits),
  * 23 k_cv_final (the predictions and scores of plsx_crossval_batch / plsx_crossval_lv_batch), 24 k_cv_lv and
  * 25 k_cvp_lv (the score correlations of the latent variables of plsx_crossval_lv_batch / plsx_crossval_perm_lv_batch).
+ * 26 k_cf_resid (plsx_simpls_set_confounds: k_cf_ztilde and k_cf_chol in one bracket, the two k_cf_resid launches in
+ * another; K formed again counts under 4), and of its fold entries 27 k_cf_fold_prep (k_cf_fold_prep and k_cf_fold_F,
+ * one bracket each per group of splits; C_s = P_s K_r counts under 4), 28 k_cf_fold_K (one launch per group) and
+ * 29 k_cf_fold_Y (the fits' own Y of a solver batch, and the expansion of their masks under permutations); their fits
+ * count under 6 and 9, the reduction over the splits under 9.
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

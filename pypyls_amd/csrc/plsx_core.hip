@@ -10,7 +10,7 @@ const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
                                                  "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm",
                                                  "k_sd_cv_class", "k_sd_cv_auc", "k_weights_prod", "k_cvp_moments", "k_cvp_gram", "k_cvp_w", "k_cvp_g",
-                                                 "k_cvp_mean", "k_cv_final", "k_cv_lv", "k_cvp_lv"};
+                                                 "k_cvp_mean", "k_cv_final", "k_cv_lv", "k_cvp_lv", "k_cf_resid", "k_cf_fold_prep", "k_cf_fold_K", "k_cf_fold_Y"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).
@@ -417,7 +417,7 @@ try {
                    &ctx->Xn, &ctx->ppart, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
-                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
+                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->Zcv, &ctx->cfZ, &ctx->cfL, &ctx->cfP, &ctx->cfC, &ctx->cfF, &ctx->cfK, &ctx->cfnte, &ctx->cfstat, &ctx->cfY, &ctx->cffit, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
                    &ctx->Cv, &ctx->Cfrag, &ctx->cpart, &ctx->mbpart, &ctx->cls, &ctx->clsfreq})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
@@ -555,6 +555,7 @@ try {
     count_close(ctx->cls_series);                      // (... and the class codes of its rows with their open series)
     count_close(ctx->auc_series);
     ctx->has_cls = 0;
+    ctx->cf_q = 0;                                     // (... and the confounds of plsx_simpls_set_confounds)
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;
     HIPCHK(hipMemsetAsync(ctx->status.p, 0, 4 * sizeof(int), st));

@@ -12,6 +12,7 @@
 //   plsx_simpls_api.hip  SIMPLS regression: the solver batch (run_simpls_dual on an SdRequest), products with K (sd_times_K), one cross-validation body (cv_fit_score), the count series of PLS-DA (CountSeries)
 //   plsx_cvperm.hip      permutation null of the behavioural cross-validation in dual space: plsx_crossval_perm_batch (plsx_k_cvperm.h)
 //   plsx_weightsci.hip   percentile intervals of the PLS-C x_weights: plsx_boot_keep, plsx_boot_weights_ci
+//   plsx_confound.hip    confound regression of the SIMPLS front end: plsx_simpls_set_confounds, the fold-wise K_s and Y_s of its cross-validation (plsx_k_confound.h)
 //   plsx_comm.hip        the exported collective (RCCL through dlopen)
 #pragma once
 #include "plsx_kernels.h"
@@ -203,6 +204,11 @@ struct plsx_ctx {
     // [k][G][2] int64 appended to the caller's buffer (k_sd_cv_auc): twice the Mann-Whitney U of every class against the
     // rest, and the pairs it was counted over
     CountSeries auc_series{"AUC counts", "plsx_simpls_cv_auc_begin"};
+    // plsx_simpls_set_confounds: cf_q > 0 confounds are bound -- Z~ = [1, Z - zbar] as [16][S] (cfZ) and the Cholesky
+    // factor of Z~^T Z~ (cfL); per group of splits of the fold entries P_s, C_s, F_s [ns][q + 1][S], K_s [ns][S][S], the
+    // usable test rows [ns], the rank status [ns], the fits' own Y [fits][S][T] and, under permutations, their scores
+    int cf_q = 0;
+    Buf cfZ, cfL, cfP, cfC, cfF, cfK, cfnte, cfstat, cfY, cffit;
     bool has_okx = false, has_oky = false;
     int n_okx = 0;                                      // usable rows of X under the row masks (has_okx)
     double* mom_out_arg = nullptr;                      // set while a launch should export feature moments
@@ -310,7 +316,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_CVFINAL, KC_CVLV, KC_CVPLV, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_CVFINAL, KC_CVLV, KC_CVPLV, KC_CFRESID, KC_CFPREP, KC_CFK, KC_CFY, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -478,5 +484,11 @@ bool simpls_single_pass(const plsx_ctx* ctx);
 size_t simpls_global_lds_bytes(int T, int k);
 bool simpls_onchip_fits(int S, int T, int k);
 int simpls_form_K(plsx_ctx* ctx, hipStream_t st);
+// ---- plsx_confound.hip ----
+int cf_fold_prepare(plsx_ctx* ctx, const uint8_t* d_masks, int s0, int ns, hipStream_t st);
+int cf_fold_Y(plsx_ctx* ctx, int ngc, const int32_t* d_perm, int mb, double* Ys, hipStream_t st);
+int cf_expand_masks(plsx_ctx* ctx, const uint8_t* d_masks, int mb, int nfit, uint8_t* pmask, hipStream_t st);
+int cf_cvp_acc(plsx_ctx* ctx, const double* r, const double* r2, const double* sse, int ngc, int mb, int n, bool last,
+               double* out_r, double* out_r2, double* out_mse, hipStream_t st);
 
 }  // namespace plsxi

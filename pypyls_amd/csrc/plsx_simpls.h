@@ -1317,7 +1317,8 @@ void k_sd_cv_score(SdArgs a)
     const uint8_t* pm = a.pmask + (size_t)r * S;
     const double* Y0 = a.Y0 + (size_t)r * S * T;
     const double* ym = a.ymean + (size_t)r * T;
-    const double* Yc = a.Yc;                               // identity sources: the observed row of position p is row p
+    // identity sources: the observed row of position p is row p of the fit's own Y (y_stride = 0: of the bound Y)
+    const double* Yc = PERM ? a.Yc : a.Yc + (size_t)r * a.y_stride;
     const int* ysp = a.ys + (size_t)r * S;                 // (PERM: ... is row ys[p])
     auto yrow = [&](int p) { if constexpr (PERM) return ysp[p]; else return p; };
     double* Z = a.cvZ + (size_t)r * k * S;

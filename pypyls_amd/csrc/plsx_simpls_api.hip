@@ -55,10 +55,26 @@ int simpls_form_K(plsx_ctx* ctx, hipStream_t st)
     return nt_strips(ctx, ptr<double>(ctx->Xc), ctx->Bpad, S, ptr<double>(ctx->Xc), ctx->Bpad, S, ctx->B, K, S, st);
 }
 
-// A [rows][S] against the bound K (S x S, symmetric) into Z [rows][S], on the route of the component step
-static int sd_times_K(plsx_ctx* ctx, const double* A, int rows, double* Z, hipStream_t st)
+// A K of their own for groups of consecutive fits of a batch (the fold-wise confound regression: the fits of one split
+// share K_s): K of group g at base + g S^2, `fits` fits per group.  base = nullptr: the bound K for every fit.
+struct KGroups {
+    const double* base = nullptr;
+    int fits = 0;
+};
+
+// A [rows][S] against the bound K (S x S, symmetric) into Z [rows][S], on the route of the component step.  With kg:
+// `per_fit` rows per fit, the rows of group g against its own K -- still one (batched) launch.  On-chip route only.
+static int sd_times_K(plsx_ctx* ctx, const double* A, int rows, double* Z, hipStream_t st, const KGroups& kg = KGroups(),
+                      int per_fit = 1)
 {
     const int S = ctx->S;
+    if (kg.base) {
+        const int grows = kg.fits * per_fit;
+        // (one chunk: every entry is one block's full contraction, so a fit's bits do not depend on how the splits are
+        // grouped or the permutations chunked)
+        return run_nt(ctx, A, (long long)grows * S, S, grows, kg.base, (long long)S * S, S, S, nullptr, 0, 0, 0, S,
+                      rows / grows, Z, (long long)grows * S, S, nullptr, 0, 0, st, false, false, true);
+    }
     const double* K = ptr<double>(ctx->Kmat);
     if (simpls_global(ctx)) return nt_strips(ctx, A, S, rows, K, S, S, S, Z, S, st);
     return run_nt(ctx, A, 0, S, rows, K, 0, S, S, nullptr, 0, 0, 0, S, 1, Z, 0, S, nullptr, 0, 0, st);
@@ -83,6 +99,7 @@ struct SdRequest {
     bool weights_only = false;          // (without scatter) k_sd_step keeps the dual weights WD in the batch's state
                                         // (a.weights), nothing leaves the solver but pctvar -- k_sd_final does not run (the
                                         // permutation test of the coefficients reads the state)
+    KGroups kgroups;                    // a K of their own per group of fits (nres a multiple of kgroups.fits), or none
 };
 
 int run_simpls_dual(plsx_ctx* ctx, const SdRequest& q, hipStream_t st)
@@ -161,7 +178,7 @@ int run_simpls_dual(plsx_ctx* ctx, const SdRequest& q, hipStream_t st)
         LAUNCHCHK();
     }
     // GEMM 0: (T + 1) subject-space vectors per resample against K (symmetric)
-    if (int e = sd_times_K(ctx, a.Wt, (int)gemm_rows, a.Zt, st)) return e;
+    if (int e = sd_times_K(ctx, a.Wt, (int)gemm_rows, a.Zt, st, q.kgroups, T + 1)) return e;
     {
         KTimer tm(ctx, KC_SIMPLS, st);
         void (*post0_kernel)(SdArgs) =
@@ -192,7 +209,7 @@ int run_simpls_dual(plsx_ctx* ctx, const SdRequest& q, hipStream_t st)
         }
         // GEMM c: K beta for every resample of the batch (the last component needs none)
         if (c + 1 < k)
-            if (int e = sd_times_K(ctx, a.Wt, nres, a.Zt, st)) return e;
+            if (int e = sd_times_K(ctx, a.Wt, nres, a.Zt, st, q.kgroups)) return e;
     }
     if (scatter) {          // (permutations: pctvar is all that leaves the solver -- no y-loadings, no weights)
         a.Qs = q.align_signs ? ptr<double>(ctx->Qs) : nullptr;
@@ -514,10 +531,11 @@ struct CvScores { double* r; double* r2; double* sse; double* nte; };
 // the ms fits on their training positions (`pmask` [ms][S]; X keeps its rows, Y takes rows `ysrc` or its own), ONE
 // product with K, the scores, `after_score` in the scores' timed bracket (the reduction of the permuted entry), and the
 // counts of the series that are open, whose blocks are addressed as count_launch says.  nb: the fits cv_scratch was
-// sized for.
+// sized for.  ystack / kg: a Y ([ms][S][T]) and a K of the fits' own (the fold-wise confound regression), or the bound ones.
 template <bool PERM, class F>
 static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const uint8_t* pmask, const CvScores& out,
-                        long long blk0, long long f0, int n, hipStream_t st, F after_score)
+                        long long blk0, long long f0, int n, hipStream_t st, F after_score,
+                        const double* ystack = nullptr, const KGroups& kg = KGroups())
 {
     const int k = ctx->ncomp;
     SdArgs a;
@@ -527,10 +545,11 @@ static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const ui
     q.ysrc = ysrc; q.nres = ms; q.scatter = true;
     q.pctvar = ptr<double>(ctx->spct); q.yload = q.pctvar + (size_t)nb * k; q.cvec = ptr<double>(ctx->sc);
     q.Vd = ptr<double>(ctx->Vdq); q.pmask = pmask; q.args_out = &a;
+    q.ystack = ystack; q.kgroups = kg;
     if (int e = run_simpls_dual(ctx, q, st)) return e;
     // ONE product with K: the scores of all k nested models at every row, training and test
     a.cvZ = ptr<double>(ctx->Zcv);
-    if (int e = sd_times_K(ctx, q.Vd, ms * k, a.cvZ, st)) return e;
+    if (int e = sd_times_K(ctx, q.Vd, ms * k, a.cvZ, st, kg, k)) return e;
     a.cvr = out.r; a.cvr2 = out.r2; a.cvsse = out.sse; a.cvnte = out.nte;
     {
         KTimer tm(ctx, KC_CVSCORE, st);
@@ -716,6 +735,126 @@ try {
     }
     if (ctx->cls_series.active) ctx->cls_series.n += m;
     if (ctx->auc_series.active) ctx->auc_series.n += m;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+// What both fold entries of the confound regression check first and how they group the splits: bytes of one K_s and of
+// one fit (solver state, dense dual weights and Z = Vd . K_s, its own Y, `extra`), and as many splits per group as fit
+// half the scratch budget with one fit each.
+static int cf_fold_plan(plsx_ctx* ctx, const char* who, int n, double extra, double* k_bytes, double* fit_bytes, int* ng)
+{
+    char msg[320];
+    if (ctx->method != PLSX_REGRESSION) {
+        snprintf(msg, sizeof msg, "%s: data not bound for regression", who);
+        return fail(ctx, PLSX_ERR_STATE, msg);
+    }
+    if (!ctx->cf_q) {
+        snprintf(msg, sizeof msg, "%s: no confounds are bound (plsx_simpls_set_confounds)", who);
+        return fail(ctx, PLSX_ERR_STATE, msg);
+    }
+    if (ctx->cls_series.active || ctx->auc_series.active) {
+        snprintf(msg, sizeof msg, "%s: a series of counts is open; the fold-wise confound regression has none", who);
+        return fail(ctx, PLSX_ERR_STATE, msg);
+    }
+    const double S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    if (simpls_global(ctx)) {
+        snprintf(msg, sizeof msg, "%s: the fold-wise confound regression forms K_s (S x S) per split and runs on the "
+                 "on-chip route of the solver only; S = %d (or the simpls_global option) takes the global route, where "
+                 "K_s is %.2f GB a split", who, ctx->S, 8.0 * S * S / 1073741824.0);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    *k_bytes = 8.0 * S * S;
+    *fit_bytes = 8.0 * (double)sd_scratch_doubles(ctx->S, ctx->T, ctx->ncomp, false) + 2.0 * k * S * 8.0 + 8.0 * S * T + extra;
+    const double budget = 0.5 * ctx->scratch_gb * 1073741824.0;
+    if (*k_bytes + *fit_bytes > budget) {
+        snprintf(msg, sizeof msg, "%s: one K_s (%.3f GB) and one fit (%.3f GB) do not fit half the scratch budget of "
+                 "%.6f GB", who, *k_bytes / 1073741824.0, *fit_bytes / 1073741824.0, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    *ng = (int)std::min<double>(std::min(n, 8192), std::floor(budget / (*k_bytes + *fit_bytes)));
+    return 0;
+}
+
+int plsx_simpls_crossval_confound_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, double* d_r, double* d_r2,
+                                        double* d_sse, void* stream)
+try {
+    NEED_DATA();
+    if (!d_masks || !d_r || !d_r2 || !d_sse || n < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_crossval_confound_batch: bad arguments");
+    double kb = 0.0, fb = 0.0;
+    int ng = 0;
+    if (int e = cf_fold_plan(ctx, "plsx_simpls_crossval_confound_batch", n, 0.0, &kb, &fb, &ng)) return e;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    ng = std::min(ng, 8192);
+    if (int e = cv_scratch(ctx, ng)) return e;
+    if (int e = ensure(ctx, ctx->cfY, (size_t)ng * S * T * 8)) return e;
+    for (int s0 = 0; s0 < n; s0 += ng) {
+        // a group of splits: K_s and Y_s of each, then one fit per split on its own (K_s, Y_s)
+        const int ns = std::min(ng, n - s0);
+        const uint8_t* masks = d_masks + (size_t)s0 * S;
+        if (int e = cf_fold_prepare(ctx, masks, s0, ns, st)) return e;
+        if (int e = cf_fold_Y(ctx, ns, nullptr, 1, ptr<double>(ctx->cfY), st)) return e;
+        const CvScores out = {d_r + (size_t)s0 * k * T, d_r2 + (size_t)s0 * k * T, d_sse + (size_t)s0 * (k + 1) * T, nullptr};
+        KGroups kg;
+        kg.base = ptr<double>(ctx->cfK); kg.fits = 1;
+        if (int e = cv_fit_score<false>(ctx, ng, ns, nullptr, masks, out, 0, 0, 1, st, [] { return 0; },
+                                        ptr<double>(ctx->cfY), kg))
+            return e;
+    }
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_crossval_confound_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                                             double* d_r, double* d_r2, double* d_mse, void* stream)
+try {
+    NEED_DATA();
+    if (!d_masks || !d_perm_idx || !d_r || !d_r2 || !d_mse || n < 1 || m < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_crossval_confound_perm_batch: bad arguments");
+    const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
+    const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T;           // doubles of scores per fit
+    double kb = 0.0, fb = 0.0;
+    int ng = 0;
+    if (int e = cf_fold_plan(ctx, "plsx_simpls_crossval_confound_perm_batch", n, 8.0 * per_fit + S, &kb, &fb, &ng)) return e;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    // the splits in groups of ng, the permutations in chunks of mb: a solver batch is [splits of the group][mb], the
+    // fits of one split share its K_s.  (About 8192 fits a batch where the budget allows, as everywhere.)
+    const double budget = 0.5 * ctx->scratch_gb * 1073741824.0;
+    const int mb = (int)std::max(1.0, std::min<double>(std::min(m, std::max(1, 8192 / ng)),
+                                                       std::floor((budget - ng * kb) / (ng * fb))));
+    const int nb = ng * mb;
+    if (int e = cv_scratch(ctx, nb)) return e;
+    if (int e = ensure(ctx, ctx->cfY, (size_t)nb * S * T * 8)) return e;
+    if (int e = ensure(ctx, ctx->cffit, (size_t)nb * per_fit * 8 + (size_t)nb * S)) return e;
+    double* fr = ptr<double>(ctx->cffit);
+    const CvScores fs = {fr, fr + (size_t)nb * kT, fr + 2 * (size_t)nb * kT, nullptr};
+    uint8_t* pmask = reinterpret_cast<uint8_t*>(fr + (size_t)nb * per_fit);
+    // the running sums over the splits live in the outputs (k_cf_cvp_acc)
+    HIPCHK(hipMemsetAsync(d_r, 0, (size_t)m * kT * 8, st));
+    HIPCHK(hipMemsetAsync(d_r2, 0, (size_t)m * kT * 8, st));
+    HIPCHK(hipMemsetAsync(d_mse, 0, (size_t)m * (k + 1) * 8, st));
+    for (int s0 = 0; s0 < n; s0 += ng) {
+        const int ns = std::min(ng, n - s0);
+        if (int e = cf_fold_prepare(ctx, d_masks + (size_t)s0 * S, s0, ns, st)) return e;
+        for (int p0 = 0; p0 < m; p0 += mb) {
+            const int mp = std::min(mb, m - p0);
+            // fit f = split f / mp of the group under permutation p0 + f % mp: its training mask, its own Y (the
+            // permutation is inside it: identity sources, the identity variant of the scores)
+            if (int e = cf_expand_masks(ctx, d_masks + (size_t)s0 * S, mp, ns * mp, pmask, st)) return e;
+            if (int e = cf_fold_Y(ctx, ns, d_perm_idx + (size_t)p0 * S, mp, ptr<double>(ctx->cfY), st)) return e;
+            KGroups kg;
+            kg.base = ptr<double>(ctx->cfK); kg.fits = mp;
+            auto reduce = [&] {
+                return cf_cvp_acc(ctx, fs.r, fs.r2, fs.sse, ns, mp, n, s0 + ns == n, d_r + (size_t)p0 * kT,
+                                  d_r2 + (size_t)p0 * kT, d_mse + (size_t)p0 * (k + 1), st);
+            };
+            if (int e = cv_fit_score<false>(ctx, nb, ns * mp, nullptr, pmask, fs, 0, 0, 1, st, reduce,
+                                            ptr<double>(ctx->cfY), kg))
+                return e;
+        }
+    }
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 

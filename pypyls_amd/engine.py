@@ -98,6 +98,9 @@ def _load():
         'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_split_half_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
+        'plsx_simpls_set_confounds': ([vp, vp, i32, vp, vp, vp], i32),
+        'plsx_simpls_crossval_confound_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_simpls_crossval_confound_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_coef_begin': ([vp, i32, vp], i32),
         'plsx_simpls_coef_finish': ([vp, vp, vp, vp], i32),
         'plsx_simpls_coef_keep': ([vp, vp, ctypes.c_longlong], i32),
@@ -147,7 +150,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_set_confounds', 'plsx_simpls_crossval_confound_batch', 'plsx_simpls_crossval_confound_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
              'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
@@ -922,6 +925,52 @@ class Engine(object):
         self._check(self.lib.plsx_simpls_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
                                                              r_dev.data_ptr(), r2_dev.data_ptr(), mse_dev.data_ptr(),
                                                              self._stream()))
+
+    def simpls_set_confounds(self, Z):
+        """Z (S, q) host array, 1 <= q <= 15, finite on the usable rows: residualises the bound X and Y on [1, Z] over
+        the usable rows, in place, forms K again and keeps Z for the fold entries (plsx_simpls_set_confounds; after
+        :meth:`set_data_regression` and :meth:`simpls_set_row_masks`).  -> the slopes of X (q, B) and of Y (q, T) on
+        Z - zbar, device tensors.  PlsxError status -4 without bound regression data, -1 for q outside 1 .. 15 or rank
+        deficient confounds."""
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[0] != self.S:
+            raise ValueError('confounds must have shape ({}, q); got {}'.format(self.S, Z.shape))
+        d = self._dev(Z, np.float64)
+        gx, gy = self._empty((max(Z.shape[1], 1), self.B)), self._empty((max(Z.shape[1], 1), self.T))
+        self._check(self.lib.plsx_simpls_set_confounds(self.ctx, d.data_ptr(), int(Z.shape[1]), gx.data_ptr(),
+                                                       gy.data_ptr(), self._stream()))
+        return gx, gy
+
+    def simpls_crossval_confound_into(self, masks_dev, r_dev, r2_dev, sse_dev):
+        """:meth:`simpls_crossval_into` with the confound regression fitted on the training rows of every split and
+        applied to all its rows (plsx_simpls_crossval_confound_batch; after :meth:`simpls_set_confounds`).  PlsxError
+        status -2, the context still usable, on the global route of the solver or when one K_s and one fit do not fit
+        half the scratch budget."""
+        m = masks_dev.shape[0]
+        if tuple(masks_dev.shape) != (m, self.S) or masks_dev.dtype != _torch().uint8 or not masks_dev.is_contiguous():
+            raise ValueError('split masks must be a contiguous (m, {}) uint8 tensor'.format(self.S))
+        for t, rows in ((r_dev, self.k), (r2_dev, self.k), (sse_dev, self.k + 1)):
+            if tuple(t.shape) != (m, rows, self.T) or not t.is_contiguous():
+                raise ValueError('cross-validation outputs must be contiguous (m, k, T), (m, k, T) and (m, k + 1, T)')
+        self._check(self.lib.plsx_simpls_crossval_confound_batch(self.ctx, masks_dev.data_ptr(), m, r_dev.data_ptr(),
+                                                                 r2_dev.data_ptr(), sse_dev.data_ptr(), self._stream()))
+
+    def simpls_crossval_confound_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev, mse_dev):
+        """:meth:`simpls_crossval_perm_into` under the fold-wise confound regression: the residualised Y is permuted and
+        residualised again per fold (plsx_simpls_crossval_confound_perm_batch).  No row masks."""
+        torch = _torch()
+        n, m = masks_dev.shape[0], idx_dev.shape[0]
+        if tuple(masks_dev.shape) != (n, self.S) or masks_dev.dtype != torch.uint8 or not masks_dev.is_contiguous():
+            raise ValueError('split masks must be a contiguous (n, {}) uint8 tensor'.format(self.S))
+        if tuple(idx_dev.shape) != (m, self.S) or idx_dev.dtype != torch.int32 or not idx_dev.is_contiguous():
+            raise ValueError('permutations must be a contiguous (m, {}) int32 tensor'.format(self.S))
+        for t, shape in ((r_dev, (m, self.k, self.T)), (r2_dev, (m, self.k, self.T)), (mse_dev, (m, self.k + 1))):
+            if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('permuted cross-validation outputs must be contiguous float64 (m, k, T), (m, k, T) and '
+                                 '(m, k + 1)')
+        self._check(self.lib.plsx_simpls_crossval_confound_perm_batch(
+            self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m, r_dev.data_ptr(), r2_dev.data_ptr(),
+            mse_dev.data_ptr(), self._stream()))
 
     def simpls_split_half_into(self, perm_dev, masks_dev, uc_dev, vc_dev):
         """Split-half reliability of the SIMPLS components.  perm_dev (n, S) int32, one permutation of the rows of Y per

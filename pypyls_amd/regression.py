@@ -121,7 +121,8 @@ def _check_cvsplits(masks, usable, k, B):
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
-                   cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, n_split=0, **kwargs):
+                   cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, n_split=0, confounds=None,
+                   **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -206,7 +207,27 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     perm[p] of Y are); every half must keep at least 2 usable rows.  With one behaviour (T = 1) ``vcorr`` is NaN, as
     numpy's correlation of single values is.  The observed data's masks are drawn after everything else the call
     draws: every other array of the call keeps its bits.  Per split the device forms two S-long vectors per component
-    and multiplies them with K = Xc Xc^T: 4 S^2 k flop, nothing B-sized (plsx_simpls_split_half_batch)."""
+    and multiplies them with K = Xc Xc^T: 4 S^2 k flop, nothing B-sized (plsx_simpls_split_half_batch).
+
+    Confounds: ``confounds=Z`` (S, q) or (S,), 1 <= q <= 15 (None, the default: nothing is added, nothing is drawn
+    differently, every array keeps its bits) adjusts the analysis for nuisance variables.  A row is usable iff it is
+    usable in X and in Y and Z is not NaN throughout there (a row unusable on either side is unusable on both; a row of Z
+    that is non-finite only in part raises).  X and Y are residualised on ``[1, Z]`` over the usable rows, once, on the
+    device (plsx_simpls_set_confounds), and the observed fit, ``n_perm``, ``n_boot``, ``n_split``, ``coef_components``,
+    ``coef_ci`` and ``vip_components`` run on the residuals (X_r, Y_r): permutations permute rows of Y_r, bootstraps
+    resample residual rows -- the confound regression is NOT refitted per bootstrap, a limit of this version -- and a
+    seeded call draws what the call without the keyword draws.  The result gains ``confound_mean`` (q,) = zbar and
+    ``confound_x`` (q, B) / ``confound_y`` (q, T), the slopes of X and Y on Z - zbar; ``intercept`` stays in the units
+    of the raw data (:func:`predict` takes ``confounds=Z_new``).  With ``test_split > 0`` the confound regression is
+    fitted on the TRAINING rows of every split and applied to all its rows (cross-validated confound regression, Snoek
+    et al. 2019, NeuroImage 184: residuals taken over the whole cohort would leak the test rows into the training
+    data): ``cvres`` keeps its keys and shapes, the scores are those of the fold-residualised test Y against its
+    prediction from the fold-residualised test X (plsx_simpls_crossval_confound_batch: a rank-2 (q + 1) update of K per
+    split, nothing B-sized).  ``cv_perm=P`` permutes the residualised Y and residualises it again per fold, which is
+    what Freedman & Lane's arrangement reduces to under the fold's own regression
+    (plsx_simpls_crossval_confound_perm_batch).  Refused: Z of the wrong shape, q > 15, Z rank deficient together with
+    the intercept on the usable rows or on the training rows of a split, 3-D Y, ``coef_perm=True``, ``cv_perm`` with
+    masked rows, and ``pls_da``."""
     from .engine import Engine
     X, Y = np.asarray(X), np.asarray(Y)
     if X.ndim != 2:
@@ -330,6 +351,43 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     else:
         Y_agg = Y
         bootsamples_out = None
+    # ---- confounds: validated on the host before any engine is created or looked up
+    cf = None
+    if confounds is not None:
+        if kwargs.get('_classes') is not None:
+            raise ValueError('`confounds` is not supported by pls_da: residualised class indicators are no classes')
+        if Y.ndim == 3:
+            raise ValueError('`confounds` needs a 2-D Y: a 3-D Y is aggregated anew for every bootstrap, after which its '
+                             'residuals would have to be taken again')
+        if coef_perm:
+            raise ValueError('`confounds` cannot be combined with `coef_perm=True`: its feature scale is that of the '
+                             'raw X')
+        Zc = np.asarray(confounds)
+        if Zc.ndim == 1:
+            Zc = Zc[:, None]
+        if Zc.ndim != 2 or len(Zc) != S or Zc.shape[1] < 1 or not (np.issubdtype(Zc.dtype, np.number)
+                                                                   or Zc.dtype == bool):
+            raise ValueError('Provided `confounds` must be numeric with shape (S, q) or (S,), S = {}; got {}'
+                             .format(S, np.shape(confounds)))
+        if Zc.shape[1] > 15:
+            raise ValueError('Provided `confounds` can have at most 15 columns; got {}'.format(Zc.shape[1]))
+        Zc = Zc.astype(np.float64)
+        zok = ~np.isnan(Zc).all(axis=1)
+        usable = _usable_rows(X, Y_agg) & zok
+        if not np.isfinite(Zc[usable]).all():
+            raise ValueError('Provided `confounds` must be finite on every usable row (a row that is NaN throughout is '
+                             'masked like such a row of X or Y); row {} is not'
+                             .format(int(np.flatnonzero(usable & ~np.isfinite(Zc).all(axis=1))[0])))
+        if cv_perm > 0 and not usable.all():
+            raise ValueError('`confounds` with `cv_perm` needs complete data: {} rows of X, Y or the confounds are NaN '
+                             'throughout'.format(int((~usable).sum())))
+        zmean = Zc[usable].mean(axis=0)
+        Zt = np.c_[np.ones(S), np.where(usable[:, None], Zc - zmean, 0.0)]
+        if np.linalg.matrix_rank(Zt[usable]) < Zt.shape[1]:
+            raise ValueError('Provided `confounds` are rank deficient together with the intercept on the {} usable rows'
+                             .format(int(usable.sum())))
+        cf = dict(Z=np.where(usable[:, None], Zc, 0.0), Zt=Zt, usable=usable, zmean=zmean)
+        kwargs['confounds'] = Zc                       # (recorded in `inputs` only when given)
     kwargs.update(n_split=n_split)                 # (the reference forces 0, regression.py:238; so does test_split there)
     kwargs.setdefault('permindices', True)
     test_split = int(test_split or 0)
@@ -348,12 +406,14 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 raise ValueError('Provided `cvsamples` must have shape (S, test_split) = ({}, {}); got {}'
                                  .format(S, n_cv, cvmasks.shape))
             cvmasks = cvmasks.astype(bool)
-            _check_cvsplits(cvmasks, _usable_rows(X, Y_agg), n_components, X.shape[1])
+            _check_cvsplits(cvmasks, _usable_rows(X, Y_agg) if cf is None else cf['usable'], n_components, X.shape[1])
+            if cf is not None:
+                _check_cvrank(cf, cvmasks)
         else:
             # gen_splits keeps ceil or floor of S (1 - test_size) training rows.  Whichever side the masked (all-NaN)
             # rows fall on, every split it can draw must pass: the worst case is checked, so nothing is left to
             # check once the masks exist
-            n_bad = int((~_usable_rows(X, Y_agg)).sum())
+            n_bad = int((~(_usable_rows(X, Y_agg) if cf is None else cf['usable'])).sum())
             lo_tr = int(np.floor(S * (1 - test_size))) - n_bad
             lo_te = S - int(np.ceil(S * (1 - test_size))) - n_bad
             if kwargs.get('_classes') is not None:
@@ -462,7 +522,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             bstream = resampling.IndexStream.of_array(check_index_array(bs, S))
     cv = None
     if n_cv > 0:
-        cv = dict(n=n_cv, masks=cvmasks, classes=kwargs.get('_classes'))
+        cv = dict(n=n_cv, masks=cvmasks, classes=kwargs.get('_classes'), given=cvmasks)
         cv['auc'] = bool(kwargs.get('_auc')) and cv['classes'] is not None
         if cvmasks is None:
             # one more job at the END of the list: what a seeded call drew before, it draws still
@@ -507,7 +567,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
                 k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
                 coef_c=coef_components, coef_ci=coef_ci,
-                vip_c=vip_components, coef_perm=coef_perm, sh=sh))
+                vip_c=vip_components, coef_perm=coef_perm, sh=sh, cf=cf))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -517,7 +577,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
                                       kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci,
-                                      vip_c=vip_components, coef_perm=coef_perm, sh=sh)
+                                      vip_c=vip_components, coef_perm=coef_perm, sh=sh, cf=cf)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -532,7 +592,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
                 bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None,
-                coef_ci=False, vip_c=None, coef_perm=False, sh=None):
+                coef_ci=False, vip_c=None, coef_perm=False, sh=None, cf=None):
     import time
     import torch
     S = len(X)
@@ -561,15 +621,23 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         clean = bool(torch.isfinite(eng.colmean_dev()).all().item())
     if clean:
         okx = oky = mask = np.ones(S, dtype=bool)
-        masked = False
     else:
         Xc = X.astype(np.float64) - np.nanmean(X, axis=0, keepdims=True)
         okx, oky = _row_ok(Xc), _row_ok(Yc)
         mask = okx & oky
-        masked = not mask.all()
         eng.set_data_regression(np.nan_to_num(Xc), np.nan_to_num(Yc), k)
-        if masked:
-            eng.simpls_set_row_masks(okx, oky)
+    if cf is not None:
+        okx = oky = mask = cf['usable']                # (a row unusable on either side is unusable on both)
+    masked = not mask.all()
+    if masked:
+        eng.simpls_set_row_masks(okx, oky)
+    Y_fit = Y_agg                                      # the Y whose rows the fit saw (_fit_yloadings)
+    d_gx = d_gy = None
+    if cf is not None:
+        # X and Y residualised on [1, Z] over the usable rows, on the device, in place; K formed again.  The host
+        # arithmetic below reads Y: its residuals (S x T) are formed in numpy, nothing B-sized is
+        d_gx, d_gy = eng.simpls_set_confounds(cf['Z'])
+        Yc = Y_fit = _residualise(Y_agg.astype(np.float64), cf['Zt'], mask)
     classes = cv.get('classes') if cv is not None else None
     if classes is not None:
         # pls_da: Y is the indicator matrix of these class codes; the cross-validation below also classifies its test
@@ -612,7 +680,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             # shard: the permutations' coefficients are formed tile by tile along the solver batches, counted against the
             # observed ones and reduced to their maxima over the features (plsx_simpls_coef_perm_begin)
             eng.sync()                                  # (the x_weights are on the host)
-            coefs_obs = _model_coefs(_host_array(h_W), Yc[mask].T @ x_scores[mask], x_scores, Y_agg, mask, coef_c)
+            coefs_obs = _model_coefs(_host_array(h_W), Yc[mask].T @ x_scores[mask], x_scores, Y_fit, mask, coef_c)
             d_cobs = eng._dev(coefs_obs, np.float64)
             d_ccnt = torch.zeros((B, T), dtype=torch.int32, device=eng.device)
             d_cmax = eng._zeros((hi - lo, T))
@@ -688,6 +756,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     d_cv = d_conf = d_confp = d_auc = d_aucp = None
     if cv is not None:
         cvmasks = cv['masks']
+        if cf is not None and cv.get('given') is None:
+            _check_cvrank(cf, cvmasks)                   # (drawn splits: they exist only now)
         lo, hi = parallel.shard_bounds(cv['n'], rank, world)
         d_cv = [eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k, T)), eng._zeros((hi - lo, k + 1, T))]
         if classes is not None:
@@ -704,7 +774,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         for a in range(lo, hi, 8192):
             b = min(hi, a + 8192)
             dm = torch.from_numpy(np.ascontiguousarray(cvmasks[:, a:b].T, dtype=np.uint8)).to(eng.device)
-            eng.simpls_crossval_into(dm, *(t[a - lo:b - lo] for t in d_cv))
+            (eng.simpls_crossval_into if cf is None else eng.simpls_crossval_confound_into)(
+                dm, *(t[a - lo:b - lo] for t in d_cv))
             for done in bars:
                 done.poll()
             bars[-1].queued(b - a)
@@ -737,7 +808,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         for a in range(lo, hi, step):
             b = min(hi, a + step)
             cvp.wait(b)
-            eng.simpls_crossval_perm_into(dm_all, eng.rows_tensor(cvp.rows[a:b]), *(t[a - lo:b - lo] for t in d_cvp))
+            (eng.simpls_crossval_perm_into if cf is None else eng.simpls_crossval_confound_perm_into)(
+                dm_all, eng.rows_tensor(cvp.rows[a:b]), *(t[a - lo:b - lo] for t in d_cvp))
             for done in bars:
                 done.poll()
             bars[-1].queued(b - a)
@@ -906,10 +978,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     if coef_c is not None:
         # the model of the first coef_c components (simpls' beta, regression.py:149-151): Y ~ intercept + X @ coefs
         res['coefs'] = coefs_obs if coefs_obs is not None else \
-            _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_agg, mask, coef_c)
+            _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_fit, mask, coef_c)
         res['intercept'] = _model_means(X, Y_agg, mask, res['coefs'])
     if vip_c is not None:
-        res['vip'] = _vip_scores(res['x_weights'], _fit_yloadings(res['y_loadings'], x_scores, Y_agg, mask, vip_c), vip_c)
+        res['vip'] = _vip_scores(res['x_weights'], _fit_yloadings(res['y_loadings'], x_scores, Y_fit, mask, vip_c), vip_c)
     if bootsamp is not None:
         # add the original back, n_boot + 1 (regression.py:409-415)
         d_bsr, d_se = eng.boot_rel_dev(d_W, usum, usq, bootsamp.shape[1] + 1, add_orig=True)
@@ -932,8 +1004,28 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             res['bootres'].update(dict(vip_stderr=d_vci[0].cpu().numpy(),
                                        vip_ci=np.stack([d_vci[1].cpu().numpy(), d_vci[2].cpu().numpy()], -1)))
     res['varexp'] = pctvar                                          # regression.py:425-426
+    if cf is not None:
+        res['confound_mean'] = cf['zmean']
+        res['confound_x'], res['confound_y'] = d_gx.cpu().numpy(), d_gy.cpu().numpy()
     tick('host_finish')
     return res
+
+
+def _residualise(A, Zt, rows):
+    """A (S, n) residualised on the columns of Zt (S, q + 1: the intercept and the centred confounds) by the least
+    squares fit over ``rows`` (bool), applied to every row; rows outside ``rows`` whose Zt is zero keep A."""
+    G = np.linalg.lstsq(Zt[rows], A[rows], rcond=None)[0]
+    return A - Zt @ G
+
+
+def _check_cvrank(cf, masks):
+    """The confounds must have full column rank, together with the intercept, on the training rows of every split."""
+    Zt, usable = cf['Zt'], cf['usable']
+    for s in range(masks.shape[1]):
+        tr = masks[:, s] & usable
+        if np.linalg.matrix_rank(Zt[tr]) < Zt.shape[1]:
+            raise ValueError('Provided `confounds` are rank deficient together with the intercept on the {} training '
+                             'rows of split {}'.format(int(tr.sum()), s))
 
 
 def _feature_scale(X, okx, Xc=None):
@@ -1030,14 +1122,22 @@ def _fit_of(results, n_components, default_key, X_new=None):
             raise ValueError('`results.inputs.aggfunc` must be callable or one of {}'.format(sorted(_AGGFUNCS)))
         Y = _AGGFUNCS.get(aggfunc, aggfunc)(Y, axis=-1)
     mask = ~(np.isnan(X).all(axis=1) | np.isnan(Y).all(axis=1))
+    Z = inputs.get('confounds')
+    Y_fit = Y
+    if Z is not None:
+        # a fit with confounds saw the residuals of Y on [1, Z] over its usable rows
+        Z = np.asarray(Z, dtype=np.float64).reshape(len(X), -1)
+        mask = mask & ~np.isnan(Z).all(axis=1)
+        Zt = np.c_[np.ones(len(X)), np.where(mask[:, None], Z - Z[mask].mean(axis=0), 0.0)]
+        Y_fit = _residualise(Y, Zt, mask)
     x_scores = results.get('x_scores')
     if x_scores is None and not mask.all():
         x_scores = np.full((len(X), k), np.nan)
-        x_scores[mask] = X[mask] @ W
-    return W, Q, X, Y, mask, x_scores, c
+        x_scores[mask] = (X[mask] if Z is None else _residualise(X, Zt, mask)[mask]) @ W
+    return W, Q, X, Y, mask, x_scores, c, Y_fit
 
 
-def predict(results, X_new, n_components=None):
+def predict(results, X_new, n_components=None, confounds=None):
     """Predict Y (S_new, T) for new rows ``X_new`` (S_new, B) with the model of the first ``n_components`` SIMPLS
     components of a ``pls_regression`` result: ``intercept + X_new @ coefs`` with
     ``coefs = x_weights[:, :c] @ y_loadings[:, :c].T`` (simpls' ``beta``, pyls/types/regression.py:149-151).
@@ -1045,11 +1145,34 @@ def predict(results, X_new, n_components=None):
     Works on any ``pls_regression`` result, also one read back by ``load_results``: the means come from
     ``results.inputs`` (X, Y, ``aggfunc``), over the rows the fit used (rows that are NaN throughout are left out).
     ``n_components=None``: the ``coef_components`` the result was computed with, otherwise all components.
-    Host numpy: one thin product."""
+    Host numpy: one thin product.
+
+    A fit with ``confounds`` needs the new rows' ``confounds=Z_new`` (S_new, q) and predicts
+    ``intercept + X_new @ coefs + (Z_new - confound_mean) @ (confound_y - confound_x @ coefs)``: the model of the
+    residuals, written in the raw variables.  ValueError when a fit with confounds is given none, or a fit without
+    confounds is given some."""
     X_new = np.asarray(X_new, dtype=np.float64)
-    W, Q, X, Y, mask, x_scores, c = _fit_of(results, n_components, 'coef_components', X_new)
-    coefs = _model_coefs(W, Q, x_scores, Y, mask, c)
-    return _model_means(X, Y, mask, coefs) + X_new @ coefs
+    W, Q, X, Y, mask, x_scores, c, Y_fit = _fit_of(results, n_components, 'coef_components', X_new)
+    fitted = results['inputs'].get('confounds') is not None
+    if fitted and confounds is None:
+        raise ValueError('`results` was fitted with confounds: predict needs `confounds=Z_new` for the new rows')
+    if not fitted and confounds is not None:
+        raise ValueError('`results` was fitted without confounds: predict takes none')
+    coefs = _model_coefs(W, Q, x_scores, Y_fit, mask, c)
+    out = _model_means(X, Y, mask, coefs) + X_new @ coefs
+    if fitted:
+        zmean, gx, gy = (results.get(key) for key in ('confound_mean', 'confound_x', 'confound_y'))
+        if zmean is None or gx is None or gy is None:
+            raise ValueError('`results` was fitted with confounds but lacks confound_mean / confound_x / confound_y')
+        zmean, gx, gy = (np.asarray(a, dtype=np.float64) for a in (zmean, gx, gy))
+        Z_new = np.asarray(confounds, dtype=np.float64)
+        if Z_new.ndim == 1:
+            Z_new = Z_new[:, None]
+        if Z_new.ndim != 2 or Z_new.shape != (len(X_new), len(zmean)):
+            raise ValueError('`confounds` must have shape (S_new, q) = ({}, {}); got {}'
+                             .format(len(X_new), len(zmean), Z_new.shape))
+        out = out + (Z_new - zmean) @ (gy - gx @ coefs)
+    return out
 
 
 def vip(results, n_components=None):
@@ -1065,5 +1188,5 @@ def vip(results, n_components=None):
     fit (as for :func:`predict`).  ``n_components=None``: the ``vip_components`` the result was computed with,
     otherwise all components.  ``results.vip`` of ``pls_regression(vip_components=c)`` is this function's value.  Host
     numpy."""
-    W, Q, X, Y, mask, x_scores, c = _fit_of(results, n_components, 'vip_components')
-    return _vip_scores(W, _fit_yloadings(Q, x_scores, Y, mask, c), c)
+    W, Q, X, Y, mask, x_scores, c, Y_fit = _fit_of(results, n_components, 'vip_components')
+    return _vip_scores(W, _fit_yloadings(Q, x_scores, Y_fit, mask, c), c)
