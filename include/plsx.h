@@ -396,6 +396,56 @@ int plsx_crossval_perm_lv_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, co
                                 double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, void* stream);
 
 /*
+ * Confound regression of behavioural PLS (no reference counterpart).  Z (S, q), 1 <= q <= 15; the design is
+ * Z~ = [1, Z - zbar] (q' = q + 1 columns: one intercept and common slopes over the whole cohort, whatever the groups
+ * and conditions; the per-cell centring of PLS-C follows as always).
+ *
+ * plsx_residualize: A <- A - Z~ (Z~^T Z~)^-1 Z~^T A, in place, for the ncols columns of d_A (S rows, pitch lda) --
+ * stateless, no binding needed or touched (k_cf_ztilde, k_cf_chol, k_cf_resid: lanes over the columns, sums over the
+ * rows in ascending order, no atomics).  d_slopes (q, ld) out or NULL: the slopes on Z - zbar.  The caller
+ * residualises its device copies of X and Y BEFORE plsx_set_data, so that everything a binding derives (K, the
+ * fixed-X operands, the scale tables) is built from the residuals and every entry -- decomposition, permutations,
+ * bootstraps, split-half -- runs on (X_r, Y_r); the regression is not refitted per resample.
+ * PLSX_ERR_ARG: null pointers, S < 1, ncols < 1, lda < ncols, q outside 1 .. 15, or a Cholesky pivot of Z~^T Z~ at or
+ * below 1e-10 of its diagonal entry (rank deficiency): nothing is written.
+ *
+ * plsx_set_confounds: binds Z~ for the two fold entries below; plsx_set_data clears it.  PLSX_ERR_ARG for a binding
+ * that is not behavioural, a null d_Z, q outside 1 .. 15, rank deficiency.
+ *
+ * plsx_crossval_confound_batch: cross-validation with the confound regression fitted on the TRAINING rows of every
+ * split and applied to all its rows.  With D the training indicator of split s, P_s = (Z~^T D Z~)^-1 Z~^T D and
+ * M_s = I - Z~ P_s, the scores are those of the cross-validation on (M_s X_r, M_s Y_r); M_s M = M_s, so the bound
+ * residuals serve.  PLS-C scales every feature by its per-cell training standard deviation, so no update of an S x S
+ * kernel carries over: X_s exists, for one group of splits at a time (k_cf_fold_prep, then k_cfb_fold_X: B_s = P_s X_r
+ * with lanes over the features and up to 4 x 16 register accumulators over ascending rows, then the copies
+ * X_s = X_r - Z~ B_s by plain stores, padding columns as zeros; X_r is read twice per four splits, each copy written
+ * once).  Each split then runs the dual-space body of plsx_crossval_perm_batch on its own copy -- tables
+ * (k_cvp_moments), the scaled S x S matrix (k_cvp_gram), A from Y_s = M_s Y_r (k_cf_fold_Y), the small solver, the
+ * scores -- under the identity arrangement, which is why the identity column of the entry below repeats the split
+ * mean of this one to the bit.
+ *   d_masks (m, S) uint8, 1 = training row;  d_r, d_r2 (m, T) out;  d_lv (m, L) out or NULL: the score correlations
+ *   of the latent variables, as plsx_crossval_lv_batch defines them, on the same fold data
+ * plsx_crossval_confound_perm_batch: its permutation null, Y_{s,p} = M_s (Y_r[perm_p]) against X_s (the residualised
+ * Y is permuted and residualised again per fold); arguments and outputs as plsx_crossval_perm_lv_batch, d_lv and
+ * d_lv_pairs or both NULL.
+ * Both: every sum in a fixed order, no atomics -- the bits depend neither on the group size, the scratch budget nor on
+ * how the permutations are cut into calls.  The size model of plsx_crossval_perm_batch with 8 S Bpad more per split
+ * (the fold copy) and 8 S T more per permutation; the group shrinks down to one split, then PLSX_ERR_UNSUPPORTED with
+ * the sizes.  Refusals and error codes as the counterparts without confounds; PLSX_ERR_STATE when no confounds are
+ * bound; PLSX_ERR_ARG, naming the split by its index in the call, when Z~ is rank deficient on the training rows of
+ * a split (checked for all splits before anything else runs).  The context is left as found.
+ * plsx_crossval_confound_group: splits per group of fold copies of the last such call.
+ */
+int plsx_residualize(plsx_ctx* ctx, double* d_A, int lda, int ncols, int S, const double* d_Z, int q, double* d_slopes,
+                     int ld, void* stream);
+int plsx_set_confounds(plsx_ctx* ctx, const double* d_Z, int q, void* stream);
+int plsx_crossval_confound_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, double* d_r2, double* d_lv,
+                                 void* stream);
+int plsx_crossval_confound_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                                      double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, void* stream);
+int plsx_crossval_confound_group(plsx_ctx* ctx);
+
+/*
  * SIMPLS regression (pyls/types/regression.py:56-186, 248-373), solved per
  * resample in the S-dimensional dual space (K = X0 X0^T); k = n_components.
  *   plsx_simpls_decompose   original data: d_xwT (k, B) x_weights transposed,
@@ -984,6 +1034,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * one bracket each per group of splits; C_s = P_s K_r counts under 4), 28 k_cf_fold_K (one launch per group) and
  * 29 k_cf_fold_Y (the fits' own Y of a solver batch, and the expansion of their masks under permutations); their fits
  * count under 6 and 9, the reduction over the splits under 9.
+ * 30 k_cfb_fold_X (the fold copies X_s of plsx_crossval_confound_batch / _perm_batch: one bracket per group of splits;
+ * their P_s count under 27, their Y under 29, plsx_residualize / plsx_set_confounds under 26).
  * plsx_kernel_class_name returns the label, NULL past the last class.
  * Measurement only; no reference counterpart. */
 int plsx_kernel_timing(const plsx_ctx* ctx, int kernel_class, double* ms, int* launches);

@@ -10,7 +10,7 @@ const char* const kKernelClassNames[KC_COUNT] = {"k_xprod", "k_gram", "k_small",
                                                  "k_ucorr_partial", "k_simpls_dual", "k_build_A", "k_xprod_moments",
                                                  "k_sd_cv_score", "k_sd_coef", "k_coef_prod", "k_percentile", "k_contrast", "k_mb_rownorm",
                                                  "k_sd_cv_class", "k_sd_cv_auc", "k_weights_prod", "k_cvp_moments", "k_cvp_gram", "k_cvp_w", "k_cvp_g",
-                                                 "k_cvp_mean", "k_cv_final", "k_cv_lv", "k_cvp_lv", "k_cf_resid", "k_cf_fold_prep", "k_cf_fold_K", "k_cf_fold_Y"};
+                                                 "k_cvp_mean", "k_cv_final", "k_cv_lv", "k_cvp_lv", "k_cf_resid", "k_cf_fold_prep", "k_cf_fold_K", "k_cf_fold_Y", "k_cfb_fold_X"};
 
 // Choose resamples per group so that data + moment tiles fill MT tiles; when one
 // resample does not fit a block, cut its rows into slices (one group each).

@@ -13,6 +13,7 @@
 //   plsx_cvperm.hip      permutation null of the behavioural cross-validation in dual space: plsx_crossval_perm_batch (plsx_k_cvperm.h)
 //   plsx_weightsci.hip   percentile intervals of the PLS-C x_weights: plsx_boot_keep, plsx_boot_weights_ci
 //   plsx_confound.hip    confound regression of the SIMPLS front end: plsx_simpls_set_confounds, the fold-wise K_s and Y_s of its cross-validation (plsx_k_confound.h)
+//   plsx_confound_behav.hip  confound regression of the PLS-C front end: plsx_residualize, plsx_set_confounds, the fold copies X_s of its cross-validation (plsx_k_confound_behav.h)
 //   plsx_comm.hip        the exported collective (RCCL through dlopen)
 #pragma once
 #include "plsx_kernels.h"
@@ -207,7 +208,9 @@ struct plsx_ctx {
     // plsx_simpls_set_confounds: cf_q > 0 confounds are bound -- Z~ = [1, Z - zbar] as [16][S] (cfZ) and the Cholesky
     // factor of Z~^T Z~ (cfL); per group of splits of the fold entries P_s, C_s, F_s [ns][q + 1][S], K_s [ns][S][S], the
     // usable test rows [ns], the rank status [ns], the fits' own Y [fits][S][T] and, under permutations, their scores
-    int cf_q = 0;
+    // plsx_set_confounds (behavioural binding): the same cf_q / cfZ; the fold entries keep P_s of ALL the splits of a call
+    // in cfP and report the splits per group of fold copies of the last call (cfb_group_l)
+    int cf_q = 0, cfb_group_l = 0;
     Buf cfZ, cfL, cfP, cfC, cfF, cfK, cfnte, cfstat, cfY, cffit;
     bool has_okx = false, has_oky = false;
     int n_okx = 0;                                      // usable rows of X under the row masks (has_okx)
@@ -316,7 +319,7 @@ hipError_t set_lds(F* fn, size_t bytes)
 
 // kernel classes of plsx_kernel_timing()
 enum { KC_XPROD = 0, KC_GRAM, KC_SMALL, KC_UROT, KC_NT, KC_UCORR, KC_SIMPLS, KC_BUILD, KC_MOM, KC_CVSCORE, KC_COEF, KC_COEFPROD, KC_PCTL,
-       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_CVFINAL, KC_CVLV, KC_CVPLV, KC_CFRESID, KC_CFPREP, KC_CFK, KC_CFY, KC_COUNT };
+       KC_CONTRAST, KC_ROWNORM, KC_CVCLASS, KC_CVAUC, KC_WEIGHTSPROD, KC_CVPMOM, KC_CVPGRAM, KC_CVPW, KC_CVPG, KC_CVPMEAN, KC_CVFINAL, KC_CVLV, KC_CVPLV, KC_CFRESID, KC_CFPREP, KC_CFK, KC_CFY, KC_CFBX, KC_COUNT };
 extern const char* const kKernelClassNames[KC_COUNT];
 
 // Brackets the launches of one kernel class with two events when timing is on.
@@ -490,5 +493,15 @@ int cf_fold_Y(plsx_ctx* ctx, int ngc, const int32_t* d_perm, int mb, double* Ys,
 int cf_expand_masks(plsx_ctx* ctx, const uint8_t* d_masks, int mb, int nfit, uint8_t* pmask, hipStream_t st);
 int cf_cvp_acc(plsx_ctx* ctx, const double* r, const double* r2, const double* sse, int ngc, int mb, int n, bool last,
                double* out_r, double* out_r2, double* out_mse, hipStream_t st);
+// ---- plsx_confound_behav.hip ----
+int cfb_prepare(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, hipStream_t st);
+int cfb_fold_X(plsx_ctx* ctx, int s0, int g, double* Xf, hipStream_t st);
+int cfb_fold_Y(plsx_ctx* ctx, int s, const int32_t* d_perm, int mb, int nfit, double* Ys, hipStream_t st);
+int cfb_identity(plsx_ctx* ctx, int* idx, int n, hipStream_t st);
+// ---- plsx_cvperm.hip ----
+// both fold entries of the behavioural confound regression: d_perm_idx == nullptr (observed): the identity, m = 1, and
+// the scores of every split instead of their mean
+int cvperm_fold_entry(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
+                      double* d_r, double* d_r2, double* d_lv, double* d_lv_pairs, bool observed, void* stream);
 
 }  // namespace plsxi

@@ -214,14 +214,17 @@ static __global__ void k_cvp_reduce(const double* __restrict__ part, int nchunk,
 //   A[r][j T + t][p] = zscore(Y[perm_r[p]][t]) / (n_j - 1)   for the training positions p of cell j, 0 elsewhere,
 // mean / std (ddof = 1; covariance: centred only) over the n_j training positions of the cell in position order --
 // the arithmetic of k_build_A_behav with the mask selecting the rows and the count.
+// y_stride (here and in k_cvp_final / k_cvp_lv; 0 on every route but the fold-wise confound regression): permutation r
+// reads Y + r * y_stride, the fold's Y_{s,p} already in position order, through an identity index row.
 // grid (permutations, J), block 256, dynamic LDS 2 T doubles.
 static __global__ void k_cvp_build_A(const double* __restrict__ Y, int T, int S, const int* __restrict__ cell_start,
                                      const int* __restrict__ cell_len, const uint8_t* __restrict__ mask,
                                      const int* __restrict__ perm, int Tp, int covariance,
-                                     double* __restrict__ A, int ld)
+                                     double* __restrict__ A, int ld, long long y_stride = 0)
 {
     extern __shared__ double sm_cvp[];
     const int r = blockIdx.x, j = blockIdx.y, tid = threadIdx.x;
+    Y += (size_t)r * y_stride;                         // (y_stride != 0: every permutation reads a Y of its own)
     const int start = cell_start[j], len = cell_len[j];
     const int* ys = perm + (size_t)r * S;
     double* mean = sm_cvp;
@@ -269,9 +272,10 @@ void k_cvp_final(const double* __restrict__ W /* [m][Tp][ld] */, int ld,
                  const int* __restrict__ cell_of_pos, int S, int T, int J, int Tp, int L,
                  double* __restrict__ ybar /* scratch [m][J][T] */, double* __restrict__ zbuf /* scratch [m][S][L] */,
                  double* __restrict__ pred /* [m][S][T] */,
-                 double* __restrict__ out_r, double* __restrict__ out_r2, long long out_stride)
+                 double* __restrict__ out_r, double* __restrict__ out_r2, long long out_stride, long long y_stride = 0)
 {
     const int i = blockIdx.x, tid = threadIdx.x;
+    Y += (size_t)i * y_stride;
     const int* ys = perm + (size_t)i * S;
     double* yb = ybar + (size_t)i * J * T;
     double* zb = zbuf + (size_t)i * S * L;
@@ -338,12 +342,14 @@ void k_cvp_lv(const double* __restrict__ V /* [m][Tp][L] */, const double* __res
               const double* __restrict__ Y, const uint8_t* __restrict__ mk, const int* __restrict__ perm,
               const int* __restrict__ cell_of_pos, const int* __restrict__ cell_start, const int* __restrict__ cell_len,
               int S, int T, int J, int Tp, int L, int covariance, const double* zbuf /* [m][S][L] */,
-              double* ybuf /* scratch [m][S][L] */, double* __restrict__ out_lv, long long out_stride)
+              double* ybuf /* scratch [m][S][L] */, double* __restrict__ out_lv, long long out_stride,
+              long long y_stride = 0)
 {
     extern __shared__ double sm_cvlv[];
     double* mean = sm_cvlv;
     double* rstd = sm_cvlv + J * T;
     const int i = blockIdx.x, tid = threadIdx.x;
+    Y += (size_t)i * y_stride;
     const int* ys = perm + (size_t)i * S;
     const double* Vi = V + (size_t)i * Tp * L;
     const double* di = d + (size_t)i * L;

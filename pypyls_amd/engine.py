@@ -64,6 +64,11 @@ def _load():
         'plsx_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
         'plsx_crossval_lv_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_crossval_perm_lv_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp, vp], i32),
+        'plsx_residualize': ([vp, vp, i32, i32, i32, vp, i32, vp, i32, vp], i32),
+        'plsx_set_confounds': ([vp, vp, i32, vp], i32),
+        'plsx_crossval_confound_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_crossval_confound_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp, vp], i32),
+        'plsx_crossval_confound_group': ([vp], i32),
         'plsx_boot_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_boot_begin': ([vp, ctypes.c_longlong, vp], i32),
         'plsx_boot_finish': ([vp, vp, vp, vp], i32),
@@ -146,7 +151,7 @@ def exported_symbols():
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
              'plsx_crosscov_batch', 'plsx_scratch_read', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
-             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_crossval_lv_batch', 'plsx_crossval_perm_lv_batch', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
+             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_crossval_lv_batch', 'plsx_crossval_perm_lv_batch', 'plsx_residualize', 'plsx_set_confounds', 'plsx_crossval_confound_batch', 'plsx_crossval_confound_perm_batch', 'plsx_crossval_confound_group', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
@@ -741,6 +746,78 @@ class Engine(object):
         self.crossval_perm_into(dm, di, r, r2)
         self.sync()
         return r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy()
+
+    # -- confound regression of behavioural PLS -------------------------------
+    def residualize(self, A, Z, slopes=True):
+        """A (S, n) device tensor (contiguous) <- its residuals on [1, Z - zbar], Z (S, q) numpy or device tensor, in
+        place (plsx_residualize: stateless, before :meth:`set_data`) -> the slopes on Z - zbar (q, n) as a device
+        tensor, or None.  PlsxError (status -1) for rank deficient confounds: nothing is written."""
+        torch = _torch()
+        dZ = Z if isinstance(Z, torch.Tensor) else self._dev(np.ascontiguousarray(Z, dtype=np.float64), np.float64)
+        if A.dim() != 2 or not A.is_contiguous() or dZ.dim() != 2 or dZ.shape[0] != A.shape[0]:
+            raise ValueError('residualize takes a contiguous (S, n) tensor and confounds (S, q)')
+        S, n = A.shape
+        g = self._empty((dZ.shape[1], n)) if slopes else None
+        self._check(self.lib.plsx_residualize(self.ctx, A.data_ptr(), n, n, S, dZ.data_ptr(), int(dZ.shape[1]),
+                                              None if g is None else g.data_ptr(), n, self._stream()))
+        return g
+
+    def set_confounds(self, Z):
+        """Binds Z (S, q) for :meth:`crossval_confound` / :meth:`crossval_confound_perm_into` (plsx_set_confounds; a
+        behavioural binding, after :meth:`set_data`, which clears it)."""
+        torch = _torch()
+        dZ = Z if isinstance(Z, torch.Tensor) else self._dev(np.ascontiguousarray(Z, dtype=np.float64), np.float64)
+        if dZ.dim() != 2 or dZ.shape[0] != self.S:
+            raise ValueError('confounds must have shape ({}, q); got {}'.format(self.S, tuple(dZ.shape)))
+        self._check(self.lib.plsx_set_confounds(self.ctx, dZ.data_ptr(), int(dZ.shape[1]), self._stream()))
+
+    def crossval_confound(self, splits, lv=False):
+        """:meth:`crossval` with the confound regression fitted on the training rows of every split and applied to
+        all its rows (plsx_crossval_confound_batch; after :meth:`set_confounds`)."""
+        torch = _torch()
+        splits = np.asarray(splits)
+        if splits.ndim != 2 or splits.shape[0] != self.S:
+            raise ValueError('split masks must have shape (S, m) with S = {}'.format(self.S))
+        dm = torch.from_numpy(np.ascontiguousarray(splits.T, dtype=np.uint8)).to(self.device)
+        m = dm.shape[0]
+        r, r2 = self._empty((m, self.T)), self._empty((m, self.T))
+        c = self._empty((m, self.L)) if lv else None
+        self._check(self.lib.plsx_crossval_confound_batch(self.ctx, dm.data_ptr(), m, r.data_ptr(), r2.data_ptr(),
+                                                          None if c is None else c.data_ptr(), self._stream()))
+        self.sync()
+        out = (r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy())
+        return out + (c.cpu().numpy().T.copy(),) if lv else out
+
+    def crossval_confound_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev, lv_dev=None, lv_pairs_dev=None):
+        """:meth:`crossval_perm_into` under the fold-wise confound regression: the residualised Y is permuted and
+        residualised again per fold (plsx_crossval_confound_perm_batch)."""
+        n, m = masks_dev.shape[0], idx_dev.shape[0]
+        self._check(self.lib.plsx_crossval_confound_perm_batch(
+            self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m, r_dev.data_ptr(), r2_dev.data_ptr(),
+            None if lv_dev is None else lv_dev.data_ptr(), None if lv_pairs_dev is None else lv_pairs_dev.data_ptr(),
+            self._stream()))
+
+    def crossval_confound_perm(self, splits, perms, lv=False):
+        """:meth:`crossval_perm` (``lv``: :meth:`crossval_perm_lv` without the pairs) under the fold-wise confound
+        regression."""
+        torch = _torch()
+        splits = np.asarray(splits)
+        if splits.ndim != 2 or splits.shape[0] != self.S:
+            raise ValueError('split masks must have shape (S, n) with S = {}'.format(self.S))
+        idx = check_index_array(np.asarray(perms), self.S)
+        dm = torch.from_numpy(np.ascontiguousarray(splits.T, dtype=np.uint8)).to(self.device)
+        di = torch.from_numpy(np.ascontiguousarray(idx.T, dtype=np.int32)).to(self.device)
+        m = di.shape[0]
+        r, r2 = self._empty((m, self.T)), self._empty((m, self.T))
+        c = self._empty((m, self.L)) if lv else None
+        self.crossval_confound_perm_into(dm, di, r, r2, c)
+        self.sync()
+        out = (r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy())
+        return out + (c.cpu().numpy().T.copy(),) if lv else out
+
+    def crossval_confound_group(self):
+        """Splits per group of fold copies of the last fold-wise call (plsx_crossval_confound_group)."""
+        return int(self.lib.plsx_crossval_confound_group(self.ctx))
 
     # -- SIMPLS regression ---------------------------------------------------
     def set_data_regression(self, Xc, Yc, n_components):

@@ -131,6 +131,53 @@ def _check_weights_ci(weights_ci, method, L, n_boot, bootsamples, contrasts):
     return int(weights_ci)
 
 
+def _check_confounds(confounds, X, permindices, cvsplits=None):
+    """The checks of ``behavioral_pls(confounds=)``, on the host before any engine is created or looked up (wording of
+    ``pls_regression``) -> dict(Z (S, q) float64, Zt = [1, Z - zbar] (S, q + 1), zmean (q,))."""
+    S = len(X)
+    Zc = np.asarray(confounds)
+    if Zc.ndim == 1:
+        Zc = Zc[:, None]
+    if Zc.ndim != 2 or len(Zc) != S or Zc.shape[1] < 1 or not (np.issubdtype(Zc.dtype, np.number) or Zc.dtype == bool):
+        raise ValueError('Provided `confounds` must be numeric with shape (S, q) or (S,), S = {}; got {}'
+                         .format(S, np.shape(confounds)))
+    if Zc.shape[1] > 15:
+        raise ValueError('Provided `confounds` can have at most 15 columns; got {}'.format(Zc.shape[1]))
+    Zc = np.ascontiguousarray(Zc, dtype=np.float64)
+    if not np.isfinite(Zc).all():
+        raise ValueError('Provided `confounds` must be finite; row {} is not'
+                         .format(int(np.flatnonzero(~np.isfinite(Zc).all(axis=1))[0])))
+    if not permindices:
+        raise ValueError('`confounds` cannot be combined with `permindices=False`: pre-permuted Y matrices are not '
+                         'residualised')
+    zmean = Zc.mean(axis=0)
+    Zt = np.c_[np.ones(S), Zc - zmean]
+    if np.linalg.matrix_rank(Zt) < Zt.shape[1]:
+        raise ValueError('Provided `confounds` are rank deficient together with the intercept on the {} rows'.format(S))
+    cf = dict(Z=Zc, Zt=Zt, zmean=zmean)
+    if cvsplits is not None and np.ndim(cvsplits) == 2 and np.shape(cvsplits)[0] == S:
+        _check_cvrank(cf, np.asarray(cvsplits, dtype=bool))
+    return cf
+
+
+def _check_cvrank(cf, masks):
+    """The confounds must have full column rank, together with the intercept, on the training rows of every split."""
+    Zt = cf['Zt']
+    for s in range(masks.shape[1]):
+        tr = masks[:, s]
+        if np.linalg.matrix_rank(Zt[tr]) < Zt.shape[1]:
+            raise ValueError('Provided `confounds` are rank deficient together with the intercept on the {} training '
+                             'rows of split {}'.format(int(tr.sum()), s))
+
+
+def _refuse_confounds(kwargs, what):
+    """``confounds`` belongs to behavioral_pls (and pls_regression): refused on the host, before any engine."""
+    if kwargs.get('confounds') is not None:
+        raise ValueError('`confounds` (the confound regression) is not available for {}: residualise the data before '
+                         'the call, or use behavioral PLS'.format(what))
+    kwargs.pop('confounds', None)
+
+
 class _PLSCRun(object):
     """One analysis; the counterpart of BasePLS + subclass (pyls/base.py:232)."""
 
@@ -179,6 +226,7 @@ class _PLSCRun(object):
         # per-phase wall times; (rank, world) of a world emulated on one GPU
         self.cvperm_given = kwargs.pop('_cvpermsamples', None)     # behavioral_pls(cv_perm=): validated (S, P) or None
         self.cv_lv_m = kwargs.pop('_cv_lv_m', None)                # behavioral_pls(cv_lv=): validated LV count or None
+        self.cf = kwargs.pop('_confounds', None)                   # behavioral_pls(confounds=): validated dict or None
         self.phases = kwargs.pop('_phases', None)
         self.emulate = kwargs.pop('_emulate', None)
         self.device_ids = kwargs.pop('device_ids', None)
@@ -352,9 +400,22 @@ class _PLSCRun(object):
             phases[name] = phases.get(name, 0.0) + 1e3 * (now - t_last[0])
             t_last[0] = now
 
-        eng.set_data(X, Y, self.cells, len(inp.groups), inp.n_cond, _METHOD_CODE[self.method],
-                     mean_centering=inp.get('mean_centering') or 0,
-                     covariance=bool(inp.get('covariance')))
+        cf = self.cf
+        d_gx = d_gy = None
+        if cf is not None:
+            # confounds: this device's copies of X and Y are residualised on [1, Z - zbar] BEFORE they are bound, so
+            # that everything the binding derives is built from the residuals; the host's Y becomes Y_r as well
+            _check_finite(Y, 'Y')
+            dX, dY, dZ = eng._dev(X, np.float64), eng._dev(Y, np.float64), eng._dev(cf['Z'], np.float64)
+            d_gx, d_gy = eng.residualize(dX, dZ), eng.residualize(dY, dZ)
+            eng.set_data(dX, dY, self.cells, len(inp.groups), inp.n_cond, _METHOD_CODE[self.method],
+                         mean_centering=inp.get('mean_centering') or 0, covariance=bool(inp.get('covariance')))
+            Y = dY.cpu().numpy()
+            del dX
+        else:
+            eng.set_data(X, Y, self.cells, len(inp.groups), inp.n_cond, _METHOD_CODE[self.method],
+                         mean_centering=inp.get('mean_centering') or 0,
+                         covariance=bool(inp.get('covariance')))
         tick('h2d_and_bind')
         L = eng.L
         res = PLSResults(inputs=inp)
@@ -530,17 +591,23 @@ class _PLSCRun(object):
                 slices.append(d_keep)
                 totals.append(n_boot_tot)
         cv_splits = self.cv_splits
+        if cv_splits is not None and cf is not None:
+            # the fold-wise confound regression: drawn masks are checked as soon as they exist, then Z~ is bound
+            if inp.get('_cvsplits') is None:
+                _check_cvrank(cf, np.asarray(cv_splits, dtype=bool))
+            eng.set_confounds(dZ)
         if cv_splits is not None:
             # cross-validation (behavioral.py:219-221, 82-170): its shard rides in the same buffer
             clo, chi = parallel.shard_bounds(cv_splits.shape[1], rank, world)
             # cv_lv: the score correlations of the first lvm latent variables come out of the same pass
             # (plsx_crossval_lv_batch) and ride in the same slice, 2 T + lvm columns wide
             lvm = self.cv_lv_m or 0
+            crossval = eng.crossval if cf is None else eng.crossval_confound
             if chi > clo and lvm:
-                r, r2, lvc = eng.crossval(cv_splits[:, clo:chi], lv=True)
+                r, r2, lvc = crossval(cv_splits[:, clo:chi], lv=True)
                 local_cv = np.vstack([r, r2, lvc[:lvm]]).T                            # (m_loc, 2 T + lvm)
             elif chi > clo:
-                r, r2 = eng.crossval(cv_splits[:, clo:chi])
+                r, r2 = crossval(cv_splits[:, clo:chi])
                 local_cv = np.vstack([r, r2]).T                                       # (m_loc, 2 T)
             else:
                 local_cv = np.zeros((0, 2 * Y.shape[1] + lvm))
@@ -558,13 +625,14 @@ class _PLSCRun(object):
                 cvp.wait(qhi)
                 dmk = torch.from_numpy(np.ascontiguousarray(cv_splits.T, dtype=np.uint8)).to(eng.device)
                 nr, nr2 = eng._empty((qhi - qlo, Y.shape[1])), eng._empty((qhi - qlo, Y.shape[1]))
+                crossval_perm_into = eng.crossval_perm_into if cf is None else eng.crossval_confound_perm_into
                 if lvm:
                     # cv_lv: the split means of every permutation's score correlations (plsx_crossval_perm_lv_batch)
                     nlv = eng._empty((qhi - qlo, eng.L))
-                    eng.crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2, nlv)
+                    crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2, nlv)
                     d_null = torch.cat([nr, nr2, nlv[:, :lvm]], dim=1)
                 else:
-                    eng.crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2)
+                    crossval_perm_into(dmk, eng.rows_tensor(cvp.rows[qlo:qhi]), nr, nr2)
                     d_null = torch.cat([nr, nr2], dim=1)
                 eng.sync()
             slices.append(d_null)
@@ -712,6 +780,9 @@ class _PLSCRun(object):
 
         res['varexp'] = hostmath.varexp(sv)
         res['singvals'] = sv
+        if cf is not None:
+            res['confound_mean'] = cf['zmean']
+            res['confound_x'], res['confound_y'] = d_gx.cpu().numpy(), d_gy.cpu().numpy()
         tick('host_finish')
         self.engine_used = eng
         return res
@@ -798,7 +869,8 @@ def _refuse_cv_perm(kwargs, what):
 def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_split=0,
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
-                   contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, cv_lv=False, **kwargs):
+                   contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, cv_lv=False, confounds=None,
+                   **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
     shard the resamples over (module docstring); ``device_ids=[...]`` names them.
 
@@ -840,11 +912,31 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     splits of the observed value} + 1) / (P + 1), NaN where that observed mean is NaN.  Every other array of the
     result keeps its bits and a seeded call draws the same resampling arrays.  A single latent variable, unlike the
     prediction, is only as stable as the gap around its singular value.  Not available with ``contrasts``
-    (ValueError)."""
+    (ValueError).
+
+    Confounds: ``confounds=Z`` (S, q) or (S,), 1 <= q <= 15 (None, the default: nothing is added, nothing is drawn
+    differently, every array keeps its bits).  X and Y are residualised on ``[1, Z - zbar]`` -- one intercept and common
+    slopes over the whole cohort, whatever the groups and conditions; the per-cell centring follows as always -- once,
+    on the device, before the data set is bound (plsx_residualize).  The observed decomposition, ``n_perm``, ``n_boot``,
+    ``n_split``, ``weights_ci`` and ``contrasts`` run on the residuals: permutations permute rows of the residualised
+    Y, bootstraps resample residual rows -- the confound regression is NOT refitted per bootstrap, a limit of this
+    version -- and a seeded call draws what the call without the keyword draws.  The result gains ``confound_mean``
+    (q,) = zbar and ``confound_x`` (q, B) / ``confound_y`` (q, T), the slopes of X and Y on Z - zbar; every other array
+    speaks of the residuals.  With ``test_split`` > 0 the confound regression is fitted on the TRAINING rows of every
+    split and applied to all its rows (cross-validated confound regression: whole-cohort residuals leak the test rows
+    into the training data): ``cvres.pearson_r`` / ``r_squared`` and ``cv_lv`` are scored on that fold's data
+    (plsx_crossval_confound_batch: one fold copy of X per split, a group of splits at a time), and ``cv_perm`` permutes
+    the residualised Y and residualises it again per fold (plsx_crossval_confound_perm_batch).  Refused (ValueError):
+    Z of the wrong shape, q > 15, non-finite Z, Z rank deficient together with the intercept on all rows or on the
+    training rows of a split, ``permindices=False`` (pre-permuted Y matrices are not residualised)."""
     if contrasts is not None:
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
+    if confounds is not None:
+        cf = _check_confounds(confounds, np.asarray(X), kwargs.get('permindices', True), kwargs.get('_cvsplits'))
+        kwargs['confounds'] = cf['Z']              # (recorded in `inputs` only when given)
+        kwargs['_confounds'] = cf
     cvperm = _check_cv_perm(cv_perm, cvpermsamples, np.asarray(X), test_split, test_size, contrasts)
     if cvperm is not False:
         kwargs['cv_perm'] = int(cv_perm)           # (recorded in `inputs` only when asked for)
@@ -903,6 +995,7 @@ def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000,
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
     _refuse_cv_perm(kwargs, 'mean-centred PLS')
+    _refuse_confounds(kwargs, 'mean-centred PLS')
     _refuse_cv_lv(kwargs, 'mean-centred PLS')
     X = np.asarray(X)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
@@ -969,6 +1062,7 @@ def multiblock_pls(X, Y, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000
     ``permindices=False``, a behaviour block on a subset of the conditions; one group with one condition (the task
     block is identically zero).  ``mean_centering`` is reset with a warning as in :func:`meancentered_pls`."""
     _refuse_cv_perm(kwargs, 'multiblock PLS')
+    _refuse_confounds(kwargs, 'multiblock PLS')
     _refuse_cv_lv(kwargs, 'multiblock PLS')
     X, Y = np.asarray(X), np.asarray(Y)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)

@@ -98,7 +98,7 @@ class PLSInputs(KeyedRecord):
         'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         'weights_ci',                       # behavioral_pls / meancentered_pls: percentile intervals of the x_weights (only when given)
-        'confounds',                        # pls_regression: the nuisance variables Z (S, q) (only when given)
+        'confounds',                        # pls_regression / behavioral_pls: the nuisance variables Z (S, q) (only when given)
         'cv_lv',                            # behavioral_pls: out-of-sample score correlation of the latent variables (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
@@ -189,7 +189,7 @@ class PLSResults(KeyedRecord):
                'coefs', 'intercept',
                # pls_regression(vip_components=c): (B,) variable importance in projection of the c-component model
                'vip',
-               # pls_regression(confounds=Z): zbar (q,) over the rows of the fit and the slopes of X (q, B) and of Y
+               # pls_regression / behavioral_pls(confounds=Z): zbar (q,) over the rows of the fit and the slopes of X (q, B) and of Y
                # (q, T) on Z - zbar; every other array of the result speaks of the residuals
                'confound_mean', 'confound_x', 'confound_y',
                # pls_da: (G,) the sorted distinct labels; column g of Y is the indicator of classes[g]
