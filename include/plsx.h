@@ -794,6 +794,64 @@ int plsx_crossval_confound_group(plsx_ctx* ctx);
  *                           PLSX_ERR_ARG for c outside 1 .. k, a null pointer or
  *                           capacity < 1; PLSX_ERR_STATE without bound regression
  *                           data or before plsx_simpls_set_original.
+ *   plsx_simpls_vip_perm_test / plsx_simpls_vip_perm_begin / plsx_simpls_vip_perm_end
+ *                           permutation test of the VIP scores of the c-component
+ *                           model: per feature the number of permutations whose
+ *                           score is at least the observed one (one-sided: VIP is
+ *                           non-negative and large means important), and per
+ *                           permutation the maximum of its scores over the features
+ *                           (the null of the single-step maxT statistic; VIP is
+ *                           comparable across features, no scale enters).  No score
+ *                           is ever stored.
+ *                           _test is stateless: for ANY stack d_G [n][c][S] (the
+ *                           layout of plsx_simpls_vip_keep) and the bound, centred
+ *                           features, with v_b[f] = sqrt(B sum_a (sum_s Xc[s][f]
+ *                           G[b][a][s])^2) -- the bits k_vip_prod writes for the
+ *                           same stack row --: d_count (B,) int32 += #{b < n :
+ *                           v_b[f] >= d_obs[f]}, d_max (n,) = max_f v_b[f].  A
+ *                           permutation whose rows are NaN (a degenerate fit: the
+ *                           formula's 0 / 0) counts nowhere and leaves its maximum
+ *                           at 0, below every real fit's (sum_f v^2 = B, so
+ *                           max_f v >= 1); a NaN in d_obs counts nowhere.  Kernel
+ *                           k_vip_perm_prod has k_vip_prod's tiling and loop (fp64
+ *                           MFMA, M = 128 features, N = 64 permutations,
+ *                           K = subjects, each component's finished contraction
+ *                           squared into a second register tile); a block walks a
+ *                           run of consecutive tiles of its 128 features -- runs
+ *                           sized so that a chunk launches about 8192 blocks: a
+ *                           block per whole piece would leave ceil(B / 128) blocks,
+ *                           5 at B = 600 --, counts in registers, stores its counts
+ *                           per (run, feature) and the per-tile maxima of its 128
+ *                           features; k_vip_perm_count adds the runs of a feature,
+ *                           k_coef_perm_max (T = 1) reduces the maxima over the
+ *                           feature blocks.  The stack goes in pieces of at most 16384
+ *                           permutations, the features in chunks of whole
+ *                           128-feature blocks whose partial maxima (8 n bytes per
+ *                           block) fit 2 GB and, next to the stack, the scratch
+ *                           budget and free device memory.  Integer counts, maxima,
+ *                           one owner per feature, no atomics: the same bits run to
+ *                           run and whatever the chunking.  PLSX_ERR_ARG for a null
+ *                           pointer, n < 1 or c outside 1 .. k, PLSX_ERR_STATE
+ *                           without bound regression data, PLSX_ERR_UNSUPPORTED
+ *                           (context still usable, sizes in the message) when not
+ *                           even one block of 64 permutations fits.
+ *                           _begin (after plsx_simpls_set_original) opens a series
+ *                           that rides along plsx_simpls_perm_batch, next to an
+ *                           open coefficient series or without one: every solver
+ *                           batch runs with the dual weights on (d_out keeps its
+ *                           bits), k_sd_vip writes the scaled dual weights of its
+ *                           permutations into scratch (c S doubles each, counted in
+ *                           the batch's share of the scratch budget), the test
+ *                           above runs on that piece against d_obs, adds to d_count
+ *                           and appends the maxima to d_max (capacity,) in
+ *                           submission order.  A batch that would pass `capacity`
+ *                           returns PLSX_ERR_ARG before it computes anything.
+ *                           _end, plsx_set_data, plsx_simpls_set_original and a
+ *                           second _begin end the series (the buffers stay the
+ *                           caller's).  _begin: PLSX_ERR_ARG for c outside 1 .. k,
+ *                           a null pointer or capacity < 1; PLSX_ERR_STATE without
+ *                           bound regression data or before
+ *                           plsx_simpls_set_original.
  *   plsx_simpls_set_classes / plsx_simpls_cv_class_begin / plsx_simpls_cv_class_end
  *                           PLS discriminant analysis: the bound Y is the indicator
  *                           matrix of G = T classes minus its column means over all
@@ -928,6 +986,11 @@ int plsx_simpls_cv_auc_end(plsx_ctx* ctx);
 int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity);
 int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
                        double* d_sd, double* d_lo, double* d_hi, void* stream);
+int plsx_simpls_vip_perm_test(plsx_ctx* ctx, const double* d_G, long long n, int c, const double* d_obs,
+                              int32_t* d_count, double* d_max, void* stream);
+int plsx_simpls_vip_perm_begin(plsx_ctx* ctx, int c, const double* d_obs, int32_t* d_count, double* d_max,
+                               long long capacity);
+int plsx_simpls_vip_perm_end(plsx_ctx* ctx);
 
 /* Bootstrap ratios -- compute.boot_rel (pyls/compute.py:212-237), elementwise
  * on (B, L) arrays: se = sqrt(|usq - usum^2/n| / (n-1)), bsr = orig / se.
@@ -1015,7 +1078,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * reduction over the splits of plsx_simpls_crossval_perm_batch, and k_row_sum / k_sd_sh_prep / k_sd_sh_expand /
  * k_sd_sh_score of plsx_simpls_split_half_batch), ..., 11 k_coef_prod (the feature pass of
  * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
- * k_col_sd of plsx_simpls_coef_perm_test count here too, k_sd_vip under 10 with
+ * k_col_sd of plsx_simpls_coef_perm_test and k_vip_perm_prod / k_vip_perm_count / k_coef_perm_max of plsx_simpls_vip_perm_test count
+ * here too, k_sd_vip under 10 with
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci),
  * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill),
  * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale),

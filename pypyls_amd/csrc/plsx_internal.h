@@ -195,6 +195,16 @@ struct plsx_ctx {
     double* cperm_max = nullptr;
     long long cperm_cap = 0, cperm_n = 0;
     Buf cpA, cppart, colsd;
+    // plsx_simpls_vip_perm_begin: a permutation series of the VIP scores rides along plsx_simpls_perm_batch, open or not
+    // whatever the coefficient series is -- the caller's observed scores (B,), counts (B,) and maxima [vperm_n] (appended),
+    // the batch's scaled dual weights dense [m][vperm_c][S] (vpG, k_sd_vip), the counts of every run of permutation
+    // tiles [runs][Bpad] int32 (vpcnt); the partial maxima share cppart
+    int vperm_active = 0, vperm_c = 0;
+    const double* vperm_obs = nullptr;
+    int* vperm_count = nullptr;
+    double* vperm_max = nullptr;
+    long long vperm_cap = 0, vperm_n = 0;
+    Buf vpG, vpcnt;
     // plsx_simpls_set_classes: one class code per row of the bound regression data (the context's own copy), G = T
     // classes; plsx_simpls_cv_class_begin: a series of confusion counts rides along plsx_simpls_crossval_batch /
     // plsx_simpls_crossval_perm_batch -- blocks [k][G][G] int32 appended to the caller's buffer (k_sd_cv_class)
@@ -426,6 +436,14 @@ inline void cperm_close(plsx_ctx* ctx)
     ctx->cperm_active = 0; ctx->cperm_c = 0; ctx->cperm_std = 0;
     ctx->cperm_obs = nullptr; ctx->cperm_count = nullptr; ctx->cperm_max = nullptr;
     ctx->cperm_cap = 0; ctx->cperm_n = 0;
+}
+// an open permutation series of the VIP scores ends (plsx_set_data, plsx_simpls_set_original, a second
+// plsx_simpls_vip_perm_begin, plsx_simpls_vip_perm_end); the buffers stay the caller's
+inline void vperm_close(plsx_ctx* ctx)
+{
+    ctx->vperm_active = 0; ctx->vperm_c = 0;
+    ctx->vperm_obs = nullptr; ctx->vperm_count = nullptr; ctx->vperm_max = nullptr;
+    ctx->vperm_cap = 0; ctx->vperm_n = 0;
 }
 // ---- plsx_xprod.hip ----
 int launch_xprod(plsx_ctx* ctx, int groups, hipStream_t st);

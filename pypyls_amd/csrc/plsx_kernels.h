@@ -38,11 +38,11 @@
 //   plsx_k_urot.h      the rotation kernel k_urot
 //   plsx_k_misc.h      small helpers, dual-space products of one wave (k_dual_gp), the quadratic-form route of the bootstrap sums, sign flip / scaling / transposition kernels
 //   plsx_k_finish.h    split-half projections and finishing (k_ucorr_partial, k_split_final), cross-validation, percentile intervals
-//   plsx_k_coefci.h    percentile intervals of the SIMPLS model coefficients: the feature pass k_coef_prod, and the tile contraction (cp_fetch / cp_store / cp_mma / cp_contract / cp_feature) it shares with k_coef_perm_prod and k_vip_prod
+//   plsx_k_coefci.h    percentile intervals of the SIMPLS model coefficients: the feature pass k_coef_prod, and the tile contraction (cp_fetch / cp_store / cp_mma / cp_contract / cp_feature) it shares with k_coef_perm_prod, k_vip_prod and k_vip_perm_prod
 //   plsx_k_coefperm.h  permutation test of the SIMPLS model coefficients: the feature pass k_coef_perm_prod (counts and maxima, no product stored), k_coef_perm_max, the feature scale k_col_sd
 //   plsx_k_contrast.h  non-rotated PLS (plsx_set_contrasts): k_contrast_norms (|| R_r^T v_l || in one pass over R_r), k_contrast_quad (the same from G_p), k_contrast_fill (V as every resample's rotation operand)
 //   plsx_k_multiblock.h  multiblock PLS (PLSX_MULTIBLOCK): the row normalisation of the stacked cross-covariance matrix (k_mb_rownorm, k_mb_rowscale)
-//   plsx_k_vip.h       VIP scores of the SIMPLS bootstraps: the feature pass k_vip_prod, the moments of its series (k_vip_moments)
+//   plsx_k_vip.h       VIP scores of the SIMPLS resamples: the feature pass of the bootstraps k_vip_prod, the moments of its series (k_vip_moments); the feature pass of the permutation test k_vip_perm_prod (counts and maxima, no score stored; its counts are added by k_vip_perm_count, its maxima reduced by k_coef_perm_max)
 //   plsx_k_weightsci.h percentile intervals of the PLS-C x_weights: the kept rotation operands (k_keep_M), the dual weights rebuilt from them (k_weights_W), the scale table of the correlation mode (k_weights_scale), the feature pass k_weights_prod
 //   plsx_k_cvperm.h    (included by plsx_cvperm.hip alone, not from here) permutation null of the behavioural cross-validation in dual space: k_cvp_moments, the scaled Gram product k_cvp_gram + k_cvp_reduce, k_cvp_build_A, k_cvp_final, the score correlations of the latent variables k_cvp_lv (its stages shared with k_cv_lv: plsx_k_finish.h)
 #pragma once

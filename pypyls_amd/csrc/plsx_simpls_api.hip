@@ -348,25 +348,30 @@ static int coef_accumulate(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 }
 
 
-// The VIP stack's share of a solver batch (plsx_simpls_vip_keep): k_sd_vip writes the c scaled dual-weight rows of each
-// of the batch's `ms` bootstraps where they stay, in the caller's buffer.  `a`: the state run_simpls_dual just left
-// (args_out).  Nothing else reads or writes what it touches, so everything else a call computes keeps its bits.
+// k_sd_vip on the state `a` run_simpls_dual just left (args_out) for a batch of `ms` resamples: the cc scaled dual-weight
+// rows of each, dense into G [ms][cc][S].  Nothing else reads or writes what it touches.
+static int sd_vip_launch(plsx_ctx* ctx, SdArgs a, int cc, int ms, double* G, hipStream_t st)
+{
+    const bool gl = simpls_global(ctx);
+    size_t lds;
+    const int wpb = sd_waves(gl ? 0 : (size_t)ctx->S * 8, &lds);
+    a.vpG = G; a.vp_c = cc;
+    KTimer tm(ctx, KC_COEF, st);
+    void (*vip_kernel)(SdArgs) = gl ? k_sd_vip<true> : k_sd_vip<false>;
+    HIPCHK(set_lds(vip_kernel, lds));
+    hipLaunchKernelGGL(vip_kernel, dim3(ceil_div(ms, wpb)), dim3(wpb * 64), lds, st, a);
+    LAUNCHCHK();
+    return 0;
+}
+
+// The VIP stack's share of a solver batch (plsx_simpls_vip_keep): the rows of the batch's `ms` bootstraps go where they
+// stay, in the caller's buffer, so everything else a call computes keeps its bits.
 static int vip_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
 {
     const int S = ctx->S, cc = ctx->vip_c;
-    const bool gl = simpls_global(ctx);
     if (ctx->vip_n + ms > ctx->vip_cap)
         return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_boot_batch: the kept VIP stack is full");
-    size_t lds;
-    const int wpb = sd_waves(gl ? 0 : (size_t)S * 8, &lds);
-    a.vpG = ctx->vipG + (size_t)ctx->vip_n * cc * S; a.vp_c = cc;
-    {
-        KTimer tm(ctx, KC_COEF, st);
-        void (*vip_kernel)(SdArgs) = gl ? k_sd_vip<true> : k_sd_vip<false>;
-        HIPCHK(set_lds(vip_kernel, lds));
-        hipLaunchKernelGGL(vip_kernel, dim3(ceil_div(ms, wpb)), dim3(wpb * 64), lds, st, a);
-        LAUNCHCHK();
-    }
+    if (int e = sd_vip_launch(ctx, a, cc, ms, ctx->vipG + (size_t)ctx->vip_n * cc * S, st)) return e;
     ctx->vip_n += ms;
     return 0;
 }
@@ -443,6 +448,79 @@ static int coef_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
                               "plsx_simpls_perm_batch", st))
         return e;
     ctx->cperm_n += ms;
+    return 0;
+}
+
+// The permutation statistics of a stack G [n][c][S] against the observed VIP scores `obs` (plsx_simpls_vip_perm_test and
+// the open series of plsx_simpls_vip_perm_begin): count (B,) += exceedances, dmax (n,) = maxima over the features.
+// coef_perm_run's rule with one row per permutation: the stack goes in pieces of at most 16384 permutations, the
+// features of a piece in chunks of whole 128-feature blocks whose partial maxima, 8 n bytes per block, fit `room` bytes
+// and 2 GB.  The permutation tiles of a piece go in runs of tpb tiles, one block per (feature block, run), tpb the
+// largest for which a chunk still launches VIP_PERM_BLOCKS blocks -- sixteen rounds of the chip's two blocks per CU, so
+// that the last, partial round costs a few percent -- and every run leaves its counts in a row of vpcnt.  Counts are
+// integers and a maximum has no order: the result depends on none of this.
+static const int VIP_PERM_BLOCKS = 8192;
+static int vip_perm_run(plsx_ctx* ctx, const double* G, long long n, int c, const double* obs, int* count, double* dmax,
+                        double room, const char* who, hipStream_t st)
+{
+    const int S = ctx->S, B = ctx->B;
+    room = std::min(room, 2147483648.0);
+    long long piece = std::min<long long>(n, 16384);
+    if (room < 8.0 * (double)piece) piece = (long long)(room / 8.0) / 64 * 64;
+    if (piece < 1) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "%s: the partial maxima of one 128-feature block and 64 permutations (512 bytes) do "
+                 "not fit next to the stack of n = %lld permutations (8 n c S = %.6f GB for c = %d, S = %d): the scratch "
+                 "budget is %.6f GB", who, n, 8.0 * (double)n * c * S / 1073741824.0, c, S, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    const int nfb_all = ceil_div(B, 128);
+    const int nfb = (int)std::max<long long>(1, std::min<long long>(nfb_all, (long long)(room / (8.0 * (double)piece))));
+    if (int e = ensure(ctx, ctx->cppart, (size_t)nfb * (size_t)piece * 8)) return e;
+    const int tiles = (int)((piece + 63) / 64);
+    const int tpb = std::max(1, tiles / std::max(1, ceil_div(VIP_PERM_BLOCKS, std::min(nfb, nfb_all))));
+    if (int e = ensure(ctx, ctx->vpcnt, (size_t)ceil_div(tiles, tpb) * ctx->Bpad * sizeof(int))) return e;
+    VipPermArgs a;
+    a.Xc = ptr<double>(ctx->Xc); a.ldx = ctx->Bpad;
+    a.S = S; a.c = c; a.B = B;
+    a.obs = obs; a.pmax = ptr<double>(ctx->cppart);
+    a.tpb = tpb; a.pcount = ptr<int>(ctx->vpcnt);
+    for (long long p0 = 0; p0 < n; p0 += piece) {
+        a.n = (int)std::min<long long>(piece, n - p0);
+        a.G = G + (size_t)p0 * c * S;
+        const int runs = ceil_div(ceil_div(a.n, 64), tpb);
+        for (int fb0 = 0; fb0 < nfb_all; fb0 += nfb) {
+            const int nb = std::min(nfb, nfb_all - fb0);
+            a.f0 = fb0 * 128; a.fc = std::min(nb * 128, B - a.f0);
+            KTimer tm(ctx, KC_COEFPROD, st);
+            hipLaunchKernelGGL(k_vip_perm_prod, dim3(nb, runs), dim3(256), 0, st, a);
+            LAUNCHCHK();
+            hipLaunchKernelGGL(k_vip_perm_count, dim3(ceil_div(a.fc, 256)), dim3(256), 0, st, a.pcount, a.ldx, runs, a.f0,
+                               a.f0 + a.fc, count);
+            LAUNCHCHK();
+            hipLaunchKernelGGL(k_coef_perm_max, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st,
+                               a.pmax, nb, 1, a.n, fb0 == 0 ? 1 : 0, dmax + (size_t)p0);
+            LAUNCHCHK();
+        }
+    }
+    return 0;
+}
+
+// The open VIP series' share of a solver batch (plsx_simpls_vip_perm_begin): k_sd_vip writes the scaled dual weights of
+// the batch's `ms` permutations dense into scratch, the test above runs on that piece and appends its maxima.  `a`: the
+// state run_simpls_dual just left (args_out; weights on).
+static int vip_perm_append(plsx_ctx* ctx, SdArgs a, int ms, hipStream_t st)
+{
+    const int S = ctx->S, cc = ctx->vperm_c;
+    if (int e = ensure(ctx, ctx->vpG, (size_t)ms * cc * S * 8)) return e;
+    if (int e = sd_vip_launch(ctx, a, cc, ms, ptr<double>(ctx->vpG), st)) return e;
+    double have;
+    if (int e = free_bytes(ctx, ctx->cppart, &have)) return e;
+    const double room = std::min(0.25 * ctx->scratch_gb * 1073741824.0, have);
+    if (int e = vip_perm_run(ctx, ptr<double>(ctx->vpG), ms, cc, ctx->vperm_obs, ctx->vperm_count,
+                             ctx->vperm_max + (size_t)ctx->vperm_n, room, "plsx_simpls_perm_batch", st))
+        return e;
+    ctx->vperm_n += ms;
     return 0;
 }
 
@@ -605,6 +683,7 @@ try {
     coef_close(ctx);
     vip_close(ctx);
     cperm_close(ctx);
+    vperm_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -615,19 +694,27 @@ try {
     if (!d_perm_idx || !d_out || n < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_perm_batch: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
-    // (an open permutation series of the coefficients that cannot take the call: refused before anything is computed)
-    const bool series = ctx->cperm_active != 0;
+    // (an open permutation series that cannot take the call: refused before anything is computed)
+    const bool series = ctx->cperm_active != 0, vseries = ctx->vperm_active != 0;
     if (series && ctx->cperm_n + n > ctx->cperm_cap) {
         char msg[200];
         snprintf(msg, sizeof msg, "plsx_simpls_perm_batch: the open coefficient series holds %lld of %lld permutations, "
                  "%d more do not fit (plsx_simpls_coef_perm_begin)", ctx->cperm_n, ctx->cperm_cap, n);
         return fail(ctx, PLSX_ERR_ARG, msg);
     }
+    if (vseries && ctx->vperm_n + n > ctx->vperm_cap) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "plsx_simpls_perm_batch: the open VIP series holds %lld of %lld permutations, "
+                 "%d more do not fit (plsx_simpls_vip_perm_begin)", ctx->vperm_n, ctx->vperm_cap, n);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
     // solver batches are as large as the call: a launch of the component step lasts as long as one
     // wave's latency chain whatever the batch (one wave per resample, up to 8 per SIMD)
     // (8192, or fewer where the solver state of 8192 resamples would exceed half the scratch budget: sd_batch; an open
-    // series adds a permutation's A_p, T S doubles, and its y-loadings to that state)
-    const int nb = sd_batch(ctx, 8192, 1, series ? 8.0 * ctx->T * ((double)ctx->S + ctx->cperm_c) : 0.0);
+    // coefficient series adds a permutation's A_p, T S doubles, and its y-loadings to that state, an open VIP series its
+    // scaled dual weights, c S doubles)
+    const int nb = sd_batch(ctx, 8192, 1, (series ? 8.0 * ctx->T * ((double)ctx->S + ctx->cperm_c) : 0.0) +
+                                              (vseries ? 8.0 * ctx->vperm_c * (double)ctx->S : 0.0));
     if (int e = ensure(ctx, ctx->spct, (size_t)nb * ctx->T * ctx->ncomp * 8)) return e;
     if (int e = ensure(ctx, ctx->sc, (size_t)nb * ctx->T * ctx->ncomp * 8)) return e;
     for (int off = 0; off < n; off += nb) {
@@ -637,10 +724,12 @@ try {
         SdRequest q;
         q.ysrc = d_perm_idx + (size_t)off * ctx->S; q.nres = m;
         q.pctvar = d_out + (size_t)off * ctx->ncomp; q.yload = ptr<double>(ctx->spct); q.cvec = ptr<double>(ctx->sc);
-        q.args_out = series ? &sda : nullptr; q.weights_only = series;
+        q.args_out = (series || vseries) ? &sda : nullptr; q.weights_only = series || vseries;
         if (int e = run_simpls_dual(ctx, q, st)) return e;
         if (series)
             if (int e = coef_perm_append(ctx, sda, m, st)) return e;
+        if (vseries)
+            if (int e = vip_perm_append(ctx, sda, m, st)) return e;
     }
     return PLSX_OK;
 } PLSX_CATCH(ctx)
@@ -1114,6 +1203,59 @@ int plsx_simpls_coef_perm_end(plsx_ctx* ctx)
 try {
     if (!ctx) return PLSX_ERR_ARG;
     cperm_close(ctx);
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_vip_perm_test(plsx_ctx* ctx, const double* d_G, long long n, int c, const double* d_obs,
+                              int32_t* d_count, double* d_max, void* stream)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_vip_perm_test: data not bound for regression");
+    if (!d_G || !d_obs || !d_count || !d_max || n < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_vip_perm_test: null pointer or n < 1");
+    if (c < 1 || c > ctx->ncomp) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "plsx_simpls_vip_perm_test: c = %d outside 1 .. n_components = %d", c, ctx->ncomp);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    // the partial maxima stay next to the caller's stack inside the scratch budget and in free device memory (what an
+    // earlier pass left allocated counts as free)
+    double have;
+    if (int e = free_bytes(ctx, ctx->cppart, &have)) return e;
+    const double stack = 8.0 * (double)n * c * ctx->S;
+    const double room = std::min(ctx->scratch_gb * 1073741824.0 - stack, have);
+    return vip_perm_run(ctx, d_G, n, c, d_obs, d_count, d_max, room, "plsx_simpls_vip_perm_test", st);
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_vip_perm_begin(plsx_ctx* ctx, int c, const double* d_obs, int32_t* d_count, double* d_max,
+                               long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_vip_perm_begin: data not bound for regression");
+    if (!ctx->has_orig)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_vip_perm_begin: plsx_simpls_set_original has not been called");
+    vperm_close(ctx);
+    if (c < 1 || c > ctx->ncomp) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "plsx_simpls_vip_perm_begin: c = %d outside 1 .. n_components = %d", c, ctx->ncomp);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (!d_obs || !d_count || !d_max || capacity < 1)
+        return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_vip_perm_begin: null pointer or capacity < 1");
+    ctx->vperm_c = c; ctx->vperm_obs = d_obs;
+    ctx->vperm_count = d_count; ctx->vperm_max = d_max; ctx->vperm_cap = capacity; ctx->vperm_n = 0;
+    ctx->vperm_active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_vip_perm_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    vperm_close(ctx);
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 

@@ -146,14 +146,17 @@ def _label(classes, g):
 
 def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamples=None, bootsamples=None, seed=None,
            verbose=True, n_proc=None, test_split=0, test_size=0.25, cvsamples=None, cv_perm=0, cvpermsamples=None,
-           coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, auc=False, **kwargs):
+           coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, auc=False, vip_perm=False,
+           **kwargs):
     """PLS discriminant analysis of the labels ``y`` (S,) on ``X`` (S, B).
 
     ``classes = np.unique(y)`` (integers, strings, booleans: anything numpy sorts), ``codes`` the position of every
     label in it, G = len(classes), 2 <= G <= 32.  The model is ``pls_regression(X, Y)`` with ``Y = one_hot(codes)``,
     (S, G) float64: every keyword above means what it means there and goes to the same code path, and every key that
     call returns is returned unchanged -- for the same ``cvsamples`` / ``cvpermsamples`` bit for bit.  ``vip_components``
-    gives the usual feature-importance score of PLS-DA, ``coef_components`` the model :func:`predict_class` applies.
+    gives the usual feature-importance score of PLS-DA -- with ``vip_perm=True`` also its permutation p-values,
+    ``permres.vip_pvals`` / ``vip_max`` / ``vip_pvals_fwe``, in place of the "VIP > 1" rule of thumb --,
+    ``coef_components`` the model :func:`predict_class` applies.
     Added to the result: ``classes``.
 
     Cross-validation (``test_split`` > 0): the splits are STRATIFIED -- drawn with ``gen_splits(counts, 1, test_split,
@@ -252,7 +255,7 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
                          permsamples=permsamples, bootsamples=bootsamples, seed=seed, verbose=verbose, n_proc=n_proc,
                          test_split=test_split, test_size=test_size, cvsamples=cvsamples, cv_perm=cv_perm,
                          cvpermsamples=cvpermsamples, coef_components=coef_components, coef_ci=coef_ci,
-                         coef_perm=coef_perm, vip_components=vip_components, _classes=codes, **kwargs)
+                         coef_perm=coef_perm, vip_components=vip_components, vip_perm=vip_perm, _classes=codes, **kwargs)
     res['classes'] = classes
     return res
 

@@ -120,6 +120,9 @@ def _load():
         'plsx_simpls_cv_auc_end': ([vp], i32),
         'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
         'plsx_simpls_vip_ci': ([vp, vp, ctypes.c_longlong, i32, i32, c_d, i32, c_d, vp, vp, vp, vp], i32),
+        'plsx_simpls_vip_perm_test': ([vp, vp, ctypes.c_longlong, i32, vp, vp, vp, vp], i32),
+        'plsx_simpls_vip_perm_begin': ([vp, i32, vp, vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_vip_perm_end': ([vp], i32),
         'plsx_gen_permsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_bootsamp': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp], i32),
         'plsx_gen_permsamp_stream': ([vp, i32, i32, i32, vp, ctypes.POINTER(i32), vp, ctypes.POINTER(i32)], i32),
@@ -158,7 +161,7 @@ def exported_symbols():
              'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_set_confounds', 'plsx_simpls_crossval_confound_batch', 'plsx_simpls_crossval_confound_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
              'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end',
-             'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
+             'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_simpls_vip_perm_test', 'plsx_simpls_vip_perm_begin', 'plsx_simpls_vip_perm_end', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
              'plsx_svd_flip', 'plsx_scale_columns', 'plsx_transpose', 'plsx_center_rows', 'plsx_mean_splits',
@@ -1233,6 +1236,43 @@ class Engine(object):
         self._check(self.lib.plsx_simpls_vip_ci(self.ctx, stack.data_ptr(), n, c, idx[0][0], idx[0][1], idx[1][0],
                                                 idx[1][1], sd.data_ptr(), lo.data_ptr(), hi.data_ptr(), self._stream()))
         return sd, lo, hi
+
+    def simpls_vip_perm_test(self, stack, obs, count, dmax):
+        """The permutation statistics of ``stack`` (n, c, S) -- any contiguous float64 device tensor in the layout of
+        :meth:`simpls_vip_keep` -- against the observed VIP scores ``obs`` (B,): ``count`` (B,) int32 += the number of b
+        with ``sqrt(B * ((Xc.T @ stack[b].T)**2).sum(-1))[f] >= obs[f]``, ``dmax`` (n,) = the maximum over the features
+        of the left side, 0 for a permutation whose scores are NaN (plsx_simpls_vip_perm_test).  No sync."""
+        torch = _torch()
+        if stack.dim() != 3 or stack.shape[2] != self.S or stack.dtype != torch.float64 or not stack.is_contiguous():
+            raise ValueError('the stack must be a contiguous (n, c, {}) float64 tensor'.format(self.S))
+        n, c = int(stack.shape[0]), int(stack.shape[1])
+        self._check_vip_perm(obs, count, dmax, n)
+        self._check(self.lib.plsx_simpls_vip_perm_test(self.ctx, stack.data_ptr(), n, c, obs.data_ptr(),
+                                                       count.data_ptr(), dmax.data_ptr(), self._stream()))
+
+    def _check_vip_perm(self, obs, count, dmax, n):
+        torch = _torch()
+        if tuple(obs.shape) != (self.B,) or obs.dtype != torch.float64 or not obs.is_contiguous():
+            raise ValueError('the observed VIP scores must be a contiguous ({},) float64 tensor'.format(self.B))
+        if tuple(count.shape) != (self.B,) or count.dtype != torch.int32 or not count.is_contiguous():
+            raise ValueError('the counts must be a contiguous ({},) int32 tensor'.format(self.B))
+        if tuple(dmax.shape) != (n,) or dmax.dtype != torch.float64 or not dmax.is_contiguous():
+            raise ValueError('the maxima must be a contiguous ({},) float64 tensor'.format(n))
+
+    def simpls_vip_perm_begin(self, c, obs, count, dmax):
+        """Open a permutation series of the VIP scores of the ``c``-component model: until
+        :meth:`simpls_vip_perm_end` every :meth:`simpls_perm_into` also forms its permutations' scores tile by tile,
+        adds their exceedances of ``obs`` (B,) to ``count`` (B,) int32 and appends their maxima over the features to
+        ``dmax`` (capacity,) in submission order (plsx_simpls_vip_perm_begin).  Independent of a coefficient series:
+        both may be open.  The three tensors must stay alive until the series ends.  PlsxError: status -1 for c
+        outside 1 .. k and from the batch that would pass the capacity, -4 before the original fit is set."""
+        self._check_vip_perm(obs, count, dmax, int(dmax.shape[0]))
+        self._check(self.lib.plsx_simpls_vip_perm_begin(self.ctx, int(c), obs.data_ptr(), count.data_ptr(),
+                                                        dmax.data_ptr(), int(dmax.shape[0])))
+
+    def simpls_vip_perm_end(self):
+        """Close the permutation series of the VIP scores (plsx_simpls_vip_perm_end)."""
+        self._check(self.lib.plsx_simpls_vip_perm_end(self.ctx))
 
     def simpls_boot_into(self, idx_dev, usum, usq, yl_dev, ystack=None):
         """idx_dev (n, S) int32; usum / usq (B, k) accumulated in place; yl_dev (n, T, k);

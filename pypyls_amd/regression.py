@@ -43,7 +43,10 @@ Differences from the reference at this commit, on purpose:
     ``bootres.vip_stderr`` / ``vip_ci``.  VIP is a square root of a sum of squares over the components, so every
     bootstrap's scaled dual weights are kept in subject space and one closing pass over the features forms and reduces
     the series chunk by chunk (plsx_simpls_vip_keep / plsx_simpls_vip_ci; csrc/plsx_simpls.h, k_sd_vip;
-    csrc/plsx_k_vip.h).  :func:`vip` computes the scores of any ``pls_regression`` result.
+    csrc/plsx_k_vip.h).  :func:`vip` computes the scores of any ``pls_regression`` result.  ``vip_perm=True`` tests
+    them against permuted behaviour -- ``permres.vip_pvals`` / ``vip_max`` / ``vip_pvals_fwe`` --: the scores of every
+    permutation's fit are formed tile by tile along the permutation batches, counted against the observed ones and
+    reduced to their maxima over the features in registers (plsx_simpls_vip_perm_begin / _end; k_vip_perm_prod).
   * ``n_split=n`` runs the split-half reliability of the components (the reference forces ``n_split=0``: "not
     implemented for PLSRegression", regression.py:237-238): BasePLS.split_half (base.py:366-397, 704-770) with the
     x_weights and y_loadings of SIMPLS in place of the singular vectors, for the observed data and for every
@@ -122,7 +125,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
                    cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, n_split=0, confounds=None,
-                   **kwargs):
+                   vip_perm=False, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -191,6 +194,21 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     the components: no alignment.  The (B, n_boot) scores exist on the device only, one chunk of features at a time;
     what is kept is 8 c S n_boot bytes (on every GPU of a team: the closing pass runs on the first).
     ``n_boot`` <= 16384.  Every other array of the call keeps its bits.
+
+    ``vip_perm=True`` (needs ``vip_components`` and ``n_perm > 0``; False, the default: nothing is added) tests the VIP
+    scores against permuted behaviour, where the usual "VIP > 1" cut-off flags about the same share of features on pure
+    noise as on real signal (``sum(vip**2) == B`` either way).  The c-component model is fitted on ``(X, Y[perm_p])``
+    for the SAME permutations as ``permres.permsamples`` -- the fits of ``coef_perm`` (3-D Y: the aggregated Y is
+    permuted; rows that are NaN throughout: position p is usable iff row p of X and row perm[p] of Y are; with
+    ``confounds`` the rows of Y_r are permuted against X_r) --, giving scores ``vip_p`` (B,) by the formula above that
+    exist on the device only, one tile at a time.  ``permres`` gains ``vip_pvals`` (B,), the uncorrected one-sided
+    p-value ``(#{p : vip_p[f] >= vip[f]} + 1) / (n_perm + 1)`` (VIP is non-negative and large means important);
+    ``vip_max`` (n_perm,) ``= max_f vip_p[f]``, the null of the single-step max statistic (VIP is already comparable
+    across features: no feature scale enters); and ``vip_pvals_fwe`` (B,) ``= (#{p : vip_max[p] >= vip[f]} + 1) /
+    (n_perm + 1)``, the maxT p-value of Westfall & Young, family-wise over the features.  The comparison is ``>=``: a
+    feature without variance has VIP 0 under every arrangement and comes out at p = 1.  A degenerate permuted fit (the
+    formula's 0 / 0) counts nowhere and has ``vip_max = NaN``; where ``vip[f]`` is NaN both p-values are NaN.
+    Independent of ``coef_components`` and ``coef_perm``.  Every other array of the call keeps its bits.
 
     Split-half reliability: ``n_split=n`` (0 or None, the default: nothing is added, nothing is drawn) asks whether the
     components replicate between two halves of the cohort, as ``behavioral_pls(n_split=n)`` does (BasePLS.split_half,
@@ -289,6 +307,17 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              'device only, one chunk of features at a time'
                              .format(n_boot, 8.0 * X.shape[1] * n_boot / 2 ** 30))
         kwargs['vip_components'] = vip_components          # (recorded in `inputs` only when asked for)
+    if isinstance(vip_perm, (bool, np.bool_)):
+        vip_perm = bool(vip_perm)
+    else:
+        raise ValueError('Provided `vip_perm` must be True or False; got {!r}'.format(vip_perm))
+    if vip_perm:                                   # (as above: on the host, before any engine)
+        if vip_components is None:
+            raise ValueError('`vip_perm` needs `vip_components`: the p-values are those of the VIP scores of the model '
+                             'of that many components')
+        if not n_perm or n_perm < 1:
+            raise ValueError('`vip_perm` needs permutations: n_perm = {!r}'.format(n_perm))
+        kwargs['vip_perm'] = True                  # (recorded in `inputs` only when asked for)
     if isinstance(cv_perm, (bool, np.bool_)) or not isinstance(cv_perm, (int, np.integer)) or cv_perm < 0:
         raise ValueError('Provided `cv_perm` must be a non-negative integer; got {!r}'.format(cv_perm))
     cv_perm = int(cv_perm)
@@ -567,7 +596,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples, bootsamples_out,
                 k, ci, e, kwargs.get('_phases') if rank == 0 else None, None, team=(rank, team), cv=cv,
                 coef_c=coef_components, coef_ci=coef_ci,
-                vip_c=vip_components, coef_perm=coef_perm, sh=sh, cf=cf))
+                vip_c=vip_components, coef_perm=coef_perm, sh=sh, cf=cf, vip_perm=vip_perm))
             unrefined = team.unrefined
         else:
             eng = eng or default_engine()
@@ -577,7 +606,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                     res = _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples,
                                       bootsamples, bootsamples_out, k, ci, eng, kwargs.get('_phases'),
                                       kwargs.get('_emulate'), cv=cv, coef_c=coef_components, coef_ci=coef_ci,
-                                      vip_c=vip_components, coef_perm=coef_perm, sh=sh, cf=cf)
+                                      vip_c=vip_components, coef_perm=coef_perm, sh=sh, cf=cf, vip_perm=vip_perm)
                     ok = True
                 finally:
                     if getattr(eng, 'ctx', None):      # nothing of this call leaks into the next one on the context
@@ -592,7 +621,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
 
 def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsamples, bootsamples,
                 bootsamples_out, k, ci, engine, phases=None, emulate=None, team=None, cv=None, coef_c=None,
-                coef_ci=False, vip_c=None, coef_perm=False, sh=None, cf=None):
+                coef_ci=False, vip_c=None, coef_perm=False, sh=None, cf=None, vip_perm=False):
     import time
     import torch
     S = len(X)
@@ -667,6 +696,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     # this rank's shards (permutations contiguous, bootstraps chunk-cyclic), launched chunk by chunk as the index rows arrive; the
     # results stay on the device until the one collective
     d_perm = d_yl = usum = usq = bsum = bsq = d_keep = d_vkeep = d_cmax = d_ccnt = coefs_obs = None
+    d_vmax = d_vcnt = vip_obs = None
     n_perm_tot = pstream.n if pstream is not None else 0
     n_boot_tot = bstream.n if bstream is not None else 0
     from .progress import Bar                            # verbose=True: the reference's bars (pyls/utils.py:128-152)
@@ -687,6 +717,19 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             if hi > lo:
                 eng.simpls_coef_perm_begin(coef_c, d_cobs, d_ccnt, d_cmax)
             tick('coefs_perm')                          # (the set-up; the series itself runs inside 'permutations')
+        if vip_perm:
+            # the same for the VIP scores: the observed ones are the host's `vip`, uploaded once; the permutations' scores
+            # are formed tile by tile, counted and reduced to their maxima (plsx_simpls_vip_perm_begin; independent of
+            # the coefficient series)
+            eng.sync()                                  # (the x_weights are on the host)
+            vip_obs = _vip_scores(_host_array(h_W),
+                                  _fit_yloadings(Yc[mask].T @ x_scores[mask], x_scores, Y_fit, mask, vip_c), vip_c)
+            d_vobs = eng._dev(vip_obs, np.float64)
+            d_vcnt = torch.zeros((B,), dtype=torch.int32, device=eng.device)
+            d_vmax = eng._zeros((hi - lo,))
+            if hi > lo:
+                eng.simpls_vip_perm_begin(vip_c, d_vobs, d_vcnt, d_vmax)
+            tick('vip_perm')
         bars.append(Bar('Running permutations', hi - lo, show, eng.device))
         # (a solver batch is a latency chain of ~3 k launches whatever its size: few, large chunks -- the first 2048 rows
         # are drawn in 5 ms)
@@ -695,6 +738,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             bars[-1].queued(b - a)
         if d_cmax is not None:
             eng.simpls_coef_perm_end()
+        if d_vmax is not None:
+            eng.simpls_vip_perm_end()
     tick('permutations')
     if bstream is not None:
         bchunks = parallel.shard_chunks(n_boot_tot, rank, world)     # chunk-cyclic share of the bootstraps
@@ -861,9 +906,11 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     finally:
         for bar in bars:
             bar.close()
-    # (the maxima of the coefficient series ride next to d_perm, a contiguous slice like it)
-    slices = [t for t in (d_perm, d_cmax, d_yl) if t is not None]
-    totals = [n for t, n in ((d_perm, n_perm_tot), (d_cmax, n_perm_tot), (d_yl, n_boot_tot)) if t is not None]
+    # (the maxima of the coefficient series and of the VIP series ride next to d_perm, contiguous slices like it)
+    d_vmax2 = d_vmax[:, None] if d_vmax is not None else None
+    slices = [t for t in (d_perm, d_cmax, d_vmax2, d_yl) if t is not None]
+    totals = [n for t, n in ((d_perm, n_perm_tot), (d_cmax, n_perm_tot), (d_vmax2, n_perm_tot), (d_yl, n_boot_tot))
+              if t is not None]
     cyclic = [len(slices) - 1] if d_yl is not None else []
     if d_cv is not None:                                # the cross-validation rows ride in the same buffer: ONE collective
         slices, totals = slices + d_cv, totals + [cv['n']] * 3
@@ -888,6 +935,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     sums = [t for t in (usum, usq, bsum, bsq) if t is not None]      # (the coefficient sums join the summed part)
     if d_ccnt is not None:                              # ... and the exceedance counts, as float64: they are exact
         sums = sums + [d_ccnt.to(torch.float64)]
+    if d_vcnt is not None:                              # ... and those of the VIP series, the same way
+        sums = sums + [d_vcnt.to(torch.float64)[:, None]]
     full, summed = parallel.collect_device(slices, totals, sums, emulate=emulate, cyclic=cyclic, team=team)
     if not lead:
         return None                                     # rank 0 holds everything the ranks computed: it finishes
@@ -917,6 +966,9 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         i += 1
         if d_cmax is not None:
             coefs_max = np.ascontiguousarray(full[i].T)             # (T, n_perm)
+            i += 1
+        if d_vmax is not None:
+            vip_max = np.ascontiguousarray(full[i][:, 0])           # (n_perm,)
             i += 1
     if bstream is not None:
         distrib = np.ascontiguousarray(np.moveaxis(full[i], 0, -1))  # (T, k, n_boot)
@@ -966,9 +1018,12 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         res['permres']['permsamples'] = permsamp
         res['permres']['perm_singval'] = d_perm
         if d_cmax is not None:
-            cnt = np.rint(summed[-1].detach().cpu().numpy()).astype(np.int64)
+            cnt = np.rint(summed[-2 if d_vcnt is not None else -1].detach().cpu().numpy()).astype(np.int64)
             res['permres'].update(_coef_perm_pvals(coefs_obs, cnt, coefs_max,
                                                    _feature_scale(X, okx, None if clean else Xc)))
+        if d_vmax is not None:
+            cnt = np.rint(summed[-1].detach().cpu().numpy()[:, 0]).astype(np.int64)
+            res['permres'].update(_vip_perm_pvals(vip_obs, cnt, vip_max))
 
     res['y_loadings'] = Yc[mask].T @ x_scores[mask]                # regression.py:401
     y_scores = np.full((S, k), np.nan)
@@ -981,7 +1036,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             _model_coefs(res['x_weights'], res['y_loadings'], x_scores, Y_fit, mask, coef_c)
         res['intercept'] = _model_means(X, Y_agg, mask, res['coefs'])
     if vip_c is not None:
-        res['vip'] = _vip_scores(res['x_weights'], _fit_yloadings(res['y_loadings'], x_scores, Y_fit, mask, vip_c), vip_c)
+        res['vip'] = vip_obs if vip_obs is not None else \
+            _vip_scores(res['x_weights'], _fit_yloadings(res['y_loadings'], x_scores, Y_fit, mask, vip_c), vip_c)
     if bootsamp is not None:
         # add the original back, n_boot + 1 (regression.py:409-415)
         d_bsr, d_se = eng.boot_rel_dev(d_W, usum, usq, bootsamp.shape[1] + 1, add_orig=True)
@@ -1055,6 +1111,22 @@ def _coef_perm_pvals(coefs, count, coefs_max, scale):
         null = np.sort(coefs_max[t])
         fwe[:, t] = (n_perm - np.searchsorted(null, obs[:, t], side='left') + 1) / (n_perm + 1)
     return dict(coefs_pvals=(count + 1) / (n_perm + 1), coefs_max=coefs_max, coefs_pvals_fwe=fwe)
+
+
+def _vip_perm_pvals(vip, count, vip_max):
+    """The three arrays ``vip_perm`` adds to permres.  vip (B,) observed; count (B,) = #{p : vip_p >= vip}; vip_max
+    (n_perm,) = max_f vip_p[f] as the device leaves it: 0, the identity of its maximum, for a degenerate permuted fit --
+    every real fit has max_f vip >= 1 since sum(vip**2) == B -- which is reported as NaN and counts nowhere.  The maxT
+    p-value counts the maxima at or above the observed score: one sort and one searchsorted.  Where vip is NaN both
+    p-values are NaN."""
+    vip = np.asarray(vip, dtype=np.float64)
+    n_perm = vip_max.shape[0]
+    null = np.sort(vip_max[vip_max > 0])
+    nan = np.isnan(vip)
+    fwe = (null.shape[0] - np.searchsorted(null, np.where(nan, 0.0, vip), side='left') + 1) / (n_perm + 1)
+    return dict(vip_pvals=np.where(nan, np.nan, (count + 1) / (n_perm + 1)),
+                vip_max=np.where(vip_max > 0, vip_max, np.nan),
+                vip_pvals_fwe=np.where(nan, np.nan, fwe))
 
 
 def _fit_yloadings(Q, x_scores, Y_agg, mask, c):

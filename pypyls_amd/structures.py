@@ -96,6 +96,7 @@ class PLSInputs(KeyedRecord):
         'cv_perm',                          # pls_regression: permutations of the cross-validation (only when asked for)
         'coef_perm',                        # pls_regression: permutation p-values of its coefficients (only when asked for)
         'vip_components',                   # pls_regression: component count of the VIP scores (only when asked for)
+        'vip_perm',                         # pls_regression: permutation p-values of its VIP scores (only when asked for)
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         'weights_ci',                       # behavioral_pls / meancentered_pls: percentile intervals of the x_weights (only when given)
         'confounds',                        # pls_regression / behavioral_pls: the nuisance variables Z (S, q) (only when given)
@@ -148,7 +149,11 @@ class PLSPermResults(KeyedRecord):
     # pls_regression(coef_components=c, coef_perm=True): coefs_pvals (B, T) uncorrected two-sided p-values of the
     # coefficients, coefs_max (T, n_perm) the null of the max statistic over standardised coefficients per behaviour,
     # coefs_pvals_fwe (B, T) the maxT p-values (family-wise over the features of one behaviour)
-    allowed = ('pvals', 'permsamples', 'perm_singval', 'coefs_pvals', 'coefs_max', 'coefs_pvals_fwe')
+    # pls_regression(vip_components=c, vip_perm=True): vip_pvals (B,) uncorrected one-sided p-values of the VIP scores,
+    # vip_max (n_perm,) the null of the max statistic over the features (NaN for a degenerate permuted fit),
+    # vip_pvals_fwe (B,) the maxT p-values (family-wise over the features)
+    allowed = ('pvals', 'permsamples', 'perm_singval', 'coefs_pvals', 'coefs_max', 'coefs_pvals_fwe',
+               'vip_pvals', 'vip_max', 'vip_pvals_fwe')
 
 
 class PLSSplitHalfResults(KeyedRecord):
