@@ -521,6 +521,59 @@ int plsx_crossval_confound_group(plsx_ctx* ctx);
  *                           No bound on m beyond the outputs.  PLSX_ERR_STATE
  *                           without bound regression data; PLSX_ERR_ARG for a null
  *                           pointer, n < 1 or m < 1.
+ *   plsx_simpls_crossval_nested_batch  nested cross-validation of the component
+ *                           count (no reference counterpart): inner splits inside the
+ *                           training rows of every outer split choose c, the outer
+ *                           test rows -- which took no part in the choice -- score
+ *                           the chosen model.  d_codes (n, 1 + ni, S) uint8 holds
+ *                           CODES: 1 = training row, 0 = test row, 2 = on neither
+ *                           side.  Row 0 of group s is outer split s (1 / 0 only),
+ *                           rows 1 .. ni its inner folds: 2 on every outer test row,
+ *                           1 / 0 on the outer training rows (the caller checks).
+ *                           The solver includes a position iff its code is 1, the
+ *                           scores take it iff its code is 0; the masks of every
+ *                           other entry hold 0 / 1 and mean what they meant.  The
+ *                           n (1 + ni) fits go through the fit-and-score body of
+ *                           plsx_simpls_crossval_batch; then, per group
+ *                           (k_sd_cvn_select, one wavefront, no atomics),
+ *                             inner_mse[c] = mean over the ni inner folds, ascending,
+ *                               of sum_t sse[c][t] / n_test of the fold, c = 0 .. k
+ *                               (row 0 the intercept-only model);
+ *                             best = 1; for c = 2 .. k: if inner_mse[c] <
+ *                               inner_mse[best]: best = c -- the first minimum, a NaN
+ *                               is never smaller, c = 0 is no candidate;
+ *                             ncomp = best, or 0 where inner_mse[best] is not finite:
+ *                               the group is undefined and its scores are NaN.
+ *                           d_r, d_r2 (n, T) out: the outer fit's test-row Pearson r
+ *                           / R^2 at c = ncomp; d_mse (n,) its sum_t sse / n_test;
+ *                           d_ncomp (n,) int32; d_inner_mse (n, k + 1).
+ *   plsx_simpls_crossval_nested_perm_batch  its null under permuted Y: the WHOLE
+ *                           procedure, selection included, for each of m
+ *                           permutations (d_perm_idx (m, S) int32, as
+ *                           plsx_simpls_crossval_perm_batch; usability is that of
+ *                           the (permutation, fit) pair), each outer split scored at
+ *                           the c selected inside that permutation; then the plain
+ *                           mean over the n outer splits.  d_r, d_r2 (m, T), d_mse
+ *                           (m,) out; d_ncomp_count (m, k) int32 out: how many outer
+ *                           splits of permutation i chose c (an undefined group
+ *                           counts nowhere and makes the means NaN).  Fit f =
+ *                           ((permutation, outer split), member), counted in 64
+ *                           bits, member 0 the outer fit (k_sd_cvn_expand).  Solver
+ *                           batches hold whole groups of 1 + ni fits, sized like
+ *                           plsx_simpls_crossval_perm_batch's, so the selection runs
+ *                           next to the fits; k_sd_cvn_reduce adds a permutation's
+ *                           groups in outer-split order into the running sums
+ *                           carried in the outputs and divides by n after the last:
+ *                           the same bits whatever the batch size or the scratch
+ *                           budget and however the permutations are spread over
+ *                           contexts.
+ *                           Both nested entries: PLSX_ERR_STATE without bound
+ *                           regression data or while a series of counts is open;
+ *                           PLSX_ERR_ARG for a null pointer or n, ni, m < 1;
+ *                           PLSX_ERR_UNSUPPORTED, the context still usable, with
+ *                           bound confounds and when one group of 1 + ni fits does
+ *                           not fit half the scratch budget (the message has the
+ *                           sizes).
  *   plsx_simpls_set_confounds  confound regression (no reference counterpart):
  *                           d_Z (S, q) nuisance variables, 1 <= q <= 15.  Call it
  *                           after plsx_set_data(PLSX_REGRESSION) and, with masked
@@ -961,6 +1014,11 @@ int plsx_simpls_crossval_batch(plsx_ctx* ctx, const uint8_t* d_masks, int m, dou
                                double* d_sse, void* stream);
 int plsx_simpls_crossval_perm_batch(plsx_ctx* ctx, const uint8_t* d_masks, int n, const int32_t* d_perm_idx, int m,
                                     double* d_r, double* d_r2, double* d_mse, void* stream);
+int plsx_simpls_crossval_nested_batch(plsx_ctx* ctx, const uint8_t* d_codes, int n, int ni, double* d_r, double* d_r2,
+                                      double* d_mse, int32_t* d_ncomp, double* d_inner_mse, void* stream);
+int plsx_simpls_crossval_nested_perm_batch(plsx_ctx* ctx, const uint8_t* d_codes, int n, int ni,
+                                           const int32_t* d_perm_idx, int m, double* d_r, double* d_r2, double* d_mse,
+                                           int32_t* d_ncomp_count, void* stream);
 int plsx_simpls_split_half_batch(plsx_ctx* ctx, const int32_t* d_perm_idx, int np, const uint8_t* d_masks, int ns,
                                  double* d_ucorr, double* d_vcorr, void* stream);
 int plsx_simpls_set_confounds(plsx_ctx* ctx, const double* d_Z, int q, double* d_gx, double* d_gy, void* stream);

@@ -114,6 +114,7 @@ struct SdArgs {
     // cross-validation (plsx_simpls_crossval_batch): a split is a resample with identity sources whose test positions
     // are excluded
     const uint8_t* pmask;       // [nres][S] 1 = position included (training row), or nullptr: every position
+                                // (0 = test row; the nested cross-validation also writes 2 = on neither side)
     double* cvZ;                // [nres][k][S] Vd . K: un-centred scores of every row (k_sd_cv_score centres them in place)
     double* cvr;                // [nres][k][T] Pearson r of the nested predictions on the test rows
     double* cvr2;               // [nres][k][T] R^2
@@ -210,7 +211,7 @@ void k_sd_init(SdArgs a)
     for (int p = lane; p < S; p += 64) {
         const int x = a.xsrc ? a.xsrc[(size_t)r * S + p] : p;
         const int y = a.ysrc ? a.ysrc[(size_t)r * S + p] : p;
-        const int ok = (!a.okx || a.okx[x]) && (!a.oky || a.oky[y]) && (!a.pmask || a.pmask[(size_t)r * S + p]);
+        const int ok = (!a.okx || a.okx[x]) && (!a.oky || a.oky[y]) && (!a.pmask || a.pmask[(size_t)r * S + p] == 1);
         xs[p] = ok ? x : -1;
         ys[p] = y;
         cnt += ok;
@@ -1734,6 +1735,130 @@ void k_sd_cvp_reduce(const double* __restrict__ r, const double* __restrict__ r2
             acc += s / nte[f - f0];
         }
         *dst = last ? acc / n : acc;
+    }
+}
+
+// Nested cross-validation (plsx_simpls_crossval_nested_batch, plsx_simpls_crossval_nested_perm_batch): inner splits
+// inside the training rows of every outer split choose the component count, the outer test rows score the chosen model.
+// The position masks carry CODES: 1 = training row, 0 = test row, 2 = on neither side (the outer test rows under an
+// inner fold) -- k_sd_init includes a position iff its code is 1, sd_cv_is_test takes it iff its code is 0.  The fit
+// list: fit f = group f / (1 + ni), member f % (1 + ni); group g = permutation g / n under outer split g % n; member 0
+// the outer fit, members 1 .. ni the inner fits (64-bit, as the pair list of k_sd_cvp_expand).  The codes come as
+// [n][1 + ni][S].  perm = nullptr: the identity (the observed data).  grid (ceil(S / 256), ms).
+static __global__ __launch_bounds__(256)
+void k_sd_cvn_expand(const int* __restrict__ perm, const uint8_t* __restrict__ codes, int S, int n, int ni, long long f0,
+                     int* __restrict__ ysrc, uint8_t* __restrict__ pmask)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= S) return;
+    const long long f = f0 + blockIdx.y;
+    const long long g = f / (1 + ni), mem = f % (1 + ni);
+    const long long pi = g / n, si = g % n;
+    ysrc[(size_t)blockIdx.y * S + p] = perm ? perm[(size_t)pi * S + p] : p;
+    pmask[(size_t)blockIdx.y * S + p] = codes[((size_t)si * (1 + ni) + mem) * S + p];
+}
+
+// ... the selection of a group, next to its fits: from the scores k_sd_cv_score left for the group's 1 + ni fits
+//     inner_mse[c] = (sum over the inner members j = 1 .. ni, ascending, of (sum_t sse_j[c][t], t ascending) / nte_j) / ni,
+//                    c = 0 .. k -- the per-fit term of k_sd_cvp_reduce; row 0 the intercept-only model
+//     best = 1; for c = 2 .. k: if inner_mse[c] < inner_mse[best] then best = c    (first minimum; a NaN is never smaller)
+//     ncomp = best, or 0 where inner_mse[best] is not finite: the group is undefined and its scores are NaN
+//     r[t], r2[t] = the outer member's at c = ncomp;  mse = (sum_t sse_0[ncomp][t]) / nte_0
+// One wavefront per group: lanes over c for inner_mse (kept in the wave's slice of LDS, (k + 1) doubles), one lane
+// selects, lanes over t copy.  No atomics, every sum in a fixed order.  nte = nullptr (the fits were scored by the
+// identity variant, which does not write it): the usable test rows of a fit are counted here from its codes -- an
+// integer, so the same double k_sd_cv_score<., true> sums.  out_inner: [groups][k + 1] or nullptr.
+// grid ceil(groups / 4), dynamic LDS 4 (k + 1) doubles.
+static __global__ __launch_bounds__(256)
+void k_sd_cvn_select(const double* __restrict__ r, const double* __restrict__ r2, const double* __restrict__ sse,
+                     const double* __restrict__ nte, const uint8_t* __restrict__ codes, const uint8_t* __restrict__ okx,
+                     const uint8_t* __restrict__ oky, int S, int k, int T, int ni, int groups,
+                     double* __restrict__ out_r, double* __restrict__ out_r2, double* __restrict__ out_mse,
+                     int* __restrict__ out_nc, double* __restrict__ out_inner)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm_cvn[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = blockIdx.x * 4 + wave;
+    if (g >= groups) return;
+    double* im = sm_cvn + (size_t)wave * (k + 1);
+    const size_t fit0 = (size_t)g * (1 + ni), kT = (size_t)k * T;
+    auto usable_tests = [&](size_t f) {
+        if (nte) return nte[f];
+        const uint8_t* c = codes + f * S;
+        int cnt = 0;
+        for (int p = lane; p < S; p += 64) cnt += (c[p] == 0 && (!okx || okx[p]) && (!oky || oky[p])) ? 1 : 0;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+        return (double)cnt;
+    };
+    for (int c0 = 0; c0 <= k; c0 += 64) {
+        const int c = c0 + lane;
+        double acc = 0.0;
+        for (int j = 1; j <= ni; ++j) {
+            const double nj = usable_tests(fit0 + j);                          // (wave-uniform)
+            if (c <= k) {
+                const double* row = sse + ((fit0 + j) * (k + 1) + c) * T;
+                double s = 0.0;
+                for (int t = 0; t < T; ++t) s += row[t];
+                acc += s / nj;
+            }
+        }
+        if (c <= k) {
+            im[c] = acc / ni;
+            if (out_inner) out_inner[(size_t)g * (k + 1) + c] = acc / ni;
+        }
+    }
+    const double n0 = usable_tests(fit0);
+    wave_sync();
+    int best = 1;
+    for (int c = 2; c <= k; ++c)
+        if (im[c] < im[best]) best = c;
+    const double vbest = im[best];
+    const bool defined = vbest - vbest == 0.0;                                 // (finite: neither NaN nor an infinity)
+    const double nan = __builtin_nan("");
+    for (int t = lane; t < T; t += 64) {
+        out_r[(size_t)g * T + t] = defined ? r[fit0 * kT + (size_t)(best - 1) * T + t] : nan;
+        out_r2[(size_t)g * T + t] = defined ? r2[fit0 * kT + (size_t)(best - 1) * T + t] : nan;
+    }
+    if (lane == 0) {
+        const double* row = sse + (fit0 * (k + 1) + best) * T;
+        double s = 0.0;
+        for (int t = 0; t < T; ++t) s += row[t];
+        out_mse[g] = defined ? s / n0 : nan;
+        out_nc[g] = defined ? best : 0;
+    }
+}
+
+// ... and the reduction over the outer splits, after the selection: out_r / out_r2 [.][T], out_mse [.] of permutation pi
+// take the selected scores of its groups in this batch, added ONE BY ONE IN SPLIT ORDER to what the earlier batches left
+// there (the entry starts from zero) and divided by n once the last split is in -- the device of k_sd_cvp_reduce: the
+// same bits wherever a batch ends.  out_cnt [.][k] int32: how many of the permutation's splits chose c = 1 .. k (an
+// undefined group counts nowhere).  One thread per output entry, no atomics.  g0: the batch's first group, mg of them.
+// grid (ceil(E / 256), perms touched), E = 2 T + 1 + k.
+static __global__ __launch_bounds__(256)
+void k_sd_cvn_reduce(const double* __restrict__ r, const double* __restrict__ r2, const double* __restrict__ mse,
+                     const int* __restrict__ nc, int k, int T, int n, long long g0, int mg,
+                     double* __restrict__ out_r, double* __restrict__ out_r2, double* __restrict__ out_mse,
+                     int* __restrict__ out_cnt)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 2 * T + 1 + k) return;
+    const long long pi = g0 / n + blockIdx.y;
+    const long long lo = pi * n > g0 ? pi * n : g0, end = (pi + 1) * n < g0 + mg ? (pi + 1) * n : g0 + mg;
+    const bool last = end == (pi + 1) * n;
+    if (e <= 2 * T) {
+        const double* src = e < T ? r + e : (e < 2 * T ? r2 + (e - T) : mse);
+        const int stride = e < 2 * T ? T : 1;
+        double* dst = e < T ? out_r + (size_t)pi * T + e : (e < 2 * T ? out_r2 + (size_t)pi * T + (e - T) : out_mse + pi);
+        double acc = *dst;
+        for (long long g = lo; g < end; ++g) acc += src[(size_t)(g - g0) * stride];
+        *dst = last ? acc / n : acc;
+    } else {
+        const int c = e - 2 * T;                                               // 1 .. k
+        int* dst = out_cnt + (size_t)pi * k + (c - 1);
+        int acc = *dst;
+        for (long long g = lo; g < end; ++g) acc += nc[g - g0] == c ? 1 : 0;
+        *dst = acc;
     }
 }
 

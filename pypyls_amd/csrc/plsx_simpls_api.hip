@@ -827,6 +827,111 @@ try {
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
+// Nested cross-validation, both entries (perm = false: the observed data, Y keeps its rows, m = 1).  The fit list (k_sd_cvn_expand)
+// is cut into solver batches of WHOLE groups of 1 + ni fits, so the selection of a group (k_sd_cvn_select) finds all its
+// members' scores in the batch's scratch; observed: the selected scores are the outputs, permuted: they are reduced over
+// the outer splits in split order (k_sd_cvn_reduce), which does not care where a batch ends.
+static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d_codes, int n, int ni,
+                     const int32_t* d_perm_idx, int m, double* d_r, double* d_r2, double* d_mse, int32_t* d_nc, double* d_inner, void* stream)
+{
+    NEED_DATA();
+    const std::string w = who;
+    if (ctx->method != PLSX_REGRESSION) return fail(ctx, PLSX_ERR_STATE, w + ": data not bound for regression");
+    if (ctx->cls_series.active || ctx->auc_series.active)
+        return fail(ctx, PLSX_ERR_STATE, w + ": a series of counts is open; the nested selection has none");
+    if ((perm && !d_perm_idx) || !d_codes || !d_r || !d_r2 || !d_mse || !d_nc || (!perm && !d_inner) || n < 1 || ni < 1 || m < 1)
+        return fail(ctx, PLSX_ERR_ARG, w + ": bad arguments");
+    if (ctx->cf_q)
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": confounds are bound; the nested selection is not available with "
+                                                   "the fold-wise confound regression");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int S = ctx->S, T = ctx->T, k = ctx->ncomp, unit = 1 + ni;
+    // a fit holds what a fit of plsx_simpls_crossval_perm_batch holds; a group also its selected scores
+    const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T + 1, per_group = 2 * (size_t)T + 2;
+    const double extra = 2.0 * k * S * 8.0 + 5.0 * S + 8.0 * per_fit + 8.0 * per_group / unit;
+    const double fit_bytes = 8.0 * (double)sd_scratch_doubles(S, T, k, simpls_global(ctx)) + extra;
+    if ((double)unit * fit_bytes > 0.5 * ctx->scratch_gb * 1073741824.0) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "%s: one group of 1 + %d fits of %.3g MB each (S = %d, T = %d, k = %d) does not fit half "
+                 "the scratch budget of %.3g GB", who, ni, fit_bytes / 1048576.0, S, T, k, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    const long long groups = (long long)m * n;
+    long long gb = std::min<long long>(groups, std::max(1, sd_batch(ctx, 8192, unit, extra) / unit));   // groups per batch
+    // (the tail-spreading rule of plsx_simpls_crossval_perm_batch, in whole groups)
+    if (groups > gb && groups % gb != 0 && groups % gb < gb / 8) {
+        const long long full = groups / gb, bs = (groups + full - 1) / full;
+        if (bs * unit <= 2147483647LL && sd_batch(ctx, (int)(bs * unit), unit, extra) == (int)(bs * unit)) gb = bs;
+    }
+    const int nb = (int)(gb * unit);
+    if (int e = cv_scratch(ctx, nb)) return e;
+    if (int e = ensure(ctx, ctx->cvpsrc, (size_t)nb * S * 5)) return e;
+    if (int e = ensure(ctx, ctx->cvpfit, ((size_t)nb * per_fit + (size_t)gb * per_group) * 8)) return e;
+    int* ysrc = ptr<int>(ctx->cvpsrc);
+    uint8_t* pmask = reinterpret_cast<uint8_t*>(ysrc + (size_t)nb * S);
+    double* fr = ptr<double>(ctx->cvpfit);
+    double* fsse = fr + 2 * (size_t)nb * kT;
+    const CvScores fs = {fr, fr + (size_t)nb * kT, fsse, perm ? fsse + (size_t)nb * (k + 1) * T : nullptr};
+    double* gr = fsse + (size_t)nb * (k + 1) * T + nb;             // the selected scores of a batch's groups: [gb][T],
+    double* gr2 = gr + (size_t)gb * T;                             // [gb][T], [gb] and, as ints, [gb]
+    double* gmse = gr2 + (size_t)gb * T;
+    int* gnc = reinterpret_cast<int*>(gmse + gb);
+    const uint8_t* okx = ctx->has_okx ? ptr<uint8_t>(ctx->okx) : nullptr;
+    const uint8_t* oky = ctx->has_oky ? ptr<uint8_t>(ctx->oky) : nullptr;
+    if (perm) {
+        // the running sums over the outer splits live in the outputs (k_sd_cvn_reduce)
+        HIPCHK(hipMemsetAsync(d_r, 0, (size_t)m * T * 8, st));
+        HIPCHK(hipMemsetAsync(d_r2, 0, (size_t)m * T * 8, st));
+        HIPCHK(hipMemsetAsync(d_mse, 0, (size_t)m * 8, st));
+        HIPCHK(hipMemsetAsync(d_nc, 0, (size_t)m * k * 4, st));
+    }
+    for (long long g0 = 0; g0 < groups; g0 += gb) {
+        const int mg = (int)std::min<long long>(gb, groups - g0), ms = mg * unit;
+        const long long f0 = g0 * unit;
+        // observed: the codes are the fits' masks as they lie, [n][1 + ni][S], and Y keeps its rows
+        const uint8_t* pm = perm ? pmask : d_codes + (size_t)f0 * S;
+        if (perm) {
+            KTimer tm(ctx, KC_CVSCORE, st);
+            hipLaunchKernelGGL(k_sd_cvn_expand, dim3(ceil_div(S, 256), ms), dim3(256), 0, st, d_perm_idx, d_codes, S, n, ni,
+                               f0, ysrc, pmask);
+            LAUNCHCHK();
+        }
+        auto select = [&] {
+            hipLaunchKernelGGL(k_sd_cvn_select, dim3(ceil_div(mg, 4)), dim3(256), (size_t)4 * (k + 1) * 8, st, fs.r, fs.r2,
+                               fs.sse, fs.nte, pm, okx, oky, S, k, T, ni, mg, perm ? gr : d_r + (size_t)g0 * T,
+                               perm ? gr2 : d_r2 + (size_t)g0 * T, perm ? gmse : d_mse + g0, perm ? gnc : d_nc + g0,
+                               perm ? nullptr : d_inner + (size_t)g0 * (k + 1));
+            LAUNCHCHK();
+            if (!perm) return 0;
+            const int touched = (int)((g0 + mg - 1) / n - g0 / n) + 1;
+            hipLaunchKernelGGL(k_sd_cvn_reduce, dim3(ceil_div(2 * T + 1 + k, 256), touched), dim3(256), 0, st, gr, gr2, gmse,
+                               gnc, k, T, n, g0, mg, d_r, d_r2, d_mse, d_nc);
+            LAUNCHCHK();
+            return 0;
+        };
+        if (int e = perm ? cv_fit_score<true>(ctx, nb, ms, ysrc, pm, fs, 0, 0, 1, st, select)
+                         : cv_fit_score<false>(ctx, nb, ms, nullptr, pm, fs, 0, 0, 1, st, select))
+            return e;
+    }
+    return PLSX_OK;
+}
+
+int plsx_simpls_crossval_nested_batch(plsx_ctx* ctx, const uint8_t* d_codes, int n, int ni, double* d_r, double* d_r2,
+                                      double* d_mse, int32_t* d_ncomp, double* d_inner_mse, void* stream)
+try {
+    return cvn_entry(ctx, "plsx_simpls_crossval_nested_batch", false, d_codes, n, ni, nullptr, 1, d_r, d_r2, d_mse, d_ncomp,
+                     d_inner_mse, stream);
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_crossval_nested_perm_batch(plsx_ctx* ctx, const uint8_t* d_codes, int n, int ni, const int32_t* d_perm_idx,
+                                           int m, double* d_r, double* d_r2, double* d_mse, int32_t* d_ncomp_count,
+                                           void* stream)
+try {
+    return cvn_entry(ctx, "plsx_simpls_crossval_nested_perm_batch", true, d_codes, n, ni, d_perm_idx, m, d_r, d_r2, d_mse,
+                     d_ncomp_count, nullptr, stream);
+} PLSX_CATCH(ctx)
+
 // What both fold entries of the confound regression check first and how they group the splits: bytes of one K_s and of
 // one fit (solver state, dense dual weights and Z = Vd . K_s, its own Y, `extra`), and as many splits per group as fit
 // half the scratch budget with one fit each.

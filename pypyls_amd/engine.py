@@ -102,6 +102,8 @@ def _load():
         'plsx_simpls_set_row_masks': ([vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
         'plsx_simpls_crossval_perm_batch': ([vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
+        'plsx_simpls_crossval_nested_batch': ([vp, vp, i32, i32, vp, vp, vp, vp, vp, vp], i32),
+        'plsx_simpls_crossval_nested_perm_batch': ([vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp], i32),
         'plsx_simpls_split_half_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
         'plsx_simpls_set_confounds': ([vp, vp, i32, vp, vp, vp], i32),
         'plsx_simpls_crossval_confound_batch': ([vp, vp, i32, vp, vp, vp, vp], i32),
@@ -158,7 +160,7 @@ def exported_symbols():
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
-             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_set_confounds', 'plsx_simpls_crossval_confound_batch', 'plsx_simpls_crossval_confound_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
+             'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_crossval_nested_batch', 'plsx_simpls_crossval_nested_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_set_confounds', 'plsx_simpls_crossval_confound_batch', 'plsx_simpls_crossval_confound_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
              'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_simpls_vip_perm_test', 'plsx_simpls_vip_perm_begin', 'plsx_simpls_vip_perm_end', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
@@ -1005,6 +1007,87 @@ class Engine(object):
         self._check(self.lib.plsx_simpls_crossval_perm_batch(self.ctx, masks_dev.data_ptr(), n, idx_dev.data_ptr(), m,
                                                              r_dev.data_ptr(), r2_dev.data_ptr(), mse_dev.data_ptr(),
                                                              self._stream()))
+
+    def _check_nested_codes(self, codes_dev):
+        torch = _torch()
+        if codes_dev.dim() != 3 or codes_dev.shape[1] < 2 or codes_dev.shape[2] != self.S \
+                or codes_dev.dtype != torch.uint8 or not codes_dev.is_contiguous():
+            raise ValueError('nested split codes must be a contiguous (n, 1 + ni, {}) uint8 tensor with ni >= 1'
+                             .format(self.S))
+        return int(codes_dev.shape[0]), int(codes_dev.shape[1]) - 1
+
+    def simpls_crossval_nested_into(self, codes_dev, r_dev, r2_dev, mse_dev, ncomp_dev, inner_dev):
+        """Nested cross-validation of the component count.  codes_dev (n, 1 + ni, S) uint8: 1 = training row, 0 = test
+        row, 2 = on neither side; row 0 of group s is outer split s, rows 1 .. ni its inner folds.  r_dev / r2_dev (n, T):
+        the outer test rows' Pearson r and R^2 at the component count the inner folds chose; mse_dev (n,); ncomp_dev (n,)
+        int32, 0 = undefined; inner_dev (n, k + 1): the mean inner-fold mse of c = 0 .. k components
+        (plsx_simpls_crossval_nested_batch)."""
+        torch = _torch()
+        n, ni = self._check_nested_codes(codes_dev)
+        for t, shape in ((r_dev, (n, self.T)), (r2_dev, (n, self.T)), (mse_dev, (n,)), (inner_dev, (n, self.k + 1))):
+            if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('nested cross-validation outputs must be contiguous float64 (n, T), (n, T), (n,) and '
+                                 '(n, k + 1)')
+        if tuple(ncomp_dev.shape) != (n,) or ncomp_dev.dtype != torch.int32 or not ncomp_dev.is_contiguous():
+            raise ValueError('the selected component counts must be a contiguous (n,) int32 tensor')
+        self._check(self.lib.plsx_simpls_crossval_nested_batch(
+            self.ctx, codes_dev.data_ptr(), n, ni, r_dev.data_ptr(), r2_dev.data_ptr(), mse_dev.data_ptr(),
+            ncomp_dev.data_ptr(), inner_dev.data_ptr(), self._stream()))
+
+    def simpls_crossval_nested_perm_into(self, codes_dev, idx_dev, r_dev, r2_dev, mse_dev, count_dev):
+        """The null of :meth:`simpls_crossval_nested_into` under permuted Y, selection included: idx_dev (m, S) int32,
+        one permutation of the rows of Y per row.  r_dev / r2_dev (m, T), mse_dev (m,): per permutation the mean over
+        the n outer splits of the nested scores, each split at the component count selected inside that permutation;
+        count_dev (m, k) int32: how many outer splits chose c (plsx_simpls_crossval_nested_perm_batch)."""
+        torch = _torch()
+        n, ni = self._check_nested_codes(codes_dev)
+        m = idx_dev.shape[0]
+        if tuple(idx_dev.shape) != (m, self.S) or idx_dev.dtype != torch.int32 or not idx_dev.is_contiguous():
+            raise ValueError('permutations must be a contiguous (m, {}) int32 tensor'.format(self.S))
+        for t, shape in ((r_dev, (m, self.T)), (r2_dev, (m, self.T)), (mse_dev, (m,))):
+            if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('permuted nested cross-validation outputs must be contiguous float64 (m, T), (m, T) and '
+                                 '(m,)')
+        if tuple(count_dev.shape) != (m, self.k) or count_dev.dtype != torch.int32 or not count_dev.is_contiguous():
+            raise ValueError('the selection counts must be a contiguous (m, k) int32 tensor')
+        self._check(self.lib.plsx_simpls_crossval_nested_perm_batch(
+            self.ctx, codes_dev.data_ptr(), n, ni, idx_dev.data_ptr(), m, r_dev.data_ptr(), r2_dev.data_ptr(),
+            mse_dev.data_ptr(), count_dev.data_ptr(), self._stream()))
+
+    def _nested_codes_dev(self, codes):
+        codes = np.asarray(codes)
+        if codes.ndim != 3 or codes.shape[0] != self.S:
+            raise ValueError('nested split codes must have shape (S, n, 1 + ni) with S = {}'.format(self.S))
+        return _torch().from_numpy(np.ascontiguousarray(codes.transpose(1, 2, 0), dtype=np.uint8)).to(self.device)
+
+    def simpls_crossval_nested(self, codes):
+        """codes (S, n, 1 + ni) of {0, 1, 2}, ``[:, s, 0]`` outer split s and ``[:, s, 1:]`` its inner folds -> dict of
+        nested_pearson_r, nested_r_squared (T, n), nested_mse (n,), nested_ncomp (n,) int, inner_mse (k + 1, n)."""
+        torch = _torch()
+        dc = self._nested_codes_dev(codes)
+        n = dc.shape[0]
+        r, r2, mse, inner = self._empty((n, self.T)), self._empty((n, self.T)), self._empty((n,)), self._empty((n, self.k + 1))
+        nc = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        self.simpls_crossval_nested_into(dc, r, r2, mse, nc, inner)
+        self.sync()
+        return dict(nested_pearson_r=r.cpu().numpy().T.copy(), nested_r_squared=r2.cpu().numpy().T.copy(),
+                    nested_mse=mse.cpu().numpy(), nested_ncomp=nc.cpu().numpy().astype(np.int64),
+                    inner_mse=inner.cpu().numpy().T.copy())
+
+    def simpls_crossval_nested_perm(self, codes, perms):
+        """codes as :meth:`simpls_crossval_nested`; perms (S, m), one permutation of 0 .. S-1 per column -> dict of
+        perm_nested_pearson_r, perm_nested_r_squared (T, m), perm_nested_mse (m,), perm_nested_ncomp (k, m) int."""
+        torch = _torch()
+        dc = self._nested_codes_dev(codes)
+        idx = check_index_array(np.asarray(perms), self.S)
+        di = torch.from_numpy(np.ascontiguousarray(idx.T, dtype=np.int32)).to(self.device)
+        m = di.shape[0]
+        r, r2, mse = self._empty((m, self.T)), self._empty((m, self.T)), self._empty((m,))
+        cnt = torch.zeros((m, self.k), dtype=torch.int32, device=self.device)
+        self.simpls_crossval_nested_perm_into(dc, di, r, r2, mse, cnt)
+        self.sync()
+        return dict(perm_nested_pearson_r=r.cpu().numpy().T.copy(), perm_nested_r_squared=r2.cpu().numpy().T.copy(),
+                    perm_nested_mse=mse.cpu().numpy(), perm_nested_ncomp=cnt.cpu().numpy().T.astype(np.int64))
 
     def simpls_set_confounds(self, Z):
         """Z (S, q) host array, 1 <= q <= 15, finite on the usable rows: residualises the bound X and Y on [1, Z] over

@@ -121,11 +121,32 @@ def _check_cvsplits(masks, usable, k, B):
                          'training set has {} usable rows'.format(max(min(int(n_tr.min()) - 1, B), 0), int(n_tr.min())))
 
 
+def _draw_inner_codes(cvmasks, inner_split, rs, test_size):
+    """The inner folds of a nested cross-validation, drawn from the generator ``rs``: for s = 0 .. n - 1
+    ``gen_splits([n_tr_s], 1, inner_split, seed=rs, test_size=test_size)`` on the training rows of outer split s
+    (``cvmasks`` (S, n) bool, True = training row) in ascending row order, scattered back -> (S, n, inner_split) uint8
+    codes: 1 = inner training row, 0 = inner test row, 2 = on neither side (the outer test rows)."""
+    cvmasks = np.asarray(cvmasks, dtype=bool)
+    S, n = cvmasks.shape
+    codes = np.full((S, n, int(inner_split)), 2, dtype=np.uint8)
+    for s in range(n):
+        rows = np.flatnonzero(cvmasks[:, s])
+        codes[rows, s, :] = resampling.gen_splits([len(rows)], 1, inner_split, seed=rs, test_size=test_size)
+    return codes
+
+
+def nested_codes(cvmasks, innersamples):
+    """(S, n, 1 + ni) uint8 codes of a nested cross-validation as the device takes them: ``[:, s, 0]`` outer split s
+    (1 / 0), ``[:, s, 1:]`` its inner folds."""
+    cvmasks = np.asarray(cvmasks, dtype=bool)
+    return np.concatenate([cvmasks[:, :, None].astype(np.uint8), np.asarray(innersamples, dtype=np.uint8)], axis=2)
+
+
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
                    cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, n_split=0, confounds=None,
-                   vip_perm=False, **kwargs):
+                   vip_perm=False, inner_split=0, innersamples=None, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -183,6 +204,28 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     (permutation, split) pair with fewer than two usable test rows gives NaN.  The P x test_split fits run and are
     reduced over the splits on the device (plsx_simpls_crossval_perm_batch); only P rows come back.  Every array the
     call returned before keeps its bits.
+
+    Nested cross-validation of ``n_components``: ``inner_split=ni`` (needs cross-validation; 0, the default: nothing is
+    added, nothing is drawn, every array keeps its bits).  Reading ``cvres.mse``, picking the best c and quoting
+    ``pearson_r_ncomp[:, c - 1]`` selects and scores on the same test rows.  Here ni inner splits INSIDE the training
+    rows of every outer split choose c, and the outer test rows, which took no part in the choice, score the chosen
+    model.  The inner folds are codes ``innersamples`` (S, test_split, ni) uint8 -- 1 = training row, 0 = test row, 2 =
+    on neither side, which is exactly the outer test rows of that split -- given (then ``cvsamples`` must be given too)
+    or drawn: one more job at the END of the draw list, for s = 0 .. test_split - 1
+    ``gen_splits([n_tr_s], 1, ni, test_size=test_size)`` on the training rows of split s in ascending row order,
+    scattered back.  Per outer split s: ``inner_mse[c, s]``, c = 0 .. k, the mean over the inner folds of the fold's
+    squared error per usable test row (row 0 the intercept-only model); ``nested_ncomp[s]`` its first minimum over
+    c = 1 .. k (a NaN is never smaller; 0 and NaN scores where that minimum is not finite); and ``nested_pearson_r`` /
+    ``nested_r_squared`` (T, test_split), ``nested_mse`` (test_split,): the outer fit's ``pearson_r_ncomp`` /
+    ``r_squared_ncomp`` / ``mse`` at c = ``nested_ncomp[s]``.  With ``cv_perm=P`` the WHOLE procedure, selection
+    included, is repeated under the same ``cvpermsamples``: ``perm_nested_pearson_r`` / ``perm_nested_r_squared`` (T, P)
+    and ``perm_nested_mse`` (P,), the plain means over the outer splits, each split at the c selected inside that
+    permutation; ``perm_nested_ncomp`` (k, P) int, how many outer splits of a permutation chose c; and
+    ``nested_pearson_r_pvals`` / ``nested_r_squared_pvals`` (T,) = (#{null > observed split-mean} + 1) / (P + 1),
+    ``nested_mse_pvals`` with ``<`` (a NaN null value counts as not larger / not smaller).  That is
+    P x test_split x (1 + ni) fits, selected and reduced on the device (plsx_simpls_crossval_nested_batch,
+    plsx_simpls_crossval_nested_perm_batch); ranks and teams shard the permutations.  Refused: ``confounds`` and
+    ``pls_da``.
 
     VIP scores: ``vip_components=c`` (1 <= c <= n_components, independent of ``coef_components``; None, the default:
     nothing is added, no memory is taken) returns ``vip`` (B,), the variable importance in projection of the
@@ -327,6 +370,23 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                              '`test_size` > 0 (drawn, or given as `cvsamples`); got test_split = {!r}, test_size = {!r}'
                              .format(test_split, test_size))
         kwargs['cv_perm'] = cv_perm                # (recorded in `inputs` only when asked for)
+    if isinstance(inner_split, (bool, np.bool_)) or not isinstance(inner_split, (int, np.integer)) or inner_split < 0:
+        raise ValueError('Provided `inner_split` must be a non-negative integer; got {!r}'.format(inner_split))
+    inner_split = int(inner_split)
+    if inner_split == 0 and innersamples is not None:
+        raise ValueError('`innersamples` needs `inner_split` > 0, the number of inner folds it holds per outer split')
+    if inner_split > 0:                            # (as above: on the host, before any engine)
+        if not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+            raise ValueError('`inner_split` needs cross-validation: the inner folds lie inside the training rows of the '
+                             'splits of `test_split` > 0 with `test_size` > 0; got test_split = {!r}, test_size = {!r}'
+                             .format(test_split, test_size))
+        if kwargs.get('_classes') is not None:
+            raise ValueError('`inner_split` is not available for pls_da: its confusion and AUC counts are not selected '
+                             '(not in this version)')
+        if confounds is not None:
+            raise ValueError('`inner_split` cannot be combined with `confounds`: the fold-wise confound regression has '
+                             'its own K per split (not in this version)')
+        kwargs['inner_split'] = inner_split        # (recorded in `inputs` only when asked for)
     if n_split is None:
         n_split = 0
     if isinstance(n_split, (bool, np.bool_)) or not isinstance(n_split, (int, np.integer)) or n_split < 0:
@@ -479,6 +539,52 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             raise ValueError('Provided `n_components` cannot be greater than {} when permuting the cross-validation: '
                              'a permutation can leave {} usable training rows'
                              .format(max(min(lo_tr - 1, X.shape[1]), 0), max(lo_tr, 0)))
+    # ---- nested cross-validation: validated on the host before any engine is created or looked up
+    inner = None
+    if inner_split > 0:
+        usable = _usable_rows(X, Y_agg)
+        n_bad = int((~usable).sum())
+        # (under cv_perm a permutation can leave every masked row of X and of Y on the training side of one fold: the
+        # worst-case rule of `cv_perm` above)
+        n_bad_tr = n_bad if cv_perm == 0 else \
+            int((~_usable_rows(X, np.zeros((S, 1)))).sum()) + int(np.isnan(Y_agg).all(axis=1).sum())
+        if innersamples is not None:
+            inner = np.asarray(innersamples)
+            if inner.ndim != 3 or inner.shape != (S, n_cv, inner_split):
+                raise ValueError('Provided `innersamples` must have shape (S, test_split, inner_split) = ({}, {}, {}); '
+                                 'got {}'.format(S, n_cv, inner_split, inner.shape))
+            if cvmasks is None:
+                raise ValueError('`innersamples` needs `cvsamples`: the inner folds lie inside the training rows of given '
+                                 'outer splits')
+            if not np.isin(inner, (0, 1, 2)).all():
+                raise ValueError('Provided `innersamples` must hold the codes 0 (test row), 1 (training row) and 2 (on '
+                                 'neither side) only')
+            inner = inner.astype(np.uint8)
+            leak = (inner == 2) != ~cvmasks[:, :, None]
+            if leak.any():
+                p, s_, j = (int(v[0]) for v in np.nonzero(leak))
+                raise ValueError('Provided `innersamples` must hold 2 exactly on the outer test rows of its split: an '
+                                 'inner fold that touches outer test rows leaks them into the selection; row {} of '
+                                 'inner fold {} of split {} does not'.format(p, j, s_))
+            te = ((inner == 0) & usable[:, None, None]).sum(axis=0)
+            tr = (inner == 1).sum(axis=0) - (n_bad_tr if cv_perm > 0 and n_bad_tr
+                                             else ((inner == 1) & ~usable[:, None, None]).sum(axis=0))
+            lo_te_in, lo_tr_in = int(te.min()), int(tr.min())
+        else:
+            # drawn: gen_splits keeps ceil or floor of n (1 - test_size) training rows, of the S rows and again of an
+            # outer training set; the worst case over both is checked
+            n_out = [int(cvmasks.sum(axis=0).min()), int(cvmasks.sum(axis=0).max())] if cvmasks is not None else \
+                [int(np.floor(S * (1 - test_size))), int(np.ceil(S * (1 - test_size)))]
+            lo_tr_in = int(np.floor(n_out[0] * (1 - test_size))) - n_bad_tr
+            lo_te_in = min(nt - int(np.ceil(nt * (1 - test_size))) for nt in range(n_out[0], n_out[1] + 1)) - n_bad
+        if lo_te_in < 2:
+            raise ValueError('Every inner fold needs at least 2 usable test rows; {} of {} ({} rows are NaN throughout)'
+                             .format('`innersamples` leaves' if inner is not None else
+                                     'test_size = {} can leave'.format(test_size), max(lo_te_in, 0), S, n_bad))
+        if n_components > min(lo_tr_in - 1, X.shape[1]):
+            raise ValueError('Provided `n_components` cannot be greater than {} with `inner_split`: the smallest inner '
+                             'training set has {} usable rows'
+                             .format(max(min(lo_tr_in - 1, X.shape[1]), 0), max(lo_tr_in, 0)))
     # ---- split-half: validated on the host before any engine is created or looked up
     sh = None
     if n_split > 0:
@@ -575,6 +681,15 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
         def sh_draw(r):
             sh['masks'] = resampling.gen_splits([S], 1, n_split, seed=r, test_size=0.5)
         jobs.append(sh_draw)
+    if inner_split > 0:
+        cv['inner'] = inner
+        cv['ni'] = inner_split
+        if inner is None:
+            # the inner folds: one more job at the END of the list, behind the split-half masks -- per outer split the
+            # training rows in ascending row order are split again, everything else holds 2
+            def inner_draw(r):
+                cv['inner'] = _draw_inner_codes(cv['masks'], inner_split, r, test_size)
+            jobs.append(inner_draw)
     from .engine import default_engine, touch_idle_release
     from . import team as _team
     touch_idle_release()                               # (a pending idle release is pushed back before the engine is looked up)
@@ -865,6 +980,38 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         if lead and cv.get('perm_given') is None:
             cvp.warn()
         tick('crossval_perm')
+    # nested cross-validation of n_components: the observed pass where the observed cross-validation ran -- this rank's
+    # shard of the OUTER splits, each with its inner folds -- and, under cv_perm, this rank's shard of the permutations
+    # under all the groups.  Fits, selection and the reduction over the outer splits stay on the device
+    # (plsx_simpls_crossval_nested_batch / _perm_batch); a rank keeps 2 T + 1 + k numbers per permutation.
+    d_cvn = d_cvnp = None
+    if cv is not None and cv.get('ni'):
+        ni = cv['ni']
+        codes = nested_codes(cv['masks'], cv['inner'])           # (S, n, 1 + ni)
+        d_codes = torch.from_numpy(np.ascontiguousarray(codes.transpose(1, 2, 0))).to(eng.device)
+        lo, hi = parallel.shard_bounds(cv['n'], rank, world)
+        d_cvn = [eng._zeros((hi - lo, T)), eng._zeros((hi - lo, T)), eng._zeros((hi - lo,)),
+                 torch.zeros((hi - lo,), dtype=torch.int32, device=eng.device), eng._zeros((hi - lo, k + 1))]
+        step = max(1, 8192 // (1 + ni))
+        for a in range(lo, hi, step):
+            b = min(hi, a + step)
+            eng.simpls_crossval_nested_into(d_codes[a:b], *(t[a - lo:b - lo] for t in d_cvn))
+        tick('crossval_nested')
+        if cvp is not None:
+            lo, hi = parallel.shard_bounds(cvp.n, rank, world)
+            d_cvnp = [eng._zeros((hi - lo, T)), eng._zeros((hi - lo, T)), eng._zeros((hi - lo,)),
+                      torch.zeros((hi - lo, k), dtype=torch.int32, device=eng.device)]
+            bars.append(Bar('Running nested cross-validation permutations', hi - lo, show, eng.device))
+            step = max(1, 65536 // (cv['n'] * (1 + ni)))
+            for a in range(lo, hi, step):
+                b = min(hi, a + step)
+                cvp.wait(b)
+                eng.simpls_crossval_nested_perm_into(d_codes, eng.rows_tensor(cvp.rows[a:b]),
+                                                     *(t[a - lo:b - lo] for t in d_cvnp))
+                for done in bars:
+                    done.poll()
+                bars[-1].queued(b - a)
+            tick('crossval_nested_perm')
     # split-half reliability: this rank's contiguous shard of the permutations, block by block as their masks arrive
     # (permutation i: RandomState(i)), the mean over the splits taken on the device in fixed order; the observed
     # arrangement runs on the lead rank.  Per-split values exist in scratch of one block only.
@@ -926,6 +1073,13 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         if t is not None:                               # ... and the AUC counts, the same way: exact below 2^53
             assert t.numel() == 0 or int(t.max().item()) < 2 ** 53, 'AUC counts beyond 2^53 do not ride as float64'
             slices, totals = slices + [t.to(torch.float64)], totals + [n]
+    nest_at = len(slices)
+    if d_cvn is not None:                               # ... and the nested scores per outer split, the counts as float64
+        slices = slices + [d_cvn[0], d_cvn[1], d_cvn[2][:, None], d_cvn[3].to(torch.float64)[:, None], d_cvn[4]]
+        totals = totals + [cv['n']] * 5
+    if d_cvnp is not None:                              # ... and their null per permutation
+        slices = slices + [d_cvnp[0], d_cvnp[1], d_cvnp[2][:, None], d_cvnp[3].to(torch.float64)]
+        totals = totals + [cvp.n] * 4
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
@@ -1002,6 +1156,24 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 from .discriminant import auc_results
                 j += 2 if d_confp is not None else 1
                 res['cvres'].update(auc_results(full[j], full[j + 1] if d_aucp is not None else None))
+        if d_cvn is not None:
+            nr, nr2, nmse, nnc, nin = full[nest_at:nest_at + 5]
+            res['cvres'].update(dict(
+                nested_ncomp=np.rint(nnc[:, 0]).astype(np.int64), nested_pearson_r=np.ascontiguousarray(nr.T),
+                nested_r_squared=np.ascontiguousarray(nr2.T), nested_mse=np.ascontiguousarray(nmse[:, 0]),
+                inner_mse=np.ascontiguousarray(nin.T), innersamples=np.asarray(cv['inner'], dtype=np.uint8)))
+            if d_cvnp is not None:
+                # the null of the split means, each permutation with its own selection; the observed statistic is the
+                # plain mean over the outer splits of the nested scores
+                pr, pr2, pmse, pcnt = full[nest_at + 5:nest_at + 9]
+                pr, pr2, pmse = np.ascontiguousarray(pr.T), np.ascontiguousarray(pr2.T), np.ascontiguousarray(pmse[:, 0])
+                cr = res['cvres']
+                res['cvres'].update(dict(
+                    perm_nested_pearson_r=pr, perm_nested_r_squared=pr2, perm_nested_mse=pmse,
+                    perm_nested_ncomp=np.ascontiguousarray(np.rint(pcnt).astype(np.int64).T),
+                    nested_pearson_r_pvals=hostmath.perm_sig(cr['nested_pearson_r'].mean(axis=-1), pr),
+                    nested_r_squared_pvals=hostmath.perm_sig(cr['nested_r_squared'].mean(axis=-1), pr2),
+                    nested_mse_pvals=float(hostmath.perm_sig(-np.atleast_1d(cr['nested_mse'].mean()), -pmse[None, :])[0])))
     if d_sh0 is not None:
         orig_uc, orig_vc = (t.cpu().numpy()[0] for t in d_sh0)
         res['splitres'].update(dict(ucorr=orig_uc, vcorr=orig_vc))

@@ -100,6 +100,7 @@ class PLSInputs(KeyedRecord):
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         'weights_ci',                       # behavioral_pls / meancentered_pls: percentile intervals of the x_weights (only when given)
         'confounds',                        # pls_regression / behavioral_pls: the nuisance variables Z (S, q) (only when given)
+        'inner_split',                      # pls_regression: inner folds of the nested cross-validation (only when asked for)
         'cv_lv',                            # behavioral_pls: out-of-sample score correlation of the latent variables (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
@@ -182,7 +183,18 @@ class PLSCrossValidationResults(KeyedRecord):
                # perm_auc_counts (G, 2, k, P) summed over the splits of a permutation, perm_auc (G, k, P) / perm_auc_macro
                # (k, P) of that sum, auc_pvals (G, k) / auc_macro_pvals (k,)
                'auc_counts', 'auc', 'auc_macro', 'perm_auc_counts', 'perm_auc', 'perm_auc_macro', 'auc_pvals',
-               'auc_macro_pvals')
+               'auc_macro_pvals',
+               # pls_regression(inner_split=ni): nested cross-validation of n_components -- nested_ncomp (n,) int the
+               # component count the ni inner folds of outer split s chose (0: undefined), nested_pearson_r /
+               # nested_r_squared (T, n) and nested_mse (n,) the outer test rows' scores at that count, inner_mse
+               # (k + 1, n) the mean inner-fold mse per count (row 0 the intercept-only model), innersamples
+               # (S, n, ni) uint8 codes (1 = training row, 0 = test row, 2 = on neither side: the outer test rows);
+               # with cv_perm=P: perm_nested_pearson_r / perm_nested_r_squared (T, P), perm_nested_mse (P,) the split
+               # means with the selection repeated inside every permutation, perm_nested_ncomp (k, P) int how many outer
+               # splits of a permutation chose c, nested_pearson_r_pvals / nested_r_squared_pvals (T,), nested_mse_pvals
+               'nested_ncomp', 'nested_pearson_r', 'nested_r_squared', 'nested_mse', 'inner_mse', 'innersamples',
+               'perm_nested_pearson_r', 'perm_nested_r_squared', 'perm_nested_mse', 'perm_nested_ncomp',
+               'nested_pearson_r_pvals', 'nested_r_squared_pvals', 'nested_mse_pvals')
 
 
 class PLSResults(KeyedRecord):
