@@ -291,6 +291,55 @@ int plsx_boot_weights_ci(plsx_ctx* ctx, const int32_t* d_boot_idx, const double*
                          double g_lo, int i_hi, double g_hi, double* d_lo, double* d_hi, void* stream);
 
 /*
+ * Permutation test of the PLS-C x_weights (behavioral and mean-centred PLS; no reference counterpart: the (B, L, n_perm)
+ * series is 400 GB at B = 200 000, L = 50, n_perm = 5000).  With V0 (T' x m) the first m columns of the observed
+ * y_weights (with contrasts: of the normalised contrasts) and R_p the cross-covariance matrix of permutation p --
+ * gen_covcorr of make_permutation: behavioral PLS moves the rows of Y against X, mean-centred PLS the rows of X across
+ * the cells -- the null is
+ *   Z_p = R_p^T V0   (B x m),
+ * the permuted cross-covariance read along the observed behavioural pattern.  Where the Procrustes rotation of the
+ * permutation leg is exact (L = T', every LV live) this is the rotated, singular-value-scaled permuted x_weights, whose
+ * column norms are the rotated perm_singval; everywhere else R_p^T V0 is the definition.  The observed statistic is
+ * Z = x_weights[:, :m] * singvals[:m], the units of plsx_boot_weights_ci.  Both entries keep no state of a series, take
+ * ANY index rows with values in 0 .. S - 1 and leave the permutation leg's routes alone.
+ *
+ *   plsx_perm_weights_build d_perm_idx (n, S) int32, d_V (T', m) fp64 row-major -> d_W [n][m][S]: the subject-space
+ *                           operand of every permutation, Z_p = W_p . Xf with Xf the resample-independent feature
+ *                           matrix of the binding (the per-cell scaled X in correlation mode, else the centred X).
+ *                           Behavioral PLS (k_perm_W_behav): W_p[l][s] = sum_t V0[j T + t][l] z_p(s, t) over the T
+ *                           behaviours of s's cell j, z_p the scaled z-score of row perm[s] of Y among the rows the
+ *                           permutation places in the cell (centred only with PLSX_FLAG_COVARIANCE), divided by
+ *                           n_j - 1: the moment loops of the permutation leg's builders in their order, t ascending.
+ *                           Mean-centred PLS (k_perm_VA, k_perm_W_mc): R_p = A X[perm] with A the averaging weights
+ *                           of the design, so W_p[l][perm[s]] = (V0^T A)[l][s]; rows that repeat in the index row
+ *                           are added in position order, rows it skips get 0.  One writer per entry, a fixed order,
+ *                           no floating-point atomics.
+ *   plsx_perm_weights_test  the same operands in pieces of at most 16384 permutations, each piece through the counting
+ *                           feature pass of plsx_simpls_coef_perm_test (k_coef_perm_prod over Xf with T := m, then
+ *                           k_coef_perm_max; the kernels are unchanged), the features in chunks of whole 128-feature
+ *                           blocks: d_count (B, m) int32 += #{p < n : q_f |Z_p[f][l]| >= q_f |d_obs[f][l]|}, d_max
+ *                           (n, m) = max_f q_f |Z_p[f][l]|.  q_f = 1, or with `standardise` 1 / s_f, s_f the standard
+ *                           deviation (ddof 1) of feature f over all S rows about its grand mean (k_col_rsd, once
+ *                           per binding), and 0 for a feature without variance (its count is then n).  A piece's
+ *                           operands (8 m S bytes a permutation) and partial maxima (8 m bytes a permutation and
+ *                           feature block) stay inside the scratch budget and free device memory.  Integer counts,
+ *                           maxima, one owner per (f, l): the same bits whatever the piece size and the chunking,
+ *                           and counts / maxima of disjoint sets of index rows add / concatenate.
+ *   plsx_perm_weights_scale d_rsd (B,) <- the table q_f = 1 / s_f that `standardise` applies (0 for a feature without
+ *                           variance), so that a host forms the observed side of the family-wise comparison with the
+ *                           scale the maxima carry.  PLSX_ERR_STATE without bound PLS-C data, PLSX_ERR_ARG for a null
+ *                           pointer.
+ *   Statuses (both): PLSX_ERR_STATE without bound data or with a regression binding; PLSX_ERR_UNSUPPORTED (context
+ *   still usable) for a multiblock binding and, _test only, when not even 64 permutations fit (plsx_last_error names the
+ *   bytes); PLSX_ERR_ARG for a null pointer, n < 1, m < 1 or m > T'.
+ */
+int plsx_perm_weights_build(plsx_ctx* ctx, const int32_t* d_perm_idx, int n, const double* d_V, int m, double* d_W,
+                            void* stream);
+int plsx_perm_weights_test(plsx_ctx* ctx, const int32_t* d_perm_idx, int n, const double* d_V, int m, const double* d_obs,
+                           int standardise, int32_t* d_count, double* d_max, void* stream);
+int plsx_perm_weights_scale(plsx_ctx* ctx, double* d_rsd, void* stream);
+
+/*
  * Split-half reliability -- BasePLS.split_half (pyls/base.py:714-770) for np
  * data arrangements (the original data and/or permuted data, base.py:705-708)
  * with ns split masks each.  For every arrangement the library decomposes
@@ -1137,7 +1186,8 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * k_sd_sh_score of plsx_simpls_split_half_batch), ..., 11 k_coef_prod (the feature pass of
  * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
  * k_col_sd of plsx_simpls_coef_perm_test and k_vip_perm_prod / k_vip_perm_count / k_coef_perm_max of plsx_simpls_vip_perm_test count
- * here too, k_sd_vip under 10 with
+ * here too, and so do k_coef_perm_prod / k_coef_perm_max / k_col_rsd of plsx_perm_weights_test, whose builders
+ * k_perm_W_behav / k_perm_VA / k_perm_W_mc count under 7; k_sd_vip under 10 with
  * k_sd_coef), 12 k_percentile (selection / sort of plsx_percentile_ci, plsx_simpls_coef_ci and plsx_simpls_vip_ci),
  * 13 k_contrast (non-rotated PLS: k_contrast_norms + its chunk sum, k_contrast_quad, k_contrast_fill),
  * 14 k_mb_rownorm (multiblock PLS: the row norms of a batch's R slots and their scaling, k_mb_rownorm + k_mb_rowscale),

@@ -1,6 +1,6 @@
 """Build libplsx.so (hipcc, gfx950 only) in-tree next to this file.
 
-The library is fifteen translation units (csrc/plsx_internal.h has the map), compiled in parallel into
+The library is sixteen translation units (csrc/plsx_internal.h has the map), compiled in parallel into
 csrc/build/*.o and linked; a unit is recompiled when it or a header it includes is newer than its object."""
 import os
 import shutil
@@ -12,11 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJDIR = os.path.join(CSRC, 'build')
 UNITS = ['plsx_smallql1', 'plsx_smallql2', 'plsx_gram', 'plsx_urot', 'plsx_xprod', 'plsx_small', 'plsx_compact',
-         'plsx_simpls_api', 'plsx_split', 'plsx_core', 'plsx_cvperm', 'plsx_weightsci', 'plsx_confound', 'plsx_confound_behav', 'plsx_comm']                                   # (longest compile first)
+         'plsx_simpls_api', 'plsx_split', 'plsx_core', 'plsx_cvperm', 'plsx_weightsci', 'plsx_permweights', 'plsx_confound', 'plsx_confound_behav', 'plsx_comm']                                   # (longest compile first)
 COMMON = ['plsx_internal.h', 'plsx_kernels.h', 'plsx_common.h', 'plsx_k_prep.h', 'plsx_k_xprod.h', 'plsx_k_gram.h',
           'plsx_k_small.h', 'plsx_k_urot.h', 'plsx_k_misc.h', 'plsx_k_finish.h', 'plsx_k_coefci.h', 'plsx_k_coefperm.h', 'plsx_k_vip.h', 'plsx_k_contrast.h', 'plsx_k_multiblock.h', 'plsx_k_weightsci.h', 'plsx_symeig.h']
 EXTRA = {'plsx_core': ['plsx_resample.h'], 'plsx_smallql1': ['plsx_smallql.h'], 'plsx_smallql2': ['plsx_smallql.h'],
-          'plsx_simpls_api': ['plsx_simpls.h'], 'plsx_split': ['plsx_splitfused.h'], 'plsx_cvperm': ['plsx_k_cvperm.h'],
+          'plsx_simpls_api': ['plsx_simpls.h'], 'plsx_split': ['plsx_splitfused.h'], 'plsx_cvperm': ['plsx_k_cvperm.h'], 'plsx_permweights': ['plsx_k_permweights.h'],
           'plsx_confound': ['plsx_simpls.h', 'plsx_k_confound.h'],
           'plsx_confound_behav': ['plsx_simpls.h', 'plsx_k_confound.h', 'plsx_k_confound_behav.h']}
 PUBLIC = os.path.join(os.path.dirname(HERE), 'include', 'plsx.h')

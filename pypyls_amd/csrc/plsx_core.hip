@@ -410,7 +410,7 @@ try {
     (void)plsx_comm_destroy(ctx);
     for (Buf* b : {&ctx->Xc, &ctx->xmean, &ctx->Y, &ctx->cell_of_row, &ctx->cell_start, &ctx->cell_len,
                    &ctx->out_row, &ctx->mom_idx, &ctx->mom_n, &ctx->Afrag, &ctx->R, &ctx->Gm, &ctx->Pm,
-                   &ctx->wciW, &ctx->wciCnt, &ctx->wciScale, &ctx->part, &ctx->Mfrag, &ctx->U0T, &ctx->V0, &ctx->d0, &ctx->tmpW,
+                   &ctx->wciW, &ctx->wciCnt, &ctx->wciScale, &ctx->pwW, &ctx->pwA, &ctx->pwVA, &ctx->pwInv, &ctx->pwRsd, &ctx->part, &ctx->Mfrag, &ctx->U0T, &ctx->V0, &ctx->d0, &ctx->tmpW,
                    &ctx->Rfull, &ctx->Vp, &ctx->dp, &ctx->Mvd, &ctx->Cm, &ctx->srcx, &ctx->srcy, &ctx->part2,
                    &ctx->Kmat, &ctx->swork, &ctx->spct, &ctx->sc,
                    &ctx->momout, &ctx->R2, &ctx->cvc, &ctx->Qm, &ctx->Vs, &ctx->ds, &ctx->ybar, &ctx->pred, &ctx->lvsc,
@@ -556,6 +556,7 @@ try {
     count_close(ctx->cls_series);                      // (... and the class codes of its rows with their open series)
     count_close(ctx->auc_series);
     ctx->has_cls = 0;
+    ctx->pw_rsd = ctx->pw_Xn = 0;                      // (... and what plsx_perm_weights_test derived from its features)
     ctx->cf_q = 0;                                     // (... and the confounds of plsx_simpls_set_confounds)
     // a new binding starts a new analysis: numerical status and graded-spectrum counters of the last one are dropped
     ctx->n_refined = ctx->n_unrefined = 0;

@@ -12,6 +12,7 @@
 //   plsx_simpls_api.hip  SIMPLS regression: the solver batch (run_simpls_dual on an SdRequest), products with K (sd_times_K), one cross-validation body (cv_fit_score), the count series of PLS-DA (CountSeries)
 //   plsx_cvperm.hip      permutation null of the behavioural cross-validation in dual space: plsx_crossval_perm_batch (plsx_k_cvperm.h)
 //   plsx_weightsci.hip   percentile intervals of the PLS-C x_weights: plsx_boot_keep, plsx_boot_weights_ci
+//   plsx_permweights.hip permutation test of the PLS-C x_weights: plsx_perm_weights_build, plsx_perm_weights_test (plsx_k_permweights.h)
 //   plsx_confound.hip    confound regression of the SIMPLS front end: plsx_simpls_set_confounds, the fold-wise K_s and Y_s of its cross-validation (plsx_k_confound.h)
 //   plsx_confound_behav.hip  confound regression of the PLS-C front end: plsx_residualize, plsx_set_confounds, the fold copies X_s of its cross-validation (plsx_k_confound_behav.h)
 //   plsx_comm.hip        the exported collective (RCCL through dlopen)
@@ -186,6 +187,13 @@ struct plsx_ctx {
     long long wkeep_cap = 0, wkeep_n = 0;
     int wkeep_m = 0;
     Buf wciW, wciCnt, wciScale;
+    // plsx_perm_weights_build / plsx_perm_weights_test: the operands W_p of a piece of permutations [n][m][S] (pwW), of
+    // mean-centred PLS the design's averaging weights A (T' x round_up(S, 8), pwA), V0^T A (m x S, pwVA) and the builder's
+    // index counters [n][2][S] (pwInv), the table
+    // 1 / s_f of the bound features (pwRsd; pw_rsd: current for this binding); pw_Xn: Xn was formed for this pass by a
+    // binding that keeps none (option "no_fixed_x").  The partial maxima share cppart.
+    Buf pwW, pwA, pwVA, pwInv, pwRsd;
+    int pw_rsd = 0, pw_Xn = 0;
     // plsx_simpls_coef_perm_begin: a permutation series of the coefficients rides along plsx_simpls_perm_batch -- the
     // caller's observed coefficients (B, T), counts (B, T) and maxima [cperm_n][T] (appended), the batch's A_p dense
     // [m][T][S] (cpA), the partial maxima of a chunk of feature blocks (cppart), the feature scale s_f (colsd)

@@ -75,6 +75,9 @@ def _load():
         'plsx_boot_route': ([vp], i32),
         'plsx_boot_keep': ([vp, vp, ctypes.c_longlong, i32], i32),
         'plsx_boot_weights_ci': ([vp, vp, vp, i32, i32, i32, c_d, i32, c_d, vp, vp, vp], i32),
+        'plsx_perm_weights_build': ([vp, vp, i32, vp, i32, vp, vp], i32),
+        'plsx_perm_weights_test': ([vp, vp, i32, vp, i32, vp, i32, vp, vp, vp], i32),
+        'plsx_perm_weights_scale': ([vp, vp, vp], i32),
         'plsx_split_route': ([vp], i32),
         'plsx_split_half_batch': ([vp, vp, i32, vp, i32, vp, vp, vp], i32),
         'plsx_split_half_batch_y': ([vp, vp, vp, i32, vp, i32, vp, vp, vp], i32),
@@ -156,7 +159,7 @@ def exported_symbols():
     names = ['plsx_version', 'plsx_max_tprime', 'plsx_ctx_create', 'plsx_ctx_destroy',
              'plsx_last_error', 'plsx_sync', 'plsx_set_data', 'plsx_num_lv', 'plsx_tprime',
              'plsx_crosscov_batch', 'plsx_scratch_read', 'plsx_decompose', 'plsx_set_original', 'plsx_set_contrasts', 'plsx_project',
-             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_crossval_lv_batch', 'plsx_crossval_perm_lv_batch', 'plsx_residualize', 'plsx_set_confounds', 'plsx_crossval_confound_batch', 'plsx_crossval_confound_perm_batch', 'plsx_crossval_confound_group', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
+             'plsx_colmean', 'plsx_perm_batch', 'plsx_perm_batch_y', 'plsx_crossval_batch', 'plsx_crossval_perm_batch', 'plsx_crossval_lv_batch', 'plsx_crossval_perm_lv_batch', 'plsx_residualize', 'plsx_set_confounds', 'plsx_crossval_confound_batch', 'plsx_crossval_confound_perm_batch', 'plsx_crossval_confound_group', 'plsx_boot_batch', 'plsx_boot_begin', 'plsx_boot_finish', 'plsx_boot_route', 'plsx_boot_keep', 'plsx_boot_weights_ci', 'plsx_perm_weights_build', 'plsx_perm_weights_test', 'plsx_perm_weights_scale', 'plsx_split_route', 'plsx_split_half_batch', 'plsx_split_half_batch_y',
              'plsx_boot_rel', 'plsx_last_timing', 'plsx_set_timing', 'plsx_kernel_timing',
              'plsx_kernel_class_name', 'plsx_set_perm_path', 'plsx_set_scratch', 'plsx_mfma_f64_peak',
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
@@ -970,6 +973,59 @@ class Engine(object):
                                                   idx[0][1], idx[1][0], idx[1][1], lo.data_ptr(), hi.data_ptr(),
                                                   self._stream()))
         return lo, hi
+
+    def _check_perm_weights(self, idx_dev, V):
+        """The operands both permutation entries of the x_weights share -> (n, m)."""
+        torch = _torch()
+        if V.dim() != 2 or V.shape[0] != self.Tp or V.dtype != torch.float64 or not V.is_contiguous():
+            raise ValueError('the pattern V must be a contiguous ({}, m) float64 tensor'.format(self.Tp))
+        if idx_dev.dim() != 2 or idx_dev.shape[1] != self.S or idx_dev.dtype != torch.int32 \
+                or not idx_dev.is_contiguous():
+            raise ValueError('the index rows must be a contiguous (n, {}) int32 tensor'.format(self.S))
+        # (the builders index device memory with these values unchecked)
+        if idx_dev.numel() and not (int(idx_dev.min()) >= 0 and int(idx_dev.max()) < self.S):
+            raise IndexError('the index rows must hold row indices in 0 .. {}'.format(self.S - 1))
+        return int(idx_dev.shape[0]), int(V.shape[1])
+
+    def perm_weights_build(self, idx_dev, V):
+        """The subject-space operands of the permutation null of the x_weights: ``idx_dev`` (n, S) int32 index rows,
+        ``V`` (T', m) the observed pattern -> W (n, m, S) device tensor with ``W[p] @ Xf == (R_p.T @ V).T``, R_p the
+        cross-covariance matrix of permutation p and Xf the resample-independent feature matrix of the binding: the
+        per-cell scaled X in correlation mode, else the centred X (plsx_perm_weights_build).  No sync.  PlsxError status
+        -4 without bound PLS-C data, -2 for multiblock data, -1 for m outside 1 .. T'."""
+        n, m = self._check_perm_weights(idx_dev, V)
+        W = self._empty((max(n, 1), max(m, 1), self.S))
+        self._check(self.lib.plsx_perm_weights_build(self.ctx, idx_dev.data_ptr(), n, V.data_ptr(), m, W.data_ptr(),
+                                                     self._stream()))
+        return W
+
+    def perm_weights_test(self, idx_dev, V, obs, count, dmax, standardise=False):
+        """The permutation statistics of the x_weights along ``V`` (T', m) for the index rows ``idx_dev`` (n, S) int32
+        against the observed ``obs`` (B, m) = ``x_weights[:, :m] * singvals[:m]``: ``count`` (B, m) int32 += the number of
+        p with ``q_f |(R_p.T @ V)[f, l]| >= q_f |obs[f, l]|``, ``dmax`` (n, m) = the maximum over the features of the left
+        side; q_f = 1 / s_f (0 for a feature without variance) with s_f the standard deviation of feature f over all rows
+        when ``standardise``, else 1 (plsx_perm_weights_test).  Stateless: counts of disjoint sets of index rows add, their
+        maxima concatenate.  No sync.  PlsxError status -2 (context still usable) when not even 64 permutations fit the
+        scratch budget and for multiblock data, -4 without bound PLS-C data, -1 for m outside 1 .. T'."""
+        torch = _torch()
+        n, m = self._check_perm_weights(idx_dev, V)
+        if tuple(obs.shape) != (self.B, m) or obs.dtype != torch.float64 or not obs.is_contiguous():
+            raise ValueError('the observed statistic must be a contiguous ({}, {}) float64 tensor'.format(self.B, m))
+        if tuple(count.shape) != (self.B, m) or count.dtype != torch.int32 or not count.is_contiguous():
+            raise ValueError('the counts must be a contiguous ({}, {}) int32 tensor'.format(self.B, m))
+        if tuple(dmax.shape) != (n, m) or dmax.dtype != torch.float64 or not dmax.is_contiguous():
+            raise ValueError('the maxima must be a contiguous ({}, {}) float64 tensor'.format(n, m))
+        self._check(self.lib.plsx_perm_weights_test(self.ctx, idx_dev.data_ptr(), n, V.data_ptr(), m, obs.data_ptr(),
+                                                    1 if standardise else 0, count.data_ptr(), dmax.data_ptr(),
+                                                    self._stream()))
+
+    def perm_weights_scale(self):
+        """(B,) device tensor: q_f = 1 / s_f, what ``perm_weights_test(standardise=True)`` scales feature f by -- s_f the
+        standard deviation (ddof = 1) of the bound feature over all rows, q_f = 0 for a feature without variance
+        (plsx_perm_weights_scale).  No sync."""
+        q = self._empty((self.B,))
+        self._check(self.lib.plsx_perm_weights_scale(self.ctx, q.data_ptr(), self._stream()))
+        return q
 
     def simpls_perm_into(self, idx_dev, out_dev):
         """idx_dev (n, S) int32, out_dev (n, k): pctvar of the permuted Y."""

@@ -131,6 +131,40 @@ def _check_weights_ci(weights_ci, method, L, n_boot, bootsamples, contrasts):
     return int(weights_ci)
 
 
+def _check_weights_perm(weights_perm, method, L, n_perm, permsamples, permindices):
+    """What ``weights_perm`` does not cover, refused on the host before any engine is created or looked up -> the number
+    of latent variables m (True: all L; with ``contrasts`` L is their number)."""
+    if method == 'multiblock':
+        raise ValueError('Permutation p-values of the x_weights (`weights_perm`) are not available for multiblock PLS')
+    if not permindices:
+        raise ValueError('`weights_perm` cannot be combined with `permindices=False`: the test rebuilds every permutation '
+                         'from its index row, pre-permuted Y matrices have none')
+    n_perm = n_perm or 0
+    if n_perm > 0 and permsamples is not None and np.ndim(permsamples) == 2:
+        n_perm = np.shape(permsamples)[1]
+    if n_perm < 1:
+        raise ValueError('`weights_perm` needs permutations (`n_perm` > 0)')
+    if weights_perm is True:
+        return L
+    if isinstance(weights_perm, (bool, np.bool_)) or not isinstance(weights_perm, (int, np.integer)) \
+            or not 1 <= int(weights_perm) <= L:
+        raise ValueError('`weights_perm` must be True or a number of latent variables in 1 .. {}; got {!r}'
+                         .format(L, weights_perm))
+    return int(weights_perm)
+
+
+def _weights_perm_pvals(obs, count, wmax):
+    """The three arrays ``weights_perm`` adds to permres.  obs (B, m) = |Z| / s_f, the observed side of the family-wise
+    comparison; count (B, m) = #{p : |Z_p| >= |Z|}; wmax (m, n_perm) = max_f |Z_p[f, l]| / s_f.  The maxT p-value counts,
+    per latent variable, the maxima at or above the observed scaled magnitude: one sort and one searchsorted each."""
+    n_perm = wmax.shape[1]
+    fwe = np.empty(obs.shape)
+    for l in range(obs.shape[1]):
+        null = np.sort(wmax[l])
+        fwe[:, l] = (n_perm - np.searchsorted(null, obs[:, l], side='left') + 1) / (n_perm + 1)
+    return dict(x_weights_pvals=(count + 1) / (n_perm + 1), x_weights_max=wmax, x_weights_pvals_fwe=fwe)
+
+
 def _check_confounds(confounds, X, permindices, cvsplits=None):
     """The checks of ``behavioral_pls(confounds=)``, on the host before any engine is created or looked up (wording of
     ``pls_regression``) -> dict(Z (S, q) float64, Zt = [1, Z - zbar] (S, q + 1), zmean (q,))."""
@@ -222,6 +256,18 @@ class _PLSCRun(object):
                                                kwargs.get('n_boot'), kwargs.get('bootsamples'), self.V is not None)
         else:
             kwargs.pop('weights_ci', None)
+        # weights_perm: LVs whose weights are tested against the permutations (None: not asked for)
+        self.wperm_m = None
+        if kwargs.get('weights_perm', False) is not False and kwargs.get('weights_perm') is not None:
+            Xa = np.asarray(X)
+            T = 1 if Y is None else (np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 0)
+            if Xa.ndim != 2 or T < 1:
+                raise ValueError('Expected 2D arrays for `X` and `Y`')
+            L = self.V.shape[1] if self.V is not None else min(len(groups) * n_cond * T, Xa.shape[1])
+            self.wperm_m = _check_weights_perm(kwargs['weights_perm'], method, L, kwargs.get('n_perm'),
+                                               kwargs.get('permsamples'), kwargs.get('permindices'))
+        else:
+            kwargs.pop('weights_perm', None)
         # measurement hooks of bench.py --mode analysis (not inputs of the analysis): a dict that receives
         # per-phase wall times; (rank, world) of a world emulated on one GPU
         self.cvperm_given = kwargs.pop('_cvpermsamples', None)     # behavioral_pls(cv_perm=): validated (S, P) or None
@@ -494,6 +540,26 @@ class _PLSCRun(object):
             host = eng.perm_ystack(ystack[plo:phi], rotate=rotate) if phi > plo else np.zeros((L, 0))
             d_perm = torch.from_numpy(np.ascontiguousarray(host.T)).to(eng.device)
         tick('permutations')
+        d_wcnt = d_wmax = d_wobs = None
+        if self.wperm_m is not None:
+            # weights_perm: this rank's share of the index rows once more, through the stateless test
+            # (plsx_perm_weights_test): the null Z_p = R_p^T V0 is formed tile by tile, counted against the observed
+            # x_weights @ diag(singvals) and reduced to its maxima over the features; counts and maxima ride in the
+            # collective.  The rows of R are correlations in correlation-mode behavioral PLS; elsewhere the maxima are
+            # taken over |Z_p| / s_f
+            wm = self.wperm_m
+            wstd = not (self.method == 'behavioral' and not inp.get('covariance'))
+            d_wobs = eng.scale_columns(d_xw, d_sv)[:, :wm].contiguous()
+            d_wcnt = torch.zeros((eng.B, wm), dtype=torch.int32, device=eng.device)
+            d_wmax = eng._zeros((phi - plo, wm))
+            if phi > plo:
+                eng.perm_weights_test(eng.rows_tensor(pstream.rows[plo:phi]), d_yw[:, :wm].contiguous(), d_wobs, d_wcnt,
+                                      d_wmax, standardise=wstd)
+            if wstd:
+                d_wobs = d_wobs.abs() * eng.perm_weights_scale()[:, None]      # (the observed side of the maxT comparison)
+            else:
+                d_wobs = d_wobs.abs()
+            tick('weights_perm')
         if bstream is not None:
             # chunk-cyclic share (parallel.shard_chunks): no rank waits for the END of the draw
             # before its device has anything to do
@@ -579,6 +645,9 @@ class _PLSCRun(object):
                 d_perm = torch.cat([d_perm, d_uc, d_vc], dim=1)
                 eng.sync()
                 tick('split_half')
+            if d_wmax is not None:
+                # weights_perm: the maxima ride behind everything else in the permutation block
+                d_perm = torch.cat([d_perm, d_wmax], dim=1)
             slices.append(d_perm)
             totals.append(n_perm_tot)
         cyclic = []
@@ -639,11 +708,13 @@ class _PLSCRun(object):
             totals.append(cvp.n)
             tick('crossval_perm')
         sums = [usum, usq] if usum is not None else []
+        if d_wcnt is not None:
+            sums.append(d_wcnt.to(torch.float64))      # (integers far below 2^53: their sum over the ranks is exact)
         full, summed = parallel.collect_device(slices, totals, sums, cyclic=cyclic, emulate=emulate, team=team)
         if not lead:
             return None                                # rank 0 holds everything the ranks computed: it finishes
         if usum is not None:
-            usum, usq = summed
+            usum, usq = summed[:2]
         tick('collective')
 
         # ---- finish on the device; one trip home -----------------------------------------------------
@@ -651,11 +722,14 @@ class _PLSCRun(object):
         d_perm = distrib = None
         lo_hi = None
         if n_perm_tot > 0:
-            blk = full[k].cpu().numpy().T                                             # (L or 3 L, n_perm)
+            blk = full[k].cpu().numpy().T                                             # (L or 3 L [+ m], n_perm)
             k += 1
             d_perm = np.ascontiguousarray(blk[:Lc])
             if orig_splits is not None:
-                ucorrs, vcorrs = np.ascontiguousarray(blk[L:2 * L]), np.ascontiguousarray(blk[2 * L:])
+                ucorrs, vcorrs = np.ascontiguousarray(blk[L:2 * L]), np.ascontiguousarray(blk[2 * L:3 * L])
+            if d_wmax is not None:
+                wmax = np.ascontiguousarray(blk[blk.shape[0] - self.wperm_m:])         # (m, n_perm)
+                wcnt = np.rint(summed[-1].detach().cpu().numpy()).astype(np.int64)
         h_bsr = h_se = h_dist = None
         if bstream is not None:
             d_full = full[k]                                                           # (n_boot, T', L)
@@ -729,6 +803,8 @@ class _PLSCRun(object):
             res['permres']['permsamples'] = permsamp if ystack is None else \
                 np.transpose(ystack, (1, 2, 0))                   # base.py:638-639 layout
             res['permres']['perm_singval'] = d_perm
+            if d_wmax is not None:
+                res['permres'].update(_weights_perm_pvals(d_wobs.cpu().numpy(), wcnt, wmax))
 
         # ---- scores / loadings (subclass run_pls) --------------------------
         if self.method in ('behavioral', 'multiblock'):
@@ -870,7 +946,7 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
                    contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, cv_lv=False, confounds=None,
-                   **kwargs):
+                   weights_perm=False, **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
     shard the resamples over (module docstring); ``device_ids=[...]`` names them.
 
@@ -889,6 +965,23 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     ``y_loadings_ci``).  The (B, m, n_boot) series is formed on the device one chunk of features at a time and never
     exists whole.  Needs 1 <= ``n_boot`` <= 16384; not available with ``contrasts`` (ValueError).  Every other array of
     the result keeps its bits and a seeded call draws the same resampling arrays.
+
+    ``weights_perm`` (True: all L latent variables; an int m: the first m, 1 <= m <= L, with ``contrasts`` L = Lc; False,
+    the default: nothing is added, nothing is drawn differently, every array keeps its bits): permutation p-values of
+    the x_weights, feature by feature, for the permutations of ``permres.permsamples``.  With V0 = ``y_weights[:, :m]``
+    and R_p the cross-covariance matrix of permutation p, the null is Z_p = R_p.T @ V0 (B, m) -- the permuted
+    cross-covariance read along the observed behavioural pattern -- and the observed statistic Z = ``x_weights[:, :m] *
+    singvals[:m]``, the units of ``weights_ci``.  Where the Procrustes rotation of the permutation test is exact (L = T',
+    every latent variable live) Z_p is the rotated, singular-value-scaled permuted weights, whose column norms are the
+    rotated ``perm_singval``; everywhere else R_p.T @ V0 is its definition, and ``rotate`` does not enter.  ``permres``
+    gains ``x_weights_pvals`` (B, m) = (#{p : |Z_p[f, l]| >= |Z[f, l]|} + 1) / (n_perm + 1); ``x_weights_max`` (m,
+    n_perm) = max_f |Z_p[f, l]| / s_f; ``x_weights_pvals_fwe`` (B, m) = (#{p : x_weights_max[l, p] >= |Z[f, l]| / s_f} +
+    1) / (n_perm + 1), corrected over the features of a latent variable's map (single-step maxT).  s_f = 1 in
+    correlation mode, where the rows of R are correlations already; with ``covariance=True`` s_f is the standard
+    deviation (ddof = 1) of feature f over all rows, and a feature without variance has statistic 0 and both p-values
+    1.  The (B, m, n_perm) series never exists: the device forms it tile by tile, counts and keeps the maxima
+    (plsx_perm_weights_test).  GPUs shard the permutations.  Needs ``n_perm`` > 0 and index permutations
+    (``permindices=False`` raises).  Every other array of the result keeps its bits.
 
     Permutation test of the cross-validation: ``cv_perm=P`` (needs ``test_split`` > 0 and ``test_size`` > 0; 0, the
     default: nothing is added, nothing changes) runs the whole cross-validation, under the same splits, for P
@@ -933,6 +1026,8 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
+    if weights_perm is not False:
+        kwargs['weights_perm'] = weights_perm      # (recorded in `inputs` only when given)
     if confounds is not None:
         cf = _check_confounds(confounds, np.asarray(X), kwargs.get('permindices', True), kwargs.get('_cvsplits'))
         kwargs['confounds'] = cf['Z']              # (recorded in `inputs` only when given)
@@ -981,7 +1076,8 @@ def _meancentered_design(X, groups, n_cond, mean_centering):
 
 def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000, n_boot=5000,
                      n_split=0, rotate=True, ci=95, permsamples=None, bootsamples=None,
-                     seed=None, verbose=True, n_proc=None, contrasts=None, weights_ci=False, **kwargs):
+                     seed=None, verbose=True, n_proc=None, contrasts=None, weights_ci=False, weights_perm=False,
+                     **kwargs):
     """Mean-centred PLS of X (S, B) sorted into groups x conditions; see
     pyls.meancentered_pls (argument checks of pyls/types/meancentered.py:16-38).
 
@@ -989,11 +1085,17 @@ def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000,
     :func:`behavioral_pls`; the bootstrap keeps the mean-centred conventions (no add-back of the original).
 
     ``weights_ci`` (True or an int m): ``bootres.x_weights_ci`` (B, m, 2), percentile intervals of the rotated bootstrap
-    weights in the units of ``x_weights @ diag(singvals)``, as for :func:`behavioral_pls`."""
+    weights in the units of ``x_weights @ diag(singvals)``, as for :func:`behavioral_pls`.
+
+    ``weights_perm`` (True or an int m): ``permres.x_weights_pvals`` / ``x_weights_max`` / ``x_weights_pvals_fwe``, the
+    permutation p-values of the x_weights as for :func:`behavioral_pls`; the permutations move the rows of X across the
+    cells, and s_f is the standard deviation of feature f over all rows."""
     if contrasts is not None:
         kwargs['contrasts'] = contrasts            # (recorded in `inputs` only when given)
     if weights_ci is not False:
         kwargs['weights_ci'] = weights_ci          # (recorded in `inputs` only when given)
+    if weights_perm is not False:
+        kwargs['weights_perm'] = weights_perm      # (recorded in `inputs` only when given)
     _refuse_cv_perm(kwargs, 'mean-centred PLS')
     _refuse_confounds(kwargs, 'mean-centred PLS')
     _refuse_cv_lv(kwargs, 'mean-centred PLS')
@@ -1058,7 +1160,7 @@ def multiblock_pls(X, Y, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000
     the behavioural convention (the original is added back, n_boot + 1).  Result keys are those of
     :func:`behavioral_pls`; a seeded call draws its arrays in the same order.
 
-    Not available (ValueError): ``n_split`` > 0, cross-validation (``test_split``), ``contrasts``,
+    Not available (ValueError): ``n_split`` > 0, cross-validation (``test_split``), ``contrasts``, ``weights_perm``,
     ``permindices=False``, a behaviour block on a subset of the conditions; one group with one condition (the task
     block is identically zero).  ``mean_centering`` is reset with a warning as in :func:`meancentered_pls`."""
     _refuse_cv_perm(kwargs, 'multiblock PLS')

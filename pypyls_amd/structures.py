@@ -99,6 +99,7 @@ class PLSInputs(KeyedRecord):
         'vip_perm',                         # pls_regression: permutation p-values of its VIP scores (only when asked for)
         'contrasts',                        # behavioral_pls / meancentered_pls: non-rotated PLS, (T', Lc) (only when given)
         'weights_ci',                       # behavioral_pls / meancentered_pls: percentile intervals of the x_weights (only when given)
+        'weights_perm',                     # behavioral_pls / meancentered_pls: permutation p-values of the x_weights (only when given)
         'confounds',                        # pls_regression / behavioral_pls: the nuisance variables Z (S, q) (only when given)
         'inner_split',                      # pls_regression: inner folds of the nested cross-validation (only when asked for)
         'cv_lv',                            # behavioral_pls: out-of-sample score correlation of the latent variables (only when given)
@@ -153,8 +154,12 @@ class PLSPermResults(KeyedRecord):
     # pls_regression(vip_components=c, vip_perm=True): vip_pvals (B,) uncorrected one-sided p-values of the VIP scores,
     # vip_max (n_perm,) the null of the max statistic over the features (NaN for a degenerate permuted fit),
     # vip_pvals_fwe (B,) the maxT p-values (family-wise over the features)
+    # behavioral_pls / meancentered_pls(weights_perm=m): x_weights_pvals (B, m) uncorrected two-sided p-values of
+    # x_weights @ diag(singvals) against Z_p = R_p.T @ y_weights[:, :m], x_weights_max (m, n_perm) the null of the max
+    # statistic over the features per latent variable (scaled by the feature's standard deviation outside correlation
+    # mode), x_weights_pvals_fwe (B, m) the maxT p-values (family-wise over the features of one latent variable)
     allowed = ('pvals', 'permsamples', 'perm_singval', 'coefs_pvals', 'coefs_max', 'coefs_pvals_fwe',
-               'vip_pvals', 'vip_max', 'vip_pvals_fwe')
+               'vip_pvals', 'vip_max', 'vip_pvals_fwe', 'x_weights_pvals', 'x_weights_max', 'x_weights_pvals_fwe')
 
 
 class PLSSplitHalfResults(KeyedRecord):
