@@ -1051,6 +1051,53 @@ int plsx_crossval_confound_group(plsx_ctx* ctx);
  *                           _begin: PLSX_ERR_STATE without bound regression data or
  *                           before plsx_simpls_set_classes, PLSX_ERR_ARG for a null
  *                           buffer or capacity < 1.
+ *   plsx_simpls_cv_pred_begin / plsx_simpls_cv_pred_end
+ *                           The out-of-fold predictions themselves: a third series,
+ *                           independent of the two series of counts.  While it is
+ *                           open every plsx_simpls_crossval_batch and every
+ *                           plsx_simpls_crossval_confound_batch of m splits appends m
+ *                           slots [T][S] of doubles to d_pred in submission order,
+ *                           and every plsx_simpls_crossval_nested_batch of n outer
+ *                           splits n slots, those of its OUTER fits.  slot[t][p] is
+ *                           the prediction of behaviour t at row p by the model of
+ *                           c components fitted on the split's training rows,
+ *                             ybar_tr[t] + sum_{j <= c} t_j[p] q_j[t]
+ *                           -- [1, x_p] @ simpls(X_tr, Y_tr, c)['beta'] in the units
+ *                           of the bound (globally centred, on the confound route
+ *                           fold-residualised) Y -- on the usable test rows of the
+ *                           split and NaN on every other row: all S T entries of a
+ *                           slot are written.  After plsx_simpls_set_classes the
+ *                           slot holds the prediction of the RAW indicators
+ *                           (f + sum z_c q_c), the values k_sd_cv_class takes the
+ *                           argmax of and k_sd_cv_auc ranks.  c = 1 .. k is the
+ *                           count of every slot; c = 0 takes, per outer fit of the
+ *                           nested entry, the count its selection has just chosen
+ *                           (read on the device; an undefined group, count 0, gets
+ *                           an all-NaN slot) -- the other two entries then return
+ *                           PLSX_ERR_ARG.  d_ncomp [capacity] int32 or NULL: the
+ *                           count used for every slot.  d_true [capacity][T][S] or
+ *                           NULL: the rows of the fit's own Y at the same positions
+ *                           (on the confound route the fold-residualised Y, which
+ *                           exists on the device only), NaN elsewhere.  Kernel
+ *                           k_sd_cv_pred runs behind k_sd_cv_score (and behind
+ *                           k_sd_cv_class / k_sd_cv_auc / k_sd_cvn_select where they
+ *                           run): one wavefront per kept fit, lanes over positions,
+ *                           no LDS on either solver route; q_j[t] and the update go
+ *                           through the device functions of k_sd_cv_score and
+ *                           k_sd_cv_class, so the values are the ones those kernels
+ *                           scored and do not depend on the batch size, the scratch
+ *                           budget or where a call ends.  The permutation entries
+ *                           append nothing, and every output of every entry keeps its
+ *                           bits with the series open.  A call that would pass
+ *                           `capacity` (slots) returns PLSX_ERR_ARG before it
+ *                           computes or writes anything.  _end, plsx_set_data and a
+ *                           second _begin end the series (the buffers stay the
+ *                           caller's).  _begin: PLSX_ERR_STATE without bound
+ *                           regression data, PLSX_ERR_ARG for a null stack,
+ *                           capacity < 1 or c outside 0 .. k, PLSX_ERR_UNSUPPORTED
+ *                           (context still usable, sizes in the message) for a
+ *                           stack -- 8 S T capacity bytes, twice that with d_true --
+ *                           beyond the scratch budget.
  */
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
@@ -1090,6 +1137,27 @@ int plsx_simpls_cv_class_begin(plsx_ctx* ctx, int32_t* d_conf, long long capacit
 int plsx_simpls_cv_class_end(plsx_ctx* ctx);
 int plsx_simpls_cv_auc_begin(plsx_ctx* ctx, int64_t* d_auc, long long capacity);
 int plsx_simpls_cv_auc_end(plsx_ctx* ctx);
+int plsx_simpls_cv_pred_begin(plsx_ctx* ctx, int c, int32_t* d_ncomp, double* d_pred, double* d_true, long long capacity);
+int plsx_simpls_cv_pred_end(plsx_ctx* ctx);
+
+/* The out-of-fold predictions of the behavioural cross-validation.  While a series is
+ * open every plsx_crossval_batch, plsx_crossval_lv_batch and
+ * plsx_crossval_confound_batch of m splits appends m slots [T][S] of doubles to d_pred
+ * in submission order: slot[t][p] = z V_j^T + mean_train_j(Y) over the live latent
+ * variables -- the `pred` of k_cv_final / k_cvp_final, which those kernels score -- on
+ * the test rows of the split, NaN on its training rows; every entry of a slot is
+ * written (kernel k_cv_pred_export, behind k_cv_final / k_cvp_final).  d_true
+ * [capacity][T][S] or NULL: the observed rows at the same positions, on the confound
+ * route the fold-residualised Y, which exists on the device only.  The permutation
+ * entries append nothing; d_r, d_r2 and d_lv keep their bits with the series open.  A
+ * call that would pass `capacity` (slots) returns PLSX_ERR_ARG before it computes or
+ * writes anything.  _end, plsx_set_data and a second _begin end the series (the
+ * buffers stay the caller's).  _begin: PLSX_ERR_STATE without bound behavioural data,
+ * PLSX_ERR_ARG for a null stack or capacity < 1, PLSX_ERR_UNSUPPORTED (context still
+ * usable, sizes in the message) for a stack -- 8 S T capacity bytes, twice that with
+ * d_true -- beyond the scratch budget. */
+int plsx_crossval_pred_begin(plsx_ctx* ctx, double* d_pred, double* d_true, long long capacity);
+int plsx_crossval_pred_end(plsx_ctx* ctx);
 int plsx_simpls_vip_keep(plsx_ctx* ctx, int c, double* d_G, long long capacity);
 int plsx_simpls_vip_ci(plsx_ctx* ctx, const double* d_G, long long n, int c, int i_lo, double g_lo, int i_hi, double g_hi,
                        double* d_sd, double* d_lo, double* d_hi, void* stream);
@@ -1183,7 +1251,7 @@ int plsx_set_timing(plsx_ctx* ctx, int enable);
  * 2 k_small / k_small_ql (eigen-solve + Procrustes), 3 k_urot (+ split add), 4 k_nt_gemm
  * (+ reduce), 5 k_ucorr_partial, 6 k_simpls_dual, 7 reserved, ..., 9 k_sd_cv_score (with the pair expansion and the
  * reduction over the splits of plsx_simpls_crossval_perm_batch, and k_row_sum / k_sd_sh_prep / k_sd_sh_expand /
- * k_sd_sh_score of plsx_simpls_split_half_batch), ..., 11 k_coef_prod (the feature pass of
+ * k_sd_sh_score of plsx_simpls_split_half_batch, and k_sd_cv_pred / k_cv_pred_export of an open plsx_simpls_cv_pred_begin / plsx_crossval_pred_begin series), ..., 11 k_coef_prod (the feature pass of
  * plsx_simpls_coef_ci; k_vip_prod and k_vip_moments of plsx_simpls_vip_ci and k_coef_perm_prod / k_coef_perm_max /
  * k_col_sd of plsx_simpls_coef_perm_test and k_vip_perm_prod / k_vip_perm_count / k_coef_perm_max of plsx_simpls_vip_perm_test count
  * here too, and so do k_coef_perm_prod / k_coef_perm_max / k_col_rsd of plsx_perm_weights_test, whose builders

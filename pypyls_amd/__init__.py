@@ -16,7 +16,7 @@ from .resampling import (gen_permsamp, gen_bootsamp, gen_splits, dummy_code,  # 
                          dummy_label, permute_cols)
 from .plsc import behavioral_pls, meancentered_pls, multiblock_pls  # noqa: F401
 from .regression import pls_regression, predict, vip  # noqa: F401
-from .discriminant import auc_from_counts, pls_da, predict_class, scores_from_confusion  # noqa: F401
+from .discriminant import auc_from_counts, pls_da, predict_class, roc_curve, scores_from_confusion  # noqa: F401
 from .matlab_io import import_matlab_result  # noqa: F401
 from .io import save_results, load_results  # noqa: F401
 from .engine import release_default_engine  # noqa: F401

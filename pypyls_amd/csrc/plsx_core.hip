@@ -555,6 +555,8 @@ try {
     wkeep_close(ctx);                                  // (... and a kept stack of rotation operands)
     count_close(ctx->cls_series);                      // (... and the class codes of its rows with their open series)
     count_close(ctx->auc_series);
+    pred_close(ctx->pred_series);                      // (... and an open series of out-of-fold predictions)
+    pred_close(ctx->bpred_series);
     ctx->has_cls = 0;
     ctx->pw_rsd = ctx->pw_Xn = 0;                      // (... and what plsx_perm_weights_test derived from its features)
     ctx->cf_q = 0;                                     // (... and the confounds of plsx_simpls_set_confounds)

@@ -224,6 +224,9 @@ int cvperm_impl(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, c
                                        (long long)n * T, ystride);
                     LAUNCHCHK();
                 }
+                // (the observed fold entry: the split's predictions and its fold-residualised Y go to an open series)
+                if (fold == 2)
+                    if (int e = cv_pred_export(ctx, ptr<double>(ctx->pred), mks, 1, Yp, 0, s0 + s, st)) return e;
                 if (d_lv) {
                     KTimer tm(ctx, KC_CVPLV, st);
                     hipLaunchKernelGGL(k_cvp_lv, dim3(mm), dim3(256), (size_t)2 * J * T * 8, st, ptr<double>(ctx->Vs),
@@ -241,6 +244,7 @@ int cvperm_impl(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, c
         HIPCHK(hipMemcpyAsync(d_r, sc.r.p, (size_t)n * T * 8, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(d_r2, sc.r2.p, (size_t)n * T * 8, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (ctx->bpred_series.active) ctx->bpred_series.n += n;
         return PLSX_OK;
     }
     // the mean over the splits, in split order (a NaN score makes its permutation's mean NaN)
@@ -295,6 +299,8 @@ int cvperm_fold_entry(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, in
         return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": cross-validation predicts from a fitted "
                                                 "decomposition, which non-rotated PLS (contrasts are set) does not have");
     if (!ctx->cf_q) return fail(ctx, PLSX_ERR_STATE, w + ": no confounds are bound (plsx_set_confounds)");
+    if (observed)
+        if (int e = cv_pred_reserve(ctx, who, n)) return e;
     HIPCHK(hipSetDevice(ctx->device));
     return cvperm_impl(ctx, who, d_masks, n, observed ? nullptr : d_perm_idx, m, d_r, d_r2, d_lv, d_lv_pairs,
                        static_cast<hipStream_t>(stream), observed ? 2 : 1);

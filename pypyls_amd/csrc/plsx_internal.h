@@ -83,6 +83,19 @@ inline void count_close(CountSeries& s)
     s.active = 0; s.base = nullptr; s.cap = 0; s.n = 0;
 }
 
+// The series of out-of-fold predictions that rides along plsx_simpls_crossval_batch, plsx_simpls_crossval_confound_batch
+// and the outer fits of plsx_simpls_crossval_nested_batch (plsx_simpls_cv_pred_begin; plsx_simpls_api.hip: pred_reserve,
+// pred_launch): one slot [T][S] per observed fit, appended to the caller's stack.
+struct PredSeries {
+    int active = 0;
+    int c = 0;                                          // the component count of every slot; 0: the nested selection's
+    int* ncomp = nullptr;                               // the caller's [cap] int32 of the counts used, or nullptr
+    double* pred = nullptr;                             // the caller's stack [cap][T][S]
+    double* ytrue = nullptr;                            // ... and that of the observed values, or nullptr
+    long long cap = 0, n = 0;                           // slots it holds / slots appended
+};
+inline void pred_close(PredSeries& s) { s = PredSeries(); }
+
 struct plsx_ctx {
     int device = 0;
     std::string err;
@@ -223,6 +236,12 @@ struct plsx_ctx {
     // [k][G][2] int64 appended to the caller's buffer (k_sd_cv_auc): twice the Mann-Whitney U of every class against the
     // rest, and the pairs it was counted over
     CountSeries auc_series{"AUC counts", "plsx_simpls_cv_auc_begin"};
+    // plsx_simpls_cv_pred_begin: the predictions of the observed fits' test rows (k_sd_cv_pred), open or not whatever
+    // the two series of counts are
+    PredSeries pred_series;
+    // plsx_crossval_pred_begin: the same for the behavioural cross-validation -- the `pred` scratch of every split of
+    // plsx_crossval_batch / plsx_crossval_lv_batch / plsx_crossval_confound_batch goes out (k_cv_pred_export; c unused)
+    PredSeries bpred_series;
     // plsx_simpls_set_confounds: cf_q > 0 confounds are bound -- Z~ = [1, Z - zbar] as [16][S] (cfZ) and the Cholesky
     // factor of Z~^T Z~ (cfL); per group of splits of the fold entries P_s, C_s, F_s [ns][q + 1][S], K_s [ns][S][S], the
     // usable test rows [ns], the rank status [ns], the fits' own Y [fits][S][T] and, under permutations, their scores
@@ -524,6 +543,13 @@ int cfb_prepare(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int n, h
 int cfb_fold_X(plsx_ctx* ctx, int s0, int g, double* Xf, hipStream_t st);
 int cfb_fold_Y(plsx_ctx* ctx, int s, const int32_t* d_perm, int mb, int nfit, double* Ys, hipStream_t st);
 int cfb_identity(plsx_ctx* ctx, int* idx, int n, hipStream_t st);
+// ---- plsx_split.hip ----
+// the open series of plsx_crossval_pred_begin: room for m more slots (PLSX_ERR_ARG before anything is computed), and the
+// export of the `pred` scratch [mm][S][T] of a pass into slots slot0 .. of this call (Y: the rows the pass observed,
+// split i at Y + i * ystride)
+int cv_pred_reserve(plsx_ctx* ctx, const char* who, int m);
+int cv_pred_export(plsx_ctx* ctx, const double* pred, const uint8_t* masks, int mm, const double* Y, long long ystride,
+                   long long slot0, hipStream_t st);
 // ---- plsx_cvperm.hip ----
 // both fold entries of the behavioural confound regression: d_perm_idx == nullptr (observed): the identity, m = 1, and
 // the scores of every split instead of their mean

@@ -362,6 +362,27 @@ void k_cv_final(const double* __restrict__ Q /* [m*J][Tp][S] */, const double* _
     }
 }
 
+// The predictions k_cv_final / k_cvp_final left in scratch, out to the caller's stack (plsx_crossval_pred_begin): slot
+// [i][t][p] = pred[i][p][t] on the test rows of split i, NaN on its training rows (which the scratch never held); ytrue,
+// where wanted, the observed rows Y + i * y_stride at the same positions.  Every entry of a slot is written.  The
+// stores are contiguous along p; the loads stride by T doubles, S T of them per split.  grid (ceil(S / 256), m).
+static __global__ __launch_bounds__(256)
+void k_cv_pred_export(const double* __restrict__ pred /* [m][S][T] */, const uint8_t* __restrict__ masks /* [m][S] */,
+                      const double* __restrict__ Y, long long y_stride, int S, int T,
+                      double* __restrict__ out /* [m][T][S] */, double* __restrict__ ytrue /* [m][T][S] or nullptr */)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (p >= S) return;
+    const bool te = !masks[(size_t)i * S + p];
+    const double nan = __builtin_nan("");
+    const double* pr = pred + ((size_t)i * S + p) * T;
+    const double* yr = Y + (size_t)i * y_stride + (size_t)p * T;
+    for (int t = 0; t < T; ++t) {
+        out[((size_t)i * T + t) * S + p] = te ? pr[t] : nan;
+        if (ytrue) ytrue[((size_t)i * T + t) * S + p] = te ? yr[t] : nan;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // out-of-sample score correlation of the latent variables (plsx_crossval_lv_batch, plsx_crossval_perm_lv_batch)
 // ---------------------------------------------------------------------------

@@ -1288,6 +1288,32 @@ __device__ __forceinline__ bool sd_cv_is_test(const SdArgs& a, const uint8_t* pm
     return !pm[p] && (!a.okx || a.okx[p]) && (!a.oky || a.oky[PERM ? ysp[p] : p]);
 }
 
+// One step of the running prediction of a cross-validated fit, yhat_c = yhat_{c-1} + z_c q_c: the ONE expression
+// k_sd_cv_score, k_sd_cv_class, k_sd_cv_auc and k_sd_cv_pred update their predictions with, so that what the last
+// returns is what the others scored, classified and ranked.
+__device__ __forceinline__ double sd_cv_step(double yhat, double z, double q) { return yhat + z * q; }
+
+// The y-loadings q_j[t] = sum_p Y0[t][p] z_j[p] of four components (rows z0 .. z3 of the centred Z, clamped by the
+// caller) as per-lane partial sums for k_sd_cv_pred, in the order of k_sd_cv_score's own loop below: a lane adds the
+// products of the positions it owns in ascending order, whatever the tile, and the caller reduces with wave_sum4 -- the
+// same sums, bit for bit.  (k_sd_cv_score keeps its loop in place, where it takes the test means of the scores along:
+// routed through this function its instantiations come out of the compiler as other code, 100 instructions shorter
+// at RC = 16 and 17 longer at RC = 8; DESIGN.md section 5, "Out-of-fold predictions".)
+template <int RC>
+__device__ __forceinline__ void sd_cv_q4(const double* y0t, const double* z0, const double* z1, const double* z2,
+                                         const double* z3, int S, int lane, double (&q)[4])
+{
+    for (int p0 = 0; p0 < S; p0 += SD_TILE) {
+        SD_TILE_PC(pc, p0);
+        SD_OWN(i) {
+            const bool in = SD_IN(p0, i);
+            const double yv = y0t[pc[i]], y = in ? yv : 0.0;
+            const double a0 = z0[pc[i]], a1 = z1[pc[i]], a2 = z2[pc[i]], a3 = z3[pc[i]];
+            q[0] += y * a0; q[1] += y * a1; q[2] += y * a2; q[3] += y * a3;
+        }
+    }
+}
+
 // Cross-validation of one train / test split (plsx_simpls_crossval_batch), after the solver ran on the training rows
 // (a.pmask: test positions excluded like masked rows) and Z = Vd . K was formed.  With wd_j the dual weights (centred
 // over the training rows, zero elsewhere) and K of the bound, globally centred data,
@@ -1422,7 +1448,7 @@ void k_sd_cv_score(SdArgs a)
                     const double dy = y - ybar;
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        pred += zz[u] * q[u];
+                        pred = sd_cv_step(pred, zz[u], q[u]);
                         const double e = y - pred, d = pred - mh[u];
                         se[u] += te ? e * e : 0.0;
                         shh[u] += te ? d * d : 0.0;
@@ -1551,7 +1577,7 @@ void k_sd_cv_class(SdArgs a)
 #pragma unroll
             for (int g = 0; g < GB; ++g)
                 if (g < G) {
-                    const double v = (c == 0 ? f[g] : yh[(size_t)g * S + p]) + z * q[g];
+                    const double v = sd_cv_step(c == 0 ? f[g] : yh[(size_t)g * S + p], z, q[g]);
                     if (c + 1 < k) yh[(size_t)g * S + p] = v;
                     if (g == 0 || v > best) { best = v; arg = g; }
                 }
@@ -1647,7 +1673,7 @@ void k_sd_cv_auc(SdArgs a)
 #pragma unroll
             for (int g = 0; g < GB; ++g)
                 if (g < G) {
-                    const double v = (c == 0 ? f[g] : yh[(size_t)g * S + i]) + z * q[g];
+                    const double v = sd_cv_step(c == 0 ? f[g] : yh[(size_t)g * S + i], z, q[g]);
                     yh[(size_t)g * S + i] = v;
                 }
         }
@@ -1682,6 +1708,109 @@ void k_sd_cv_auc(SdArgs a)
             }
         }
         wave_cu_sync();                                                    // (this c's reads before the next c's writes)
+    }
+}
+
+// The out-of-fold predictions of an open series (plsx_simpls_cv_pred_begin): which fits of the batch are kept and where.
+struct SdPredArgs {
+    double* pred;               // slots [T][S] of the caller's stack, from the batch's first kept fit on
+    double* ytrue;              // the same slots of the observed values, or nullptr
+    int* ncomp_out;             // [slots] the component count used, or nullptr
+    const int* ncomp_in;        // [slots] the component count to use (the nested selection's; 0: undefined), or nullptr: c
+    int c;                      // ... the count of every slot
+    int unit, slots;            // slot i is fit i * unit of the batch (nested: the outer member of group i)
+};
+
+// The predictions themselves, behind k_sd_cv_score (and k_sd_cv_class / k_sd_cv_auc / k_sd_cvn_select where they run):
+// slot [t][p] = yhat_c[p][t] of the c-component model on the usable test positions p of the fit, NaN on every other
+// position -- all S positions of all T rows are written.  One wavefront per kept fit, lanes over positions, no LDS on
+// either solver route; the running prediction lives in the slot itself, touched by the lane that owns p only.
+//   GB = 0 (regression): q_j[t] from the fit's Y0 and the centred Z by sd_cv_q4 -- four components at a time, wave_sum4,
+//     the order of k_sd_cv_score's own loop -- then yhat = ybar_tr, yhat = sd_cv_step(yhat, z_j, q_j[t]) for j ascending; a row
+//     beyond c in the last group of four has q = 0 and leaves yhat as it is, as a row beyond k does there.
+//   GB > 0 (PLS-DA, the bound of G as in k_sd_cv_class): the prediction of the RAW indicators by sd_cv_roles,
+//     sd_cv_class_f and sd_cv_class_q, one component at a time as in k_sd_cv_class (the roles are written to the first
+//     half of the fit's `va` again: the same ints).
+// ytrue: row p of the fit's own Y (y_stride) at the same positions.
+template <int GB>
+static __global__ __launch_bounds__(256)
+void k_sd_cv_pred(SdArgs a, SdPredArgs pa)
+{
+    constexpr int RC = 8;                                  // (the tile of sd_cv_q4; the sums do not depend on it)
+    const int S = a.S, T = a.T, k = a.k, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar pointers
+    const int slot = blockIdx.x * 4 + wave;
+    if (slot >= pa.slots) return;
+    const int r = slot * pa.unit;
+    int c = pa.ncomp_in ? pa.ncomp_in[slot] : pa.c;
+    c = c < 0 ? 0 : (c > k ? k : c);
+    if (pa.ncomp_out && lane == 0) pa.ncomp_out[slot] = c;
+    const uint8_t* pm = a.pmask + (size_t)r * S;
+    const int* ysp = a.ys + (size_t)r * S;
+    const double* Z = a.cvZ + (size_t)r * k * S;
+    double* out = pa.pred + (size_t)slot * T * S;
+    const double nan = __builtin_nan("");
+    if (pa.ytrue) {
+        const double* Yc = a.Yc + (size_t)r * a.y_stride;
+        double* yt = pa.ytrue + (size_t)slot * T * S;
+        for (int t = 0; t < T; ++t)
+            for (int p = lane; p < S; p += 64)
+                yt[(size_t)t * S + p] = sd_cv_is_test<false>(a, pm, ysp, p) ? Yc[(size_t)p * T + t] : nan;
+    }
+    if (c == 0) {                                          // (an undefined group of the nested selection)
+        for (int i = lane; i < T * S; i += 64) out[i] = nan;
+        return;
+    }
+    if constexpr (GB == 0) {
+        const double* Y0 = a.Y0 + (size_t)r * S * T;
+        const double* ym = a.ymean + (size_t)r * T;
+        for (int t = 0; t < T; ++t) {
+            const double ymt = ym[t];
+            const double* y0t = Y0 + (size_t)t * S;
+            double* o = out + (size_t)t * S;
+            for (int c0 = 0; c0 < c; c0 += 4) {
+                const double* z0 = Z + (size_t)min(c0, k - 1) * S;
+                const double* z1 = Z + (size_t)min(c0 + 1, k - 1) * S;
+                const double* z2 = Z + (size_t)min(c0 + 2, k - 1) * S;
+                const double* z3 = Z + (size_t)min(c0 + 3, k - 1) * S;
+                double q[4] = {0.0, 0.0, 0.0, 0.0};
+                sd_cv_q4<RC>(y0t, z0, z1, z2, z3, S, lane, q);
+                wave_sum4(q[0], q[1], q[2], q[3]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (c0 + u >= c) q[u] = 0.0;
+                const bool last = c0 + 4 >= c;
+                for (int p = lane; p < S; p += 64) {
+                    double pred = c0 == 0 ? ymt : o[p];
+                    pred = sd_cv_step(pred, z0[p], q[0]);
+                    pred = sd_cv_step(pred, z1[p], q[1]);
+                    pred = sd_cv_step(pred, z2[p], q[2]);
+                    pred = sd_cv_step(pred, z3[p], q[3]);
+                    o[p] = (last && !sd_cv_is_test<false>(a, pm, ysp, p)) ? nan : pred;
+                }
+            }
+        }
+    } else {
+        const int G = T;
+        int* role = reinterpret_cast<int*>(a.va + (size_t)r * S);
+        sd_cv_roles<false>(a, r, lane, role);
+        double f[GB];
+        sd_cv_class_f(a, r, f);
+        for (int j = 0; j < c; ++j) {
+            const double* zc = Z + (size_t)j * S;
+            double q[GB];
+            sd_cv_class_q(role, zc, S, G, lane, f, q);
+            const bool last = j + 1 == c;
+            for (int p = lane; p < S; p += 64) {
+                const bool te = role[p] >= 64;
+                const double z = zc[p];
+#pragma unroll
+                for (int g = 0; g < GB; ++g)
+                    if (g < G) {
+                        const double v = sd_cv_step(j == 0 ? f[g] : out[(size_t)g * S + p], z, q[g]);
+                        out[(size_t)g * S + p] = (last && !te) ? nan : v;
+                    }
+            }
+        }
     }
 }
 

@@ -591,6 +591,53 @@ static int count_launch(plsx_ctx* ctx, const CountSeries& s, SdArgs a, int ms, l
     return 0;
 }
 
+// The series of out-of-fold predictions (PredSeries).  Room for m more slots, or PLSX_ERR_ARG before anything is computed
+// or written; `nested`: the entry selects the component count per fit, which a series opened with c = 0 waits for.
+static int pred_reserve(plsx_ctx* ctx, const char* who, int m, bool nested)
+{
+    const PredSeries& s = ctx->pred_series;
+    if (!s.active) return 0;
+    char msg[260];
+    if (s.c == 0 && !nested) {
+        snprintf(msg, sizeof msg, "%s: the open series of predictions takes the component count of the nested selection "
+                 "(c = 0); this entry selects none (plsx_simpls_cv_pred_begin)", who);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    if (s.n + m > s.cap) {
+        snprintf(msg, sizeof msg, "%s: the open series of predictions holds %lld of %lld fits, %d more do not fit "
+                 "(plsx_simpls_cv_pred_begin)", who, s.n, s.cap, m);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    return 0;
+}
+
+// Which fits of a batch the open series keeps: slot `slot0` of this call onwards takes fits 0, unit, 2 unit, ... of the
+// batch, `ncomp` their component counts on the device (the nested selection's) or nullptr: the series' own c.
+struct PredAppend { long long slot0; int unit; const int* ncomp; };
+
+// k_sd_cv_pred on the fits k_sd_cv_score has just scored (and the kernels of the counts have classified), in the
+// scoring kernels' timing class
+static int pred_launch(plsx_ctx* ctx, SdArgs a, int ms, const PredAppend& pa, hipStream_t st)
+{
+    const PredSeries& s = ctx->pred_series;
+    const size_t slot = (size_t)(s.n + pa.slot0), TS = (size_t)a.T * a.S;
+    SdPredArgs q;
+    q.pred = s.pred + slot * TS;
+    q.ytrue = s.ytrue ? s.ytrue + slot * TS : nullptr;
+    q.ncomp_out = s.ncomp ? s.ncomp + slot : nullptr;
+    q.ncomp_in = s.c == 0 ? pa.ncomp : nullptr;
+    q.c = s.c;
+    q.unit = pa.unit; q.slots = ms / pa.unit;
+    const bool da = ctx->has_cls != 0;
+    if (da) { a.cls = ptr<int>(ctx->cls); a.cfreq = ptr<double>(ctx->clsfreq); }
+    KTimer tm(ctx, KC_CVSCORE, st);
+    void (*kernel)(SdArgs, SdPredArgs) =
+        !da ? k_sd_cv_pred<0> : (a.T <= 4 ? k_sd_cv_pred<4> : (a.T <= 16 ? k_sd_cv_pred<16> : k_sd_cv_pred<32>));
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(q.slots, 4)), dim3(256), 0, st, a, q);
+    LAUNCHCHK();
+    return 0;
+}
+
 // Scratch of a cross-validation batch of nb fits: pctvar [nb][k] with the y-loadings [nb][T][k] behind it, the right
 // singular vectors, the dense dual weights Vd and Z = Vd . K
 static int cv_scratch(plsx_ctx* ctx, int nb)
@@ -610,10 +657,11 @@ struct CvScores { double* r; double* r2; double* sse; double* nte; };
 // product with K, the scores, `after_score` in the scores' timed bracket (the reduction of the permuted entry), and the
 // counts of the series that are open, whose blocks are addressed as count_launch says.  nb: the fits cv_scratch was
 // sized for.  ystack / kg: a Y ([ms][S][T]) and a K of the fits' own (the fold-wise confound regression), or the bound ones.
+// pred: what an open series of predictions keeps of the batch (observed fits only), or nullptr: nothing.
 template <bool PERM, class F>
 static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const uint8_t* pmask, const CvScores& out,
                         long long blk0, long long f0, int n, hipStream_t st, F after_score,
-                        const double* ystack = nullptr, const KGroups& kg = KGroups())
+                        const double* ystack = nullptr, const KGroups& kg = KGroups(), const PredAppend* pred = nullptr)
 {
     const int k = ctx->ncomp;
     SdArgs a;
@@ -640,6 +688,9 @@ static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const ui
     for (const CountSeries* s : {&ctx->cls_series, &ctx->auc_series})
         if (s->active)
             if (int e = count_launch<PERM>(ctx, *s, a, ms, blk0, f0, n, st)) return e;
+    if constexpr (!PERM)
+        if (pred && ctx->pred_series.active)
+            if (int e = pred_launch(ctx, a, ms, *pred, st)) return e;
     return 0;
 }
 
@@ -746,6 +797,7 @@ try {
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
     // (an open series of counts that cannot take the call: refused before anything is computed)
+    if (int e = pred_reserve(ctx, "plsx_simpls_crossval_batch", m, false)) return e;
     if (int e = count_reserve(ctx, "plsx_simpls_crossval_batch", m, st)) return e;
     // solver batches as for the permutations; a split also holds its dense dual weights Vd and Z = Vd . K
     const int nb = std::min(m, sd_batch(ctx, 8192, 1, 2.0 * k * S * 8.0));
@@ -755,12 +807,14 @@ try {
         // the fits on the training rows of the splits themselves; one block of counts per split, in submission order
         const CvScores out = {d_r + (size_t)off * k * T, d_r2 + (size_t)off * k * T, d_sse + (size_t)off * (k + 1) * T,
                               nullptr};
+        const PredAppend pa = {off, 1, nullptr};
         if (int e = cv_fit_score<false>(ctx, nb, ms, nullptr, d_masks + (size_t)off * S, out, off, 0, 1, st,
-                                        [] { return 0; }))
+                                        [] { return 0; }, nullptr, KGroups(), &pa))
             return e;
     }
     if (ctx->cls_series.active) ctx->cls_series.n += m;
     if (ctx->auc_series.active) ctx->auc_series.n += m;
+    if (ctx->pred_series.active) ctx->pred_series.n += m;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -844,6 +898,9 @@ static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d
     if (ctx->cf_q)
         return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": confounds are bound; the nested selection is not available with "
                                                    "the fold-wise confound regression");
+    // (an open series of predictions takes the outer fits of the observed entry, m = 1: n slots; the permuted one none)
+    if (!perm)
+        if (int e = pred_reserve(ctx, who, n, true)) return e;
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp, unit = 1 + ni;
@@ -910,10 +967,12 @@ static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d
             LAUNCHCHK();
             return 0;
         };
+        const PredAppend pa = {g0, unit, perm ? nullptr : d_nc + g0};
         if (int e = perm ? cv_fit_score<true>(ctx, nb, ms, ysrc, pm, fs, 0, 0, 1, st, select)
-                         : cv_fit_score<false>(ctx, nb, ms, nullptr, pm, fs, 0, 0, 1, st, select))
+                         : cv_fit_score<false>(ctx, nb, ms, nullptr, pm, fs, 0, 0, 1, st, select, nullptr, KGroups(), &pa))
             return e;
     }
+    if (!perm && ctx->pred_series.active) ctx->pred_series.n += n;
     return PLSX_OK;
 }
 
@@ -978,6 +1037,7 @@ try {
     double kb = 0.0, fb = 0.0;
     int ng = 0;
     if (int e = cf_fold_plan(ctx, "plsx_simpls_crossval_confound_batch", n, 0.0, &kb, &fb, &ng)) return e;
+    if (int e = pred_reserve(ctx, "plsx_simpls_crossval_confound_batch", n, false)) return e;
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp;
@@ -993,10 +1053,12 @@ try {
         const CvScores out = {d_r + (size_t)s0 * k * T, d_r2 + (size_t)s0 * k * T, d_sse + (size_t)s0 * (k + 1) * T, nullptr};
         KGroups kg;
         kg.base = ptr<double>(ctx->cfK); kg.fits = 1;
+        const PredAppend pa = {s0, 1, nullptr};
         if (int e = cv_fit_score<false>(ctx, ng, ns, nullptr, masks, out, 0, 0, 1, st, [] { return 0; },
-                                        ptr<double>(ctx->cfY), kg))
+                                        ptr<double>(ctx->cfY), kg, &pa))
             return e;
     }
+    if (ctx->pred_series.active) ctx->pred_series.n += n;
     return PLSX_OK;
 } PLSX_CATCH(ctx)
 
@@ -1485,6 +1547,41 @@ try {
 int plsx_simpls_cv_auc_end(plsx_ctx* ctx)
 try {
     return count_end(ctx, true);
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cv_pred_begin(plsx_ctx* ctx, int c, int32_t* d_ncomp, double* d_pred, double* d_true, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_REGRESSION)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_cv_pred_begin: data not bound for regression");
+    pred_close(ctx->pred_series);
+    if (!d_pred || capacity < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_simpls_cv_pred_begin: null stack or capacity < 1");
+    char msg[320];
+    if (c < 0 || c > ctx->ncomp) {
+        snprintf(msg, sizeof msg, "plsx_simpls_cv_pred_begin: c = %d outside 1 .. k = %d (0: the count the nested selection "
+                 "chooses per fit)", c, ctx->ncomp);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
+    // the stack is the caller's, and so large that the batches beside it must still find their scratch
+    const double bytes = 8.0 * ctx->S * ctx->T * (double)capacity * (d_true ? 2.0 : 1.0);
+    const double budget = ctx->scratch_gb * 1073741824.0;
+    if (bytes > budget) {
+        snprintf(msg, sizeof msg, "plsx_simpls_cv_pred_begin: a stack of %lld fits x T = %d x S = %d doubles%s is %.3f GB, "
+                 "beyond the scratch budget of %.3f GB (plsx_set_scratch)", capacity, ctx->T, ctx->S,
+                 d_true ? " with the observed values beside it" : "", bytes / 1073741824.0, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    PredSeries& s = ctx->pred_series;
+    s.c = c; s.ncomp = d_ncomp; s.pred = d_pred; s.ytrue = d_true; s.cap = capacity; s.n = 0;
+    s.active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cv_pred_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    pred_close(ctx->pred_series);
+    return PLSX_OK;
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_set_row_masks(plsx_ctx* ctx, const uint8_t* d_okx, const uint8_t* d_oky, void* stream)

@@ -386,14 +386,20 @@ int crossval_entry(plsx_ctx* ctx, const char* who, const uint8_t* d_masks, int m
     if (ctx->nc > 0)
         return fail(ctx, PLSX_ERR_UNSUPPORTED, w + ": cross-validation predicts from a fitted decomposition, "
                                                "which non-rotated PLS (contrasts are set) does not have");
+    if (int e = cv_pred_reserve(ctx, who, m)) return e;
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->momrows) return crossval_impl(ctx, d_masks, m, d_r, d_r2, d_lv, st);
-    HIPCHK(hipStreamSynchronize(st));                  // the row maps of queued launches are about to change
-    if (int e = replan_moments(ctx, 1)) return e;
-    const int rc = crossval_impl(ctx, d_masks, m, d_r, d_r2, d_lv, st);
-    HIPCHK(hipStreamSynchronize(st));
-    if (int e = replan_moments(ctx, 0)) return e;
+    int rc;
+    if (ctx->momrows) {
+        rc = crossval_impl(ctx, d_masks, m, d_r, d_r2, d_lv, st);
+    } else {
+        HIPCHK(hipStreamSynchronize(st));              // the row maps of queued launches are about to change
+        if (int e = replan_moments(ctx, 1)) return e;
+        rc = crossval_impl(ctx, d_masks, m, d_r, d_r2, d_lv, st);
+        HIPCHK(hipStreamSynchronize(st));
+        if (int e = replan_moments(ctx, 0)) return e;
+    }
+    if (rc == PLSX_OK && ctx->bpred_series.active) ctx->bpred_series.n += m;
     return rc;
 }
 
@@ -414,9 +420,60 @@ try {
     return crossval_entry(ctx, "plsx_crossval_lv_batch", d_masks, m, d_r, d_r2, d_lv, true, stream);
 } PLSX_CATCH(ctx)
 
+int plsx_crossval_pred_begin(plsx_ctx* ctx, double* d_pred, double* d_true, long long capacity)
+try {
+    NEED_DATA();
+    if (ctx->method != PLSX_BEHAVIORAL)
+        return fail(ctx, PLSX_ERR_STATE, "plsx_crossval_pred_begin: data not bound for behavioral PLS");
+    pred_close(ctx->bpred_series);
+    if (!d_pred || capacity < 1) return fail(ctx, PLSX_ERR_ARG, "plsx_crossval_pred_begin: null stack or capacity < 1");
+    const double bytes = 8.0 * ctx->S * ctx->T * (double)capacity * (d_true ? 2.0 : 1.0);
+    if (bytes > ctx->scratch_gb * 1073741824.0) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "plsx_crossval_pred_begin: a stack of %lld splits x T = %d x S = %d doubles%s is %.3f GB, "
+                 "beyond the scratch budget of %.3f GB (plsx_set_scratch)", capacity, ctx->T, ctx->S,
+                 d_true ? " with the observed values beside it" : "", bytes / 1073741824.0, ctx->scratch_gb);
+        return fail(ctx, PLSX_ERR_UNSUPPORTED, msg);
+    }
+    PredSeries& s = ctx->bpred_series;
+    s.pred = d_pred; s.ytrue = d_true; s.cap = capacity; s.n = 0;
+    s.active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_crossval_pred_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    pred_close(ctx->bpred_series);
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
 }  // extern "C"
 
 namespace plsxi {
+
+int cv_pred_reserve(plsx_ctx* ctx, const char* who, int m)
+{
+    const PredSeries& s = ctx->bpred_series;
+    if (!s.active || s.n + m <= s.cap) return 0;
+    char msg[260];
+    snprintf(msg, sizeof msg, "%s: the open series of predictions holds %lld of %lld splits, %d more do not fit "
+             "(plsx_crossval_pred_begin)", who, s.n, s.cap, m);
+    return fail(ctx, PLSX_ERR_ARG, msg);
+}
+
+int cv_pred_export(plsx_ctx* ctx, const double* pred, const uint8_t* masks, int mm, const double* Y, long long ystride,
+                   long long slot0, hipStream_t st)
+{
+    const PredSeries& s = ctx->bpred_series;
+    if (!s.active) return 0;
+    const size_t at = (size_t)(s.n + slot0) * ctx->T * ctx->S;
+    KTimer tm(ctx, KC_CVSCORE, st);
+    hipLaunchKernelGGL(k_cv_pred_export, dim3(ceil_div(ctx->S, 256), mm), dim3(256), 0, st, pred, masks, Y, ystride,
+                       ctx->S, ctx->T, s.pred + at, s.ytrue ? s.ytrue + at : nullptr);
+    LAUNCHCHK();
+    return 0;
+}
 
 // d_lv (m, L) != nullptr: also the out-of-sample score correlations of the latent variables (k_cv_lv), from the Q, c,
 // V and d of the same pass
@@ -470,6 +527,7 @@ int crossval_impl(plsx_ctx* ctx, const uint8_t* d_masks, int m, double* d_r, dou
                                ptr<double>(ctx->pred), d_r + (size_t)off * T, d_r2 + (size_t)off * T);
             LAUNCHCHK();
         }
+        if (int e2 = cv_pred_export(ctx, ptr<double>(ctx->pred), mk, mm, ptr<double>(ctx->Y), 0, off, st)) return e2;
         if (d_lv) {
             // the x- and y-scores of the pass's test rows, [mm][S][L] each
             if (int e2 = ensure(ctx, ctx->lvsc, (size_t)2 * mm * S * L * 8)) return e2;

@@ -13,6 +13,8 @@ ratios, intervals and p-values, the regression scores of the cross-validation) i
     counts come back, per split for the observed labels and summed over the splits per permutation;
   * ``auc=True``: the same fits also rank their test rows (plsx_simpls_cv_auc_begin; k_sd_cv_auc) -- per class the
     ordered pairs (row of the class, other row) that its predicted indicator puts in the right order, again integers;
+  * ``cv_predict=``: the predicted indicators of every held-out row themselves (plsx_simpls_cv_pred_begin;
+    k_sd_cv_pred), their first maximum ``cvres.predicted``, and :func:`roc_curve` on the host;
   * :func:`predict_class` for new rows.
 
 There is no split-half reliability (``n_split``) here: the correlation between two halves of indicator loadings answers
@@ -147,7 +149,7 @@ def _label(classes, g):
 def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamples=None, bootsamples=None, seed=None,
            verbose=True, n_proc=None, test_split=0, test_size=0.25, cvsamples=None, cv_perm=0, cvpermsamples=None,
            coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, auc=False, vip_perm=False,
-           **kwargs):
+           cv_predict=False, **kwargs):
     """PLS discriminant analysis of the labels ``y`` (S,) on ``X`` (S, B).
 
     ``classes = np.unique(y)`` (integers, strings, booleans: anything numpy sorts), ``codes`` the position of every
@@ -189,6 +191,14 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
     statistic -- and ``auc_pvals`` (G, k) / ``auc_macro_pvals`` (k,) against ``auc_from_counts(auc_counts.sum(-1))``, by
     the same ``>=`` rule as below; a NaN observed value gives a NaN p-value.  Without ``auc=True`` nothing is added and
     nothing else changes.
+
+    ``cv_predict`` (needs ``test_split`` > 0; ``True`` for the full model or an int c, 1 <= c <= n_components; False, the
+    default: nothing is added and nothing else changes): the predictions themselves.  ``cvres`` gains ``y_pred``
+    (S, G, test_split), the predicted RAW indicators ``yhat_c`` of every usable test row of every split -- the values the
+    argmax above is taken of and ``auc`` ranks; NaN on every other row --, ``y_pred_ncomp`` (test_split,) int32 and
+    ``predicted`` (S, test_split) int32, the index into ``classes`` of the first maximum (-1 off the test rows), from
+    which ``confusion[:, :, c - 1, s]`` can be recounted exactly.  :func:`roc_curve` draws the ROC curve of a class and a
+    split from them.  ``'nested'`` is refused, as ``inner_split`` is.
 
     ``cv_perm=P``: the true class of position p under a permutation is ``codes[perm[p]]``.  The device returns, per
     permutation, the confusion SUMMED over the splits, and ``cvres`` gains ``perm_confusion`` (G, G, k, P),
@@ -255,9 +265,57 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
                          permsamples=permsamples, bootsamples=bootsamples, seed=seed, verbose=verbose, n_proc=n_proc,
                          test_split=test_split, test_size=test_size, cvsamples=cvsamples, cv_perm=cv_perm,
                          cvpermsamples=cvpermsamples, coef_components=coef_components, coef_ci=coef_ci,
-                         coef_perm=coef_perm, vip_components=vip_components, vip_perm=vip_perm, _classes=codes, **kwargs)
+                         coef_perm=coef_perm, vip_components=vip_components, vip_perm=vip_perm, cv_predict=cv_predict,
+                         _classes=codes, **kwargs)
     res['classes'] = classes
     return res
+
+
+def roc_points(scores, positive):
+    """The ROC curve of ``scores`` (n,) against ``positive`` (n,) bool -> ``(fpr, tpr, thresholds)``: one point per
+    distinct score, taken in descending order -- rows with equal scores enter together, so a tie is one point -- after
+    the starting point (0, 0) at threshold +inf.  ``tpr[i]`` / ``fpr[i]`` are the shares of the positive / negative rows
+    with ``score >= thresholds[i]``; NaN where a side is empty.  NaN scores are dropped.  The trapezoid area under the
+    points is the Mann-Whitney AUC with ties counted one half."""
+    scores, positive = np.asarray(scores, dtype=np.float64), np.asarray(positive, dtype=bool)
+    if scores.ndim != 1 or scores.shape != positive.shape:
+        raise ValueError('Expected 1-D `scores` and `positive` of one length, got {} and {}'
+                         .format(scores.shape, positive.shape))
+    keep = ~np.isnan(scores)
+    scores, positive = scores[keep], positive[keep]
+    order = np.argsort(-scores, kind='stable')
+    scores, positive = scores[order], positive[order]
+    last = np.r_[np.flatnonzero(np.diff(scores) != 0), len(scores) - 1] if len(scores) else np.zeros(0, dtype=int)
+    tp = np.r_[0, np.cumsum(positive)[last]].astype(np.float64)
+    fp = np.r_[0, np.cumsum(~positive)[last]].astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        tpr = tp / positive.sum() if positive.sum() else np.full(tp.shape, np.nan)
+        fpr = fp / (~positive).sum() if (~positive).sum() else np.full(fp.shape, np.nan)
+    return fpr, tpr, np.r_[np.inf, scores[last]]
+
+
+def roc_curve(results, cls, split):
+    """The one-vs-rest ROC curve of class ``cls`` (a label of ``results.classes``) on the test rows of cross-validation
+    split ``split`` of a ``pls_da(..., cv_predict=...)`` result -> ``(fpr, tpr, thresholds)`` (:func:`roc_points`), from
+    ``cvres.y_pred[:, g, split]`` and the true classes of the test rows.  Its trapezoid area is
+    ``cvres.auc[g, y_pred_ncomp[split] - 1, split]``.  Works on a result read back by ``load_results`` too.
+    ValueError for a result without ``classes`` or ``cvres.y_pred``, an unknown label, a split out of range."""
+    classes = results.get('classes') if hasattr(results, 'get') else None
+    cvres = results.get('cvres') if hasattr(results, 'get') else None
+    if classes is None or cvres is None or cvres.get('y_pred') is None:
+        raise ValueError('`results` holds no out-of-fold predictions: roc_curve needs a pls_da(..., cv_predict=...) result')
+    classes, y_pred = np.asarray(classes), np.asarray(cvres['y_pred'])
+    hit = np.flatnonzero(classes == cls)
+    if len(hit) != 1:
+        raise ValueError('`cls` = {!r} is not one of the classes {}'.format(cls, classes.tolist()))
+    g = int(hit[0])
+    if isinstance(split, (bool, np.bool_)) or int(split) != split or not 0 <= int(split) < y_pred.shape[2]:
+        raise ValueError('`split` must be an integer in 0 .. {}; got {!r}'.format(y_pred.shape[2] - 1, split))
+    codes = np.asarray(results['inputs']['_classes'] if results['inputs'].get('_classes') is not None
+                       else np.argmax(np.asarray(results['inputs']['Y']), axis=1))
+    v = y_pred[:, g, int(split)]
+    test = ~np.isnan(v)
+    return roc_points(v[test], codes[test] == g)
 
 
 def predict_class(results, X_new, n_components=None):

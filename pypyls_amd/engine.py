@@ -123,6 +123,10 @@ def _load():
         'plsx_simpls_cv_class_end': ([vp], i32),
         'plsx_simpls_cv_auc_begin': ([vp, vp, ctypes.c_longlong], i32),
         'plsx_simpls_cv_auc_end': ([vp], i32),
+        'plsx_simpls_cv_pred_begin': ([vp, i32, vp, vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_cv_pred_end': ([vp], i32),
+        'plsx_crossval_pred_begin': ([vp, vp, vp, ctypes.c_longlong], i32),
+        'plsx_crossval_pred_end': ([vp], i32),
         'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
         'plsx_simpls_vip_ci': ([vp, vp, ctypes.c_longlong, i32, i32, c_d, i32, c_d, vp, vp, vp, vp], i32),
         'plsx_simpls_vip_perm_test': ([vp, vp, ctypes.c_longlong, i32, vp, vp, vp, vp], i32),
@@ -165,7 +169,8 @@ def exported_symbols():
              'plsx_percentile_ci', 'plsx_simpls_decompose', 'plsx_simpls_set_original', 'plsx_simpls_perm_batch',
              'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_crossval_nested_batch', 'plsx_simpls_crossval_nested_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_set_confounds', 'plsx_simpls_crossval_confound_batch', 'plsx_simpls_crossval_confound_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
-             'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end',
+             'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end', 'plsx_simpls_cv_pred_begin', 'plsx_simpls_cv_pred_end',
+             'plsx_crossval_pred_begin', 'plsx_crossval_pred_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_simpls_vip_perm_test', 'plsx_simpls_vip_perm_begin', 'plsx_simpls_vip_perm_end', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
              'plsx_gen_bootsamp_stream', 'plsx_set_option', 'plsx_option_name', 'plsx_numeric_report',
@@ -704,6 +709,27 @@ class Engine(object):
                                                  self._stream()))
         self.sync()
         return r.cpu().numpy().T.copy(), r2.cpu().numpy().T.copy()
+
+    def crossval_pred_begin(self, pred_dev, true_dev=None):
+        """Open a series of out-of-fold predictions: until :meth:`crossval_pred_end` every :meth:`crossval` /
+        :meth:`crossval_confound` of m splits appends m slots (T, S) to ``pred_dev`` (capacity, T, S) float64 in
+        submission order -- the prediction of the test rows of the split, NaN on its training rows -- and to
+        ``true_dev``, where given, the observed rows at the same positions (plsx_crossval_pred_begin).  The tensors
+        must stay alive until the series ends.  PlsxError: status -1 from the call that would pass the capacity, -2
+        (context still usable) for a stack beyond the scratch budget."""
+        torch = _torch()
+        for t in (pred_dev, true_dev):
+            if t is not None and (t.dim() != 3 or tuple(t.shape[1:]) != (self.T, self.S) or t.dtype != torch.float64
+                                  or not t.is_contiguous() or t.shape[0] != pred_dev.shape[0]):
+                raise ValueError('the stacks of predictions must be contiguous (capacity, {}, {}) float64 tensors'
+                                 .format(self.T, self.S))
+        self._check(self.lib.plsx_crossval_pred_begin(self.ctx, pred_dev.data_ptr(),
+                                                      true_dev.data_ptr() if true_dev is not None else None,
+                                                      int(pred_dev.shape[0])))
+
+    def crossval_pred_end(self):
+        """Close the series of out-of-fold predictions (plsx_crossval_pred_end)."""
+        self._check(self.lib.plsx_crossval_pred_end(self.ctx))
 
     def crossval_perm_into(self, masks_dev, idx_dev, r_dev, r2_dev, lv_dev=None, lv_pairs_dev=None):
         """Device form of :meth:`crossval_perm`: masks (n, S) uint8, index rows (m, S) int32 -> r, r2 (m, T), the means
@@ -1347,6 +1373,32 @@ class Engine(object):
     def simpls_cv_auc_end(self):
         """Close the series of AUC counts (plsx_simpls_cv_auc_end)."""
         self._check(self.lib.plsx_simpls_cv_auc_end(self.ctx))
+
+    def simpls_cv_pred_begin(self, c, pred_dev, ncomp_dev=None, true_dev=None):
+        """Open a series of out-of-fold predictions: until :meth:`simpls_cv_pred_end` every :meth:`simpls_crossval_into`
+        / :meth:`simpls_crossval_confound_into` of m splits appends m slots (T, S) to ``pred_dev`` (capacity, T, S)
+        float64 in submission order -- the prediction of the ``c``-component model on the usable test rows of the split,
+        NaN elsewhere -- and every :meth:`simpls_crossval_nested_into` the slots of its outer fits; ``c = 0``: with the
+        component count its selection chose (plsx_simpls_cv_pred_begin).  ``ncomp_dev`` (capacity,) int32 takes the
+        count used per slot, ``true_dev`` (capacity, T, S) the observed values at the same positions.  The tensors must
+        stay alive until the series ends.  PlsxError: status -1 for c outside 0 .. k and from the call that would pass
+        the capacity, -2 (context still usable) for a stack beyond the scratch budget."""
+        torch = _torch()
+        for t in (pred_dev, true_dev):
+            if t is not None and (t.dim() != 3 or tuple(t.shape[1:]) != (self.T, self.S) or t.dtype != torch.float64
+                                  or not t.is_contiguous() or t.shape[0] != pred_dev.shape[0]):
+                raise ValueError('the stacks of predictions must be contiguous (capacity, {}, {}) float64 tensors'
+                                 .format(self.T, self.S))
+        if ncomp_dev is not None and (tuple(ncomp_dev.shape) != (int(pred_dev.shape[0]),) or ncomp_dev.dtype != torch.int32
+                                      or not ncomp_dev.is_contiguous()):
+            raise ValueError('the component counts must be a contiguous (capacity,) int32 tensor')
+        self._check(self.lib.plsx_simpls_cv_pred_begin(
+            self.ctx, int(c), ncomp_dev.data_ptr() if ncomp_dev is not None else None, pred_dev.data_ptr(),
+            true_dev.data_ptr() if true_dev is not None else None, int(pred_dev.shape[0])))
+
+    def simpls_cv_pred_end(self):
+        """Close the series of out-of-fold predictions (plsx_simpls_cv_pred_end)."""
+        self._check(self.lib.plsx_simpls_cv_pred_end(self.ctx))
 
     def simpls_vip_keep(self, stack):
         """Keep the VIP stack of every bootstrap the :meth:`simpls_boot_into` calls that follow solve: ``stack``

@@ -672,6 +672,22 @@ class _PLSCRun(object):
             # (plsx_crossval_lv_batch) and ride in the same slice, 2 T + lvm columns wide
             lvm = self.cv_lv_m or 0
             crossval = eng.crossval if cf is None else eng.crossval_confound
+            d_pred = None
+            if inp.get('cv_predict'):
+                # the out-of-fold predictions of this rank's shard, a slot (T, S) per split, exported by the same pass
+                # (plsx_crossval_pred_begin) -- with the fold-residualised Y beside them on the confound route
+                Tn, Sn = Y.shape[1], len(X)
+                nbytes = 8 * (chi - clo) * Tn * Sn * (2 if cf is not None else 1)
+                free = torch.cuda.mem_get_info(eng.device)[0]
+                if nbytes > free:
+                    raise MemoryError('cv_predict: the stack of predictions of {} splits x T = {} x S = {} is {:.3f} GB{}; '
+                                      '{:.3f} GB of device memory are free'
+                                      .format(chi - clo, Tn, Sn, nbytes / 2 ** 30,
+                                              ' with the fold-residualised Y beside it' if cf is not None else '',
+                                              free / 2 ** 30))
+                d_pred = [eng._empty((chi - clo, Tn, Sn)), eng._empty((chi - clo, Tn, Sn)) if cf is not None else None]
+                if chi > clo:
+                    eng.crossval_pred_begin(*d_pred)
             if chi > clo and lvm:
                 r, r2, lvc = crossval(cv_splits[:, clo:chi], lv=True)
                 local_cv = np.vstack([r, r2, lvc[:lvm]]).T                            # (m_loc, 2 T + lvm)
@@ -682,6 +698,13 @@ class _PLSCRun(object):
                 local_cv = np.zeros((0, 2 * Y.shape[1] + lvm))
             slices.append(torch.from_numpy(np.ascontiguousarray(local_cv)).to(eng.device))
             totals.append(cv_splits.shape[1])
+            if d_pred is not None:
+                if chi > clo:
+                    eng.crossval_pred_end()
+                for t in d_pred:                        # (the prediction rows ride in the same collective)
+                    if t is not None:
+                        slices.append(t)
+                        totals.append(cv_splits.shape[1])
             tick('crossval')
         cvp = self.cvperm_stream if cv_splits is not None else None
         if cvp is not None:
@@ -762,6 +785,12 @@ class _PLSCRun(object):
                                      r_squared=np.ascontiguousarray(cv[Tn:2 * Tn])))
             if lvm:
                 res['cvres']['lv_corr'] = np.ascontiguousarray(cv[2 * Tn:])           # (lvm, test_split)
+            if inp.get('cv_predict'):
+                k += 1
+                res['cvres']['y_pred'] = np.ascontiguousarray(full[k].cpu().numpy().transpose(2, 1, 0))   # (S, T, n)
+                if cf is not None:
+                    k += 1
+                    res['cvres']['y_true'] = np.ascontiguousarray(full[k].cpu().numpy().transpose(2, 1, 0))
             if cvp is not None:
                 k += 1
                 null = full[k].cpu().numpy().T                                        # (2 T [+ lvm], P)
@@ -916,6 +945,31 @@ def _check_cv_lv(cv_lv, X, Y, groups, n_cond, test_split, test_size, contrasts):
     return int(cv_lv)
 
 
+def _check_cv_predict(cv_predict, test_split, test_size, contrasts):
+    """The checks of ``behavioral_pls(cv_predict=)``, on the host before any engine -> True or False."""
+    if cv_predict is None or (isinstance(cv_predict, (bool, np.bool_)) and not cv_predict):
+        return False
+    if not (isinstance(cv_predict, (bool, np.bool_)) and cv_predict):
+        raise ValueError('`cv_predict` must be True or False for behavioral_pls (the prediction uses every live latent '
+                         'variable); got {!r}'.format(cv_predict))
+    if not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+        raise ValueError('`cv_predict` needs cross-validation: the predictions are those of the test rows of `test_split` '
+                         '> 0 splits with `test_size` > 0; got test_split = {!r}, test_size = {!r}'
+                         .format(test_split, test_size))
+    if contrasts is not None:
+        raise ValueError('`cv_predict` is not available with `contrasts`: non-rotated PLS has no fitted decomposition to '
+                         'predict from, its cross-validation is not run')
+    return True
+
+
+def _refuse_cv_predict(kwargs, what):
+    """``cv_predict`` belongs to behavioral_pls (and pls_regression / pls_da): refused on the host, before any engine."""
+    if kwargs.get('cv_predict') not in (None, False):
+        raise ValueError('`cv_predict` (the out-of-fold predictions) is not available for {}: only behavioral PLS is '
+                         'cross-validated'.format(what))
+    kwargs.pop('cv_predict', None)
+
+
 def _refuse_cv_lv(kwargs, what):
     """``cv_lv`` belongs to behavioral_pls: refused on the host, before any engine."""
     if kwargs.get('cv_lv') not in (None, False):
@@ -946,7 +1000,7 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
                    test_size=0.25, test_split=100, covariance=False, rotate=True, ci=95,
                    permsamples=None, bootsamples=None, seed=None, verbose=True, n_proc=None,
                    contrasts=None, weights_ci=False, cv_perm=0, cvpermsamples=None, cv_lv=False, confounds=None,
-                   weights_perm=False, **kwargs):
+                   weights_perm=False, cv_predict=False, **kwargs):
     """Behavioral PLS of X (S, B) against Y (S, T); see pyls.behavioral_pls.  ``n_proc``: GPUs of this node to
     shard the resamples over (module docstring); ``device_ids=[...]`` names them.
 
@@ -1007,6 +1061,15 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     prediction, is only as stable as the gap around its singular value.  Not available with ``contrasts``
     (ValueError).
 
+    Out-of-fold predictions: ``cv_predict=True`` (needs cross-validation; False, the default: nothing is added, nothing
+    is drawn differently, every array keeps its bits) returns what ``cvres.pearson_r`` / ``r_squared`` are reductions
+    of: ``cvres.y_pred`` (S, T, test_split), for a test row of split s ``z V_j^T + mean_train_j(Y)`` over the live
+    latent variables of the training decomposition (the row's cell j), in the units of Y, NaN on the training rows.
+    With ``confounds`` the prediction is that of the fold-residualised test Y, which exists on the device only and
+    comes back as ``cvres.y_true`` (S, T, test_split), NaN off the test rows.  Under ``cv_perm`` only the observed fits
+    are returned.  The stack is 8 S T test_split bytes on the device (twice that with ``confounds``) and rides in the
+    call's one collective.  Not available with ``contrasts`` (ValueError).
+
     Confounds: ``confounds=Z`` (S, q) or (S,), 1 <= q <= 15 (None, the default: nothing is added, nothing is drawn
     differently, every array keeps its bits).  X and Y are residualised on ``[1, Z - zbar]`` -- one intercept and common
     slopes over the whole cohort, whatever the groups and conditions; the per-cell centring follows as always -- once,
@@ -1040,6 +1103,8 @@ def behavioral_pls(X, Y, *, groups=None, n_cond=1, n_perm=5000, n_boot=5000, n_s
     if lvm is not False:
         kwargs['cv_lv'] = cv_lv                    # (recorded in `inputs` only when asked for)
         kwargs['_cv_lv_m'] = lvm
+    if _check_cv_predict(cv_predict, test_split, test_size, contrasts):
+        kwargs['cv_predict'] = True                # (recorded in `inputs` only when asked for)
     run = _PLSCRun('behavioral', np.asarray(X), np.asarray(Y), groups=groups, n_cond=n_cond,
                    n_perm=n_perm, n_boot=n_boot, n_split=n_split, test_size=test_size,
                    test_split=test_split, covariance=covariance, rotate=rotate, ci=ci,
@@ -1099,6 +1164,7 @@ def meancentered_pls(X, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000,
     _refuse_cv_perm(kwargs, 'mean-centred PLS')
     _refuse_confounds(kwargs, 'mean-centred PLS')
     _refuse_cv_lv(kwargs, 'mean-centred PLS')
+    _refuse_cv_predict(kwargs, 'mean-centred PLS')
     X = np.asarray(X)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     run = _PLSCRun('meancentered', X, None, groups=groups, n_cond=n_cond,
@@ -1166,6 +1232,7 @@ def multiblock_pls(X, Y, *, groups=None, n_cond=1, mean_centering=0, n_perm=5000
     _refuse_cv_perm(kwargs, 'multiblock PLS')
     _refuse_confounds(kwargs, 'multiblock PLS')
     _refuse_cv_lv(kwargs, 'multiblock PLS')
+    _refuse_cv_predict(kwargs, 'multiblock PLS')
     X, Y = np.asarray(X), np.asarray(Y)
     groups, mean_centering = _meancentered_design(X, groups, n_cond, mean_centering)
     groups = [int(g) for g in groups]

@@ -57,6 +57,8 @@ Differences from the reference at this commit, on purpose:
     (plsx_simpls_set_classes / plsx_simpls_cv_class_begin; csrc/plsx_simpls.h, k_sd_cv_class).
   * ``_auc`` (build-only, set by ``pls_da(auc=True)``; needs ``_classes``): the cross-validation also returns the
     one-vs-rest AUC counts of every class (plsx_simpls_cv_auc_begin; k_sd_cv_auc).
+  * ``cv_predict``: the out-of-fold predictions of the observed cross-validated fits themselves, one slot per split
+    written behind the scoring kernels (plsx_simpls_cv_pred_begin; csrc/plsx_simpls.h, k_sd_cv_pred).
 """
 import warnings
 
@@ -142,11 +144,39 @@ def nested_codes(cvmasks, innersamples):
     return np.concatenate([cvmasks[:, :, None].astype(np.uint8), np.asarray(innersamples, dtype=np.uint8)], axis=2)
 
 
+def _check_cv_predict(cv_predict, k, test_split, test_size, inner_split, da):
+    """``cv_predict=`` of :func:`pls_regression` / ``pls_da`` -> None (not asked for), the component count 1 .. k of the
+    returned predictions, or 0 for ``'nested'``: the count the nested selection chooses per outer split.  ValueError
+    for anything else, without cross-validation, and for ``'nested'`` without ``inner_split``."""
+    if cv_predict is None or (isinstance(cv_predict, (bool, np.bool_)) and not cv_predict):
+        return None
+    if isinstance(cv_predict, (bool, np.bool_)):
+        c = int(k)
+    elif isinstance(cv_predict, str) and cv_predict == 'nested':
+        if da:
+            raise ValueError("`cv_predict='nested'` is not available for pls_da: it has no nested selection "
+                             '(`inner_split`)')
+        if not inner_split:
+            raise ValueError("`cv_predict='nested'` needs `inner_split` > 0: the component count of every outer split "
+                             'is the one its inner folds choose')
+        c = 0
+    elif isinstance(cv_predict, (int, np.integer)) and 1 <= int(cv_predict) <= int(k):
+        c = int(cv_predict)
+    else:
+        raise ValueError("Provided `cv_predict` must be True, an integer in 1 .. n_components = {}{}; got {!r}"
+                         .format(k, '' if da else " or 'nested'", cv_predict))
+    if not (int(test_split or 0) > 0 and (test_size or 0) > 0):
+        raise ValueError('`cv_predict` needs cross-validation: the predictions are those of the test rows of `test_split` '
+                         '> 0 splits with `test_size` > 0; got test_split = {!r}, test_size = {!r}'
+                         .format(test_split, test_size))
+    return c
+
+
 def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=True, ci=95,
                    aggfunc='mean', permsamples=None, bootsamples=None, seed=None, verbose=True,
                    n_proc=None, test_split=0, test_size=0.25, cvsamples=None, coef_components=None, coef_ci=False,
                    cv_perm=0, cvpermsamples=None, vip_components=None, coef_perm=False, n_split=0, confounds=None,
-                   vip_perm=False, inner_split=0, innersamples=None, **kwargs):
+                   vip_perm=False, inner_split=0, innersamples=None, cv_predict=False, **kwargs):
     """PLS regression of Y (S, T) or (S, T, C) on X (S, B) with SIMPLS; see
     pyls.pls_regression.  ``n_proc``: GPUs of this node to shard the resamples over (one process, team.py);
     ``device_ids=[...]`` names them.
@@ -226,6 +256,19 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     P x test_split x (1 + ni) fits, selected and reduced on the device (plsx_simpls_crossval_nested_batch,
     plsx_simpls_crossval_nested_perm_batch); ranks and teams shard the permutations.  Refused: ``confounds`` and
     ``pls_da``.
+
+    Out-of-fold predictions: ``cv_predict`` (needs cross-validation; False, the default: nothing is added, nothing is
+    drawn differently, every array keeps its bits) returns the predicted value of every held-out row, which the scores
+    above are reductions of: ``True`` for the full model, the one ``cvres.pearson_r`` scores; an int c,
+    1 <= c <= n_components, for the c-component model; ``'nested'`` (needs ``inner_split``) for the model of
+    ``nested_ncomp[s]`` components per outer split s.  ``cvres`` gains ``y_pred`` (S, T, test_split): for a usable test
+    row i of split s ``[1, x_i] @ simpls(X_tr, Y_tr, c)['beta']``, in the units of the Y of the call (3-D Y: of the
+    aggregated Y) -- the scale :func:`predict` answers in --, NaN on training rows and on rows that are NaN throughout;
+    and ``y_pred_ncomp`` (test_split,) int32, the c of every split.  With ``confounds`` ``y_pred`` predicts the
+    fold-residualised test Y from the fold-residualised test X, and ``cvres.y_true`` (S, T, test_split) holds that Y,
+    which exists on the device only (NaN off the test rows).  Under ``cv_perm`` only the observed fits are returned.
+    One c per call, no predictions of inner folds.  The stack is 8 S T test_split bytes on the device (twice that with
+    ``confounds``) and rides in the call's one collective.  A K-fold partition is passed as ``cvsamples``.
 
     VIP scores: ``vip_components=c`` (1 <= c <= n_components, independent of ``coef_components``; None, the default:
     nothing is added, no memory is taken) returns ``vip`` (B,), the variable importance in projection of the
@@ -387,6 +430,11 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             raise ValueError('`inner_split` cannot be combined with `confounds`: the fold-wise confound regression has '
                              'its own K per split (not in this version)')
         kwargs['inner_split'] = inner_split        # (recorded in `inputs` only when asked for)
+    cvpred = _check_cv_predict(cv_predict, n_components, test_split, test_size, inner_split,
+                               kwargs.get('_classes') is not None)
+    if cvpred is not None:                         # (as above: on the host, before any engine)
+        kwargs['cv_predict'] = cv_predict if isinstance(cv_predict, str) else \
+            (True if isinstance(cv_predict, (bool, np.bool_)) else int(cv_predict))   # (recorded only when asked for)
     if n_split is None:
         n_split = 0
     if isinstance(n_split, (bool, np.bool_)) or not isinstance(n_split, (int, np.integer)) or n_split < 0:
@@ -659,6 +707,7 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     if n_cv > 0:
         cv = dict(n=n_cv, masks=cvmasks, classes=kwargs.get('_classes'), given=cvmasks)
         cv['auc'] = bool(kwargs.get('_auc')) and cv['classes'] is not None
+        cv['pred'] = cvpred                            # None, the component count of cv_predict=, or 0: the nested one
         if cvmasks is None:
             # one more job at the END of the list: what a seeded call drew before, it draws still
             def cv_draw(r):
@@ -913,7 +962,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             st.warn()
     # cross-validation: this rank's contiguous shard of the splits (the masks exist once the draws are through), in
     # calls of at most one solver batch
-    d_cv = d_conf = d_confp = d_auc = d_aucp = None
+    d_cv = d_conf = d_confp = d_auc = d_aucp = d_pred = None
     if cv is not None:
         cvmasks = cv['masks']
         if cf is not None and cv.get('given') is None:
@@ -930,6 +979,22 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 d_auc = torch.zeros((hi - lo, k, T, 2), dtype=torch.int64, device=eng.device)
                 if hi > lo:
                     eng.simpls_cv_auc_begin(d_auc)
+        if cv.get('pred') is not None:
+            # the out-of-fold predictions of this rank's shard: one slot (T, S) per split, appended by the batch calls
+            # below -- or, cv_predict='nested', by the outer fits of the nested calls further down -- with the component
+            # count of every slot and, on the confound route, the fold-residualised Y beside it
+            nbytes = 8 * (hi - lo) * T * S * (2 if cf is not None else 1)
+            free = torch.cuda.mem_get_info(eng.device)[0]
+            if nbytes > free:
+                raise MemoryError('cv_predict: the stack of predictions of {} splits x T = {} x S = {} is {:.3f} GB{}; '
+                                  '{:.3f} GB of device memory are free'
+                                  .format(hi - lo, T, S, nbytes / 2 ** 30,
+                                          ' with the fold-residualised Y beside it' if cf is not None else '',
+                                          free / 2 ** 30))
+            d_pred = [eng._empty((hi - lo, T, S)), torch.zeros((hi - lo,), dtype=torch.int32, device=eng.device),
+                      eng._empty((hi - lo, T, S)) if cf is not None else None]
+            if hi > lo and cv['pred'] > 0:
+                eng.simpls_cv_pred_begin(cv['pred'], d_pred[0], d_pred[1], d_pred[2])
         bars.append(Bar('Running cross-validation', hi - lo, show, eng.device))
         for a in range(lo, hi, 8192):
             b = min(hi, a + 8192)
@@ -943,6 +1008,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
             eng.simpls_cv_class_end()
         if d_auc is not None:
             eng.simpls_cv_auc_end()
+        if d_pred is not None and cv['pred'] > 0:
+            eng.simpls_cv_pred_end()                   # (before anything else cross-validates on this context)
         tick('crossval')
     # ... and its permutation test: this rank's contiguous shard of the permutations under ALL the splits.  The
     # (permutation, split) fits are formed, scored and reduced over the splits on the device; a rank keeps three rows
@@ -993,9 +1060,14 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         d_cvn = [eng._zeros((hi - lo, T)), eng._zeros((hi - lo, T)), eng._zeros((hi - lo,)),
                  torch.zeros((hi - lo,), dtype=torch.int32, device=eng.device), eng._zeros((hi - lo, k + 1))]
         step = max(1, 8192 // (1 + ni))
+        nested_pred = d_pred is not None and cv['pred'] == 0 and hi > lo
+        if nested_pred:
+            eng.simpls_cv_pred_begin(0, d_pred[0], d_pred[1], d_pred[2])
         for a in range(lo, hi, step):
             b = min(hi, a + step)
             eng.simpls_crossval_nested_into(d_codes[a:b], *(t[a - lo:b - lo] for t in d_cvn))
+        if nested_pred:
+            eng.simpls_cv_pred_end()
         tick('crossval_nested')
         if cvp is not None:
             lo, hi = parallel.shard_bounds(cvp.n, rank, world)
@@ -1080,6 +1152,10 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     if d_cvnp is not None:                              # ... and their null per permutation
         slices = slices + [d_cvnp[0], d_cvnp[1], d_cvnp[2][:, None], d_cvnp[3].to(torch.float64)]
         totals = totals + [cvp.n] * 4
+    pred_at = len(slices)
+    if d_pred is not None:                              # ... and the out-of-fold predictions, a slot per split
+        slices = slices + [d_pred[0], d_pred[1].to(torch.float64)[:, None]] + ([d_pred[2]] if d_pred[2] is not None else [])
+        totals = totals + [cv['n']] * (3 if d_pred[2] is not None else 2)
     if d_keep is not None:                              # ... and so does the kept stack, chunk-cyclic like d_yl (its
         slices, totals = slices + [d_keep], totals + [n_boot_tot]      # order is irrelevant to order statistics)
         cyclic = cyclic + [len(slices) - 1]
@@ -1174,6 +1250,19 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                     nested_pearson_r_pvals=hostmath.perm_sig(cr['nested_pearson_r'].mean(axis=-1), pr),
                     nested_r_squared_pvals=hostmath.perm_sig(cr['nested_r_squared'].mean(axis=-1), pr2),
                     nested_mse_pvals=float(hostmath.perm_sig(-np.atleast_1d(cr['nested_mse'].mean()), -pmse[None, :])[0])))
+    if d_pred is not None:
+        # (S, T, n); the centring the front end removed before binding is added back: the units of the Y of the call
+        # (not under confounds -- the residuals have no mean -- nor for pls_da, whose slots hold the raw indicators)
+        y_pred = np.ascontiguousarray(full[pred_at].transpose(2, 1, 0))
+        if cf is None and classes is None:
+            y_pred += np.nanmean(Y_agg, axis=0).astype(np.float64)[None, :, None]
+        res['cvres'].update(dict(y_pred=y_pred, y_pred_ncomp=np.rint(full[pred_at + 1][:, 0]).astype(np.int32)))
+        if d_pred[2] is not None:
+            res['cvres']['y_true'] = np.ascontiguousarray(full[pred_at + 2].transpose(2, 1, 0))
+        if classes is not None:
+            test = ~np.asarray(cv['masks'], dtype=bool) & mask[:, None]
+            res['cvres']['predicted'] = np.where(test, np.argmax(np.where(np.isnan(y_pred), -np.inf, y_pred), axis=1),
+                                                 -1).astype(np.int32)
     if d_sh0 is not None:
         orig_uc, orig_vc = (t.cpu().numpy()[0] for t in d_sh0)
         res['splitres'].update(dict(ucorr=orig_uc, vcorr=orig_vc))

@@ -102,6 +102,7 @@ class PLSInputs(KeyedRecord):
         'weights_perm',                     # behavioral_pls / meancentered_pls: permutation p-values of the x_weights (only when given)
         'confounds',                        # pls_regression / behavioral_pls: the nuisance variables Z (S, q) (only when given)
         'inner_split',                      # pls_regression: inner folds of the nested cross-validation (only when asked for)
+        'cv_predict',                       # pls_regression / pls_da / behavioral_pls: the out-of-fold predictions are returned (only when asked for)
         'cv_lv',                            # behavioral_pls: out-of-sample score correlation of the latent variables (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
         '_splitsamples', '_perm_splitsamples', '_cvsplits', '_engine',
@@ -199,7 +200,14 @@ class PLSCrossValidationResults(KeyedRecord):
                # splits of a permutation chose c, nested_pearson_r_pvals / nested_r_squared_pvals (T,), nested_mse_pvals
                'nested_ncomp', 'nested_pearson_r', 'nested_r_squared', 'nested_mse', 'inner_mse', 'innersamples',
                'perm_nested_pearson_r', 'perm_nested_r_squared', 'perm_nested_mse', 'perm_nested_ncomp',
-               'nested_pearson_r_pvals', 'nested_r_squared_pvals', 'nested_mse_pvals')
+               'nested_pearson_r_pvals', 'nested_r_squared_pvals', 'nested_mse_pvals',
+               # behavioral_pls(cv_predict=True): y_pred (S, T, n) and, with confounds=, y_true (S, T, n)
+               # pls_regression / pls_da(cv_predict=): y_pred (S, T, n) the out-of-fold prediction of every usable test
+               # row of every split (NaN elsewhere) by the model of y_pred_ncomp (n,) int32 components, in the units of
+               # the Y of the call (pls_da: the predicted indicators); with confounds= the prediction of the
+               # fold-residualised test Y, which y_true (S, T, n) holds; pls_da: predicted (S, n) int32, the index into
+               # `classes` of the first maximum of the predicted indicators (-1 off the test rows)
+               'y_pred', 'y_pred_ncomp', 'y_true', 'predicted')
 
 
 class PLSResults(KeyedRecord):
