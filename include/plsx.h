@@ -617,7 +617,9 @@ int plsx_crossval_confound_group(plsx_ctx* ctx);
  *                           budget and however the permutations are spread over
  *                           contexts.
  *                           Both nested entries: PLSX_ERR_STATE without bound
- *                           regression data or while a series of counts is open;
+ *                           regression data or while a series of counts per split
+ *                           (plsx_simpls_cv_class_begin / _auc_begin) is open -- the
+ *                           nested counts have their own, plsx_simpls_cvn_class_begin;
  *                           PLSX_ERR_ARG for a null pointer or n, ni, m < 1;
  *                           PLSX_ERR_UNSUPPORTED, the context still usable, with
  *                           bound confounds and when one group of 1 + ni fits does
@@ -1098,7 +1100,55 @@ int plsx_crossval_confound_group(plsx_ctx* ctx);
  *                           (context still usable, sizes in the message) for a
  *                           stack -- 8 S T capacity bytes, twice that with d_true --
  *                           beyond the scratch budget.
+ *   plsx_simpls_cvn_class_begin / plsx_simpls_cvn_class_end
+ *                           PLS discriminant analysis under the nested entries
+ *                           (after plsx_simpls_set_classes): the selection runs on
+ *                           COUNTS and the selected counts come back.  While the
+ *                           series is open every fit of
+ *                           plsx_simpls_crossval_nested_batch / _perm_batch is also
+ *                           classified by k_sd_cv_class (and, d_auc given, ranked by
+ *                           k_sd_cv_auc) into a block of its own in the batch's
+ *                           scratch, [k][G][G] int32 and [k][G][2] int64 per fit,
+ *                           which count towards the batch size and the
+ *                           one-group-must-fit refusal.  Then, per group
+ *                           (k_sd_cvn_class_select in place of k_sd_cvn_select, one
+ *                           wavefront, no atomics), for c = 1 .. k
+ *                             pooled[c] = sum over the ni inner folds, ascending, of
+ *                               the fold's block at c (integers);
+ *                             PLSX_CVN_SELECT_ACCURACY: crit[c] = trace / total of
+ *                               pooled[c], one division;
+ *                             PLSX_CVN_SELECT_BALANCED: crit[c] = the recalls
+ *                               pooled[g][g] / rowsum_g of the classes with
+ *                               rowsum_g > 0, added one by one in ascending g from
+ *                               0.0, divided by their number;
+ *                             best = 1; for c = 2 .. k: if crit[c] > crit[best]:
+ *                               best = c -- the first maximum, a NaN never wins;
+ *                             ncomp = best, or 0 where crit[best] is NaN (no counted
+ *                               row in the pooled block): the group is undefined,
+ *                               its scores NaN and its counts zero;
+ *                             PLSX_CVN_SELECT_MSE: k_sd_cvn_select's own rule.
+ *                           The observed entry appends, per outer split, the OUTER
+ *                           fit's block at c = ncomp to d_conf [capacity][G][G]
+ *                           int32 and d_auc [capacity][G][2] int64 (or NULL: no AUC
+ *                           counts), and pooled[1 .. k] to d_inner_conf
+ *                           [capacity][k][G][G] int32 (or NULL); the permuted entry
+ *                           appends one block per permutation, the sum over its
+ *                           outer splits (k_sd_cvn_class_reduce, next to
+ *                           k_sd_cvn_reduce; integers, so any batch cut gives the
+ *                           same result; d_inner_conf is not written).  d_r, d_r2,
+ *                           d_mse, d_ncomp(_count) and d_inner_mse of both entries
+ *                           are those of THIS selection; an open series of
+ *                           predictions with c = 0 takes its count.  A call that
+ *                           would pass `capacity` (blocks) returns PLSX_ERR_ARG
+ *                           before it computes anything.  _end, plsx_set_data,
+ *                           plsx_simpls_set_classes and a second _begin end the
+ *                           series.  _begin: PLSX_ERR_STATE without bound regression
+ *                           data or before plsx_simpls_set_classes, PLSX_ERR_ARG for
+ *                           a null d_conf, capacity < 1 or an unknown rule.
  */
+#define PLSX_CVN_SELECT_MSE 0
+#define PLSX_CVN_SELECT_ACCURACY 1
+#define PLSX_CVN_SELECT_BALANCED 2
 int plsx_simpls_decompose(plsx_ctx* ctx, double* d_xwT, double* d_pctvar, double* d_cvec,
                           double* d_yload, void* stream);
 int plsx_simpls_set_original(plsx_ctx* ctx, const double* d_w0cT, void* stream);
@@ -1139,6 +1189,9 @@ int plsx_simpls_cv_auc_begin(plsx_ctx* ctx, int64_t* d_auc, long long capacity);
 int plsx_simpls_cv_auc_end(plsx_ctx* ctx);
 int plsx_simpls_cv_pred_begin(plsx_ctx* ctx, int c, int32_t* d_ncomp, double* d_pred, double* d_true, long long capacity);
 int plsx_simpls_cv_pred_end(plsx_ctx* ctx);
+int plsx_simpls_cvn_class_begin(plsx_ctx* ctx, int rule, int32_t* d_conf, int64_t* d_auc, int32_t* d_inner_conf,
+                                long long capacity);
+int plsx_simpls_cvn_class_end(plsx_ctx* ctx);
 
 /* The out-of-fold predictions of the behavioural cross-validation.  While a series is
  * open every plsx_crossval_batch, plsx_crossval_lv_batch and

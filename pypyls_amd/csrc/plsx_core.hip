@@ -417,7 +417,7 @@ try {
                    &ctx->Xn, &ctx->ppart, &ctx->out_row_f, &ctx->mom_idx_f, &ctx->Kd, &ctx->Ad, &ctx->Wd, &ctx->gws, &ctx->cellS, &ctx->rowc, &ctx->out_row_s, &ctx->okx, &ctx->oky, &ctx->psum, &ctx->psq, &ctx->row_slice, &ctx->row_local, &ctx->slice_cell0, &ctx->cell_momrow, &ctx->status, &ctx->ScT, &ctx->out_row_w, &ctx->Qs, &ctx->out_row_d, &ctx->mom_idx_d, &ctx->Afrag_m, &ctx->momn_m, &ctx->scale,
                    &ctx->Afrag_c, &ctx->rank_c, &ctx->rowtab_c, &ctx->m1_c, &ctx->m2_c, &ctx->out_row_c, &ctx->mom_idx_c, &ctx->mask_c,
                    &ctx->refV, &ctx->refLam, &ctx->refK0, &ctx->refPart, &ctx->refPartP, &ctx->refH, &ctx->flipws, &ctx->pflags,
-                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->vpG, &ctx->vpcnt, &ctx->Zcv, &ctx->cfZ, &ctx->cfL, &ctx->cfP, &ctx->cfC, &ctx->cfF, &ctx->cfK, &ctx->cfnte, &ctx->cfstat, &ctx->cfY, &ctx->cffit, &ctx->cvpsrc, &ctx->cvpfit, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
+                   &ctx->Cq, &ctx->Vsumq, &ctx->Vdq, &ctx->Cc, &ctx->Asumc, &ctx->Adc, &ctx->Qc, &ctx->cichunk, &ctx->cpA, &ctx->cppart, &ctx->colsd, &ctx->vpG, &ctx->vpcnt, &ctx->Zcv, &ctx->cfZ, &ctx->cfL, &ctx->cfP, &ctx->cfC, &ctx->cfF, &ctx->cfK, &ctx->cfnte, &ctx->cfstat, &ctx->cfY, &ctx->cffit, &ctx->cvpsrc, &ctx->cvpfit, &ctx->cvncnt, &ctx->shrsum, &ctx->shq, &ctx->shG, &ctx->shKG, &ctx->Vtq, &ctx->Afrag_q, &ctx->qpart, &ctx->ccon, &ctx->sFt, &ctx->Yrot,
                    &ctx->Cv, &ctx->Cfrag, &ctx->cpart, &ctx->mbpart, &ctx->cls, &ctx->clsfreq})
         release(*b);
     for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
@@ -555,6 +555,7 @@ try {
     wkeep_close(ctx);                                  // (... and a kept stack of rotation operands)
     count_close(ctx->cls_series);                      // (... and the class codes of its rows with their open series)
     count_close(ctx->auc_series);
+    ncls_close(ctx->ncls_series);
     pred_close(ctx->pred_series);                      // (... and an open series of out-of-fold predictions)
     pred_close(ctx->bpred_series);
     ctx->has_cls = 0;

@@ -96,6 +96,21 @@ struct PredSeries {
 };
 inline void pred_close(PredSeries& s) { s = PredSeries(); }
 
+// The counts of the nested cross-validation of PLS-DA (plsx_simpls_cvn_class_begin; plsx_simpls_api.hip: cvn_entry): the
+// per-fit blocks of k_sd_cv_class / k_sd_cv_auc stay in the batch's scratch, the selection (k_sd_cvn_class_select) keeps
+// the outer member's block at the selected component count -- one block [G][G] int32 (and [G][2] int64) per outer split
+// of plsx_simpls_crossval_nested_batch, per permutation (summed over its outer splits) of the permuted entry, appended
+// to the caller's buffers.
+struct NestedCounts {
+    int active = 0;
+    int rule = 0;                                       // PLSX_CVN_SELECT_*: what the selection maximises (mse: minimises)
+    int* conf = nullptr;                                // the caller's [cap][G][G] int32
+    long long* auc = nullptr;                           // ... [cap][G][2] int64, or nullptr: no AUC counts
+    int* inner = nullptr;                               // ... [cap][k][G][G] int32 pooled inner counts (observed entry), or nullptr
+    long long cap = 0, n = 0;                           // blocks they hold / blocks appended
+};
+inline void ncls_close(NestedCounts& s) { s = NestedCounts(); }
+
 struct plsx_ctx {
     int device = 0;
     std::string err;
@@ -236,6 +251,10 @@ struct plsx_ctx {
     // [k][G][2] int64 appended to the caller's buffer (k_sd_cv_auc): twice the Mann-Whitney U of every class against the
     // rest, and the pairs it was counted over
     CountSeries auc_series{"AUC counts", "plsx_simpls_cv_auc_begin"};
+    // plsx_simpls_cvn_class_begin: the selected counts of the nested entries; cvncnt: the per-fit blocks of a batch
+    // ([nb][k][G][2] int64 where AUC counts are asked for, [nb][k][G][G] int32) and the selected ones of its groups
+    NestedCounts ncls_series;
+    Buf cvncnt;
     // plsx_simpls_cv_pred_begin: the predictions of the observed fits' test rows (k_sd_cv_pred), open or not whatever
     // the two series of counts are
     PredSeries pred_series;

@@ -1897,34 +1897,34 @@ void k_sd_cvn_expand(const int* __restrict__ perm, const uint8_t* __restrict__ c
 // selects, lanes over t copy.  No atomics, every sum in a fixed order.  nte = nullptr (the fits were scored by the
 // identity variant, which does not write it): the usable test rows of a fit are counted here from its codes -- an
 // integer, so the same double k_sd_cv_score<., true> sums.  out_inner: [groups][k + 1] or nullptr.
-// grid ceil(groups / 4), dynamic LDS 4 (k + 1) doubles.
-static __global__ __launch_bounds__(256)
-void k_sd_cvn_select(const double* __restrict__ r, const double* __restrict__ r2, const double* __restrict__ sse,
-                     const double* __restrict__ nte, const uint8_t* __restrict__ codes, const uint8_t* __restrict__ okx,
-                     const uint8_t* __restrict__ oky, int S, int k, int T, int ni, int groups,
-                     double* __restrict__ out_r, double* __restrict__ out_r2, double* __restrict__ out_mse,
-                     int* __restrict__ out_nc, double* __restrict__ out_inner)
+// grid ceil(groups / 4), dynamic LDS 4 (k + 1) doubles.  The three parts below are shared with k_sd_cvn_class_select.
+
+// the usable test rows of fit f of the batch (wave-uniform)
+__device__ __forceinline__ double sd_cvn_usable_tests(const double* __restrict__ nte, const uint8_t* __restrict__ codes,
+                                                      const uint8_t* __restrict__ okx, const uint8_t* __restrict__ oky,
+                                                      int S, int lane, size_t f)
 {
-    extern __shared__ __attribute__((aligned(16))) double sm_cvn[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = blockIdx.x * 4 + wave;
-    if (g >= groups) return;
-    double* im = sm_cvn + (size_t)wave * (k + 1);
-    const size_t fit0 = (size_t)g * (1 + ni), kT = (size_t)k * T;
-    auto usable_tests = [&](size_t f) {
-        if (nte) return nte[f];
-        const uint8_t* c = codes + f * S;
-        int cnt = 0;
-        for (int p = lane; p < S; p += 64) cnt += (c[p] == 0 && (!okx || okx[p]) && (!oky || oky[p])) ? 1 : 0;
+    if (nte) return nte[f];
+    const uint8_t* c = codes + f * S;
+    int cnt = 0;
+    for (int p = lane; p < S; p += 64) cnt += (c[p] == 0 && (!okx || okx[p]) && (!oky || oky[p])) ? 1 : 0;
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
-        return (double)cnt;
-    };
+    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+    return (double)cnt;
+}
+
+// inner_mse[0 .. k] of group g into im (the wave's LDS slice) and, where asked for, out_inner
+__device__ __forceinline__ void sd_cvn_inner_mse(const double* __restrict__ sse, const double* __restrict__ nte,
+                                                 const uint8_t* __restrict__ codes, const uint8_t* __restrict__ okx,
+                                                 const uint8_t* __restrict__ oky, int S, int k, int T, int ni, int g,
+                                                 int lane, double* im, double* __restrict__ out_inner)
+{
+    const size_t fit0 = (size_t)g * (1 + ni);
     for (int c0 = 0; c0 <= k; c0 += 64) {
         const int c = c0 + lane;
         double acc = 0.0;
         for (int j = 1; j <= ni; ++j) {
-            const double nj = usable_tests(fit0 + j);                          // (wave-uniform)
+            const double nj = sd_cvn_usable_tests(nte, codes, okx, oky, S, lane, fit0 + j);    // (wave-uniform)
             if (c <= k) {
                 const double* row = sse + ((fit0 + j) * (k + 1) + c) * T;
                 double s = 0.0;
@@ -1937,13 +1937,15 @@ void k_sd_cvn_select(const double* __restrict__ r, const double* __restrict__ r2
             if (out_inner) out_inner[(size_t)g * (k + 1) + c] = acc / ni;
         }
     }
-    const double n0 = usable_tests(fit0);
-    wave_sync();
-    int best = 1;
-    for (int c = 2; c <= k; ++c)
-        if (im[c] < im[best]) best = c;
-    const double vbest = im[best];
-    const bool defined = vbest - vbest == 0.0;                                 // (finite: neither NaN nor an infinity)
+}
+
+// the outer member's scores at c = best, or NaN and ncomp = 0 for an undefined group; n0: its usable test rows
+__device__ __forceinline__ void sd_cvn_copy(const double* __restrict__ r, const double* __restrict__ r2,
+                                            const double* __restrict__ sse, int k, int T, int ni, int g, int lane, int best,
+                                            bool defined, double n0, double* __restrict__ out_r, double* __restrict__ out_r2,
+                                            double* __restrict__ out_mse, int* __restrict__ out_nc)
+{
+    const size_t fit0 = (size_t)g * (1 + ni), kT = (size_t)k * T;
     const double nan = __builtin_nan("");
     for (int t = lane; t < T; t += 64) {
         out_r[(size_t)g * T + t] = defined ? r[fit0 * kT + (size_t)(best - 1) * T + t] : nan;
@@ -1956,6 +1958,119 @@ void k_sd_cvn_select(const double* __restrict__ r, const double* __restrict__ r2
         out_mse[g] = defined ? s / n0 : nan;
         out_nc[g] = defined ? best : 0;
     }
+}
+
+static __global__ __launch_bounds__(256)
+void k_sd_cvn_select(const double* __restrict__ r, const double* __restrict__ r2, const double* __restrict__ sse,
+                     const double* __restrict__ nte, const uint8_t* __restrict__ codes, const uint8_t* __restrict__ okx,
+                     const uint8_t* __restrict__ oky, int S, int k, int T, int ni, int groups,
+                     double* __restrict__ out_r, double* __restrict__ out_r2, double* __restrict__ out_mse,
+                     int* __restrict__ out_nc, double* __restrict__ out_inner)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm_cvn[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = blockIdx.x * 4 + wave;
+    if (g >= groups) return;
+    double* im = sm_cvn + (size_t)wave * (k + 1);
+    sd_cvn_inner_mse(sse, nte, codes, okx, oky, S, k, T, ni, g, lane, im, out_inner);
+    const double n0 = sd_cvn_usable_tests(nte, codes, okx, oky, S, lane, (size_t)g * (1 + ni));
+    wave_sync();
+    int best = 1;
+    for (int c = 2; c <= k; ++c)
+        if (im[c] < im[best]) best = c;
+    const double vbest = im[best];
+    const bool defined = vbest - vbest == 0.0;                                 // (finite: neither NaN nor an infinity)
+    sd_cvn_copy(r, r2, sse, k, T, ni, g, lane, best, defined, n0, out_r, out_r2, out_mse, out_nc);
+}
+
+// The selection of a group on COUNTS (PLS-DA; plsx_simpls_cvn_class_begin), in place of k_sd_cvn_select: fconf
+// [fits][k][G][G] int32 and, where AUC counts are asked for, fauc [fits][k][G][2] int64 are the blocks k_sd_cv_class /
+// k_sd_cv_auc have just counted for every fit of the batch (block = fit), G = T.  Per group and c = 1 .. k
+//     pooled[c]  = sum over the inner members j = 1 .. ni, ascending, of fconf_j[c]            (integers; out_iconf)
+//     rule 1, accuracy:           crit[c] = trace(pooled[c]) / total(pooled[c])                (one division)
+//     rule 2, balanced accuracy:  crit[c] = (0.0 + recall_0 + recall_1 + ...) / #classes, recall_g = pooled[g][g] / rowsum_g
+//                                 over the classes with rowsum_g > 0 in ascending g, one by one
+//     rule 0, mse:                k_sd_cvn_select's own rule on inner_mse (same helper, same bits)
+//     best = 1; for c = 2 .. k: if crit[c] > crit[best] then best = c      (first maximum; a NaN never wins)
+//     ncomp = best, or 0 where crit[best] is NaN -- the pooled block has no counted row: the group is undefined, its
+//     scores are NaN and its counts zero
+//     out_conf / out_auc = the OUTER member's block at c = ncomp; r, r2, mse, inner_mse as k_sd_cvn_select writes them.
+// One wavefront per group; the pooled block of the open c, its row sums and its diagonal live in the wave's LDS slice;
+// every lane forms the criterion from them in the same fixed order, lane 0 keeps it.  Integer sums and divisions only:
+// no atomics, nothing to contract.  grid ceil(groups / 4), dynamic LDS 4 (2 (k + 1) doubles + (G G + 2 G) ints).
+static __global__ __launch_bounds__(256)
+void k_sd_cvn_class_select(const double* __restrict__ r, const double* __restrict__ r2, const double* __restrict__ sse,
+                           const double* __restrict__ nte, const uint8_t* __restrict__ codes,
+                           const uint8_t* __restrict__ okx, const uint8_t* __restrict__ oky, int S, int k, int T, int ni,
+                           int groups, int rule, const int* __restrict__ fconf, const long long* __restrict__ fauc,
+                           double* __restrict__ out_r, double* __restrict__ out_r2, double* __restrict__ out_mse,
+                           int* __restrict__ out_nc, double* __restrict__ out_inner, int* __restrict__ out_conf,
+                           long long* __restrict__ out_auc, int* __restrict__ out_iconf)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm_cvn[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = blockIdx.x * 4 + wave;
+    if (g >= groups) return;
+    const int G = T, GG = G * G;
+    double* im = sm_cvn + (size_t)wave * 2 * (k + 1);
+    double* cr = im + (k + 1);
+    int* pool = reinterpret_cast<int*>(sm_cvn + (size_t)8 * (k + 1)) + (size_t)wave * (GG + 2 * G);
+    int* rows = pool + GG;
+    int* diag = rows + G;
+    const size_t fit0 = (size_t)g * (1 + ni);
+    sd_cvn_inner_mse(sse, nte, codes, okx, oky, S, k, T, ni, g, lane, im, out_inner);
+    const double n0 = sd_cvn_usable_tests(nte, codes, okx, oky, S, lane, fit0);
+    if (rule != 0 || out_iconf)
+        for (int c = 1; c <= k; ++c) {
+            for (int i = lane; i < GG; i += 64) {
+                int v = 0;
+                for (int j = 1; j <= ni; ++j) v += fconf[((fit0 + j) * k + (c - 1)) * GG + i];
+                pool[i] = v;
+                if (out_iconf) out_iconf[((size_t)g * k + (c - 1)) * GG + i] = v;
+            }
+            wave_sync();
+            for (int a = lane; a < G; a += 64) {
+                int s = 0;
+                for (int b = 0; b < G; ++b) s += pool[a * G + b];
+                rows[a] = s;
+                diag[a] = pool[a * G + a];
+            }
+            wave_sync();
+            double crit;
+            if (rule == 1) {
+                int trace = 0, total = 0;
+                for (int a = 0; a < G; ++a) { trace += diag[a]; total += rows[a]; }
+                crit = (double)trace / (double)total;
+            } else {
+                double sum = 0.0;
+                int present = 0;
+                for (int a = 0; a < G; ++a)
+                    if (rows[a] > 0) { sum += (double)diag[a] / (double)rows[a]; ++present; }
+                crit = sum / (double)present;
+            }
+            if (lane == 0) cr[c] = crit;
+            wave_sync();                                                       // (this c's reads before the next c's writes)
+        }
+    wave_sync();
+    int best = 1;
+    bool defined;
+    if (rule == 0) {
+        for (int c = 2; c <= k; ++c)
+            if (im[c] < im[best]) best = c;
+        const double vbest = im[best];
+        defined = vbest - vbest == 0.0;                                        // (finite: neither NaN nor an infinity)
+    } else {
+        for (int c = 2; c <= k; ++c)
+            if (cr[c] > cr[best]) best = c;
+        const double vbest = cr[best];
+        defined = vbest == vbest;                                              // (NaN: no counted row in the pooled block)
+    }
+    sd_cvn_copy(r, r2, sse, k, T, ni, g, lane, best, defined, n0, out_r, out_r2, out_mse, out_nc);
+    for (int i = lane; i < GG; i += 64)
+        out_conf[(size_t)g * GG + i] = defined ? fconf[(fit0 * k + (best - 1)) * GG + i] : 0;
+    if (out_auc)
+        for (int i = lane; i < 2 * G; i += 64)
+            out_auc[(size_t)g * 2 * G + i] = defined ? fauc[(fit0 * k + (best - 1)) * 2 * G + i] : 0;
 }
 
 // ... and the reduction over the outer splits, after the selection: out_r / out_r2 [.][T], out_mse [.] of permutation pi
@@ -1987,6 +2102,32 @@ void k_sd_cvn_reduce(const double* __restrict__ r, const double* __restrict__ r2
         int* dst = out_cnt + (size_t)pi * k + (c - 1);
         int acc = *dst;
         for (long long g = lo; g < end; ++g) acc += nc[g - g0] == c ? 1 : 0;
+        *dst = acc;
+    }
+}
+
+// ... and of the selected counts of k_sd_cvn_class_select next to it: out_conf [.][G][G] int32 and out_auc [.][G][2]
+// int64 (or nullptr) of permutation pi take the blocks of its groups in this batch, added to what the earlier batches
+// left there (the entry starts from zero).  Integers: the same result wherever a batch ends.  One thread per entry, no
+// atomics.  grid (ceil(E / 256), perms touched), E = G G + 2 G.
+static __global__ __launch_bounds__(256)
+void k_sd_cvn_class_reduce(const int* __restrict__ conf, const long long* __restrict__ auc, int G, int n, long long g0,
+                           int mg, int* __restrict__ out_conf, long long* __restrict__ out_auc)
+{
+    const int GG = G * G, e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= GG + 2 * G) return;
+    const long long pi = g0 / n + blockIdx.y;
+    const long long lo = pi * n > g0 ? pi * n : g0, end = (pi + 1) * n < g0 + mg ? (pi + 1) * n : g0 + mg;
+    if (e < GG) {
+        int* dst = out_conf + (size_t)pi * GG + e;
+        int acc = *dst;
+        for (long long g = lo; g < end; ++g) acc += conf[(size_t)(g - g0) * GG + e];
+        *dst = acc;
+    } else if (out_auc) {
+        const int i = e - GG;
+        long long* dst = out_auc + (size_t)pi * 2 * G + i;
+        long long acc = *dst;
+        for (long long g = lo; g < end; ++g) acc += auc[(size_t)(g - g0) * 2 * G + i];
         *dst = acc;
     }
 }

@@ -569,18 +569,14 @@ static int count_reserve(plsx_ctx* ctx, const char* who, int m, hipStream_t st)
     return 0;
 }
 
-// The counting kernel of an open series (k_sd_cv_class, or k_sd_cv_auc behind it) on the ms fits k_sd_cv_score has just
-// scored: fit r counts into block (f0 + r) / n - f0 / n behind block `blk0` of this call, the block of the batch's
-// first fit.
+// The counting kernel (k_sd_cv_class, or auc: k_sd_cv_auc behind it) on the ms fits k_sd_cv_score has just scored: fit r
+// counts into block (f0 + r) / n - f0 / n behind `out`, the block of the batch's first fit.
 template <bool PERM>
-static int count_launch(plsx_ctx* ctx, const CountSeries& s, SdArgs a, int ms, long long blk0, long long f0, int n,
-                        hipStream_t st)
+static int count_launch(plsx_ctx* ctx, bool auc, void* out, SdArgs a, int ms, long long f0, int n, hipStream_t st)
 {
-    const bool auc = &s == &ctx->auc_series;
-    char* out = s.base + (size_t)(s.n + blk0) * s.blk_bytes;
     a.cls = ptr<int>(ctx->cls);
     a.cfreq = ptr<double>(ctx->clsfreq);
-    if (auc) a.auc = reinterpret_cast<long long*>(out); else a.conf = reinterpret_cast<int*>(out);
+    if (auc) a.auc = static_cast<long long*>(out); else a.conf = static_cast<int*>(out);
     a.cls_f0 = f0; a.cls_n = n;
     KTimer tm(ctx, auc ? KC_CVAUC : KC_CVCLASS, st);
     void (*kernel)(SdArgs) =
@@ -658,10 +654,14 @@ struct CvScores { double* r; double* r2; double* sse; double* nte; };
 // counts of the series that are open, whose blocks are addressed as count_launch says.  nb: the fits cv_scratch was
 // sized for.  ystack / kg: a Y ([ms][S][T]) and a K of the fits' own (the fold-wise confound regression), or the bound ones.
 // pred: what an open series of predictions keeps of the batch (observed fits only), or nullptr: nothing.
+// fitcnt: the nested selection on counts -- every fit counts into a block of its own in scratch (zeroed by the caller),
+// and `after_score` runs BEHIND the counting kernels, in a scores' bracket of its own.
+struct FitCounts { int* conf; long long* auc; };
 template <bool PERM, class F>
 static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const uint8_t* pmask, const CvScores& out,
                         long long blk0, long long f0, int n, hipStream_t st, F after_score,
-                        const double* ystack = nullptr, const KGroups& kg = KGroups(), const PredAppend* pred = nullptr)
+                        const double* ystack = nullptr, const KGroups& kg = KGroups(), const PredAppend* pred = nullptr,
+                        const FitCounts* fitcnt = nullptr)
 {
     const int k = ctx->ncomp;
     SdArgs a;
@@ -683,11 +683,21 @@ static int cv_fit_score(plsx_ctx* ctx, int nb, int ms, const int* ysrc, const ui
         void (*score_kernel)(SdArgs) = (ms > 2048 && !simpls_global(ctx)) ? k_sd_cv_score<8, PERM> : k_sd_cv_score<16, PERM>;
         hipLaunchKernelGGL(score_kernel, dim3(ceil_div(ms, 4)), dim3(256), 0, st, a);
         LAUNCHCHK();
+        if (!fitcnt)
+            if (int e = after_score()) return e;
+    }
+    if (fitcnt) {
+        if (int e = count_launch<PERM>(ctx, false, fitcnt->conf, a, ms, 0, 1, st)) return e;
+        if (fitcnt->auc)
+            if (int e = count_launch<PERM>(ctx, true, fitcnt->auc, a, ms, 0, 1, st)) return e;
+        KTimer tm(ctx, KC_CVSCORE, st);
         if (int e = after_score()) return e;
     }
     for (const CountSeries* s : {&ctx->cls_series, &ctx->auc_series})
         if (s->active)
-            if (int e = count_launch<PERM>(ctx, *s, a, ms, blk0, f0, n, st)) return e;
+            if (int e = count_launch<PERM>(ctx, s == &ctx->auc_series, s->base + (size_t)(s->n + blk0) * s->blk_bytes, a, ms,
+                                           f0, n, st))
+                return e;
     if constexpr (!PERM)
         if (pred && ctx->pred_series.active)
             if (int e = pred_launch(ctx, a, ms, *pred, st)) return e;
@@ -884,7 +894,9 @@ try {
 // Nested cross-validation, both entries (perm = false: the observed data, Y keeps its rows, m = 1).  The fit list (k_sd_cvn_expand)
 // is cut into solver batches of WHOLE groups of 1 + ni fits, so the selection of a group (k_sd_cvn_select) finds all its
 // members' scores in the batch's scratch; observed: the selected scores are the outputs, permuted: they are reduced over
-// the outer splits in split order (k_sd_cvn_reduce), which does not care where a batch ends.
+// the outer splits in split order (k_sd_cvn_reduce), which does not care where a batch ends.  With the series of
+// plsx_simpls_cvn_class_begin open (PLS-DA) every fit is also classified into a block of its own in scratch, the selection
+// runs on those counts (k_sd_cvn_class_select) and the selected blocks go out as the scores do (k_sd_cvn_class_reduce).
 static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d_codes, int n, int ni,
                      const int32_t* d_perm_idx, int m, double* d_r, double* d_r2, double* d_mse, int32_t* d_nc, double* d_inner, void* stream)
 {
@@ -892,7 +904,11 @@ static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d
     const std::string w = who;
     if (ctx->method != PLSX_REGRESSION) return fail(ctx, PLSX_ERR_STATE, w + ": data not bound for regression");
     if (ctx->cls_series.active || ctx->auc_series.active)
-        return fail(ctx, PLSX_ERR_STATE, w + ": a series of counts is open; the nested selection has none");
+        return fail(ctx, PLSX_ERR_STATE, w + ": a series of counts per split is open (plsx_simpls_cv_class_begin / "
+                                             "plsx_simpls_cv_auc_begin); the nested selection keeps its counts in the series "
+                                             "of plsx_simpls_cvn_class_begin");
+    NestedCounts& nc = ctx->ncls_series;
+    const bool cls = nc.active != 0;
     if ((perm && !d_perm_idx) || !d_codes || !d_r || !d_r2 || !d_mse || !d_nc || (!perm && !d_inner) || n < 1 || ni < 1 || m < 1)
         return fail(ctx, PLSX_ERR_ARG, w + ": bad arguments");
     if (ctx->cf_q)
@@ -901,12 +917,23 @@ static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d
     // (an open series of predictions takes the outer fits of the observed entry, m = 1: n slots; the permuted one none)
     if (!perm)
         if (int e = pred_reserve(ctx, who, n, true)) return e;
+    if (cls && nc.n + (perm ? m : n) > nc.cap) {
+        char msg[260];
+        snprintf(msg, sizeof msg, "%s: the open series of nested counts holds %lld of %lld blocks, %d more do not fit "
+                 "(plsx_simpls_cvn_class_begin)", who, nc.n, nc.cap, perm ? m : n);
+        return fail(ctx, PLSX_ERR_ARG, msg);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIPCHK(hipSetDevice(ctx->device));
     const int S = ctx->S, T = ctx->T, k = ctx->ncomp, unit = 1 + ni;
+    // (PLS-DA: a fit also holds its blocks of counts, [k][G][G] int32 and [k][G][2] int64, a group its selected ones)
+    const size_t GG = (size_t)T * T, G2 = 2 * (size_t)T;
+    const bool cauc = cls && nc.auc;
+    const size_t cnt_fit = cls ? (size_t)k * (GG * 4 + (cauc ? G2 * 8 : 0)) : 0, cnt_group = cls ? GG * 4 + (cauc ? G2 * 8 : 0) : 0;
     // a fit holds what a fit of plsx_simpls_crossval_perm_batch holds; a group also its selected scores
     const size_t kT = (size_t)k * T, per_fit = 2 * kT + (size_t)(k + 1) * T + 1, per_group = 2 * (size_t)T + 2;
-    const double extra = 2.0 * k * S * 8.0 + 5.0 * S + 8.0 * per_fit + 8.0 * per_group / unit;
+    double extra = 2.0 * k * S * 8.0 + 5.0 * S + 8.0 * per_fit + 8.0 * per_group / unit;
+    if (cls) extra += (double)cnt_fit + (double)cnt_group / unit;
     const double fit_bytes = 8.0 * (double)sd_scratch_doubles(S, T, k, simpls_global(ctx)) + extra;
     if ((double)unit * fit_bytes > 0.5 * ctx->scratch_gb * 1073741824.0) {
         char msg[320];
@@ -936,6 +963,25 @@ static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d
     int* gnc = reinterpret_cast<int*>(gmse + gb);
     const uint8_t* okx = ctx->has_okx ? ptr<uint8_t>(ctx->okx) : nullptr;
     const uint8_t* oky = ctx->has_oky ? ptr<uint8_t>(ctx->oky) : nullptr;
+    // the counts of a batch: the 64-bit blocks first -- [nb][k][G][2] of the fits, [gb][G][2] of the groups -- then the
+    // 32-bit ones, [nb][k][G][G] and [gb][G][G]
+    long long* fauc = nullptr; long long* gauc = nullptr;
+    int* fconf = nullptr; int* gconf = nullptr;
+    if (cls) {
+        if (int e = ensure(ctx, ctx->cvncnt, (size_t)nb * cnt_fit + (size_t)gb * cnt_group)) return e;
+        long long* base = ptr<long long>(ctx->cvncnt);
+        if (cauc) { fauc = base; gauc = fauc + (size_t)nb * k * G2; base = gauc + (size_t)gb * G2; }
+        fconf = reinterpret_cast<int*>(base);
+        gconf = fconf + (size_t)nb * k * GG;
+    }
+    int* oconf = cls ? nc.conf + (size_t)nc.n * GG : nullptr;                     // this call's blocks of the series
+    long long* oauc = cauc ? nc.auc + (size_t)nc.n * G2 : nullptr;
+    int* oinner = (cls && !perm && nc.inner) ? nc.inner + (size_t)nc.n * k * GG : nullptr;
+    if (cls && perm) {
+        // ... and so do the sums of the selected counts (k_sd_cvn_class_reduce)
+        HIPCHK(hipMemsetAsync(oconf, 0, (size_t)m * GG * 4, st));
+        if (cauc) HIPCHK(hipMemsetAsync(oauc, 0, (size_t)m * G2 * 8, st));
+    }
     if (perm) {
         // the running sums over the outer splits live in the outputs (k_sd_cvn_reduce)
         HIPCHK(hipMemsetAsync(d_r, 0, (size_t)m * T * 8, st));
@@ -954,25 +1000,48 @@ static int cvn_entry(plsx_ctx* ctx, const char* who, bool perm, const uint8_t* d
                                f0, ysrc, pmask);
             LAUNCHCHK();
         }
+        if (cls) {
+            // (the fits' blocks are counted into with integer atomics: zeroed in stream order before them)
+            HIPCHK(hipMemsetAsync(fconf, 0, (size_t)ms * k * GG * 4, st));
+            if (cauc) HIPCHK(hipMemsetAsync(fauc, 0, (size_t)ms * k * G2 * 8, st));
+        }
         auto select = [&] {
-            hipLaunchKernelGGL(k_sd_cvn_select, dim3(ceil_div(mg, 4)), dim3(256), (size_t)4 * (k + 1) * 8, st, fs.r, fs.r2,
-                               fs.sse, fs.nte, pm, okx, oky, S, k, T, ni, mg, perm ? gr : d_r + (size_t)g0 * T,
-                               perm ? gr2 : d_r2 + (size_t)g0 * T, perm ? gmse : d_mse + g0, perm ? gnc : d_nc + g0,
-                               perm ? nullptr : d_inner + (size_t)g0 * (k + 1));
+            if (cls)
+                hipLaunchKernelGGL(k_sd_cvn_class_select, dim3(ceil_div(mg, 4)), dim3(256),
+                                   (size_t)4 * (2 * (k + 1) * 8 + (GG + G2) * 4), st, fs.r, fs.r2, fs.sse, fs.nte, pm, okx, oky,
+                                   S, k, T, ni, mg, nc.rule, fconf, fauc, perm ? gr : d_r + (size_t)g0 * T,
+                                   perm ? gr2 : d_r2 + (size_t)g0 * T, perm ? gmse : d_mse + g0, perm ? gnc : d_nc + g0,
+                                   perm ? nullptr : d_inner + (size_t)g0 * (k + 1), perm ? gconf : oconf + (size_t)g0 * GG,
+                                   perm ? gauc : (cauc ? oauc + (size_t)g0 * G2 : nullptr),
+                                   oinner ? oinner + (size_t)g0 * k * GG : nullptr);
+            else
+                hipLaunchKernelGGL(k_sd_cvn_select, dim3(ceil_div(mg, 4)), dim3(256), (size_t)4 * (k + 1) * 8, st, fs.r, fs.r2,
+                                   fs.sse, fs.nte, pm, okx, oky, S, k, T, ni, mg, perm ? gr : d_r + (size_t)g0 * T,
+                                   perm ? gr2 : d_r2 + (size_t)g0 * T, perm ? gmse : d_mse + g0, perm ? gnc : d_nc + g0,
+                                   perm ? nullptr : d_inner + (size_t)g0 * (k + 1));
             LAUNCHCHK();
             if (!perm) return 0;
             const int touched = (int)((g0 + mg - 1) / n - g0 / n) + 1;
             hipLaunchKernelGGL(k_sd_cvn_reduce, dim3(ceil_div(2 * T + 1 + k, 256), touched), dim3(256), 0, st, gr, gr2, gmse,
                                gnc, k, T, n, g0, mg, d_r, d_r2, d_mse, d_nc);
             LAUNCHCHK();
+            if (cls) {
+                hipLaunchKernelGGL(k_sd_cvn_class_reduce, dim3(ceil_div((int)(GG + G2), 256), touched), dim3(256), 0, st,
+                                   gconf, gauc, T, n, g0, mg, oconf, oauc);
+                LAUNCHCHK();
+            }
             return 0;
         };
         const PredAppend pa = {g0, unit, perm ? nullptr : d_nc + g0};
-        if (int e = perm ? cv_fit_score<true>(ctx, nb, ms, ysrc, pm, fs, 0, 0, 1, st, select)
-                         : cv_fit_score<false>(ctx, nb, ms, nullptr, pm, fs, 0, 0, 1, st, select, nullptr, KGroups(), &pa))
+        const FitCounts fc = {fconf, fauc};
+        if (int e = perm ? cv_fit_score<true>(ctx, nb, ms, ysrc, pm, fs, 0, 0, 1, st, select, nullptr, KGroups(), nullptr,
+                                              cls ? &fc : nullptr)
+                         : cv_fit_score<false>(ctx, nb, ms, nullptr, pm, fs, 0, 0, 1, st, select, nullptr, KGroups(), &pa,
+                                               cls ? &fc : nullptr))
             return e;
     }
     if (!perm && ctx->pred_series.active) ctx->pred_series.n += n;
+    if (cls) nc.n += perm ? m : n;
     return PLSX_OK;
 }
 
@@ -1493,6 +1562,7 @@ try {
         return fail(ctx, PLSX_ERR_STATE, "plsx_simpls_set_classes: data not bound for regression");
     count_close(ctx->cls_series);
     count_close(ctx->auc_series);
+    ncls_close(ctx->ncls_series);
     ctx->has_cls = 0;
     if (!d_class) return PLSX_OK;                      // (a null pointer clears the binding)
     char msg[200];
@@ -1547,6 +1617,31 @@ try {
 int plsx_simpls_cv_auc_end(plsx_ctx* ctx)
 try {
     return count_end(ctx, true);
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cvn_class_begin(plsx_ctx* ctx, int rule, int32_t* d_conf, int64_t* d_auc, int32_t* d_inner_conf,
+                                long long capacity)
+try {
+    NEED_DATA();
+    const std::string who = "plsx_simpls_cvn_class_begin";
+    if (ctx->method != PLSX_REGRESSION) return fail(ctx, PLSX_ERR_STATE, who + ": data not bound for regression");
+    if (!ctx->has_cls) return fail(ctx, PLSX_ERR_STATE, who + ": plsx_simpls_set_classes has not been called");
+    ncls_close(ctx->ncls_series);
+    if (!d_conf || capacity < 1) return fail(ctx, PLSX_ERR_ARG, who + ": null buffer or capacity < 1");
+    if (rule != PLSX_CVN_SELECT_MSE && rule != PLSX_CVN_SELECT_ACCURACY && rule != PLSX_CVN_SELECT_BALANCED)
+        return fail(ctx, PLSX_ERR_ARG, who + ": unknown selection rule");
+    NestedCounts& s = ctx->ncls_series;
+    s.rule = rule; s.conf = d_conf; s.auc = reinterpret_cast<long long*>(d_auc); s.inner = d_inner_conf;
+    s.cap = capacity; s.n = 0;
+    s.active = 1;
+    return PLSX_OK;
+} PLSX_CATCH(ctx)
+
+int plsx_simpls_cvn_class_end(plsx_ctx* ctx)
+try {
+    if (!ctx) return PLSX_ERR_ARG;
+    ncls_close(ctx->ncls_series);
+    return PLSX_OK;
 } PLSX_CATCH(ctx)
 
 int plsx_simpls_cv_pred_begin(plsx_ctx* ctx, int c, int32_t* d_ncomp, double* d_pred, double* d_true, long long capacity)

@@ -15,6 +15,9 @@ ratios, intervals and p-values, the regression scores of the cross-validation) i
     ordered pairs (row of the class, other row) that its predicted indicator puts in the right order, again integers;
   * ``cv_predict=``: the predicted indicators of every held-out row themselves (plsx_simpls_cv_pred_begin;
     k_sd_cv_pred), their first maximum ``cvres.predicted``, and :func:`roc_curve` on the host;
+  * ``inner_split=``: nested cross-validation of ``n_components`` -- inner folds inside the training rows of every
+    split choose the component count on their pooled confusion counts (or the inner mse), the outer test rows score
+    the chosen model (plsx_simpls_cvn_class_begin; k_sd_cvn_class_select, k_sd_cvn_class_reduce);
   * :func:`predict_class` for new rows.
 
 There is no split-half reliability (``n_split``) here: the correlation between two halves of indicator loadings answers
@@ -115,6 +118,80 @@ def auc_results(blocks, perm_blocks=None):
     return out
 
 
+INNER_SELECT = ('balanced_accuracy', 'accuracy', 'mse')     # the criteria of the nested selection; the call names one
+
+
+def nested_criterion(conf, rule):
+    """The criterion of the nested selection on one block of counts conf (G, G) [true class, predicted class]:
+    ``'accuracy'``: trace / total, one division; ``'balanced_accuracy'``: the recalls ``conf[g, g] / conf[g].sum()`` of
+    the classes with a counted row, added one by one in ascending g starting from 0.0, divided by their number -- the
+    operations of the device kernel (k_sd_cvn_class_select) in its order, so the two agree to the bit.  NaN for a block
+    without a counted row."""
+    conf = np.asarray(conf)
+    if conf.ndim != 2 or conf.shape[0] != conf.shape[1]:
+        raise ValueError('Expected confusion counts of shape (G, G), got {}'.format(conf.shape))
+    G = conf.shape[0]
+    rows = [int(sum(int(v) for v in conf[g])) for g in range(G)]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if rule == 'accuracy':
+            return float(np.float64(sum(int(conf[g, g]) for g in range(G))) / np.float64(sum(rows)))
+        if rule == 'balanced_accuracy':
+            acc, present = np.float64(0.0), 0
+            for g in range(G):
+                if rows[g] > 0:
+                    acc = acc + np.float64(int(conf[g, g])) / np.float64(rows[g])
+                    present += 1
+            return float(acc / np.float64(present))
+    raise ValueError("`rule` must be 'accuracy' or 'balanced_accuracy'; got {!r}".format(rule))
+
+
+def nested_select(crit, smaller=False):
+    """The selection rule on crit (k,), the criterion of c = 1 .. k components: the first maximum (``smaller``: the first
+    minimum, the rule of the inner mse) -- ties go to the smaller model, a NaN never wins.  -> c, or 0 where the
+    optimum is NaN (``smaller``: not finite): the group is undefined."""
+    crit = np.asarray(crit, dtype=np.float64)
+    best = 0
+    for c in range(1, len(crit)):
+        if (crit[c] < crit[best]) if smaller else (crit[c] > crit[best]):
+            best = c
+    ok = np.isfinite(crit[best]) if smaller else not np.isnan(crit[best])
+    return best + 1 if ok else 0
+
+
+def nested_results(blocks, inner_blocks, auc_blocks=None, perm_blocks=None, perm_auc_blocks=None):
+    """The keys ``pls_da(inner_split=)`` adds to ``cvres`` from what the device selected and counted: blocks (n, G, G)
+    the outer fits' confusion at the selected component count, inner_blocks (n, k, G, G) the confusion pooled over the
+    inner folds, auc_blocks (n, G, 2); with ``cv_perm``, perm_blocks (P, G, G) / perm_auc_blocks (P, G, 2) summed over the
+    outer splits of every permutation (float64 holding integers)."""
+    def ints(a, axes):
+        return np.ascontiguousarray(np.rint(np.asarray(a)).astype(np.int64).transpose(axes))
+    conf = ints(blocks, (1, 2, 0))                                   # (G, G, n)
+    iconf = ints(inner_blocks, (2, 3, 1, 0))                         # (G, G, k, n)
+    acc, bal = scores_from_confusion(conf)
+    iacc, ibal = scores_from_confusion(iconf)
+    out = dict(nested_confusion=conf, nested_accuracy=acc, nested_balanced_accuracy=bal, inner_confusion=iconf,
+               inner_accuracy=iacc, inner_balanced_accuracy=ibal)
+    if auc_blocks is not None:
+        cnt = ints(auc_blocks, (1, 2, 0))                            # (G, 2, n)
+        auc, macro = auc_from_counts(cnt)
+        out.update(nested_auc_counts=cnt, nested_auc=auc, nested_auc_macro=macro)
+    if perm_blocks is not None:
+        pconf = ints(perm_blocks, (1, 2, 0))                         # (G, G, P)
+        pacc, pbal = scores_from_confusion(pconf)
+        # the pooled statistic: the same functional of the observed data, the confusion summed over the outer splits
+        oacc, obal = scores_from_confusion(conf.sum(axis=-1))
+        out.update(perm_nested_confusion=pconf, perm_nested_accuracy=pacc, perm_nested_balanced_accuracy=pbal,
+                   nested_accuracy_pvals=float(_pvals_nan(oacc, pacc)),
+                   nested_balanced_accuracy_pvals=float(_pvals_nan(obal, pbal)))
+        if auc_blocks is not None and perm_auc_blocks is not None:
+            pcnt = ints(perm_auc_blocks, (1, 2, 0))                  # (G, 2, P)
+            pauc, pmacro = auc_from_counts(pcnt)
+            oauc, omacro = auc_from_counts(out['nested_auc_counts'].sum(axis=-1))
+            out.update(perm_nested_auc_counts=pcnt, perm_nested_auc=pauc, perm_nested_auc_macro=pmacro,
+                       nested_auc_pvals=_pvals_nan(oauc, pauc), nested_auc_macro_pvals=float(_pvals_nan(omacro, pmacro)))
+    return out
+
+
 def encode_labels(y, S=None):
     """y (S,) labels -> (classes (G,) sorted distinct labels, codes (S,) int64 positions in it).  ValueError for a y that
     is not 1-D (or not of length S), a NaN or None label, fewer than 2 or more than 32 classes."""
@@ -149,7 +226,7 @@ def _label(classes, g):
 def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamples=None, bootsamples=None, seed=None,
            verbose=True, n_proc=None, test_split=0, test_size=0.25, cvsamples=None, cv_perm=0, cvpermsamples=None,
            coef_components=None, coef_ci=False, coef_perm=False, vip_components=None, auc=False, vip_perm=False,
-           cv_predict=False, **kwargs):
+           cv_predict=False, inner_split=0, innersamples=None, inner_select=None, **kwargs):
     """PLS discriminant analysis of the labels ``y`` (S,) on ``X`` (S, B).
 
     ``classes = np.unique(y)`` (integers, strings, booleans: anything numpy sorts), ``codes`` the position of every
@@ -198,7 +275,45 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
     argmax above is taken of and ``auc`` ranks; NaN on every other row --, ``y_pred_ncomp`` (test_split,) int32 and
     ``predicted`` (S, test_split) int32, the index into ``classes`` of the first maximum (-1 off the test rows), from
     which ``confusion[:, :, c - 1, s]`` can be recounted exactly.  :func:`roc_curve` draws the ROC curve of a class and a
-    split from them.  ``'nested'`` is refused, as ``inner_split`` is.
+    split from them.  ``'nested'`` (needs ``inner_split``): the model of ``nested_ncomp[s]`` components per split, from
+    whose ``predicted`` ``nested_confusion[:, :, s]`` can be recounted exactly.
+
+    Nested cross-validation of ``n_components``: ``inner_split=ni`` (needs ``test_split`` > 0; 0, the default: nothing is
+    added, nothing is drawn and every array keeps its bits).  Picking the best row of ``balanced_accuracy`` (k,
+    test_split) selects and scores on the same test rows.  Here ni inner folds INSIDE the training rows of every split
+    choose c, and the split's test rows, which took no part in the choice, score the chosen model.  The inner folds are
+    codes ``innersamples`` (S, test_split, ni) uint8 -- 1 = training row, 0 = test row, 2 = on neither side, exactly on
+    the outer test rows -- given (needs ``cvsamples``) or drawn, STRATIFIED by class
+    (``gen_stratified_splits(codes[rows], ni, test_size=test_size)`` on the training rows of every split, behind
+    everything else a seeded call draws).  Per split s and c = 1 .. k the confusion counts of the ni inner fits are
+    pooled, ``inner_confusion[:, :, c - 1, s]``, and ``inner_select`` names the criterion on them -- it has no default:
+    ``pls_da(inner_split=ni)`` alone is refused as it was before the nested selection existed:
+
+        'balanced_accuracy'  the recalls of the classes with a counted row, added in ascending class order and
+                             divided by their number (:func:`nested_criterion`)
+        'accuracy'           trace / total
+        'mse'                ``inner_mse``, smallest wins: the rule of ``pls_regression(inner_split=)``
+
+    ``nested_ncomp[s]`` is the FIRST optimum over c = 1 .. k (:func:`nested_select`): ties, common on counts, go to the
+    smaller model, a NaN never wins; 0 where the pooled block has no counted row (mse: the minimum is not finite) --
+    the split is then undefined, its scores NaN, its counts zero, and it counts nowhere under a permutation.  ``cvres``
+    gains, at c = ``nested_ncomp[s]``,
+
+        nested_confusion          (G, G, test_split) int
+        nested_accuracy           (test_split,)            nested_balanced_accuracy likewise
+        nested_auc_counts         (G, 2, test_split) int   with auc=True, and nested_auc (G, test_split), nested_auc_macro
+        inner_confusion           (G, G, k, test_split) int, inner_accuracy / inner_balanced_accuracy (k, test_split)
+
+    and the regression keys of the nested call as ``pls_regression`` returns them, at the c THIS selection chose:
+    ``nested_ncomp``, ``nested_pearson_r``, ``nested_r_squared``, ``nested_mse``, ``inner_mse``, ``innersamples`` --
+    one selection per call.  With ``cv_perm=P`` the WHOLE procedure, selection included, runs per permutation:
+    ``perm_nested_confusion`` (G, G, P) summed over the outer splits, ``perm_nested_accuracy`` /
+    ``perm_nested_balanced_accuracy`` (P,) the score of that sum, ``perm_nested_ncomp`` (k, P), the scalars
+    ``nested_accuracy_pvals`` / ``nested_balanced_accuracy_pvals`` against
+    ``scores_from_confusion(nested_confusion.sum(-1))`` by the ``>=`` rule below, with ``auc=True``
+    ``perm_nested_auc_counts`` (G, 2, P), ``perm_nested_auc``, ``perm_nested_auc_macro``, ``nested_auc_pvals`` (G,),
+    ``nested_auc_macro_pvals`` (a NaN observed value gives a NaN p-value), and the ``perm_nested_pearson_r`` ... keys of
+    ``pls_regression``.  Not offered: selection on the AUC, a one-standard-error rule, ``confounds``.
 
     ``cv_perm=P``: the true class of position p under a permutation is ``codes[perm[p]]``.  The device returns, per
     permutation, the confusion SUMMED over the splits, and ``cvres`` gains ``perm_confusion`` (G, G, k, P),
@@ -215,8 +330,9 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
     ValueError, before any engine is created or looked up: a ``y`` that is not 1-D of length S; a NaN or None label;
     fewer than 2 or more than 32 classes (the bound of the device kernel k_sd_cv_class); a class with fewer than 2
     usable rows; ``auc=True`` without ``test_split``; a ``test_size`` that can leave a class without a usable training row; ``cvsamples`` whose training
-    side lacks a usable row of some class; ``n_split``, ``aggfunc`` or ``rotate`` given; and everything
-    ``pls_regression`` refuses."""
+    side lacks a usable row of some class; an unknown ``inner_select``, one given without ``inner_split``, ``inner_split`` without one; an inner
+    fold whose training side lacks a usable row of some class (given folds as they are, drawn ones in the worst case);
+    ``n_split``, ``aggfunc`` or ``rotate`` given; and everything ``pls_regression`` refuses."""
     for name in ('n_split', 'aggfunc', 'rotate'):
         if name in kwargs:
             raise ValueError('`pls_da` takes no `{}`: split-half reliability, aggregation of a 3-D Y and rotation are '
@@ -226,6 +342,18 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
                          'splits (with `test_size` > 0)')
     if auc:
         kwargs = dict(kwargs, _auc=True)
+    if inner_select is not None and inner_select not in INNER_SELECT:
+        raise ValueError('Provided `inner_select` must be one of {}; got {!r}'.format(list(INNER_SELECT), inner_select))
+    nested = isinstance(inner_split, (int, np.integer)) and not isinstance(inner_split, (bool, np.bool_)) \
+        and inner_split > 0                            # (anything else: pls_regression's own message)
+    if inner_select is not None and not nested:
+        raise ValueError('`inner_select` needs `inner_split` > 0: it names the criterion the inner folds select by')
+    if nested and inner_select is None:
+        # (every call that was refused before the nested selection existed is refused still: the criterion is named)
+        raise ValueError('`inner_split` is not available for pls_da without `inner_select`: name the criterion the inner '
+                         'folds select by, one of {}'.format(list(INNER_SELECT)))
+    if nested:
+        kwargs = dict(kwargs, inner_select=inner_select)
     X = np.asarray(X)
     if X.ndim != 2:
         raise ValueError('Expected 2D array for `X`, got {}D array instead'.format(X.ndim))
@@ -261,12 +389,40 @@ def pls_da(X, y, *, n_components=None, n_perm=5000, n_boot=5000, ci=95, permsamp
                 raise ValueError('Every cross-validation split needs a usable training row of every class; test_size = '
                                  '{} can leave class {!r} ({} rows, {} of them NaN throughout) without one'
                                  .format(test_size, _label(classes, g), int(n_g[g]), int(n_g[g] - ok_g[g])))
+    if nested and n_cv > 0 and 0 < test_size < 1:
+        bad_g = n_g - ok_g
+        given = np.asarray(innersamples) if innersamples is not None else None
+        masks = np.asarray(cvsamples) if cvsamples is not None else None
+        if masks is not None and (masks.ndim != 2 or masks.shape != (S, n_cv)):
+            masks = None                                             # (pls_regression's own message)
+        if given is not None:
+            if given.ndim == 3 and given.shape == (S, n_cv, int(inner_split)):   # (any other shape: pls_regression's message)
+                tr = (given == 1) & usable[:, None, None]
+                per = np.stack([tr[codes == g].sum(axis=0) for g in range(G)])  # (G, n, ni) usable training rows
+                if per.min() < 1:
+                    g, s, j = np.unravel_index(int(per.argmin()), per.shape)
+                    raise ValueError('Every inner fold needs a usable training row of every class; inner fold {} of '
+                                     'split {} of `innersamples` has none of class {!r}'
+                                     .format(int(j), int(s), _label(classes, g)))
+        else:
+            # drawn, stratified: an inner fold keeps ceil or floor of m (1 - test_size) training rows of a class with m
+            # rows on the outer training side, itself ceil or floor of n_g (1 - test_size) -- or what `cvsamples` leaves
+            if masks is not None:
+                m_lo = np.stack([masks.astype(bool)[codes == g].sum(axis=0) for g in range(G)]).min(axis=1)
+            else:
+                m_lo = np.floor(n_g * (1 - test_size)).astype(int)
+            lo = np.floor(m_lo * (1 - test_size)).astype(int) - bad_g
+            if lo.min() < 1:
+                g = int(lo.argmin())
+                raise ValueError('Every inner fold needs a usable training row of every class; test_size = {} can leave '
+                                 'class {!r} ({} rows, {} of them NaN throughout) without one inside an outer training set'
+                                 .format(test_size, _label(classes, g), int(n_g[g]), int(bad_g[g])))
     res = pls_regression(X, onehot, n_components=n_components, n_perm=n_perm, n_boot=n_boot, ci=ci,
                          permsamples=permsamples, bootsamples=bootsamples, seed=seed, verbose=verbose, n_proc=n_proc,
                          test_split=test_split, test_size=test_size, cvsamples=cvsamples, cv_perm=cv_perm,
                          cvpermsamples=cvpermsamples, coef_components=coef_components, coef_ci=coef_ci,
                          coef_perm=coef_perm, vip_components=vip_components, vip_perm=vip_perm, cv_predict=cv_predict,
-                         _classes=codes, **kwargs)
+                         inner_split=inner_split, innersamples=innersamples, _classes=codes, **kwargs)
     res['classes'] = classes
     return res
 

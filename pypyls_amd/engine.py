@@ -125,6 +125,8 @@ def _load():
         'plsx_simpls_cv_auc_end': ([vp], i32),
         'plsx_simpls_cv_pred_begin': ([vp, i32, vp, vp, vp, ctypes.c_longlong], i32),
         'plsx_simpls_cv_pred_end': ([vp], i32),
+        'plsx_simpls_cvn_class_begin': ([vp, i32, vp, vp, vp, ctypes.c_longlong], i32),
+        'plsx_simpls_cvn_class_end': ([vp], i32),
         'plsx_crossval_pred_begin': ([vp, vp, vp, ctypes.c_longlong], i32),
         'plsx_crossval_pred_end': ([vp], i32),
         'plsx_simpls_vip_keep': ([vp, i32, vp, ctypes.c_longlong], i32),
@@ -170,6 +172,7 @@ def exported_symbols():
              'plsx_simpls_boot_batch', 'plsx_simpls_set_row_masks', 'plsx_simpls_crossval_batch', 'plsx_simpls_crossval_perm_batch', 'plsx_simpls_crossval_nested_batch', 'plsx_simpls_crossval_nested_perm_batch', 'plsx_simpls_split_half_batch', 'plsx_simpls_set_confounds', 'plsx_simpls_crossval_confound_batch', 'plsx_simpls_crossval_confound_perm_batch', 'plsx_simpls_coef_begin', 'plsx_simpls_coef_finish', 'plsx_simpls_coef_keep', 'plsx_simpls_coef_ci', 'plsx_simpls_coef_perm_test', 'plsx_simpls_coef_perm_begin', 'plsx_simpls_coef_perm_end',
              'plsx_simpls_set_classes', 'plsx_simpls_cv_class_begin', 'plsx_simpls_cv_class_end',
              'plsx_simpls_cv_auc_begin', 'plsx_simpls_cv_auc_end', 'plsx_simpls_cv_pred_begin', 'plsx_simpls_cv_pred_end',
+             'plsx_simpls_cvn_class_begin', 'plsx_simpls_cvn_class_end',
              'plsx_crossval_pred_begin', 'plsx_crossval_pred_end',
              'plsx_simpls_vip_keep', 'plsx_simpls_vip_ci', 'plsx_simpls_vip_perm_test', 'plsx_simpls_vip_perm_begin', 'plsx_simpls_vip_perm_end', 'plsx_gen_permsamp', 'plsx_gen_bootsamp',
              'plsx_gen_splits', 'plsx_gen_splits_seeded', 'plsx_gen_permsamp_stream',
@@ -1373,6 +1376,35 @@ class Engine(object):
     def simpls_cv_auc_end(self):
         """Close the series of AUC counts (plsx_simpls_cv_auc_end)."""
         self._check(self.lib.plsx_simpls_cv_auc_end(self.ctx))
+
+    CVN_RULES = {'mse': 0, 'accuracy': 1, 'balanced_accuracy': 2}
+
+    def simpls_cvn_class_begin(self, rule, conf_dev, auc_dev=None, inner_dev=None):
+        """Open the series of nested counts (PLS-DA; after :meth:`simpls_set_classes`): until
+        :meth:`simpls_cvn_class_end` the nested entries classify every fit, select the component count of a group by
+        ``rule`` -- 'balanced_accuracy' or 'accuracy' of the confusion counts pooled over the inner folds (first maximum),
+        or 'mse' (the rule they have without the series) -- and append the OUTER fit's counts at the selected count:
+        :meth:`simpls_crossval_nested_into` of n outer splits n blocks to ``conf_dev`` (capacity, T, T) int32,
+        ``auc_dev`` (capacity, T, 2) int64 (or None: no AUC counts) and the pooled inner counts to ``inner_dev``
+        (capacity, k, T, T) int32 (or None); :meth:`simpls_crossval_nested_perm_into` of m permutations m blocks, each
+        the sum over the outer splits (plsx_simpls_cvn_class_begin).  The tensors must stay alive until the series ends.
+        PlsxError: status -4 before :meth:`simpls_set_classes`, -1 from the call that would pass the capacity."""
+        torch = _torch()
+        if rule not in self.CVN_RULES:
+            raise ValueError('the selection rule must be one of {}; got {!r}'.format(sorted(self.CVN_RULES), rule))
+        cap = int(conf_dev.shape[0]) if conf_dev.dim() == 3 else -1
+        for t, shape, dt in ((conf_dev, (cap, self.T, self.T), torch.int32), (auc_dev, (cap, self.T, 2), torch.int64),
+                             (inner_dev, (cap, self.k, self.T, self.T), torch.int32)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+                raise ValueError('the nested counts must be contiguous (capacity, {0}, {0}) int32, (capacity, {0}, 2) int64 '
+                                 'and (capacity, {1}, {0}, {0}) int32 tensors of one capacity'.format(self.T, self.k))
+        self._check(self.lib.plsx_simpls_cvn_class_begin(
+            self.ctx, self.CVN_RULES[rule], conf_dev.data_ptr(), auc_dev.data_ptr() if auc_dev is not None else None,
+            inner_dev.data_ptr() if inner_dev is not None else None, cap))
+
+    def simpls_cvn_class_end(self):
+        """Close the series of nested counts (plsx_simpls_cvn_class_end)."""
+        self._check(self.lib.plsx_simpls_cvn_class_end(self.ctx))
 
     def simpls_cv_pred_begin(self, c, pred_dev, ncomp_dev=None, true_dev=None):
         """Open a series of out-of-fold predictions: until :meth:`simpls_cv_pred_end` every :meth:`simpls_crossval_into`

@@ -123,17 +123,22 @@ def _check_cvsplits(masks, usable, k, B):
                          'training set has {} usable rows'.format(max(min(int(n_tr.min()) - 1, B), 0), int(n_tr.min())))
 
 
-def _draw_inner_codes(cvmasks, inner_split, rs, test_size):
+def _draw_inner_codes(cvmasks, inner_split, rs, test_size, classes=None):
     """The inner folds of a nested cross-validation, drawn from the generator ``rs``: for s = 0 .. n - 1
     ``gen_splits([n_tr_s], 1, inner_split, seed=rs, test_size=test_size)`` on the training rows of outer split s
     (``cvmasks`` (S, n) bool, True = training row) in ascending row order, scattered back -> (S, n, inner_split) uint8
-    codes: 1 = inner training row, 0 = inner test row, 2 = on neither side (the outer test rows)."""
+    codes: 1 = inner training row, 0 = inner test row, 2 = on neither side (the outer test rows).  ``classes`` (S,) class
+    codes (pls_da): the draw is stratified, ``gen_stratified_splits(classes[rows], inner_split, ...)`` at the same place."""
     cvmasks = np.asarray(cvmasks, dtype=bool)
     S, n = cvmasks.shape
     codes = np.full((S, n, int(inner_split)), 2, dtype=np.uint8)
     for s in range(n):
         rows = np.flatnonzero(cvmasks[:, s])
-        codes[rows, s, :] = resampling.gen_splits([len(rows)], 1, inner_split, seed=rs, test_size=test_size)
+        if classes is not None:
+            codes[rows, s, :] = resampling.gen_stratified_splits(np.asarray(classes)[rows], inner_split, seed=rs,
+                                                                 test_size=test_size)
+        else:
+            codes[rows, s, :] = resampling.gen_splits([len(rows)], 1, inner_split, seed=rs, test_size=test_size)
     return codes
 
 
@@ -153,9 +158,9 @@ def _check_cv_predict(cv_predict, k, test_split, test_size, inner_split, da):
     if isinstance(cv_predict, (bool, np.bool_)):
         c = int(k)
     elif isinstance(cv_predict, str) and cv_predict == 'nested':
-        if da:
-            raise ValueError("`cv_predict='nested'` is not available for pls_da: it has no nested selection "
-                             '(`inner_split`)')
+        if da and not inner_split:
+            raise ValueError("`cv_predict='nested'` is not available for pls_da without `inner_split` > 0 and "
+                             '`inner_select`: the component count of every outer split is the one its inner folds choose')
         if not inner_split:
             raise ValueError("`cv_predict='nested'` needs `inner_split` > 0: the component count of every outer split "
                              'is the one its inner folds choose')
@@ -254,8 +259,8 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     ``nested_pearson_r_pvals`` / ``nested_r_squared_pvals`` (T,) = (#{null > observed split-mean} + 1) / (P + 1),
     ``nested_mse_pvals`` with ``<`` (a NaN null value counts as not larger / not smaller).  That is
     P x test_split x (1 + ni) fits, selected and reduced on the device (plsx_simpls_crossval_nested_batch,
-    plsx_simpls_crossval_nested_perm_batch); ranks and teams shard the permutations.  Refused: ``confounds`` and
-    ``pls_da``.
+    plsx_simpls_crossval_nested_perm_batch); ranks and teams shard the permutations.  Refused: ``confounds``.
+    (``pls_da`` selects on its counts instead: ``inner_select`` there.)
 
     Out-of-fold predictions: ``cv_predict`` (needs cross-validation; False, the default: nothing is added, nothing is
     drawn differently, every array keeps its bits) returns the predicted value of every held-out row, which the scores
@@ -423,9 +428,9 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
             raise ValueError('`inner_split` needs cross-validation: the inner folds lie inside the training rows of the '
                              'splits of `test_split` > 0 with `test_size` > 0; got test_split = {!r}, test_size = {!r}'
                              .format(test_split, test_size))
-        if kwargs.get('_classes') is not None:
-            raise ValueError('`inner_split` is not available for pls_da: its confusion and AUC counts are not selected '
-                             '(not in this version)')
+        if kwargs.get('_classes') is not None and kwargs.get('inner_select') is None:
+            raise ValueError('`inner_split` is not available for pls_da without `inner_select`: its confusion and AUC '
+                             'counts are selected by the criterion that keyword names')
         if confounds is not None:
             raise ValueError('`inner_split` cannot be combined with `confounds`: the fold-wise confound regression has '
                              'its own K per split (not in this version)')
@@ -625,6 +630,19 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
                 [int(np.floor(S * (1 - test_size))), int(np.ceil(S * (1 - test_size)))]
             lo_tr_in = int(np.floor(n_out[0] * (1 - test_size))) - n_bad_tr
             lo_te_in = min(nt - int(np.ceil(nt * (1 - test_size))) for nt in range(n_out[0], n_out[1] + 1)) - n_bad
+            if kwargs.get('_classes') is not None:
+                # (pls_da: both draws are stratified -- every class keeps ceil or floor of ITS rows, of the S rows and
+                # again of an outer training set; the worst case per class, summed)
+                cls_ = np.asarray(kwargs['_classes'])
+                if cvmasks is not None:
+                    m_gs = np.stack([cvmasks[cls_ == g].sum(axis=0) for g in range(int(cls_.max()) + 1)])   # (G, n)
+                    lo_tr_in = int(np.floor(m_gs * (1 - test_size)).sum(axis=0).min()) - n_bad_tr
+                    lo_te_in = int((m_gs - np.ceil(m_gs * (1 - test_size))).sum(axis=0).min()) - n_bad
+                else:
+                    n_g = np.bincount(cls_)
+                    opts = np.stack([np.floor(n_g * (1 - test_size)), np.ceil(n_g * (1 - test_size))])      # (2, G)
+                    lo_tr_in = int(np.floor(opts * (1 - test_size)).min(axis=0).sum()) - n_bad_tr
+                    lo_te_in = int((opts - np.ceil(opts * (1 - test_size))).min(axis=0).sum()) - n_bad
         if lo_te_in < 2:
             raise ValueError('Every inner fold needs at least 2 usable test rows; {} of {} ({} rows are NaN throughout)'
                              .format('`innersamples` leaves' if inner is not None else
@@ -733,11 +751,12 @@ def pls_regression(X, Y, *, n_components=None, n_perm=5000, n_boot=5000, rotate=
     if inner_split > 0:
         cv['inner'] = inner
         cv['ni'] = inner_split
+        cv['inner_select'] = kwargs.get('inner_select')     # (pls_da only; validated there)
         if inner is None:
             # the inner folds: one more job at the END of the list, behind the split-half masks -- per outer split the
             # training rows in ascending row order are split again, everything else holds 2
             def inner_draw(r):
-                cv['inner'] = _draw_inner_codes(cv['masks'], inner_split, r, test_size)
+                cv['inner'] = _draw_inner_codes(cv['masks'], inner_split, r, test_size, classes=cv['classes'])
             jobs.append(inner_draw)
     from .engine import default_engine, touch_idle_release
     from . import team as _team
@@ -1051,7 +1070,7 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     # shard of the OUTER splits, each with its inner folds -- and, under cv_perm, this rank's shard of the permutations
     # under all the groups.  Fits, selection and the reduction over the outer splits stay on the device
     # (plsx_simpls_crossval_nested_batch / _perm_batch); a rank keeps 2 T + 1 + k numbers per permutation.
-    d_cvn = d_cvnp = None
+    d_cvn = d_cvnp = d_ncls = d_nclsp = None
     if cv is not None and cv.get('ni'):
         ni = cv['ni']
         codes = nested_codes(cv['masks'], cv['inner'])           # (S, n, 1 + ni)
@@ -1063,9 +1082,19 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
         nested_pred = d_pred is not None and cv['pred'] == 0 and hi > lo
         if nested_pred:
             eng.simpls_cv_pred_begin(0, d_pred[0], d_pred[1], d_pred[2])
+        if classes is not None:
+            # pls_da: the selection runs on counts, and the selected counts of this rank's outer splits come back -- one
+            # confusion block per split, its AUC counts and the pooled inner confusion (plsx_simpls_cvn_class_begin)
+            d_ncls = [torch.zeros((hi - lo, T, T), dtype=torch.int32, device=eng.device),
+                      torch.zeros((hi - lo, T, 2), dtype=torch.int64, device=eng.device) if cv['auc'] else None,
+                      torch.zeros((hi - lo, k, T, T), dtype=torch.int32, device=eng.device)]
+            if hi > lo:
+                eng.simpls_cvn_class_begin(cv['inner_select'], *d_ncls)
         for a in range(lo, hi, step):
             b = min(hi, a + step)
             eng.simpls_crossval_nested_into(d_codes[a:b], *(t[a - lo:b - lo] for t in d_cvn))
+        if d_ncls is not None:
+            eng.simpls_cvn_class_end()
         if nested_pred:
             eng.simpls_cv_pred_end()
         tick('crossval_nested')
@@ -1075,6 +1104,12 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                       torch.zeros((hi - lo, k), dtype=torch.int32, device=eng.device)]
             bars.append(Bar('Running nested cross-validation permutations', hi - lo, show, eng.device))
             step = max(1, 65536 // (cv['n'] * (1 + ni)))
+            if classes is not None:
+                # ... and per permutation of this rank's shard, summed over the outer splits on the device
+                d_nclsp = [torch.zeros((hi - lo, T, T), dtype=torch.int32, device=eng.device),
+                           torch.zeros((hi - lo, T, 2), dtype=torch.int64, device=eng.device) if cv['auc'] else None]
+                if hi > lo:
+                    eng.simpls_cvn_class_begin(cv['inner_select'], *d_nclsp)
             for a in range(lo, hi, step):
                 b = min(hi, a + step)
                 cvp.wait(b)
@@ -1083,6 +1118,8 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                 for done in bars:
                     done.poll()
                 bars[-1].queued(b - a)
+            if d_nclsp is not None:
+                eng.simpls_cvn_class_end()
             tick('crossval_nested_perm')
     # split-half reliability: this rank's contiguous shard of the permutations, block by block as their masks arrive
     # (permutation i: RandomState(i)), the mean over the splits taken on the device in fixed order; the observed
@@ -1152,6 +1189,13 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
     if d_cvnp is not None:                              # ... and their null per permutation
         slices = slices + [d_cvnp[0], d_cvnp[1], d_cvnp[2][:, None], d_cvnp[3].to(torch.float64)]
         totals = totals + [cvp.n] * 4
+    ncls_at = len(slices)
+    for ts, n in ((d_ncls, cv['n'] if cv is not None else 0), (d_nclsp, cvp.n if cvp is not None else 0)):
+        if ts is not None:                              # ... and the selected counts of pls_da, as float64: they are exact
+            for t in ts:
+                if t is not None:
+                    assert t.numel() == 0 or int(t.max().item()) < 2 ** 53, 'counts beyond 2^53 do not ride as float64'
+                    slices, totals = slices + [t.to(torch.float64)], totals + [n]
     pred_at = len(slices)
     if d_pred is not None:                              # ... and the out-of-fold predictions, a slot per split
         slices = slices + [d_pred[0], d_pred[1].to(torch.float64)[:, None]] + ([d_pred[2]] if d_pred[2] is not None else [])
@@ -1250,6 +1294,15 @@ def _run_device(X, Y, Y_agg, agg, third, inputs, pstream, bstream, draws, permsa
                     nested_pearson_r_pvals=hostmath.perm_sig(cr['nested_pearson_r'].mean(axis=-1), pr),
                     nested_r_squared_pvals=hostmath.perm_sig(cr['nested_r_squared'].mean(axis=-1), pr2),
                     nested_mse_pvals=float(hostmath.perm_sig(-np.atleast_1d(cr['nested_mse'].mean()), -pmse[None, :])[0])))
+            if d_ncls is not None:
+                from .discriminant import nested_results
+                nper = 3 if cv['auc'] else 2
+                obs = full[ncls_at:ncls_at + nper]
+                prm = full[ncls_at + nper:ncls_at + nper + nper - 1] if d_nclsp is not None else None
+                res['cvres'].update(nested_results(
+                    obs[0], obs[-1], auc_blocks=obs[1] if cv['auc'] else None,
+                    perm_blocks=prm[0] if prm is not None else None,
+                    perm_auc_blocks=prm[1] if prm is not None and cv['auc'] else None))
     if d_pred is not None:
         # (S, T, n); the centring the front end removed before binding is added back: the units of the Y of the call
         # (not under confounds -- the residuals have no mean -- nor for pls_da, whose slots hold the raw indicators)

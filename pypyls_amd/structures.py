@@ -102,6 +102,7 @@ class PLSInputs(KeyedRecord):
         'weights_perm',                     # behavioral_pls / meancentered_pls: permutation p-values of the x_weights (only when given)
         'confounds',                        # pls_regression / behavioral_pls: the nuisance variables Z (S, q) (only when given)
         'inner_split',                      # pls_regression: inner folds of the nested cross-validation (only when asked for)
+        'inner_select',                     # pls_da: the criterion of the nested selection (only when inner_split is given)
         'cv_predict',                       # pls_regression / pls_da / behavioral_pls: the out-of-fold predictions are returned (only when asked for)
         'cv_lv',                            # behavioral_pls: out-of-sample score correlation of the latent variables (only when given)
         # build-only knobs (filtered like any other key): pre-drawn split masks, engine
@@ -201,6 +202,18 @@ class PLSCrossValidationResults(KeyedRecord):
                'nested_ncomp', 'nested_pearson_r', 'nested_r_squared', 'nested_mse', 'inner_mse', 'innersamples',
                'perm_nested_pearson_r', 'perm_nested_r_squared', 'perm_nested_mse', 'perm_nested_ncomp',
                'nested_pearson_r_pvals', 'nested_r_squared_pvals', 'nested_mse_pvals',
+               # pls_da(inner_split=ni): the selection runs on counts (inner_select) -- inner_confusion (G, G, k, n) int the
+               # confusion pooled over the inner folds, inner_accuracy / inner_balanced_accuracy (k, n) of it,
+               # nested_confusion (G, G, n) int the outer test rows' confusion at nested_ncomp, nested_accuracy /
+               # nested_balanced_accuracy (n,); with auc=True nested_auc_counts (G, 2, n) int, nested_auc (G, n),
+               # nested_auc_macro (n,); with cv_perm=P: perm_nested_confusion (G, G, P) / perm_nested_auc_counts (G, 2, P)
+               # summed over the outer splits of a permutation, their scores (P,) / (G, P) / (P,) and the p-values of
+               # the pooled statistic (scalars; nested_auc_pvals (G,))
+               'inner_confusion', 'inner_accuracy', 'inner_balanced_accuracy', 'nested_confusion', 'nested_accuracy',
+               'nested_balanced_accuracy', 'nested_auc_counts', 'nested_auc', 'nested_auc_macro',
+               'perm_nested_confusion', 'perm_nested_accuracy', 'perm_nested_balanced_accuracy',
+               'nested_accuracy_pvals', 'nested_balanced_accuracy_pvals', 'perm_nested_auc_counts', 'perm_nested_auc',
+               'perm_nested_auc_macro', 'nested_auc_pvals', 'nested_auc_macro_pvals',
                # behavioral_pls(cv_predict=True): y_pred (S, T, n) and, with confounds=, y_true (S, T, n)
                # pls_regression / pls_da(cv_predict=): y_pred (S, T, n) the out-of-fold prediction of every usable test
                # row of every split (NaN elsewhere) by the model of y_pred_ncomp (n,) int32 components, in the units of
